@@ -18,8 +18,11 @@ two-slot receive buffer, so it runs on RCCL's stream under that kernel.  `--conf
 `--host inprocess` times the OTHER host of the same partition instead: one process, one tsdf_hip_create_multi handle
 over N GPUs (what cpu_tsdf::TSDFVolumeOctree::setDevices uses), frame fan-out by peer copies instead of RCCL.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the dominant kernel
-(k_integrate, HBM-bound) and `cpu_baseline` (the reference CPU path timed on this host on a bounded sample).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps and
+prints the headline (`value`, `ms_per_step`, the timed launches' `roofline.kernel_ms`); `--full` adds, outside the timed
+region, `roofline` for the dominant kernel (k_integrate, HBM-bound), the report-only legs and `cpu_baseline` (the
+reference CPU path timed on this host on a bounded sample).  `--dump-outputs DIR` writes a seeded sample of the grid
+the timed steps produced (dump_outputs).
 
 roofline.achieved uses the ALGORITHMIC bytes of the shipped HBM layout, measured per frame by the kernel's counting
 instance: bytes of the voxel words an observed voxel must read (PACKED colour: d + colour|count word = 8 B) + bytes
@@ -76,15 +79,21 @@ def parse():
                     help="HBM weight layout (include/tsdf_hip.h TSDF_LAYOUT_*); auto = packed when max_weight <= 255")
     ap.add_argument("--frames", type=int, default=0, help="distinct frames on the turntable (default steps+warmup)")
     ap.add_argument("--overlap", type=int, default=1, help="N>1: broadcast frame i+1 under the kernel of frame i")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also run everything the headline figure does not need, outside the "
+                    "timed region: the roofline byte counts (the timed frames once more through the counting instance), "
+                    "the isolated frame broadcast, and the report-only legs selected by --extras, --keys, --scene-b, "
+                    "--host-path and --cpu-baseline (all on by default with --full, off without it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write a fixed, seeded sample of "
+                    "the voxel grid they produced (distance, weight, colour and the sampled voxel indices) as DIR/<name>.npy")
+    ap.add_argument("--cpu-baseline", type=int, default=None)
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--extras", type=int, default=1, help="1: also time renderView + marching cubes once, k_integrate2 and Scene B "
+    ap.add_argument("--extras", type=int, default=None, help="1: also time renderView + marching cubes once, k_integrate2 and Scene B "
                     "(N=1, outside the timed region); 2: only the k_integrate2 leg (A/B runs)")
-    ap.add_argument("--scene-b", type=int, default=1, help="with --extras: the Scene-B (camera inside the volume) leg; the "
+    ap.add_argument("--scene-b", type=int, default=None, help="with --extras: the Scene-B (camera inside the volume) leg; the "
                     "rocprof run turns it off so that k_integrate's average is the headline workload's alone")
     ap.add_argument("--host", choices=["process", "inprocess"], default="process",
                     help="N>1: one process per GPU over RCCL (default) or ONE process driving all GPUs through tsdf_hip_create_multi")
-    ap.add_argument("--keys", type=int, default=1, help="N=1 with --extras: also time the secondary integrate keys in this run -- the "
+    ap.add_argument("--keys", type=int, default=None, help="N=1 with --extras: also time the secondary integrate keys in this run -- the "
                     "headline grid in the SATURATED regime (w == max_weight), the colourless 2048^3 grid, one configs[4] slab "
                     "(4096x4096x512, 1280x960) -- each with kernel_ms, bytes moved, frac and its PMC quote (extras.keys)")
     ap.add_argument("--emulate-rank", type=int, default=-1, help="with --of N, on ONE GPU: integrate the Z-slab rank r of an N-rank strong-scaling "
@@ -97,7 +106,7 @@ def parse():
     ap.add_argument("--presaturate", type=int, default=0, help="launches BEFORE the warm-up (cycling through the timed frames): the "
                     "timed region then runs in the saturated regime w == max_weight (>= 100 for the default max_weight): how "
                     "tools/run_rocprof.sh profiles that key")
-    ap.add_argument("--host-path", type=int, default=1, help="N=1: also time the host-pointer entry point (report-only side field)")
+    ap.add_argument("--host-path", type=int, default=None, help="N=1: also time the host-pointer entry point (report-only side field)")
     ap.add_argument("--principal-offset", type=float, default=0.0, help="evidence runs: move the principal point by this fraction "
                     "of the half-width and yaw every turntable camera so that the grid's centre still projects to the image "
                     "centre -- the regime where the reference's frustum cull (1.1 x FOV about the optical AXIS) decides voxels "
@@ -109,6 +118,15 @@ def parse():
     ap.add_argument("--calib", type=int, default=0, help="run this many k_calib_rmw sweeps of exactly known bytes first "
                     "(PMC passes: calibrates FETCH_SIZE / WRITE_SIZE in the same process)")
     a = ap.parse_args()
+    # the report-only legs run with --full only: there they default to on, as they did before the option existed
+    for name in ("extras", "keys", "scene_b", "host_path", "cpu_baseline"):
+        v = getattr(a, name)
+        if v is None:
+            setattr(a, name, 1 if a.full else 0)
+        elif v and not a.full:
+            ap.error(f"--{name.replace('_', '-')} {v} is a report-only leg: it runs with --full only")
+    if a.dump_outputs and (a.gpus > 1 or a.host != "process" or a.dry_run_ranks):
+        ap.error("--dump-outputs: one GPU, one process only")
     if a.config == 4:
         a.res, a.width, a.height = a.res or 4096, a.width or 1280, a.height or 960
     else:
@@ -541,6 +559,37 @@ def pmc_traffic(key, sha):
     return e, None
 
 
+def dump_outputs(vol, out_dir, planes=8, per_plane=1 << 17, seed=20260101):
+    """--dump-outputs: what a caller of the timed path receives -- the voxel grid the timed steps left, as download() hands
+    it out -- on a fixed, seeded sample: `planes` z planes of the handle's slab, `per_plane` (y, x) positions in each
+    (32 MB at the defaults).  Same arguments, same sample, so two builds can be compared output for output."""
+    rx, ry, rz = vol.getResolution()
+    zb = vol._p.z_begin
+    ze = vol._p.z_end if (vol._p.z_begin or vol._p.z_end) else rz
+    rng = np.random.default_rng(seed)
+    zs = np.sort(rng.choice(np.arange(zb, ze), size=min(planes, ze - zb), replace=False))
+    color = bool(vol._p.integrate_color)
+    idx, d_out, w_out, rgb_out = [], [], [], []
+    for z in zs:
+        d, w, rgb = vol.download(0, 0, int(z), rx, ry, 1)
+        flat = rng.choice(rx * ry, size=min(per_plane, rx * ry), replace=False)
+        flat.sort()
+        y, x = np.divmod(flat, rx)
+        idx.append(np.stack([np.full_like(y, z), y, x], axis=1))
+        d_out.append(d.reshape(-1)[flat])
+        w_out.append(w.reshape(-1)[flat])
+        if color:
+            rgb_out.append(rgb.reshape(-1, 3)[flat])
+    arrays = {"tsdf_distance": np.concatenate(d_out).astype(np.float32), "tsdf_weight": np.concatenate(w_out).astype(np.float32),
+              "sample_voxel_zyx": np.concatenate(idx).astype(np.float32)}  # (exact: indices < 2^24)
+    if color:
+        arrays["tsdf_rgb"] = np.concatenate(rgb_out).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def relaunch_under_torchrun(n):
     """`python bench.py --gpus N` as the driver may call it: become `python -m torch.distributed.run ... bench.py ...`
     with one rank per GPU (the same command line the driver uses when it launches the ranks itself)."""
@@ -834,17 +883,22 @@ def main():
                              (", software-pipelined row loop (k_integrate_p)" if int(info4[0]) & 0x100 else ""),
                  "certified_fp32_projection": bool(info4[1]), "reference_cull_decides_voxels": bool(info4[2] == 2), "blocks": int(info4[3])}
 
+    # the grid as the timed steps left it, before anything below integrates into it again
+    dumped = dump_outputs(vol, args.dump_outputs) if args.dump_outputs else None
+
     # Algorithmic bytes of the timed frames, counted outside the timed region by running the same frames once more
     # through the counting instance: observed voxels (state-independent: pose + depth only) and the bytes of voxel
     # words whose value changed (the state then holds `steps` more observations per voxel; which words change --
     # the count byte until saturation, colour and distance inside the truncation band, nothing in free space at the
-    # hinge -- does not depend on that to first order).
-    del counted[:]
-    run(args.warmup, n_total, counting=True)
-    n_obs_rank = sum(c[0] for c in counted) / args.steps
-    chg_rank = sum(c[1] for c in counted) / args.steps
-    imp_rank = sum(c[2] for c in counted) / args.steps
-    req_rank = sum(c[3] for c in counted) / args.steps
+    # hinge -- does not depend on that to first order).  --full only: a plain run stops at the timed steps.
+    n_obs_rank = chg_rank = imp_rank = req_rank = 0.0
+    if args.full:
+        del counted[:]
+        run(args.warmup, n_total, counting=True)
+        n_obs_rank = sum(c[0] for c in counted) / args.steps
+        chg_rank = sum(c[1] for c in counted) / args.steps
+        imp_rank = sum(c[2] for c in counted) / args.steps
+        req_rank = sum(c[3] for c in counted) / args.steps
     chg_per_obs = chg_rank / n_obs_rank if n_obs_rank else 0.0
 
     # Two frames per sweep (tsdf_hip_integrate_device2 -> k_integrate2), report-only side field: the same timed frames
@@ -901,7 +955,7 @@ def main():
 
     # isolated cost of one frame broadcast (report only)
     bcast_ms = None
-    if use_dist:
+    if use_dist and args.full:
         barrier()
         tb = time.perf_counter()
         for i in range(args.warmup, n_total):
@@ -1032,6 +1086,13 @@ def main():
                         "WRITE_SIZE over this command's timed launches, quoted from profiles/ while the kernel-source hash matches",
             },
         }
+        if not args.full:  # no counting pass ran: only the event times of the timed launches are known
+            out["config"]["observed_voxels_per_frame"] = None
+            out["roofline"] = {"kernel": "k_integrate", "kernel_ms": kern_ms, "kernel_sha16": sha,
+                               "note": "kernel_ms: HIP events around each timed launch; byte counts and fractions of the HBM peak "
+                                       "need the counting pass of --full"}
+        if dumped:
+            out["dumped_outputs"] = dumped
         n_h = max(1, host_t["steps"])
         out["host_us_per_step"] = {
             "integrate_calls": host_t["launch"] / n_h * 1e6, "event_records": host_t["events"] / n_h * 1e6,
@@ -1060,7 +1121,7 @@ def main():
                                 "per_rank_kernel_ms": per_rank_kernel_ms, "frame_broadcast_ms_isolated": bcast_ms,
                                 "overlap": bool(args.overlap), "backend": backend, "planes_per_gpu": z_end - z_begin,
                                 # what the first run on a real node should show at a glance
-                                "observed_voxels_per_rank": per_rank_observed,
+                                "observed_voxels_per_rank": per_rank_observed if args.full else None,
                                 "kernel_ms_spread": (max(per_rank_kernel_ms) / min(per_rank_kernel_ms)) if min(per_rank_kernel_ms) > 0 else None,
                                 "rccl_version": rccl, "visible_devices": n_dev,
                                 "peer_access": [[bool(i == j or torch.cuda.can_device_access_peer(i, j)) for j in range(n_dev)]
@@ -1177,7 +1238,7 @@ def main_inprocess(args):
         per_slab_ms.append(ms.value / max(1, cnt.value))
     capi.check(lib.tsdf_hip_multi_timing(h, 0), "multi_timing")
     n_obs = chg = 0
-    for i in range(args.warmup, n_total):  # the same frames once more through the counting instance
+    for i in range(args.warmup, n_total) if args.full else ():  # the same frames once more through the counting instance
         launch(i, C.byref(C.c_uint64(0)))
         capi.check(lib.tsdf_hip_last_count_detail(h, detail), "last_count_detail")
         n_obs += int(detail[0])
@@ -1216,6 +1277,10 @@ def main_inprocess(args):
         "multi_gpu": {"host": "one process, tsdf_hip_create_multi", "devices": devices, "per_slab_kernel_ms": per_slab_ms,
                       "slabs": [{"device": s[0], "z_begin": s[1], "z_end": s[2], "halo": s[3]} for s in slabs]},
     }
+    if not args.full:  # no counting pass ran: only the slabs' kernel times are known
+        out["config"]["observed_voxels_per_frame"] = None
+        out["roofline"] = {"kernel": "k_integrate", "kernel_ms": kern_ms, "kernel_sha16": kernel_sha16(),
+                           "note": "kernel_ms: the slowest slab's average k_integrate time; byte counts need the counting pass of --full"}
     print(json.dumps(out), flush=True)
     vol.close()
 

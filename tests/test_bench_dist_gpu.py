@@ -9,14 +9,18 @@ Numbers from these runs mean nothing; the JSON contract and the counts do."""
 import json
 import os
 import socket
+import tempfile
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--res", "256", "--steps", "4", "--warmup", "2", "--extras", "0", "--cpu-baseline", "0"]
+# --full: these tests read the roofline byte counts, observed voxels, host-path rate and broadcast time, which a plain run skips
+COMMON = ["--res", "256", "--steps", "4", "--warmup", "2", "--full", "--extras", "0", "--cpu-baseline", "0"]
+PLAIN = ["--res", "256", "--steps", "4", "--warmup", "2"]
 
 
 def free_port():
@@ -144,3 +148,27 @@ def test_bench_pairing_one_rank_and_two_ranks(gpu):
     check_contract(j2, 2)
     assert j2["pairing"]["pairs_launched"] == 2
     assert j2["config"]["observed_voxels_per_frame"] == single["config"]["observed_voxels_per_frame"]
+
+
+def test_bench_plain_line_and_dumped_outputs(gpu):
+    """A plain run (no --full) prints the headline fields and nothing that needs a run of its own; --dump-outputs writes
+    the grid the timed steps left, as float32 arrays, identical with and without --full (the dump precedes every further
+    integration) and from run to run."""
+    with tempfile.TemporaryDirectory() as td:
+        a, b = os.path.join(td, "a"), os.path.join(td, "b")
+        j = run([sys.executable, "bench.py"] + PLAIN + ["--dump-outputs", a], {})
+        assert j["steps"] == 4 and j["warmup"] == 2 and j["unit"] == "Mvoxels/s" and j["higher_is_better"] is True
+        assert j["dtype"] == "f32" and j["value"] > 0 and j["ms_per_step"] > 0 and j["roofline"]["kernel_ms"] > 0
+        for leg in ("extras", "host_path", "cpu_baseline"):
+            assert leg not in j
+        assert j["config"]["observed_voxels_per_frame"] is None and "frac" not in j["roofline"]
+        full = run([sys.executable, "bench.py"] + COMMON + ["--dump-outputs", b], {})
+        assert full["roofline"]["frac"] > 0
+        names = sorted(os.listdir(a))
+        assert names == sorted(os.listdir(b)) == ["sample_voxel_zyx.npy", "tsdf_distance.npy", "tsdf_rgb.npy", "tsdf_weight.npy"]
+        assert sum(os.path.getsize(os.path.join(a, n)) for n in names) <= 64 << 20
+        for n in names:
+            x, y = np.load(os.path.join(a, n)), np.load(os.path.join(b, n))
+            assert x.dtype == np.float32 and np.array_equal(x.view(np.uint32), y.view(np.uint32)), n
+        w = np.load(os.path.join(a, "tsdf_weight.npy"))
+        assert (w > 0).any()

@@ -1,12 +1,9 @@
 """The three committed copies of the marching-cubes case tables -- product (cpu_tsdf_amd/csrc/mc_tables.h), oracle
 (oracle/mc_tables.h) and the PCL stand-in the compiled reference links (compat/mini_pcl_mc_tables.inc) -- are re-derived here
 instead of trusted (VERDICT r05 "what's weak" #1 / next #8): parsed from the committed text, compared with each other, checked
-structurally against the cube geometry pcl::MarchingCubes::createSurface uses, and, where scikit-image's
-LUT file exists on the machine (it does in this image, under another interpreter's site-packages), compared entry by entry
-with its CASESCLASSIC = Lorensen / Bourke's table -- the independent public copy tools/gen_mc_tables.py generated them from."""
-import base64
-import glob
-import importlib.util
+structurally against the cube geometry pcl::MarchingCubes::createSurface uses, and compared entry by entry
+with scikit-image's CASESCLASSIC = Lorensen / Bourke's table -- the independent public copy tools/gen_mc_tables.py generated
+them from, stored as tests/golden/mc_cases_classic.npy (tests/golden/make_golden_mc_cases.py)."""
 import os
 import re
 
@@ -15,10 +12,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EDGE_CORNERS = [(0, 1), (1, 2), (2, 3), (3, 0), (4, 5), (5, 6), (6, 7), (7, 4), (0, 4), (1, 5), (2, 6), (3, 7)]
-LUT_GLOBS = ["/opt/conda/lib/python3*/site-packages/skimage/measure/_marching_cubes_lewiner_luts.py",
-             "/usr/lib/python3*/site-packages/skimage/measure/_marching_cubes_lewiner_luts.py",
-             "/usr/lib/python3/dist-packages/skimage/measure/_marching_cubes_lewiner_luts.py",
-             "/usr/local/lib/python3*/*-packages/skimage/measure/_marching_cubes_lewiner_luts.py"]
 
 
 def _array(text, name):
@@ -83,22 +76,8 @@ def test_tables_follow_from_the_cube_geometry(copy):
     assert et[1] == 0x109 and et[2] == 0x203 and et[3] == 0x30a and et[128] == 0x8c0 and et[254] == 0x109
 
 
-def _skimage_lut():
-    for g in LUT_GLOBS:
-        for p in sorted(glob.glob(g)):
-            return p
-    return None
-
-
 def test_tables_equal_scikit_images_classic_cases():
-    lut = _skimage_lut()
-    if lut is None:
-        pytest.skip("no scikit-image LUT file on this machine (the tables' independent public copy)")
-    sp = importlib.util.spec_from_file_location("_mc_luts", lut)
-    m = importlib.util.module_from_spec(sp)
-    sp.loader.exec_module(m)
-    shape, txt = m.CASESCLASSIC
-    want = np.frombuffer(base64.decodebytes(txt.encode()), dtype=np.int8).reshape(shape).astype(np.int64)
+    want = np.load(os.path.join(ROOT, "tests", "golden", "mc_cases_classic.npy")).astype(np.int64)
     assert want.shape == (256, 16)
     for c in COPIES:
         _, tri, _ = _tables(*c)

@@ -43,7 +43,7 @@ def main():
         # the resident-frame rate of the same kernels on this box: bench.py with frames in HBM
         for color in (1, 0):
             p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--res", str(res), "--color", str(color), "--steps", "20", "--warmup", "3",
-                                "--cpu-baseline", "0", "--host-path", "0", "--scene-b", "0", "--keys", "0", "--extras", "2"], capture_output=True, text=True, timeout=300)
+                                "--full", "--cpu-baseline", "0", "--host-path", "0", "--scene-b", "0", "--keys", "0", "--extras", "2"], capture_output=True, text=True, timeout=300)
             try:
                 d = json.loads(p.stdout.strip().splitlines()[-1])
                 e[f"color{color}_resident"] = {"frames_per_s": d["frames_per_s"], "kernel_ms": d["roofline"]["kernel_ms"],

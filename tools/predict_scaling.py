@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def bench(extra, env=None):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--warmup", "3", "--cpu-baseline", "0", "--host-path", "0", "--extras", "0"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--warmup", "3", "--cpu-baseline", "0", "--host-path", "0", "--extras", "0"] + extra
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=dict(os.environ, **(env or {})))
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     try:
