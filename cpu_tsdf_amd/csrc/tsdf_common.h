@@ -307,6 +307,7 @@ struct TsdfTuning {
   int fuse2;           // tsdf_hip_integrate_device2 / frame pairing: 1 = one sweep per pair where that is the faster way (with colour; without, where k_integrate_p does not apply), 2 = wherever both poses qualify, 0 = never
   int implied_d;       // PACKED integrate launches do not read distance words the "band seen" flags and the counts determine (1)
   int pipe;            // ALLIN PACKED launches run the software-pipelined row loop: bit 0 without colour (k_integrate_p: on), bit 1 with (k_integrate_pc: measured no faster than k_integrate's own loop, off); 1
+  int lab_chunk;       // LAB volumes: voxels per host round trip of the exact LAB2RGB colours (tsdf_lab_exact_colors; tests lower it)
 };
 const TsdfTuning &tsdf_tuning();
 // Edge of the voxel blocks save / load stream through host memory: TSDF_HIP_VOL_CHUNK, read at EVERY call (an I/O path: a

@@ -58,7 +58,7 @@ static TsdfTuning &tuning_storage() {
                          env_int("TSDF_HIP_CULL", 1), std::max(1, env_int("TSDF_HIP_VOL_CHUNK", 256)),
                          env_int("TSDF_HIP_PLAIN_KERNEL", 0), env_int("TSDF_HIP_ALLOC_TRIES", 3), env_int("TSDF_HIP_ALLIN", 1),
                          env_int("TSDF_HIP_REFCULL_PLAIN", 0), env_int("TSDF_HIP_LIVE_LOG2TX", 5), env_int("TSDF_HIP_ZFAST", 1), env_int("TSDF_HIP_FUSE2", 1), env_int("TSDF_HIP_IMPLIED_D", 1),
-                         env_int("TSDF_HIP_PIPE", 1)};
+                         env_int("TSDF_HIP_PIPE", 1), std::max(1, env_int("TSDF_HIP_LAB_CHUNK", 16 << 20))};
   return t;
 }
 
@@ -108,6 +108,8 @@ extern "C" int tsdf_hip_set_tuning(const char *name, int value) {
     t.live_log2tx = value;
   else if (n == "zfast")
     t.zfast = value;
+  else if (n == "lab_chunk")
+    t.lab_chunk = std::max(1, value);
   else
     return TSDF_HIP_E_INVALID;
   return TSDF_HIP_OK;
@@ -274,7 +276,7 @@ k_rgb_scatter(const int64_t *__restrict__ idx, size_t n, const uint32_t *__restr
 int tsdf_lab_exact_colors(tsdf_hip_volume *v, const int64_t *d_idx, size_t n, uint32_t *host_rgb, bool write_plane) {
   if (!n) return TSDF_HIP_OK;
   if (!v->lab_img || !v->cn[0] || !v->cn[1] || !v->cn[2]) return TSDF_HIP_E_INVALID;
-  const size_t chunk = (size_t)16 << 20;  // voxels per round trip (192 MB of floats)
+  const size_t chunk = (size_t)tsdf_tuning().lab_chunk;  // voxels per round trip (16 M by default: 192 MB of floats)
   float *d_lab = nullptr;
   uint32_t *d_words = nullptr;
   const size_t m = std::min(n, chunk);

@@ -77,7 +77,7 @@ int tsdf_hip_selftest_read_sweep(tsdf_handle h, int stride_bytes, uint64_t *span
 int tsdf_hip_selftest_occupancy_mc(int out[2]);
 
 /* Test / A-B hook: set a launch-shape knob ("rows_per_block", "blocks_per_cu", "fast_projection",
- * "mc_flush_at", "mc_skip", "cull", "vol_chunk", "plain_kernel", "alloc_tries", "allin", "refcull_plain", "live_log2tx", "fuse2" -- the
+ * "mc_flush_at", "mc_skip", "cull", "vol_chunk", "plain_kernel", "alloc_tries", "allin", "refcull_plain", "live_log2tx", "fuse2", "lab_chunk" -- the
  * TSDF_HIP_* environment variables, which the product library reads once) at run time.  No knob changes results. */
 int tsdf_hip_set_tuning(const char *name, int value);
 

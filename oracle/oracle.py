@@ -59,6 +59,9 @@ def lib():
         L.oracle_integrate_weighted.argtypes = [C.POINTER(OracleParams), _f, _f, _u8, _f, _u8, _f, C.c_int, C.c_int, C.c_int]
         L.oracle_integrate_lab.restype = C.c_uint64
         L.oracle_integrate_lab.argtypes = [C.POINTER(OracleParams), _f, _f, _f, _u8, _f, _u8, _f, C.c_int, C.c_int]
+        L.oracle_integrate_mode.restype = C.c_uint64
+        L.oracle_integrate_mode.argtypes = [C.POINTER(OracleParams), C.c_int, _f, _f, _u8, _f, _f, _f, _f, _f, C.POINTER(C.c_int32),
+                                            _f, _u8, _f, C.c_int, C.c_int, C.c_int, _f]
         L.oracle_rgb2lab_many.restype = None
         L.oracle_rgb2lab_many.argtypes = [_u8, C.c_size_t, _f]
         L.oracle_lab2rgb_many.restype = None
@@ -98,6 +101,15 @@ def _fp(a):
 
 def _bp(a):
     return a.ctypes.data_as(_u8) if a is not None else None
+
+
+def _planes(planes):
+    """None, or the 24 floats of the reference's cull (reference_cull_planes) as a contiguous float32 array."""
+    if planes is None:
+        return None
+    planes = np.ascontiguousarray(planes, np.float32)
+    assert planes.size == 24
+    return planes
 
 
 def params_from(p):
@@ -140,13 +152,27 @@ class OracleVolume:
         lib().oracle_centers(self.p.res[axis], self.node_size(axis), _fp(out))
         return out
 
-    def integrate(self, depth, bgra, cam_from_vol, z_begin=0, z_end=0, weight_by_depth=False):
-        """weight_by_depth: hpp:200-202 (a flag only a loaded .vol can carry)."""
+    def integrate(self, depth, bgra, cam_from_vol, z_begin=0, z_end=0, weight_by_depth=False, planes=None):
+        """weight_by_depth: hpp:200-202 (a flag only a loaded .vol can carry).  planes: None, or the reference's frustum
+        cull (reference_cull_planes of the forward pose), applied as integrate_culled applies it -- likewise in
+        integrate_variance, integrate_rgbn and integrate_lab."""
         depth = np.ascontiguousarray(depth, dtype=np.float32)
         T = np.ascontiguousarray(cam_from_vol, dtype=np.float32).reshape(12)
         col = np.ascontiguousarray(bgra, dtype=np.uint8) if bgra is not None else None
+        if planes is not None:
+            return self._culled(0, depth, col, T, z_begin, z_end, weight_by_depth, planes)
         return int(lib().oracle_integrate_weighted(C.byref(self.p), _fp(self.d), _fp(self.w), _bp(self.rgb), _fp(depth),
                                                    _bp(col), _fp(T), z_begin, z_end, int(bool(weight_by_depth))))
+
+    def _culled(self, mode, depth, col, T, z_begin, z_end, weight_by_depth, planes):
+        """The planes= forms: oracle_integrate_mode (mode 0 RGB / weightings, 1 RGBNormalized, 2 LAB) on this volume."""
+        cn = [_fp(c) for c in self.cn] + [None] * (4 - len(self.cn)) if mode else [None] * 4
+        var = mode == 0 and getattr(self, "M", None) is not None
+        return int(lib().oracle_integrate_mode(C.byref(self.p), mode, _fp(self.d), _fp(self.w), _bp(self.rgb), *cn,
+                                               _fp(self.M) if var else None,
+                                               self.nsample.ctypes.data_as(C.POINTER(C.c_int32)) if var else None,
+                                               _fp(depth), _bp(col), _fp(np.ascontiguousarray(T, np.float32).reshape(12)),
+                                               z_begin, z_end, int(bool(weight_by_depth)), _fp(_planes(planes))))
 
     def reference_cull_planes(self, trans):
         """The six planes (l, r, t, b, far, near) of the reference's frustum cull for the forward pose `trans`."""
@@ -164,7 +190,7 @@ class OracleVolume:
                                                  _fp(depth), _bp(col) if col is not None else None,
                                                  _fp(np.ascontiguousarray(cam_from_vol, np.float32)), z_begin, z_end, _fp(planes)))
 
-    def integrate_variance(self, depth, bgra, cam_from_vol, weight_by_depth=False, z_begin=0, z_end=0):
+    def integrate_variance(self, depth, bgra, cam_from_vol, weight_by_depth=False, z_begin=0, z_end=0, planes=None):
         """integrateCloud with weight_by_variance_ (hpp:203-204); self.M / self.nsample = OctreeNode::M_ / nsample_
         (created at zero on first use, or set by the caller from a loaded .vol)."""
         if getattr(self, "M", None) is None:
@@ -172,13 +198,15 @@ class OracleVolume:
             self.nsample = np.zeros(self.d.shape, np.int32)
         depth = np.ascontiguousarray(depth, np.float32)
         col = np.ascontiguousarray(bgra, np.uint8) if bgra is not None else None
+        if planes is not None:
+            return self._culled(0, depth, col, cam_from_vol, z_begin, z_end, weight_by_depth, planes)
         return int(lib().oracle_integrate_variance(C.byref(self.p), _fp(self.d), _fp(self.w), _bp(self.rgb) if self.rgb is not None else None,
                                                    _fp(self.M), self.nsample.ctypes.data_as(C.POINTER(C.c_int32)), _fp(depth),
                                                    _bp(col) if col is not None else None,
                                                    _fp(np.ascontiguousarray(cam_from_vol, np.float32)), z_begin, z_end,
                                                    int(weight_by_depth)))
 
-    def integrate_rgbn(self, depth, bgra, cam_from_vol, z_begin=0, z_end=0):
+    def integrate_rgbn(self, depth, bgra, cam_from_vol, z_begin=0, z_end=0, planes=None):
         """integrate with RGBNormalized voxels (setColorMode("RGBNormalized")); self.cn holds r_n, g_n, b_n, i and
         self.rgb what getRGB() returns."""
         if not hasattr(self, "cn"):
@@ -186,10 +214,12 @@ class OracleVolume:
         depth = np.ascontiguousarray(depth, dtype=np.float32)
         T = np.ascontiguousarray(cam_from_vol, dtype=np.float32).reshape(12)
         col = np.ascontiguousarray(bgra, dtype=np.uint8)
+        if planes is not None:
+            return self._culled(1, depth, col, T, z_begin, z_end, False, planes)
         return int(lib().oracle_integrate_rgbn(C.byref(self.p), _fp(self.d), _fp(self.w), _fp(self.cn), _bp(self.rgb),
                                                _fp(depth), _bp(col), _fp(T), z_begin, z_end))
 
-    def integrate_lab(self, depth, bgra, cam_from_vol, z_begin=0, z_end=0):
+    def integrate_lab(self, depth, bgra, cam_from_vol, z_begin=0, z_end=0, planes=None):
         """integrate with LABNode voxels (setColorMode("LAB")); self.cn holds the L, A, B means and self.rgb what
         getRGB() returns (LAB2RGB of the means)."""
         if not hasattr(self, "cn"):
@@ -197,6 +227,8 @@ class OracleVolume:
         depth = np.ascontiguousarray(depth, dtype=np.float32)
         T = np.ascontiguousarray(cam_from_vol, dtype=np.float32).reshape(12)
         col = np.ascontiguousarray(bgra, dtype=np.uint8)
+        if planes is not None:
+            return self._culled(2, depth, col, T, z_begin, z_end, False, planes)
         return int(lib().oracle_integrate_lab(C.byref(self.p), _fp(self.d), _fp(self.w), _fp(self.cn), _bp(self.rgb),
                                               _fp(depth), _bp(col), _fp(T), z_begin, z_end))
 
@@ -312,7 +344,9 @@ def cells_in_box(cells, clo, chi):
 
 
 class SlabOracle:
-    """Dense oracle restricted to planes [zb, ze): arrays hold only the slab."""
+    """Dense oracle restricted to planes [zb, ze): arrays hold only the slab.  The same integrate forms as OracleVolume
+    (weight_by_depth, the variance weighting with M / nsample, RGBNormalized and LAB with their colour state cn, the
+    reference's cull through planes=), so that a few plane groups of a grid too large for the host can be checked."""
 
     def __init__(self, p, zb, ze):
         self.p = params_from(p)
@@ -323,20 +357,50 @@ class SlabOracle:
         self.w = np.zeros((n, ny, nx), np.float32)
         self.rgb = np.zeros((n, ny, nx, 3), np.uint8) if p.integrate_color else None
 
-    def integrate(self, depth, bgra, T):
-        nx, ny, _ = self.p.res
-        off = self.zb * ny * nx
-        # the oracle indexes [z][y][x] from plane 0: hand it pointers shifted back by zb planes
-        fp = C.POINTER(C.c_float)
-        d = C.cast(self.d.ctypes.data - 4 * off, fp)
-        w = C.cast(self.w.ctypes.data - 4 * off, fp)
-        rgb = C.cast(self.rgb.ctypes.data - 3 * off, C.POINTER(C.c_uint8)) if self.rgb is not None else None
+    def _at0(self, a, ctype=C.c_float):
+        """`a` (slab planes, [z][y][x]...) as a pointer shifted back by zb planes: the oracle indexes from plane 0."""
+        if a is None:
+            return None
+        plane = a.strides[0]
+        return C.cast(a.ctypes.data - plane * self.zb, C.POINTER(ctype))
+
+    def _frame(self, depth, bgra, T):
         depth = np.ascontiguousarray(depth, np.float32)
         col = np.ascontiguousarray(bgra, np.uint8) if bgra is not None else None
-        T = np.ascontiguousarray(T, np.float32)
-        return lib().oracle_integrate(C.byref(self.p), d, w, rgb, depth.ctypes.data_as(fp),
-                                        col.ctypes.data_as(C.POINTER(C.c_uint8)) if col is not None else None,
-                                        T.ctypes.data_as(fp), self.zb, self.ze)
+        return depth, col, np.ascontiguousarray(T, np.float32).reshape(12)
+
+    def _run(self, mode, depth, bgra, T, weight_by_depth=False, planes=None):
+        depth, col, T = self._frame(depth, bgra, T)
+        cn = [self._at0(c) for c in self.cn] + [None] * (4 - len(self.cn)) if mode else [None] * 4
+        var = mode == 0 and getattr(self, "M", None) is not None
+        return int(lib().oracle_integrate_mode(C.byref(self.p), mode, self._at0(self.d), self._at0(self.w), self._at0(self.rgb, C.c_uint8),
+                                               *cn, self._at0(self.M) if var else None,
+                                               self._at0(self.nsample, C.c_int32) if var else None, _fp(depth), _bp(col), _fp(T),
+                                               self.zb, self.ze, int(bool(weight_by_depth)), _fp(_planes(planes))))
+
+    def integrate(self, depth, bgra, T, weight_by_depth=False, planes=None):
+        return self._run(0, depth, bgra, T, weight_by_depth, planes)
+
+    def integrate_variance(self, depth, bgra, T, weight_by_depth=False, planes=None):
+        """self.M / self.nsample: OctreeNode::M_ / nsample_ of the slab's voxels (zero on first use)."""
+        if getattr(self, "M", None) is None:
+            self.M = np.zeros_like(self.d)
+            self.nsample = np.zeros(self.d.shape, np.int32)
+        return self._run(0, depth, bgra, T, weight_by_depth, planes)
+
+    def integrate_rgbn(self, depth, bgra, T, planes=None):
+        """self.cn: (4, slab planes, ny, nx) = r_n, g_n, b_n, i."""
+        if not hasattr(self, "cn"):
+            self.cn = [np.zeros_like(self.d) for _ in range(4)]
+        return self._run(1, depth, bgra, T, planes=planes)
+
+    def integrate_lab(self, depth, bgra, T, planes=None):
+        """self.cn: (3, slab planes, ny, nx) = the L, A, B means."""
+        if not hasattr(self, "cn"):
+            self.cn = [np.zeros_like(self.d) for _ in range(3)]
+        return self._run(2, depth, bgra, T, planes=planes)
+
+    reference_cull_planes = OracleVolume.reference_cull_planes
 
 
 def expf(x):

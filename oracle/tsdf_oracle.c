@@ -336,13 +336,13 @@ uint64_t oracle_integrate_variance(const oracle_params *p, float *d, float *w, u
 }
 
 /* The same with RGBNormalized voxels (setColorMode("RGBNormalized")): RGBNormalized::addObservation,
- * octree.cpp:380-393, and getRGB, octree.cpp:396-402.  cn = four planes (r_n, g_n, b_n, i), each nz*ny*nx
- * floats starting at 0 (octree.h:217-222); rgb receives what getRGB() returns for every voxel touched. */
-uint64_t oracle_integrate_rgbn(const oracle_params *p, float *d, float *w, float *cn, uint8_t *rgb,
-                               const float *depth, const uint8_t *bgra, const float T[12], int z_begin, int z_end) {
+ * octree.cpp:380-393, and getRGB, octree.cpp:396-402.  cn = the four planes (r_n, g_n, b_n, i), each indexed like d
+ * (octree.h:217-222); rgb receives what getRGB() returns for every voxel touched. */
+static uint64_t integrate_rgbn_impl(const oracle_params *p, float *d, float *w, float *const cn[4], uint8_t *rgb,
+                                    const float *depth, const uint8_t *bgra, const float T[12], int z_begin, int z_end,
+                                    const float *cull_planes) {
   const int nx = p->res[0], ny = p->res[1], nz = p->res[2];
-  const size_t n = (size_t)nx * ny * nz;
-  float *r_n = cn, *g_n = cn + n, *b_n = cn + 2 * n, *i_m = cn + 3 * n;
+  float *r_n = cn[0], *g_n = cn[1], *b_n = cn[2], *i_m = cn[3];
   float *cx = (float *)malloc(sizeof(float) * nx), *cy = (float *)malloc(sizeof(float) * ny),
         *cz = (float *)malloc(sizeof(float) * nz);
   oracle_centers(nx, node_size(p, 0), cx);
@@ -356,6 +356,7 @@ uint64_t oracle_integrate_rgbn(const oracle_params *p, float *d, float *w, float
       for (int i = 0; i < nx; ++i) {
         float dn;
         size_t pixel;
+        if (cull_planes && !cull_keeps(cull_planes, cx[i], cy[j], cz[k])) continue; /* hpp:93-94 */
         if (!observe(p, T, cx[i], cy[j], cz[k], depth, &dn, &pixel)) continue;
         const float w_new = 1;
         const size_t vi = ((size_t)k * ny + j) * nx + i;
@@ -381,6 +382,14 @@ uint64_t oracle_integrate_rgbn(const oracle_params *p, float *d, float *w, float
   free(cy);
   free(cz);
   return n_obs;
+}
+
+/* cn = four planes of nz*ny*nx floats starting at 0 */
+uint64_t oracle_integrate_rgbn(const oracle_params *p, float *d, float *w, float *cn, uint8_t *rgb,
+                               const float *depth, const uint8_t *bgra, const float T[12], int z_begin, int z_end) {
+  const size_t n = (size_t)p->res[0] * p->res[1] * p->res[2];
+  float *const c[4] = {cn, cn + n, cn + 2 * n, cn + 3 * n};
+  return integrate_rgbn_impl(p, d, w, c, rgb, depth, bgra, T, z_begin, z_end, NULL);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -443,13 +452,13 @@ void oracle_lab2rgb_many(const float *lab, size_t n, uint8_t *rgb) {
   for (size_t i = 0; i < n; ++i) oracle_lab2rgb(lab[3 * i], lab[3 * i + 1], lab[3 * i + 2], rgb + 3 * i, rgb + 3 * i + 1, rgb + 3 * i + 2);
 }
 
-/* integrate with LABNode voxels.  cn = three planes (L, A, B) starting at 0 (octree.h:267-270); rgb receives what
- * getRGB() returns (LAB2RGB of the means, octree.cpp:547-551) for every voxel touched. */
-uint64_t oracle_integrate_lab(const oracle_params *p, float *d, float *w, float *cn, uint8_t *rgb,
-                              const float *depth, const uint8_t *bgra, const float T[12], int z_begin, int z_end) {
+/* integrate with LABNode voxels.  cn = the three planes (L, A, B), each indexed like d (octree.h:267-270); rgb receives
+ * what getRGB() returns (LAB2RGB of the means, octree.cpp:547-551) for every voxel touched. */
+static uint64_t integrate_lab_impl(const oracle_params *p, float *d, float *w, float *const cn[3], uint8_t *rgb,
+                                   const float *depth, const uint8_t *bgra, const float T[12], int z_begin, int z_end,
+                                   const float *cull_planes) {
   const int nx = p->res[0], ny = p->res[1], nz = p->res[2];
-  const size_t n = (size_t)nx * ny * nz;
-  float *Lm = cn, *Am = cn + n, *Bm = cn + 2 * n;
+  float *Lm = cn[0], *Am = cn[1], *Bm = cn[2];
   float *cx = (float *)malloc(sizeof(float) * nx), *cy = (float *)malloc(sizeof(float) * ny),
         *cz = (float *)malloc(sizeof(float) * nz);
   oracle_centers(nx, node_size(p, 0), cx);
@@ -463,6 +472,7 @@ uint64_t oracle_integrate_lab(const oracle_params *p, float *d, float *w, float 
       for (int i = 0; i < nx; ++i) {
         float dn;
         size_t pixel;
+        if (cull_planes && !cull_keeps(cull_planes, cx[i], cy[j], cz[k])) continue; /* hpp:93-94 */
         if (!observe(p, T, cx[i], cy[j], cz[k], depth, &dn, &pixel)) continue;
         const float w_new = 1;
         const size_t vi = ((size_t)k * ny + j) * nx + i;
@@ -483,6 +493,27 @@ uint64_t oracle_integrate_lab(const oracle_params *p, float *d, float *w, float 
   free(cy);
   free(cz);
   return n_obs;
+}
+
+/* cn = three planes of nz*ny*nx floats starting at 0 */
+uint64_t oracle_integrate_lab(const oracle_params *p, float *d, float *w, float *cn, uint8_t *rgb,
+                              const float *depth, const uint8_t *bgra, const float T[12], int z_begin, int z_end) {
+  const size_t n = (size_t)p->res[0] * p->res[1] * p->res[2];
+  float *const c[3] = {cn, cn + n, cn + 2 * n};
+  return integrate_lab_impl(p, d, w, c, rgb, depth, bgra, T, z_begin, z_end, NULL);
+}
+
+/* Every integrate form on caller-placed planes, with or without the reference's cull: OracleVolume's planes= and SlabOracle
+ * (arrays that hold only some planes of a grid, handed in as pointers shifted back to plane 0).  The four entry points
+ * above keep their signatures: callers built against them stay valid.  mode 0: RGBNode / no colour with weight_by_depth, and weight_by_variance when M and
+ * nsample are given; 1: RGBNormalized (cn0..cn3); 2: LAB (cn0..cn2).  planes: NULL or the reference's cull. */
+uint64_t oracle_integrate_mode(const oracle_params *p, int mode, float *d, float *w, uint8_t *rgb, float *cn0, float *cn1,
+                               float *cn2, float *cn3, float *M, int32_t *nsample, const float *depth, const uint8_t *bgra,
+                               const float T[12], int z_begin, int z_end, int weight_by_depth, const float *planes) {
+  float *const c[4] = {cn0, cn1, cn2, cn3};
+  if (mode == 1) return integrate_rgbn_impl(p, d, w, c, rgb, depth, bgra, T, z_begin, z_end, planes);
+  if (mode == 2) return integrate_lab_impl(p, d, w, c, rgb, depth, bgra, T, z_begin, z_end, planes);
+  return integrate_impl(p, d, w, rgb, depth, bgra, T, z_begin, z_end, weight_by_depth, planes, M, nsample);
 }
 
 /* ------------------------------------------------------------------------------------------
