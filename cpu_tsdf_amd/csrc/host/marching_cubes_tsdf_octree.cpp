@@ -7,6 +7,8 @@
 #include <pcl/console/print.h>
 #include <pcl/conversions.h>
 
+#include <map>
+#include <mutex>
 #include <vector>
 
 namespace cpu_tsdf {
@@ -39,7 +41,36 @@ void MarchingCubesTSDFOctree::setInputTSDF(TSDFVolumeOctree::ConstPtr tsdf_volum
   size_voxel_ = (upper_boundary_ - lower_boundary_) * Eigen::Array3f(res_x_, res_y_, res_z_).inverse();
 }
 
-static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mode, std::vector<float> &verts,
+// setCleanup's arguments per object (the header says why they are not members).  cleanup_of: false = no cleanup asked for.
+struct CleanupArgs {
+  float face_dist;
+  int min_neighbors;
+};
+static std::mutex g_cleanup_mutex;
+static std::map<const MarchingCubesTSDFOctree *, CleanupArgs> g_cleanup;
+
+void MarchingCubesTSDFOctree::setCleanup(float face_dist, int min_neighbors) {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  g_cleanup[this] = CleanupArgs{face_dist, min_neighbors};
+}
+
+void MarchingCubesTSDFOctree::clearCleanup() {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  g_cleanup.erase(this);
+}
+
+MarchingCubesTSDFOctree::~MarchingCubesTSDFOctree() { clearCleanup(); }
+
+static bool cleanup_of(const MarchingCubesTSDFOctree *mc, CleanupArgs &out) {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  const auto it = g_cleanup.find(mc);
+  if (it == g_cleanup.end()) return false;
+  out = it->second;
+  return true;
+}
+
+// cleanup: NULL, or the arguments of setCleanup -- tsdf_hip_march_cleanup between the march and the fetch
+static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mode, const CleanupArgs *cleanup, std::vector<float> &verts,
                       std::vector<unsigned char> &rgb) {
   verts.clear();
   rgb.clear();
@@ -50,6 +81,7 @@ static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mo
   if (!vol->cubicForQueries("MarchingCubesTSDFOctree::reconstruct")) return false;
   uint64_t n_tri = 0;
   int rc = tsdf_hip_march(vol->handle(), w_min, mode, &n_tri);
+  if (rc == 0 && cleanup) rc = tsdf_hip_march_cleanup(vol->handle(), cleanup->face_dist, cleanup->min_neighbors, &n_tri);
   if (rc == 0 && n_tri) {
     verts.resize((size_t)n_tri * 9);
     if (mode) rgb.resize((size_t)n_tri * 9);
@@ -81,7 +113,8 @@ void MarchingCubesTSDFOctree::performReconstruction(pcl::PolygonMesh &output) {
   const int mode = color_by_confidence_ ? 2 : (color_by_rgb_ ? 1 : 0);
   std::vector<float> verts;
   std::vector<unsigned char> rgb;
-  run_march(tsdf_volume_, w_min_, mode, verts, rgb);
+  CleanupArgs cleanup;
+  run_march(tsdf_volume_, w_min_, mode, cleanup_of(this, cleanup) ? &cleanup : nullptr, verts, rgb);
   const size_t n = verts.size() / 3;
   const Eigen::Affine3d g = tsdf_volume_ ? tsdf_volume_->getGlobalTransform() : Eigen::Affine3d::Identity();
   if (mode) {
@@ -121,7 +154,8 @@ void MarchingCubesTSDFOctree::performReconstruction(pcl::PointCloud<pcl::PointXY
                                                     std::vector<pcl::Vertices> &polygons) {
   std::vector<float> verts;
   std::vector<unsigned char> rgb;
-  run_march(tsdf_volume_, w_min_, 0, verts, rgb);
+  CleanupArgs cleanup;
+  run_march(tsdf_volume_, w_min_, 0, cleanup_of(this, cleanup) ? &cleanup : nullptr, verts, rgb);
   const size_t n = verts.size() / 3;
   points.points.resize(n);
   points.width = (uint32_t)n;

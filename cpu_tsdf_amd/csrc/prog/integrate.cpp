@@ -307,7 +307,12 @@ int main(int argc, char **argv) {
   pcl::PolygonMesh mesh;
   mc.reconstruct(mesh);
   if (s.flatten) cpu_tsdf::mesh_post::flattenVertices(mesh);
-  if (s.cleanup) cpu_tsdf::mesh_post::cleanupMesh(mesh);
+  if (s.cleanup) {  // on the GPU (tsdf_hip_mesh_cleanup); TSDF_HIP_HOST_MESH_POST=1 keeps the host pass
+    if (const int rc = cpu_tsdf::mesh_post::cleanupMeshAuto(mesh)) {
+      PCL_ERROR("--cleanup: %s: %s\n", tsdf_hip_error_string(rc), tsdf_hip_last_error());
+      return 1;
+    }
+  }
   PCL_INFO("Entire pipeline took %f ms\n", clock.toc());
   if (s.save_ascii)
     pcl::io::savePLYFile(s.out_dir + "/mesh.ply", mesh);

@@ -9,15 +9,19 @@
 //     reference converts the cloud to PointXYZ).
 //   cleanupMesh (:160-237): faces whose centroids form a connected group (links: centroid distance strictly
 //     below face_dist) of at most min_neighbors faces are removed; vertices no face uses are removed; vertex
-//     and face order are kept.  Colours are lost likewise.
+//     and face order are kept.  Colours are lost likewise.  cleanupMeshGpu gets the same face set from the GPU
+//     (tsdf_hip_mesh_cleanup); the host pass stays: it defines the result.
 #pragma once
 
 #include <pcl/PolygonMesh.h>
 #include <pcl/conversions.h>
 #include <pcl/point_types.h>
 
+#include <tsdf_hip.h>
+
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <unordered_map>
 #include <vector>
 
@@ -113,6 +117,31 @@ inline void flattenVertices(pcl::PolygonMesh &mesh, float min_dist = 0.0001f) {
   storeVertices(xyz, seeds, mesh);
 }
 
+// The tail of cleanupMesh (:208-237): the polygons with drop[f] set go, then the vertices no face uses; vertex and face
+// order are kept, faces are re-indexed.
+inline void dropFaces(pcl::PolygonMesh &mesh, const std::vector<float> &xyz, const std::vector<char> &drop) {
+  size_t kept = 0;
+  for (size_t f = 0; f < mesh.polygons.size(); ++f) {
+    if (drop[f]) continue;
+    if (kept != f) mesh.polygons[kept] = mesh.polygons[f];
+    ++kept;
+  }
+  mesh.polygons.resize(kept);
+  const size_t n = xyz.size() / 3;
+  std::vector<int> new_index(n, -1), keep;
+  std::vector<char> used(n, 0);
+  for (const auto &p : mesh.polygons)
+    for (int k = 0; k < 3; ++k) used[p.vertices[k]] = 1;
+  for (size_t i = 0; i < n; ++i)
+    if (used[i]) {
+      new_index[i] = (int)keep.size();
+      keep.push_back((int)i);
+    }
+  for (auto &p : mesh.polygons)
+    for (int k = 0; k < 3; ++k) p.vertices[k] = (std::uint32_t)new_index[p.vertices[k]];
+  storeVertices(xyz, keep, mesh);
+}
+
 inline void cleanupMesh(pcl::PolygonMesh &mesh, float face_dist = 0.02f, int min_neighbors = 5) {
   const std::vector<float> xyz = vertexPositions(mesh);
   // centroids of the triangles (:78-92: (v0 + v1 + v2) / 3 in float)
@@ -143,26 +172,49 @@ inline void cleanupMesh(pcl::PolygonMesh &mesh, float face_dist = 0.02f, int min
     if ((int)group.size() <= min_neighbors)
       for (int g : group) drop[tri[g]] = 1;
   }
-  size_t kept = 0;
+  dropFaces(mesh, xyz, drop);
+}
+
+// The same result with the groups found on the GPU (tsdf_hip_mesh_cleanup, which reproduces the pass above face for face):
+// the triangles' keep mask comes from the library, the tail is the host's.  0, or the library's error code (its text in
+// tsdf_hip_last_error) with the mesh untouched.
+inline int cleanupMeshGpu(pcl::PolygonMesh &mesh, float face_dist = 0.02f, int min_neighbors = 5, int device = 0) {
+  const std::vector<float> xyz = vertexPositions(mesh);
+  std::vector<std::uint32_t> faces;
+  std::vector<size_t> tri;  // polygon index of each face handed over (as above: only triangles take part)
   for (size_t f = 0; f < mesh.polygons.size(); ++f) {
-    if (drop[f]) continue;
-    if (kept != f) mesh.polygons[kept] = mesh.polygons[f];
-    ++kept;
+    const auto &v = mesh.polygons[f].vertices;
+    if (v.size() != 3) continue;
+    for (int k = 0; k < 3; ++k) faces.push_back(v[k]);
+    tri.push_back(f);
   }
-  mesh.polygons.resize(kept);
-  const size_t n = xyz.size() / 3;
-  std::vector<int> new_index(n, -1), keep;
-  std::vector<char> used(n, 0);
-  for (const auto &p : mesh.polygons)
-    for (int k = 0; k < 3; ++k) used[p.vertices[k]] = 1;
-  for (size_t i = 0; i < n; ++i)
-    if (used[i]) {
-      new_index[i] = (int)keep.size();
-      keep.push_back((int)i);
-    }
-  for (auto &p : mesh.polygons)
-    for (int k = 0; k < 3; ++k) p.vertices[k] = (std::uint32_t)new_index[p.vertices[k]];
-  storeVertices(xyz, keep, mesh);
+  std::vector<std::uint8_t> keep(tri.size(), 1);
+  std::uint64_t n_kept = 0;
+  const int rc = tsdf_hip_mesh_cleanup(device, xyz.data(), xyz.size() / 3, faces.data(), tri.size(), face_dist, min_neighbors,
+                                       keep.data(), &n_kept);
+  if (rc) return rc;
+  std::vector<char> drop(mesh.polygons.size(), 0);
+  for (size_t i = 0; i < tri.size(); ++i)
+    if (!keep[i]) drop[tri[i]] = 1;
+  dropFaces(mesh, xyz, drop);
+  return 0;
+}
+
+// Triangles below which --cleanup keeps the host pass: the largest prefix at which tools/time_cleanup.py measured the
+// GPU-backed pass (upload, device pass, mask download, this file's tail) slower than cleanupMesh
+// (profiles/cleanup_timing.json, "gpu_backed_pass_loses_up_to_faces": 3000 at 512^3 and at 2048^3, the next prefix, 5000,
+// wins).
+constexpr size_t kCleanupHostBelowFaces = 3000;
+
+// --cleanup of the `integrate` program: the GPU pass from the crossover up, the host pass below it, or always with
+// TSDF_HIP_HOST_MESH_POST=1 (A/B runs, tools/time_cleanup.py).  The result does not depend on the choice.
+inline int cleanupMeshAuto(pcl::PolygonMesh &mesh, float face_dist = 0.02f, int min_neighbors = 5) {
+  const char *host = std::getenv("TSDF_HIP_HOST_MESH_POST");
+  if ((host && host[0] == '1') || mesh.polygons.size() <= kCleanupHostBelowFaces) {
+    cleanupMesh(mesh, face_dist, min_neighbors);
+    return 0;
+  }
+  return cleanupMeshGpu(mesh, face_dist, min_neighbors);
 }
 
 }  // namespace mesh_post

@@ -14,6 +14,7 @@
 
 #include "tsdf_common.h"
 #include "tsdf_occupied.h"
+#include "tsdf_meshpost.h"
 #ifdef TSDF_HIP_TEST_HOOKS
 #include "tsdf_hip_test.h"
 #endif
@@ -762,6 +763,7 @@ extern "C" int tsdf_hip_destroy(tsdf_handle h) {
   TsdfDeviceScope scope(h->device);
   (void)hipStreamSynchronize(h->stream);
   tsdf_occupied_release(h);  // the state tsdf_occupied.hip keeps for this handle, if any
+  tsdf_meshpost_release(h);  // ... and tsdf_meshpost.hip
   free_volume(h);
   return TSDF_HIP_OK;
 }

@@ -23,6 +23,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "tsdf_common.h"
+#include "tsdf_meshpost.h"
 #ifdef TSDF_HIP_TEST_HOOKS
 #include "tsdf_hip_test.h"
 #endif
@@ -703,9 +704,16 @@ static int ensure_buf(T **buf, size_t *cap_elems, size_t need, hipStream_t s) {
   return TSDF_HIP_OK;
 }
 
+static int march_single(tsdf_handle h, float w_min, int color_mode, uint64_t *n_tri);
+
 extern "C" int tsdf_hip_march(tsdf_handle h, float w_min, int color_mode, uint64_t *n_tri) {
   if (!h || color_mode < 0 || color_mode > 2) return TSDF_HIP_E_INVALID;
-  if (h->multi) return tsdf_multi_march(h, w_min, color_mode, n_tri);
+  const int rc = h->multi ? tsdf_multi_march(h, w_min, color_mode, n_tri) : march_single(h, w_min, color_mode, n_tri);
+  tsdf_meshpost_note_march(h, rc == TSDF_HIP_OK);  // tsdf_hip_march_cleanup refuses a handle whose last march did not succeed
+  return rc;
+}
+
+static int march_single(tsdf_handle h, float w_min, int color_mode, uint64_t *n_tri) {
   TSDF_ENTER(h);
   const tsdf_params &p = h->p;
   if (p.res[0] >= (1 << 20) || p.res[1] >= (1 << 20) || p.res[2] >= (1 << 20)) return TSDF_HIP_E_UNSUPPORTED;

@@ -1,0 +1,641 @@
+// libtsdf_hip.so -- floater removal of a triangle mesh.
+//
+// Replaces cleanupMesh of the reference's `integrate` program (src/prog/integrate.cpp:152-214), as this repository's host
+// restatement cpu_tsdf::mesh_post::cleanupMesh (csrc/prog/mesh_post.h) defines it operation for operation: faces whose
+// centroids form a connected group (links: centroid distance strictly below face_dist, candidates from the 27 grid cells of
+// edge face_dist around a face's own) of at most min_neighbors faces are removed.  The result is a SET, so it parallelises
+// exactly:
+//   k_mp_centroid  centroid ((v0 + v1) + v2) / 3.f and the host's cell key per face; non-finite centroids get the key ~0
+//   rocprim sort   (key, face) pairs; k_mp_gather writes the centroids in sorted order and marks run heads, a scan numbers
+//                  the cells, k_mp_cells / k_mp_cellnbr build the cell table and each cell's 27 neighbour cells
+//   k_mp_degree    links per face, leaving at min_neighbors: a face with that many links is HEAVY -- its group has more than
+//                  min_neighbors faces whatever else it holds.  On a surface nearly every face is heavy after a few tests.
+//   k_mp_link      the LIGHT faces enumerate all their links and join a lock-free union-find (CAS hooking of the larger root
+//                  under the smaller, path halving); a link to a heavy face joins that face's tree as well
+//   k_mp_count     per tree: "holds a heavy face" or the number of (light) members
+//   k_mp_keep      keep = heavy, or in a tree with a heavy face, or in a tree of more than min_neighbors faces
+// A tree without a heavy face is a whole group (every member enumerated every link), so its size is the group's size; a tree
+// with one lies inside a group that is large enough.  No kernel waits for another workgroup: the only
+// loops over shared state are CAS retries, each of which fails only because another thread's CAS succeeded.
+// Gather-bound pointer chasing and a radix sort: no MFMA.
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+#include "tsdf_meshpost.h"
+
+// ---- state -----------------------------------------------------------------------------------------------------------------
+#define MP_TEST_SLOTS 64  // counters[MP_C_TESTS ..]: link tests, striped (one address for every wave costs milliseconds)
+#define MP_C_FINITE 0     // faces with a finite centroid
+#define MP_C_BAD 1        // != 0: a face names a vertex >= n_verts
+#define MP_C_KEPT 2
+#define MP_C_TESTS 8
+#define MP_COUNTERS (MP_C_TESTS + MP_TEST_SLOTS)
+#define MP_STAGE (4u << 20)  // bytes per slot of the pinned staging buffer of the host-array entry point
+
+struct MpWork {
+  void *buf = nullptr;  // per-face arrays + rocprim's temporary storage
+  size_t cap = 0;
+  void *cells = nullptr;  // per-cell arrays (sized once the number of occupied cells is known)
+  size_t cells_cap = 0;
+  unsigned long long *counters = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // the device work before / after the host reads the counts
+};
+
+struct MpState {  // per handle
+  bool marched = false;
+  MpWork work;
+};
+
+static std::mutex g_mp_mutex;
+static std::unordered_map<tsdf_hip_volume *, std::unique_ptr<MpState>> g_mp;
+static thread_local uint64_t g_mp_stats[4] = {0, 0, 0, 0};  // tsdf_hip_mesh_cleanup_stats
+
+static MpState *mp_state(tsdf_hip_volume *v, bool create) {
+  std::lock_guard<std::mutex> lock(g_mp_mutex);
+  auto it = g_mp.find(v);
+  if (it != g_mp.end()) return it->second.get();
+  if (!create) return nullptr;
+  return (g_mp[v] = std::unique_ptr<MpState>(new MpState())).get();
+}
+
+static void mp_work_free(MpWork &w) {
+  if (w.buf) (void)hipFree(w.buf);
+  if (w.cells) (void)hipFree(w.cells);
+  if (w.counters) (void)hipFree(w.counters);
+  for (hipEvent_t e : w.ev)
+    if (e) (void)hipEventDestroy(e);
+  w = MpWork();
+}
+
+void tsdf_meshpost_note_march(tsdf_hip_volume *v, bool succeeded) {
+  if (MpState *st = mp_state(v, succeeded)) st->marched = succeeded;  // (a failure on a handle without an entry needs none)
+}
+
+void tsdf_meshpost_release(tsdf_hip_volume *v) {
+  std::unique_ptr<MpState> st;
+  {
+    std::lock_guard<std::mutex> lock(g_mp_mutex);
+    auto it = g_mp.find(v);
+    if (it == g_mp.end()) return;
+    st = std::move(it->second);
+    g_mp.erase(it);
+  }
+  TsdfDeviceScope scope(v->multi ? tsdf_multi_first(v)->device : v->device);
+  mp_work_free(st->work);
+}
+
+// ---- kernels ---------------------------------------------------------------------------------------------------------------
+#define MP_NO_KEY (~0ull)  // a face whose centroid is not finite: in no cell (PointGrid skips it), last in the sorted order
+
+// mesh_post.h:124 -- ((v0 + v1) + v2) / 3.f per component (the build keeps -ffp-contract=off and hipcc's correctly rounded
+// float division).  false: the face names a vertex that does not exist.
+static __device__ __forceinline__ bool mp_centroid(const float *__restrict__ verts, uint64_t n_verts, const uint32_t *__restrict__ faces,
+                                                   uint32_t f, float c[3]) {
+  uint64_t v0 = 3ull * f, v1 = v0 + 1ull, v2 = v0 + 2ull;
+  if (faces) v0 = faces[3ull * f], v1 = faces[3ull * f + 1ull], v2 = faces[3ull * f + 2ull];
+  if (v0 >= n_verts || v1 >= n_verts || v2 >= n_verts) return false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) c[k] = ((verts[3ull * v0 + k] + verts[3ull * v1 + k]) + verts[3ull * v2 + k]) / 3.f;
+  return true;
+}
+
+static __global__ void __launch_bounds__(256)
+k_mp_centroid(const float *__restrict__ verts, uint64_t n_verts, const uint32_t *__restrict__ faces, uint32_t n, double cell,
+              uint64_t *__restrict__ keys, uint32_t *__restrict__ idx, unsigned long long *__restrict__ counters) {
+  const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+  bool fin = false;
+  if (f < n) {
+    float c[3] = {0.f, 0.f, 0.f};
+    uint64_t key = MP_NO_KEY;
+    if (!mp_centroid(verts, n_verts, faces, f, c)) {
+      counters[MP_C_BAD] = 1ull;  // (every writer stores the same 1)
+    } else if (isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2])) {
+      // PointGrid::c / key (mesh_post.h:55-58): floor((double)v / cell), 21 bits per axis
+      const long long cx = (long long)floor((double)c[0] / cell), cy = (long long)floor((double)c[1] / cell),
+                      cz = (long long)floor((double)c[2] / cell);
+      key = ((uint64_t)(cx & 0x1fffff) << 42) | ((uint64_t)(cy & 0x1fffff) << 21) | (uint64_t)(cz & 0x1fffff);
+      fin = true;
+    }
+    keys[f] = key;
+    idx[f] = f;
+  }
+  const unsigned long long m = __ballot(fin);
+  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[MP_C_FINITE], (unsigned long long)__popcll(m));
+}
+
+// sorted position i -> centroid of the face there (computed again from the vertices: the same operations give the same
+// bits, and the unsorted centroids need not be kept), and "first face of its cell"
+static __global__ void __launch_bounds__(256)
+k_mp_gather(const float *__restrict__ verts, uint64_t n_verts, const uint32_t *__restrict__ faces, const uint32_t *__restrict__ order,
+            const uint64_t *__restrict__ keys, uint32_t n, float4 *__restrict__ cen, uint32_t *__restrict__ head) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t key = keys[i];
+  float c[3] = {0.f, 0.f, 0.f};
+  if (key != MP_NO_KEY) (void)mp_centroid(verts, n_verts, faces, order[i], c);
+  cen[i] = make_float4(c[0], c[1], c[2], 0.f);
+  head[i] = key != MP_NO_KEY && (i == 0u || keys[i - 1u] != key) ? 1u : 0u;
+}
+
+// cellno: the inclusive scan of head (cell of position i = cellno[i] - 1)
+static __global__ void __launch_bounds__(256)
+k_mp_cells(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ head, const uint32_t *__restrict__ cellno, uint32_t n,
+           uint64_t *__restrict__ cell_key, uint32_t *__restrict__ cell_start) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n || !head[i]) return;
+  const uint32_t c = cellno[i] - 1u;
+  cell_key[c] = keys[i];
+  cell_start[c] = i;
+}
+
+// the 27 cells PointGrid::forNeighbours visits (mesh_post.h:39-43), as indices into the cell table (-1: empty); slot
+// (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1), so slot 13 is the cell itself
+static __global__ void __launch_bounds__(256)
+k_mp_cellnbr(const uint64_t *__restrict__ cell_key, uint32_t n_cells, int32_t *__restrict__ nbr) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (t >= 27ull * n_cells) return;
+  const uint32_t c = (uint32_t)(t / 27ull), s = (uint32_t)(t - 27ull * c);
+  const uint64_t key = cell_key[c];
+  const int dx = (int)(s % 3u) - 1, dy = (int)((s / 3u) % 3u) - 1, dz = (int)(s / 9u) - 1;
+  const uint64_t want = ((((key >> 42) + (uint64_t)(int64_t)dx) & 0x1fffffull) << 42) | ((((key >> 21) + (uint64_t)(int64_t)dy) & 0x1fffffull) << 21) |
+                        ((key + (uint64_t)(int64_t)dz) & 0x1fffffull);
+  uint32_t lo = 0u, hi = n_cells;  // the keys ascend
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (cell_key[mid] < want)
+      lo = mid + 1u;
+    else
+      hi = mid;
+  }
+  nbr[t] = lo < n_cells && cell_key[lo] == want ? (int32_t)lo : -1;
+}
+
+struct MpGrid {
+  const float4 *cen;
+  const uint32_t *cellno;
+  const int32_t *nbr;
+  const uint32_t *cell_start;  // n_cells + 1 entries
+  uint32_t n_fin;
+  float r2;
+};
+
+// f(j) for every j != i with a link to i (mesh_post.h:44-47: (ex * ex + ey * ey) + ez * ez < r2 in float, strict), the own
+// cell first; f returns false to stop.  The link test is symmetric bit for bit (ex only changes sign).
+template <typename F>
+static __device__ __forceinline__ void mp_for_links(const MpGrid &g, uint32_t i, unsigned &tests, F f) {
+  const float4 p = g.cen[i];
+  const int32_t *nb = g.nbr + 27ull * (g.cellno[i] - 1u);
+  for (int k = 0; k < 27; ++k) {
+    const int32_t c = nb[k < 14 ? 13 - k : k];  // 13, 12 .. 0, 14 .. 26
+    if (c < 0) continue;
+    const uint32_t e = g.cell_start[c + 1];
+    for (uint32_t j = g.cell_start[c]; j < e; ++j) {
+      if (j == i) continue;
+      const float4 q = g.cen[j];
+      const float ex = q.x - p.x, ey = q.y - p.y, ez = q.z - p.z;
+      ++tests;
+      if ((ex * ex + ey * ey) + ez * ez < g.r2)
+        if (!f(j)) return;
+    }
+  }
+}
+
+static __device__ __forceinline__ void mp_add_tests(unsigned tests, unsigned long long *counters) {
+  unsigned long long t = tests;
+  for (int o = 32; o; o >>= 1) t += __shfl_xor(t, o);
+  if ((threadIdx.x & 63u) == 0u && t) atomicAdd(&counters[MP_C_TESTS + blockIdx.x % MP_TEST_SLOTS], t);
+}
+
+static __global__ void __launch_bounds__(256)
+k_mp_degree(const MpGrid g, uint32_t min_nb, uint8_t *__restrict__ heavy, uint32_t *__restrict__ parent,
+            unsigned long long *__restrict__ counters) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  unsigned tests = 0u;
+  if (i < g.n_fin) {
+    uint32_t deg = 0u;
+    if (min_nb) mp_for_links(g, i, tests, [&](uint32_t) { return ++deg < min_nb; });
+    heavy[i] = deg >= min_nb ? 1 : 0;
+    parent[i] = i;
+  }
+  mp_add_tests(tests, counters);
+}
+
+// Union-find on `parent` (every entry <= its index, roots point at themselves).  All accesses are agent-scope atomics: the
+// XCDs' L2s are not coherent for plain accesses inside one kernel.  A stale read could only name an older ancestor.
+static __device__ __forceinline__ uint32_t mp_find(uint32_t *parent, uint32_t x) {
+  uint32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  while (p != x) {
+    const uint32_t gp = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (gp != p) __hip_atomic_store(&parent[x], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // path halving: x is no root and never becomes one
+    x = p;
+    p = gp;
+  }
+  return x;
+}
+
+static __device__ __forceinline__ void mp_union(uint32_t *parent, uint32_t a, uint32_t b) {
+  for (;;) {
+    a = mp_find(parent, a);
+    b = mp_find(parent, b);
+    if (a == b) return;
+    if (a < b) {
+      const uint32_t t = a;
+      a = b, b = t;
+    }
+    // hook the larger root under the smaller (no cycle can form); fails only if another thread hooked a first
+    uint32_t expect = a;
+    if (__hip_atomic_compare_exchange_strong(&parent[a], &expect, b, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  }
+}
+
+static __global__ void __launch_bounds__(256)
+k_mp_link(const MpGrid g, const uint8_t *__restrict__ heavy, uint32_t *__restrict__ parent, unsigned long long *__restrict__ counters) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  unsigned tests = 0u;
+  if (i < g.n_fin && !heavy[i])
+    mp_for_links(g, i, tests, [&](uint32_t j) {
+      if (heavy[j] || j < i) mp_union(parent, i, j);  // (a light j > i makes this union itself)
+      return true;
+    });
+  mp_add_tests(tests, counters);
+}
+
+static __global__ void __launch_bounds__(256)
+k_mp_count(uint32_t n_fin, const uint8_t *__restrict__ heavy, uint32_t *__restrict__ parent, uint8_t *__restrict__ any_heavy,
+           uint32_t *__restrict__ members) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n_fin) return;
+  const uint32_t r = mp_find(parent, i);
+  if (heavy[i])
+    any_heavy[r] = 1;
+  else
+    atomicAdd(&members[r], 1u);
+}
+
+// positions >= n_fin hold the faces without a finite centroid: groups of one (mesh_post.h:132-145 seeds a group with every
+// face, and forNeighbours gives such a face no link, not even to itself)
+static __global__ void __launch_bounds__(256)
+k_mp_keep(uint32_t n, uint32_t n_fin, uint32_t min_nb, const uint32_t *__restrict__ order, const uint8_t *__restrict__ heavy,
+          uint32_t *__restrict__ parent, const uint8_t *__restrict__ any_heavy, const uint32_t *__restrict__ members,
+          uint8_t *__restrict__ keep, unsigned long long *__restrict__ counters) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  bool k = false;
+  if (i < n) {
+    if (i >= n_fin) {
+      k = 1u > min_nb;
+    } else if (heavy[i]) {
+      k = true;
+    } else {
+      const uint32_t r = mp_find(parent, i);
+      k = any_heavy[r] || members[r] > min_nb;
+    }
+    keep[order[i]] = k ? 1 : 0;
+  }
+  const unsigned long long m = __ballot(k);
+  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[MP_C_KEPT], (unsigned long long)__popcll(m));
+}
+
+// stable compaction of per-triangle records of K elements: one thread per input element
+template <typename T, int K>
+static __global__ void __launch_bounds__(256)
+k_mp_compact(const T *__restrict__ src, const uint8_t *__restrict__ keep, const uint32_t *__restrict__ offset, uint64_t n_elems,
+             T *__restrict__ dst) {
+  const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (e >= n_elems) return;
+  const uint64_t t = e / (uint64_t)K;
+  if (keep[t]) dst[(uint64_t)offset[t] * K + (e - t * K)] = src[e];
+}
+
+struct MpKeepCount {
+  __host__ __device__ uint32_t operator()(uint8_t k) const { return k ? 1u : 0u; }
+};
+using MpKeepIt = rocprim::transform_iterator<const uint8_t *, MpKeepCount, uint32_t>;
+
+// ---- host ------------------------------------------------------------------------------------------------------------------
+static int mp_reserve(void **p, size_t *cap, size_t need, hipStream_t s) {
+  if (need <= *cap && *p) return TSDF_HIP_OK;
+  if (*p) {
+    TSDF_HIP_TRY(hipStreamSynchronize(s));
+    TSDF_HIP_TRY(hipFree(*p));
+    *p = nullptr, *cap = 0;
+  }
+  if (hipMalloc(p, need) != hipSuccess) {
+    *p = nullptr;
+    (void)hipGetLastError();
+    tsdf_set_error("mesh cleanup: " + std::to_string(need) + " bytes of device memory for the working set are not available");
+    return TSDF_HIP_E_NOMEM;
+  }
+  *cap = need;
+  return TSDF_HIP_OK;
+}
+
+static inline size_t mp_up(size_t v) { return (v + 255) / 256 * 256; }
+
+struct MpLayout {  // the per-face arrays inside MpWork::buf
+  size_t key_a, key_b, idx_a, idx_b, cen, cellno, heavy, any_heavy, keep, tmp, tmp_bytes, total;
+};
+
+static int mp_layout(size_t n, hipStream_t s, MpLayout &L) {
+  size_t t_sort = 0, t_scan = 0, t_scan2 = 0;
+  TSDF_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t_sort, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, n,
+                                         0u, 64u, s));
+  TSDF_HIP_TRY(rocprim::inclusive_scan(nullptr, t_scan, (uint32_t *)nullptr, (uint32_t *)nullptr, n, rocprim::plus<uint32_t>(), s));
+  TSDF_HIP_TRY(rocprim::exclusive_scan(nullptr, t_scan2, MpKeepIt(nullptr, MpKeepCount()), (uint32_t *)nullptr, 0u, n, rocprim::plus<uint32_t>(), s));
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += mp_up(bytes);
+    return at;
+  };
+  L.key_a = take(n * 8), L.key_b = take(n * 8), L.idx_a = take(n * 4), L.idx_b = take(n * 4), L.cen = take(n * 16);
+  L.cellno = take(n * 4), L.heavy = take(n), L.any_heavy = take(n), L.keep = take(n);
+  L.tmp_bytes = std::max(t_sort, std::max(t_scan, t_scan2));
+  L.tmp = take(L.tmp_bytes);
+  L.total = o;
+  return TSDF_HIP_OK;
+}
+
+// The whole pass on device arrays: keep[f] (in MpWork::buf at L.keep) for the n faces, *n_kept, and the stats of the calling
+// thread.  Leaves the stream idle.
+static int mp_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_verts, const uint32_t *d_faces, uint64_t n_faces, float face_dist,
+                   int min_neighbors, MpLayout &L, uint64_t *n_kept) {
+  const uint32_t n = (uint32_t)n_faces, min_nb = (uint32_t)min_neighbors;
+  int rc = mp_layout(n, s, L);
+  if (rc || (rc = mp_reserve(&w.buf, &w.cap, L.total, s))) return rc;
+  if (!w.counters) TSDF_HIP_TRY(hipMalloc(&w.counters, MP_COUNTERS * sizeof(unsigned long long)));
+  for (int i = 0; i < 4; ++i)
+    if (!w.ev[i]) TSDF_HIP_TRY(hipEventCreate(&w.ev[i]));
+  char *b = (char *)w.buf;
+  uint64_t *key_a = (uint64_t *)(b + L.key_a), *key_b = (uint64_t *)(b + L.key_b);
+  uint32_t *idx_a = (uint32_t *)(b + L.idx_a), *idx_b = (uint32_t *)(b + L.idx_b), *cellno = (uint32_t *)(b + L.cellno);
+  float4 *cen = (float4 *)(b + L.cen);
+  uint8_t *heavy = (uint8_t *)(b + L.heavy), *any_heavy = (uint8_t *)(b + L.any_heavy), *keep = (uint8_t *)(b + L.keep);
+  // free once the sort has run: the unsorted keys' 8 n bytes hold the union-find, the unsorted indices the run heads
+  uint32_t *parent = (uint32_t *)key_a, *members = parent + n, *head = idx_a;
+  const dim3 blk(256), grid_n((n + 255u) / 256u);
+
+  TSDF_HIP_TRY(hipMemsetAsync(w.counters, 0, MP_COUNTERS * sizeof(unsigned long long), s));
+  TSDF_HIP_TRY(hipEventRecord(w.ev[0], s));
+  hipLaunchKernelGGL(k_mp_centroid, grid_n, blk, 0, s, d_verts, n_verts, d_faces, n, (double)face_dist, key_a, idx_a, w.counters);
+  TSDF_HIP_TRY(hipGetLastError());
+  size_t tmp_bytes = L.tmp_bytes;
+  TSDF_HIP_TRY(rocprim::radix_sort_pairs(b + L.tmp, tmp_bytes, key_a, key_b, idx_a, idx_b, (size_t)n, 0u, 64u, s));
+  hipLaunchKernelGGL(k_mp_gather, grid_n, blk, 0, s, d_verts, n_verts, d_faces, idx_b, key_b, n, cen, head);
+  TSDF_HIP_TRY(hipGetLastError());
+  tmp_bytes = L.tmp_bytes;
+  TSDF_HIP_TRY(rocprim::inclusive_scan(b + L.tmp, tmp_bytes, head, cellno, (size_t)n, rocprim::plus<uint32_t>(), s));
+  TSDF_HIP_TRY(hipEventRecord(w.ev[1], s));
+  unsigned long long counts[MP_COUNTERS] = {0};
+  uint32_t n_cells = 0;
+  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, MP_C_TESTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipMemcpyAsync(&n_cells, cellno + (n - 1u), sizeof n_cells, hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipStreamSynchronize(s));
+  if (counts[MP_C_BAD]) {
+    tsdf_set_error("tsdf_hip_mesh_cleanup: a face names a vertex index >= n_verts");
+    return TSDF_HIP_E_INVALID;
+  }
+  const uint32_t n_fin = (uint32_t)counts[MP_C_FINITE];
+  if (n_fin) {  // (the cell table is sized before the second timed interval opens: a hipMalloc is not device work)
+    const size_t o_start = mp_up((size_t)n_cells * 8), o_nbr = o_start + mp_up(((size_t)n_cells + 1) * 4);
+    if ((rc = mp_reserve(&w.cells, &w.cells_cap, o_nbr + (size_t)n_cells * 27 * 4, s))) return rc;
+  }
+  TSDF_HIP_TRY(hipEventRecord(w.ev[2], s));
+  if (n_fin) {
+    const size_t o_start = mp_up((size_t)n_cells * 8), o_nbr = o_start + mp_up(((size_t)n_cells + 1) * 4);
+    uint64_t *cell_key = (uint64_t *)w.cells;
+    uint32_t *cell_start = (uint32_t *)((char *)w.cells + o_start);
+    int32_t *nbr = (int32_t *)((char *)w.cells + o_nbr);
+    hipLaunchKernelGGL(k_mp_cells, grid_n, blk, 0, s, key_b, head, cellno, n, cell_key, cell_start);
+    TSDF_HIP_TRY(hipGetLastError());
+    TSDF_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(cell_start + n_cells), (int)n_fin, 1, s));
+    hipLaunchKernelGGL(k_mp_cellnbr, dim3((unsigned)((27ull * n_cells + 255ull) / 256ull)), blk, 0, s, cell_key, n_cells, nbr);
+    TSDF_HIP_TRY(hipGetLastError());
+    TSDF_HIP_TRY(hipMemsetAsync(any_heavy, 0, n, s));
+    TSDF_HIP_TRY(hipMemsetAsync(members, 0, (size_t)n * 4, s));
+    const float r2 = (float)((double)face_dist * (double)face_dist);  // mesh_post.h:129
+    const MpGrid g{cen, cellno, nbr, cell_start, n_fin, r2};
+    const dim3 grid_f((n_fin + 255u) / 256u);
+    hipLaunchKernelGGL(k_mp_degree, grid_f, blk, 0, s, g, min_nb, heavy, parent, w.counters);
+    TSDF_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_mp_link, grid_f, blk, 0, s, g, heavy, parent, w.counters);
+    TSDF_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_mp_count, grid_f, blk, 0, s, n_fin, heavy, parent, any_heavy, members);
+    TSDF_HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_mp_keep, grid_n, blk, 0, s, n, n_fin, min_nb, idx_b, heavy, parent, any_heavy, members, keep, w.counters);
+  TSDF_HIP_TRY(hipGetLastError());
+  TSDF_HIP_TRY(hipEventRecord(w.ev[3], s));
+  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, sizeof counts, hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipStreamSynchronize(s));
+  // device time = the two intervals on the stream; the host's read of the counts between them (a copy of 8 words, a
+  // synchronise, the sizing of the cell table) is not in it
+  float ms = 0.f, ms2 = 0.f;
+  (void)hipEventElapsedTime(&ms, w.ev[0], w.ev[1]);
+  (void)hipEventElapsedTime(&ms2, w.ev[2], w.ev[3]);
+  ms += ms2;
+  uint64_t tests = 0;
+  for (int i = 0; i < MP_TEST_SLOTS; ++i) tests += counts[MP_C_TESTS + i];
+  g_mp_stats[0] = n, g_mp_stats[1] = n - counts[MP_C_KEPT], g_mp_stats[2] = tests, g_mp_stats[3] = (uint64_t)(ms * 1000.f);
+  *n_kept = counts[MP_C_KEPT];
+  return TSDF_HIP_OK;
+}
+
+static int mp_check_args(float face_dist, int min_neighbors, uint64_t n_faces, const char *who) {
+  if (!(face_dist > 0.f) || !std::isfinite(face_dist) || min_neighbors < 0) {
+    tsdf_set_error(std::string(who) + ": face_dist must be finite and positive, min_neighbors >= 0");
+    return TSDF_HIP_E_INVALID;
+  }
+  if (n_faces > (1ull << 31)) {
+    tsdf_set_error(std::string(who) + ": face indices are 32-bit; more than 2^31 faces are not accepted");
+    return TSDF_HIP_E_INVALID;
+  }
+  return TSDF_HIP_OK;
+}
+
+// Is `p` host memory the runtime knows as pinned?  (As tsdf_to_host / tsdf_to_device decide: the DMA engine then reads and
+// writes it directly.)
+static bool mp_is_pinned(const void *p) {
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return attr.type == hipMemoryTypeHost;
+}
+
+struct MpStage {  // two pinned slots for pageable caller memory
+  char *pinned = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~MpStage() {
+    if (pinned) (void)hipHostFree(pinned);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  int ready() {
+    if (pinned) return TSDF_HIP_OK;
+    TSDF_HIP_TRY(hipHostMalloc((void **)&pinned, 2 * (size_t)MP_STAGE, hipHostMallocDefault));
+    for (int i = 0; i < 2; ++i) TSDF_HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+    return TSDF_HIP_OK;
+  }
+};
+
+static int mp_to_device(MpStage &st, void *dst, const void *src, size_t bytes, hipStream_t s) {
+  if (!bytes) return TSDF_HIP_OK;
+  if (bytes >= (64u << 10) && mp_is_pinned(src)) {
+    TSDF_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+    return TSDF_HIP_OK;
+  }
+  if (const int rc = st.ready()) return rc;
+  for (size_t off = 0, k = 0; off < bytes; off += MP_STAGE, ++k) {
+    const int slot = (int)(k & 1);
+    if (k >= 2) TSDF_HIP_TRY(hipEventSynchronize(st.ev[slot]));  // the copy that last read this slot has finished
+    const size_t len = std::min((size_t)MP_STAGE, bytes - off);
+    memcpy(st.pinned + (size_t)slot * MP_STAGE, (const char *)src + off, len);
+    TSDF_HIP_TRY(hipMemcpyAsync((char *)dst + off, st.pinned + (size_t)slot * MP_STAGE, len, hipMemcpyHostToDevice, s));
+    TSDF_HIP_TRY(hipEventRecord(st.ev[slot], s));
+  }
+  TSDF_HIP_TRY(hipStreamSynchronize(s));  // (the slots are free again for the way back)
+  return TSDF_HIP_OK;
+}
+
+static int mp_to_host(MpStage &st, void *dst, const void *src, size_t bytes, hipStream_t s) {
+  if (!bytes) return TSDF_HIP_OK;
+  if (bytes >= (64u << 10) && mp_is_pinned(dst)) {
+    TSDF_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+    TSDF_HIP_TRY(hipStreamSynchronize(s));
+    return TSDF_HIP_OK;
+  }
+  if (const int rc = st.ready()) return rc;
+  for (size_t off = 0; off < bytes; off += MP_STAGE) {
+    const size_t len = std::min((size_t)MP_STAGE, bytes - off);
+    TSDF_HIP_TRY(hipMemcpyAsync(st.pinned, (const char *)src + off, len, hipMemcpyDeviceToHost, s));
+    TSDF_HIP_TRY(hipStreamSynchronize(s));
+    memcpy((char *)dst + off, st.pinned, len);
+  }
+  return TSDF_HIP_OK;
+}
+
+extern "C" int tsdf_hip_mesh_cleanup(int device, const float *verts, uint64_t n_verts, const uint32_t *faces, uint64_t n_faces, float face_dist,
+                                     int min_neighbors, uint8_t *keep, uint64_t *n_kept) {
+  if (n_kept) *n_kept = 0;
+  if (const int rc = mp_check_args(face_dist, min_neighbors, n_faces, "tsdf_hip_mesh_cleanup")) return rc;
+  if (device < 0) return TSDF_HIP_E_INVALID;
+  if (n_faces == 0) {
+    g_mp_stats[0] = g_mp_stats[1] = g_mp_stats[2] = g_mp_stats[3] = 0;
+    return TSDF_HIP_OK;
+  }
+  if (!verts || !keep || n_verts == 0 || (!faces && n_verts / 3 < n_faces)) {
+    tsdf_set_error("tsdf_hip_mesh_cleanup: verts and keep must not be NULL, and a triangle soup needs 3 vertices per face");
+    return TSDF_HIP_E_INVALID;
+  }
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+    (void)hipGetLastError();
+    return TSDF_HIP_E_NODEVICE;
+  }
+  if (device >= n_dev) return TSDF_HIP_E_INVALID;
+  TSDF_ON_DEVICE(device);
+  // everything this call allocates goes when it returns: there is no handle to keep it for
+  struct Call {
+    hipStream_t s = nullptr;
+    void *in = nullptr;
+    MpWork work;
+    MpStage stage;
+    ~Call() {
+      if (s) (void)hipStreamSynchronize(s);
+      mp_work_free(work);
+      if (in) (void)hipFree(in);
+      if (s) (void)hipStreamDestroy(s);
+    }
+  } c;
+  TSDF_HIP_TRY(hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking));
+  const size_t b_verts = mp_up((size_t)n_verts * 12), b_faces = faces ? (size_t)n_faces * 12 : 0;
+  if (hipMalloc(&c.in, b_verts + b_faces) != hipSuccess) {
+    c.in = nullptr;
+    (void)hipGetLastError();
+    tsdf_set_error("tsdf_hip_mesh_cleanup: " + std::to_string(b_verts + b_faces) + " bytes of device memory for the mesh are not available");
+    return TSDF_HIP_E_NOMEM;
+  }
+  float *d_verts = (float *)c.in;
+  uint32_t *d_faces = faces ? (uint32_t *)((char *)c.in + b_verts) : nullptr;
+  int rc = mp_to_device(c.stage, d_verts, verts, (size_t)n_verts * 12, c.s);
+  if (!rc && faces) rc = mp_to_device(c.stage, d_faces, faces, b_faces, c.s);
+  if (rc) return rc;
+  MpLayout L;
+  uint64_t kept = 0;
+  if ((rc = mp_core(c.work, c.s, d_verts, n_verts, d_faces, n_faces, face_dist, min_neighbors, L, &kept))) return rc;
+  if ((rc = mp_to_host(c.stage, keep, (char *)c.work.buf + L.keep, (size_t)n_faces, c.s))) return rc;
+  if (n_kept) *n_kept = kept;
+  return TSDF_HIP_OK;
+}
+
+extern "C" int tsdf_hip_march_cleanup(tsdf_handle h, float face_dist, int min_neighbors, uint64_t *n_tri) {
+  if (!h) return TSDF_HIP_E_INVALID;
+  if (n_tri) *n_tri = 0;
+  if (const int rc = mp_check_args(face_dist, min_neighbors, 0, "tsdf_hip_march_cleanup")) return rc;
+  MpState *st = mp_state(h, false);
+  if (!st || !st->marched) {
+    tsdf_set_error("tsdf_hip_march_cleanup: the last tsdf_hip_march on this handle did not succeed, or none has run");
+    return TSDF_HIP_E_INVALID;
+  }
+  if (h->multi) return tsdf_multi_march_cleanup(h, face_dist, min_neighbors, n_tri);
+  TSDF_ENTER(h);
+  const uint64_t n = h->mc_ntri;
+  if (const int rc = mp_check_args(face_dist, min_neighbors, n, "tsdf_hip_march_cleanup")) return rc;
+  if (!n) {
+    g_mp_stats[0] = g_mp_stats[1] = g_mp_stats[2] = g_mp_stats[3] = 0;
+    return TSDF_HIP_OK;
+  }
+  MpLayout L;
+  uint64_t kept = 0;
+  int rc = mp_core(st->work, h->stream, h->mc_verts, 3 * n, nullptr, n, face_dist, min_neighbors, L, &kept);
+  if (rc) return rc;
+  if (kept < n && kept) {
+    // stable compaction of vertices, colours and cell keys: each array into the handle's scratch and back (the working set's
+    // cell numbers are done with: their 4 n bytes take the offsets)
+    char *b = (char *)st->work.buf;
+    const uint8_t *keep = (const uint8_t *)(b + L.keep);
+    uint32_t *offset = (uint32_t *)(b + L.cellno);
+    size_t tmp_bytes = L.tmp_bytes;
+    TSDF_HIP_TRY(rocprim::exclusive_scan(b + L.tmp, tmp_bytes, MpKeepIt(keep, MpKeepCount()), offset, 0u, (size_t)n, rocprim::plus<uint32_t>(),
+                                         h->stream));
+    if ((rc = tsdf_ensure_scratch(h, (size_t)kept * 36))) return rc;
+    const dim3 blk(256);
+    hipLaunchKernelGGL((k_mp_compact<float, 9>), dim3((unsigned)((9 * n + 255) / 256)), blk, 0, h->stream, h->mc_verts, keep, offset, 9 * n,
+                       (float *)h->scratch);
+    TSDF_HIP_TRY(hipGetLastError());
+    TSDF_HIP_TRY(hipMemcpyAsync(h->mc_verts, h->scratch, (size_t)kept * 36, hipMemcpyDeviceToDevice, h->stream));
+    if (h->mc_has_rgb) {
+      hipLaunchKernelGGL((k_mp_compact<uint8_t, 9>), dim3((unsigned)((9 * n + 255) / 256)), blk, 0, h->stream, h->mc_rgb, keep, offset, 9 * n,
+                         (uint8_t *)h->scratch);
+      TSDF_HIP_TRY(hipGetLastError());
+      TSDF_HIP_TRY(hipMemcpyAsync(h->mc_rgb, h->scratch, (size_t)kept * 9, hipMemcpyDeviceToDevice, h->stream));
+    }
+    hipLaunchKernelGGL((k_mp_compact<uint64_t, 1>), dim3((unsigned)((n + 255) / 256)), blk, 0, h->stream, h->mc_cell, keep, offset, n,
+                       (uint64_t *)h->scratch);
+    TSDF_HIP_TRY(hipGetLastError());
+    TSDF_HIP_TRY(hipMemcpyAsync(h->mc_cell, h->scratch, (size_t)kept * 8, hipMemcpyDeviceToDevice, h->stream));
+    TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  h->mc_ntri = kept;
+  if (n_tri) *n_tri = kept;
+  return TSDF_HIP_OK;
+}
+
+extern "C" int tsdf_hip_mesh_cleanup_stats(uint64_t out[4]) {
+  if (!out) return TSDF_HIP_E_INVALID;
+  for (int i = 0; i < 4; ++i) out[i] = g_mp_stats[i];
+  return TSDF_HIP_OK;
+}

@@ -26,6 +26,7 @@
 
 #include "tsdf_common.h"
 #include "tsdf_occupied.h"
+#include "tsdf_meshpost.h"
 
 struct tsdf_hip_multi {
   std::vector<tsdf_handle> slab;
@@ -1146,6 +1147,34 @@ int tsdf_multi_march_fetch(tsdf_handle h, float *verts, uint8_t *rgb, uint64_t *
   if (verts) memcpy(verts, m->verts.data(), n * 9 * sizeof(float));
   if (rgb) memcpy(rgb, m->rgb.data(), n * 9);
   if (cell) memcpy(cell, m->cell.data(), n * sizeof(uint64_t));
+  return TSDF_HIP_OK;
+}
+
+// tsdf_hip_march_cleanup on a set: the merged mesh is on the host, so it takes the host-array entry point on the first slab's
+// device, and the host copy is compacted in order -- what one handle holding the whole grid leaves behind.
+int tsdf_multi_march_cleanup(tsdf_handle h, float face_dist, int min_neighbors, uint64_t *n_tri) {
+  tsdf_hip_multi *m = h->multi;
+  const uint64_t n = h->mc_ntri;
+  if (n_tri) *n_tri = n;
+  std::vector<uint8_t> keep((size_t)n);
+  uint64_t kept = 0;
+  const int rc = tsdf_hip_mesh_cleanup(m->slab[0]->device, m->verts.data(), 3 * n, nullptr, n, face_dist, min_neighbors, keep.data(), &kept);
+  if (rc) return rc;
+  uint64_t o = 0;
+  for (uint64_t t = 0; t < n; ++t) {
+    if (!keep[t]) continue;
+    if (o != t) {
+      memcpy(&m->verts[o * 9], &m->verts[t * 9], 9 * sizeof(float));
+      if (m->mesh_has_rgb) memcpy(&m->rgb[o * 9], &m->rgb[t * 9], 9);
+      m->cell[o] = m->cell[t];
+    }
+    ++o;
+  }
+  m->verts.resize(o * 9);
+  if (m->mesh_has_rgb) m->rgb.resize(o * 9);
+  m->cell.resize(o);
+  h->mc_ntri = o;
+  if (n_tri) *n_tri = o;
   return TSDF_HIP_OK;
 }
 

@@ -623,6 +623,20 @@ class MarchingCubesTSDFOctree:
         self._by_rgb = False
         self._by_conf = False
         self._vol = None
+        self._cleanup = None
+
+    def setCleanup(self, face_dist=0.02, min_neighbors=5):
+        """Extension (no reference counterpart on the class): reconstruct() drops the faces in connected groups of at most
+        `min_neighbors` faces -- the `integrate` program's --cleanup (src/prog/integrate.cpp:152-214) -- on the GPU, between
+        the march and the fetch (tsdf_hip_march_cleanup).  It acts in the VOLUME frame, before the global transform, and,
+        unlike the program's pass, keeps the colours."""
+        face_dist, min_neighbors = float(face_dist), int(min_neighbors)
+        if not (np.isfinite(face_dist) and face_dist > 0) or min_neighbors < 0:
+            raise ValueError("setCleanup: face_dist must be finite and positive, min_neighbors >= 0")
+        self._cleanup = (face_dist, min_neighbors)
+
+    def clearCleanup(self):
+        self._cleanup = None
 
     def setInputTSDF(self, volume):
         self._vol = volume
@@ -646,6 +660,8 @@ class MarchingCubesTSDFOctree:
         mode = 2 if self._by_conf else (1 if self._by_rgb else 0)
         n = C.c_uint64(0)
         capi.check(lib.tsdf_hip_march(h, self._w_min, mode, C.byref(n)), "march")
+        if self._cleanup is not None:
+            capi.check(lib.tsdf_hip_march_cleanup(h, self._cleanup[0], self._cleanup[1], C.byref(n)), "march_cleanup")
         nt = int(n.value)
         verts = np.empty((nt * 3, 3), dtype=np.float32)
         rgb = np.empty((nt * 3, 3), dtype=np.uint8) if mode else None
@@ -660,6 +676,24 @@ class MarchingCubesTSDFOctree:
             verts = transform_points_f64(verts, g)
         polys = np.arange(nt * 3, dtype=np.int32).reshape(nt, 3)
         return {"vertices": verts, "polygons": polys, "rgb": rgb, "cells": cells}
+
+
+def cleanup_mesh(vertices, polygons=None, face_dist=0.02, min_neighbors=5, device=0):
+    """Which faces survive the `integrate` program's --cleanup (src/prog/integrate.cpp:152-214), computed on the GPU
+    (tsdf_hip_mesh_cleanup): a boolean keep mask, one entry per face.  vertices (n, 3) float32; polygons (m, 3) vertex
+    indices, or None for a triangle soup (face f = vertices 3f, 3f+1, 3f+2)."""
+    verts = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    faces = None if polygons is None else np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
+    if faces is None and len(verts) % 3:
+        raise ValueError("cleanup_mesh: a triangle soup needs 3 vertices per face")
+    n_faces = len(verts) // 3 if faces is None else len(faces)
+    keep = np.zeros(n_faces, dtype=np.uint8)
+    kept = C.c_uint64(0)
+    capi.check(
+        capi.load().tsdf_hip_mesh_cleanup(int(device), capi.as_f32p(verts), len(verts),
+                                          faces.ctypes.data_as(C.POINTER(C.c_uint32)) if faces is not None else None, n_faces,
+                                          float(face_dist), int(min_neighbors), capi.as_u8p(keep), C.byref(kept)), "mesh_cleanup")
+    return keep.astype(bool)
 
 
 def reference_cull_planes(p, trans):

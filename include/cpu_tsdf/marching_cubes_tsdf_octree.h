@@ -19,6 +19,7 @@ class MarchingCubesTSDFOctree : public pcl::MarchingCubes<pcl::PointXYZ> {
  public:
   MarchingCubesTSDFOctree()
       : pcl::MarchingCubes<pcl::PointXYZ>(), color_by_confidence_(false), color_by_rgb_(false), w_min_(2.5f) {}
+  ~MarchingCubesTSDFOctree() override;  // forgets the object's setCleanup (see there)
 
   // Mirrors the reference (:44-83): remembers the volume and dresses the base class the same way -- grid resolution,
   // the 8-corner "input cloud", no grid extension, iso level 0, bounding box and size_voxel_.
@@ -26,6 +27,15 @@ class MarchingCubesTSDFOctree : public pcl::MarchingCubes<pcl::PointXYZ> {
   void setColorByConfidence(bool color_by_confidence) { color_by_confidence_ = color_by_confidence; }
   void setColorByRGB(bool color_by_rgb) { color_by_rgb_ = color_by_rgb; }
   void setMinWeight(float w_min) { w_min_ = w_min; }
+  // Extension (the reference class has no such member): reconstruct drops the faces in connected groups of at most
+  // min_neighbors faces -- cleanupMesh of the `integrate` program (src/prog/integrate.cpp:152-214) -- on the GPU, between
+  // the march and the fetch (tsdf_hip_march_cleanup).  It acts in the VOLUME frame, before the global transform, and,
+  // unlike the program's pass, keeps the colours.
+  // The setting lives in the shell library, keyed by the object, NOT in a data member: the class keeps the size and layout
+  // it had, so a binary compiled against the earlier header and only re-linked keeps working (its objects end where they
+  // used to; a member read behind them would be whatever the stack held).  A copy of the object does not carry it.
+  void setCleanup(float face_dist = 0.02f, int min_neighbors = 5);
+  void clearCleanup();
 
   using pcl::MarchingCubes<pcl::PointXYZ>::reconstruct;  // reconstruct(PolygonMesh&), reconstruct(points, polygons)
 

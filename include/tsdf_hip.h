@@ -403,6 +403,36 @@ int tsdf_hip_march_stats(tsdf_handle h, uint64_t out[4]);
  * the buffers go straight to RCCL). */
 int tsdf_hip_march_fetch_device(tsdf_handle h, float *d_verts, uint8_t *d_rgb, uint64_t *d_cell);
 
+/* cleanupMesh -- src/prog/integrate.cpp:152-214 (the `integrate` program's --cleanup): which faces of a triangle mesh
+ * survive the removal of small islands.  Two faces are LINKED when their centroids -- ((v0 + v1) + v2) / 3.f per
+ * component, in float -- lie in neighbouring cells (the 27 around a face's own) of a grid of edge face_dist, cell =
+ * floor((double)c / (double)face_dist), and (ex*ex + ey*ey) + ez*ez < (float)((double)face_dist * face_dist) in float,
+ * strictly.  A face is removed iff its connected group of linked faces has at most min_neighbors members; a face whose
+ * centroid is not finite links to nothing and is a group of one.  keep[f] (one byte per face, 1 = survives) equals, face
+ * for face, what cpu_tsdf::mesh_post::cleanupMesh (csrc/prog/mesh_post.h) drops on the host.
+ *   verts, faces   HOST arrays (pinned memory is used directly): n_verts x 3 floats, n_faces x 3 vertex indices;
+ *                  faces == NULL = triangle soup, face f using vertices 3f, 3f + 1, 3f + 2.
+ * E_INVALID: face_dist not finite or <= 0, min_neighbors < 0, more than 2^31 faces (face indices are 32-bit), a vertex
+ * index >= n_verts, NULL where data is needed.  n_faces == 0 is OK and touches no device.
+ * Cost: a face evaluates link tests until it has min_neighbors links, so at most (faces in its 27 cells) tests, and on a
+ * surface a few times min_neighbors.  A min_neighbors in the range of the cell population on a dense mesh (thousands, with
+ * hundreds of faces per cell) makes every face walk all its candidates in ONE kernel launch -- as slow as the host pass per
+ * face, and long enough to matter on a GPU shared with others; the defaults of the reference (0.02, 5) are far from it. */
+int tsdf_hip_mesh_cleanup(int device, const float *verts, uint64_t n_verts, const uint32_t *faces /* NULL = soup */,
+                          uint64_t n_faces, float face_dist, int min_neighbors, uint8_t *keep, uint64_t *n_kept);
+/* The same on the DEVICE-RESIDENT result of the last tsdf_hip_march, in place (integrate.cpp:152-214 applied before the
+ * mesh leaves the GPU; an extension: the reference cleans the final PolygonMesh on the host): vertices, colours and cell
+ * keys are compacted together, order kept; tsdf_hip_march_fetch / _fetch_device then return the *n_tri surviving
+ * triangles.  E_INVALID before the first tsdf_hip_march on the handle, and after one that failed.  A second call with the same arguments removes
+ * nothing.  On a multi-GPU handle the merged mesh (host) goes through tsdf_hip_mesh_cleanup on the first slab's device;
+ * the result equals one handle holding the whole grid. */
+int tsdf_hip_march_cleanup(tsdf_handle h, float face_dist, int min_neighbors, uint64_t *n_tri);
+/* Report-only, of the last cleanup (either entry point) on the calling thread: out[0] = faces in, out[1] = faces removed,
+ * out[2] = link tests evaluated (the host pass of integrate.cpp:173-206 evaluates one per candidate of every face; here a
+ * face stops at min_neighbors links), out[3] = device microseconds: the two intervals of device work (HIP events on the
+ * stream) before and after the host reads the cell count in between; that read and all transfers are excluded. */
+int tsdf_hip_mesh_cleanup_stats(uint64_t out[4]);
+
 /* getOccupiedVoxelIndices -- src/lib/tsdf_volume_octree.cpp:590-609 (+ OctreeNode::getLeaves, src/lib/octree.cpp:99-109):
  * the voxels with w > 0 && fabsf(d) < 1, d and w being the floats tsdf_hip_download returns (PACKED layout:
  * w = min(k, max_weight); a NaN distance is not listed), in the reference's leaf order: ascending key
