@@ -1,7 +1,8 @@
 // Host shell of the MI355X drop-in: cpu_tsdf::MarchingCubesTSDFOctree on top of the C ABI.
 // Mirrors performReconstruction of the reference (src/lib/marching_cubes_tsdf_octree.cpp:108-143): build
 // the vertex cloud (3 vertices per triangle, no sharing), move it by the volume's global transform,
-// pack it into the PolygonMesh blob, polygons = {3i, 3i+1, 3i+2}.
+// pack it into the PolygonMesh blob, polygons = {3i, 3i+1, 3i+2}.  With setFlatten (an extension) the vertex cloud and the
+// polygons are the indexed mesh of tsdf_hip_march_flatten instead.
 #include <cpu_tsdf/marching_cubes_tsdf_octree.h>
 #include <pcl/common/transforms.h>
 #include <pcl/console/print.h>
@@ -59,7 +60,31 @@ void MarchingCubesTSDFOctree::clearCleanup() {
   g_cleanup.erase(this);
 }
 
-MarchingCubesTSDFOctree::~MarchingCubesTSDFOctree() { clearCleanup(); }
+// setFlatten's argument per object, kept like setCleanup's
+static std::map<const MarchingCubesTSDFOctree *, float> g_flatten;
+
+void MarchingCubesTSDFOctree::setFlatten(float min_dist) {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  g_flatten[this] = min_dist;
+}
+
+void MarchingCubesTSDFOctree::clearFlatten() {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  g_flatten.erase(this);
+}
+
+MarchingCubesTSDFOctree::~MarchingCubesTSDFOctree() {
+  clearCleanup();
+  clearFlatten();
+}
+
+static bool flatten_of(const MarchingCubesTSDFOctree *mc, float &out) {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  const auto it = g_flatten.find(mc);
+  if (it == g_flatten.end()) return false;
+  out = it->second;
+  return true;
+}
 
 static bool cleanup_of(const MarchingCubesTSDFOctree *mc, CleanupArgs &out) {
   std::lock_guard<std::mutex> lock(g_cleanup_mutex);
@@ -69,11 +94,15 @@ static bool cleanup_of(const MarchingCubesTSDFOctree *mc, CleanupArgs &out) {
   return true;
 }
 
-// cleanup: NULL, or the arguments of setCleanup -- tsdf_hip_march_cleanup between the march and the fetch
-static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mode, const CleanupArgs *cleanup, std::vector<float> &verts,
-                      std::vector<unsigned char> &rgb) {
+// cleanup: NULL, or the arguments of setCleanup -- tsdf_hip_march_cleanup between the march and the fetch.  flatten: NULL,
+// or setFlatten's min_dist -- tsdf_hip_march_flatten after that, and the INDEXED mesh is fetched: `indexed` is set and
+// `faces` holds its polygons (otherwise the soup: polygon i = {3i, 3i + 1, 3i + 2}).
+static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mode, const CleanupArgs *cleanup, const float *flatten,
+                      std::vector<float> &verts, std::vector<unsigned char> &rgb, std::vector<uint32_t> &faces, bool &indexed) {
   verts.clear();
   rgb.clear();
+  faces.clear();
+  indexed = false;
   if (!vol || !vol->handle()) {
     PCL_ERROR("[cpu_tsdf::MarchingCubesTSDFOctree::reconstruct] no TSDF volume set (or reset() not called)\n");
     return false;
@@ -82,7 +111,17 @@ static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mo
   uint64_t n_tri = 0;
   int rc = tsdf_hip_march(vol->handle(), w_min, mode, &n_tri);
   if (rc == 0 && cleanup) rc = tsdf_hip_march_cleanup(vol->handle(), cleanup->face_dist, cleanup->min_neighbors, &n_tri);
-  if (rc == 0 && n_tri) {
+  if (rc == 0 && flatten) {
+    uint64_t n_verts = 0, n_faces = 0;
+    rc = tsdf_hip_march_flatten(vol->handle(), *flatten, &n_verts, &n_faces);
+    if (rc == 0) {
+      indexed = true;
+      verts.resize((size_t)n_verts * 3);
+      if (mode) rgb.resize((size_t)n_verts * 3);
+      faces.resize((size_t)n_faces * 3);
+      if (n_verts) rc = tsdf_hip_march_fetch_indexed(vol->handle(), verts.data(), mode ? rgb.data() : nullptr, faces.data(), nullptr);
+    }
+  } else if (rc == 0 && n_tri) {
     verts.resize((size_t)n_tri * 9);
     if (mode) rgb.resize((size_t)n_tri * 9);
     rc = tsdf_hip_march_fetch(vol->handle(), verts.data(), mode ? rgb.data() : nullptr, nullptr);
@@ -92,17 +131,19 @@ static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mo
               tsdf_hip_last_error());
     verts.clear();
     rgb.clear();
+    faces.clear();
+    indexed = false;
     return false;
   }
   return true;
 }
 
-static void fill_polygons(size_t n_vertices, std::vector<pcl::Vertices> &polygons) {
-  polygons.resize(n_vertices / 3);
+static void fill_polygons(size_t n_vertices, bool indexed, const std::vector<uint32_t> &faces, std::vector<pcl::Vertices> &polygons) {
+  polygons.resize(indexed ? faces.size() / 3 : n_vertices / 3);
   for (size_t i = 0; i < polygons.size(); ++i) {
     pcl::Vertices v;
     v.vertices.resize(3);
-    for (int j = 0; j < 3; ++j) v.vertices[j] = static_cast<int>(i) * 3 + j;
+    for (int j = 0; j < 3; ++j) v.vertices[j] = indexed ? faces[3 * i + j] : static_cast<int>(i) * 3 + j;
     polygons[i] = v;
   }
 }
@@ -113,8 +154,12 @@ void MarchingCubesTSDFOctree::performReconstruction(pcl::PolygonMesh &output) {
   const int mode = color_by_confidence_ ? 2 : (color_by_rgb_ ? 1 : 0);
   std::vector<float> verts;
   std::vector<unsigned char> rgb;
+  std::vector<uint32_t> faces;
+  bool indexed = false;
   CleanupArgs cleanup;
-  run_march(tsdf_volume_, w_min_, mode, cleanup_of(this, cleanup) ? &cleanup : nullptr, verts, rgb);
+  float flatten = 0.f;
+  run_march(tsdf_volume_, w_min_, mode, cleanup_of(this, cleanup) ? &cleanup : nullptr, flatten_of(this, flatten) ? &flatten : nullptr, verts, rgb,
+            faces, indexed);
   const size_t n = verts.size() / 3;
   const Eigen::Affine3d g = tsdf_volume_ ? tsdf_volume_->getGlobalTransform() : Eigen::Affine3d::Identity();
   if (mode) {
@@ -147,15 +192,19 @@ void MarchingCubesTSDFOctree::performReconstruction(pcl::PolygonMesh &output) {
     pcl::transformPointCloud(cloud, cloud, g);
     pcl::toPCLPointCloud2(cloud, output.cloud);
   }
-  fill_polygons(n, output.polygons);
+  fill_polygons(n, indexed, faces, output.polygons);
 }
 
 void MarchingCubesTSDFOctree::performReconstruction(pcl::PointCloud<pcl::PointXYZ> &points,
                                                     std::vector<pcl::Vertices> &polygons) {
   std::vector<float> verts;
   std::vector<unsigned char> rgb;
+  std::vector<uint32_t> faces;
+  bool indexed = false;
   CleanupArgs cleanup;
-  run_march(tsdf_volume_, w_min_, 0, cleanup_of(this, cleanup) ? &cleanup : nullptr, verts, rgb);
+  float flatten = 0.f;
+  run_march(tsdf_volume_, w_min_, 0, cleanup_of(this, cleanup) ? &cleanup : nullptr, flatten_of(this, flatten) ? &flatten : nullptr, verts, rgb,
+            faces, indexed);
   const size_t n = verts.size() / 3;
   points.points.resize(n);
   points.width = (uint32_t)n;
@@ -166,7 +215,7 @@ void MarchingCubesTSDFOctree::performReconstruction(pcl::PointCloud<pcl::PointXY
     points.points[i].z = verts[3 * i + 2];
   }
   if (tsdf_volume_) pcl::transformPointCloud(points, points, tsdf_volume_->getGlobalTransform());
-  fill_polygons(n, polygons);
+  fill_polygons(n, indexed, faces, polygons);
 }
 
 }  // namespace cpu_tsdf

@@ -306,7 +306,12 @@ int main(int argc, char **argv) {
   if (s.color) mc.setColorByRGB(true);
   pcl::PolygonMesh mesh;
   mc.reconstruct(mesh);
-  if (s.flatten) cpu_tsdf::mesh_post::flattenVertices(mesh);
+  if (s.flatten) {  // on the GPU (tsdf_hip_mesh_flatten); TSDF_HIP_HOST_MESH_POST=1 keeps the host pass
+    if (const int rc = cpu_tsdf::mesh_post::flattenVerticesAuto(mesh)) {
+      PCL_ERROR("--flatten: %s: %s\n", tsdf_hip_error_string(rc), tsdf_hip_last_error());
+      return 1;
+    }
+  }
   if (s.cleanup) {  // on the GPU (tsdf_hip_mesh_cleanup); TSDF_HIP_HOST_MESH_POST=1 keeps the host pass
     if (const int rc = cpu_tsdf::mesh_post::cleanupMeshAuto(mesh)) {
       PCL_ERROR("--cleanup: %s: %s\n", tsdf_hip_error_string(rc), tsdf_hip_last_error());

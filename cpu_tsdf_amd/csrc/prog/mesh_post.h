@@ -6,7 +6,9 @@
 //   flattenVertices (:103-158): vertices are visited in index order; an unassigned vertex opens a new output
 //     vertex and EVERY vertex strictly within min_dist of it -- assigned or not -- is (re)mapped to it; faces
 //     are re-indexed, a face with two equal corners is dropped, face order is kept.  Colours are lost (the
-//     reference converts the cloud to PointXYZ).
+//     reference converts the cloud to PointXYZ).  flattenVerticesGpu gets the same seeds and faces from the GPU
+//     (tsdf_hip_mesh_flatten: the loop's result is a function of the input); the host pass stays: it
+//     defines the result.
 //   cleanupMesh (:160-237): faces whose centroids form a connected group (links: centroid distance strictly
 //     below face_dist) of at most min_neighbors faces are removed; vertices no face uses are removed; vertex
 //     and face order are kept.  Colours are lost likewise.  cleanupMeshGpu gets the same face set from the GPU
@@ -117,6 +119,32 @@ inline void flattenVertices(pcl::PolygonMesh &mesh, float min_dist = 0.0001f) {
   storeVertices(xyz, seeds, mesh);
 }
 
+// The same result with the seeds and the re-indexed faces computed on the GPU (tsdf_hip_mesh_flatten, which reproduces the
+// pass above vertex for vertex and face for face); the vertex blob is built here, as above.  A mesh with a polygon that is
+// not a triangle keeps the host pass.  0, or the library's error code (its text in tsdf_hip_last_error) with the mesh
+// untouched.
+inline int flattenVerticesGpu(pcl::PolygonMesh &mesh, float min_dist = 0.0001f, int device = 0) {
+  for (const auto &p : mesh.polygons)
+    if (p.vertices.size() != 3) {
+      flattenVertices(mesh, min_dist);
+      return 0;
+    }
+  const std::vector<float> xyz = vertexPositions(mesh);
+  const size_t n = xyz.size() / 3, nf = mesh.polygons.size();
+  std::vector<std::uint32_t> faces(3 * nf), seeds(n);
+  for (size_t f = 0; f < nf; ++f)
+    for (int k = 0; k < 3; ++k) faces[3 * f + k] = mesh.polygons[f].vertices[k];
+  std::uint64_t n_out = 0, n_kept = 0;
+  // (the re-indexed faces come back in place of the ones handed over: the library has read those before it writes)
+  const int rc = tsdf_hip_mesh_flatten(device, xyz.data(), n, faces.data(), nf, min_dist, nullptr, seeds.data(), &n_out, faces.data(), &n_kept);
+  if (rc) return rc;
+  mesh.polygons.resize((size_t)n_kept);
+  for (size_t f = 0; f < (size_t)n_kept; ++f)
+    for (int k = 0; k < 3; ++k) mesh.polygons[f].vertices[k] = faces[3 * f + k];
+  storeVertices(xyz, std::vector<int>(seeds.begin(), seeds.begin() + (size_t)n_out), mesh);
+  return 0;
+}
+
 // The tail of cleanupMesh (:208-237): the polygons with drop[f] set go, then the vertices no face uses; vertex and face
 // order are kept, faces are re-indexed.
 inline void dropFaces(pcl::PolygonMesh &mesh, const std::vector<float> &xyz, const std::vector<char> &drop) {
@@ -215,6 +243,23 @@ inline int cleanupMeshAuto(pcl::PolygonMesh &mesh, float face_dist = 0.02f, int 
     return 0;
   }
   return cleanupMeshGpu(mesh, face_dist, min_neighbors);
+}
+
+// Vertices up to which --flatten keeps the host pass: the largest prefix at which tools/time_flatten.py measured the
+// GPU-backed pass (upload, device pass, download, this file's tail) slower than flattenVertices
+// (profiles/flatten_timing.json, "gpu_backed_pass_loses_up_to_vertices": 30000 at 512^3 -- 7.6 ms against 2.6 ms; the next
+// prefix, 90000, wins).
+constexpr size_t kFlattenHostBelowVertices = 30000;
+
+// --flatten of the `integrate` program: the GPU pass from the crossover up, the host pass below it, or always with
+// TSDF_HIP_HOST_MESH_POST=1 (A/B runs, tools/time_flatten.py).  The result does not depend on the choice.
+inline int flattenVerticesAuto(pcl::PolygonMesh &mesh, float min_dist = 0.0001f) {
+  const char *host = std::getenv("TSDF_HIP_HOST_MESH_POST");
+  if ((host && host[0] == '1') || (size_t)mesh.cloud.width * mesh.cloud.height <= kFlattenHostBelowVertices) {
+    flattenVertices(mesh, min_dist);
+    return 0;
+  }
+  return flattenVerticesGpu(mesh, min_dist);
 }
 
 }  // namespace mesh_post

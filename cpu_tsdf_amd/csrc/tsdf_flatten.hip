@@ -1,0 +1,612 @@
+// libtsdf_hip.so -- merging the duplicate vertices of a triangle mesh.
+//
+// Replaces flattenVertices of the reference's `integrate` program (src/prog/integrate.cpp:103-150), as this repository's
+// host restatement cpu_tsdf::mesh_post::flattenVertices (csrc/prog/mesh_post.h) defines it operation for operation.  That
+// pass is a serial loop over the vertices in index order; its RESULT is a function of the input alone.
+// Two vertices are NEIGHBOURS when the host's test holds between them (symmetric bit for bit); then
+//   1. vertex i is a SEED (opens an output vertex) iff no earlier seed is its neighbour: the lexicographically first
+//      maximal independent set of the neighbour graph in index order.  Iterated to a fixed point: an undecided vertex is
+//      MERGED as soon as one earlier neighbour is a seed, and a SEED as soon as all earlier neighbours are merged.  The
+//      lowest undecided vertex always decides, so at most n rounds; in fact as many as the longest index-ordered chain.
+//   2. remap[j] of a merged vertex is the output index of the HIGHEST seed among its neighbours (the loop lets every seed
+//      overwrite its neighbours' entries: the last writer wins); of a seed, its own.
+//   3. the output index of a seed is the number of seeds before it: an exclusive scan of the seed flags.
+// Kernels:
+//   k_fl_key       the host's cell key per finite vertex (a non-finite vertex is in no cell: a seed that merges nothing)
+//   rocprim sort   (key, vertex) pairs, stable; k_fl_gather writes the positions in sorted order and marks run heads, a scan
+//                  numbers the cells, k_mp_cells / k_mp_cellnbr (tsdf_meshgrid.h) build the cell table
+//   k_fl_round     one round of rule 1 over the list of still undecided vertices, which it compacts for the next round
+//   k_fl_remap     rule 2; rocprim scan: rule 3; k_fl_out: remap and the seed list by output index
+//   k_fl_faces     per face: remapped corners, keep = all three differ; scan + k_mp_compact keep the order
+// The state word of a vertex carries the round that decided it, and a round ignores what the same round decided: every
+// round sees exactly the state the round before left, whatever the order the workgroups run in (so the number of rounds is
+// the depth of the dependency chains, the same in every run), and no kernel waits for another workgroup.
+// Gather-bound pointer chasing and a radix sort: no MFMA.
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include "tsdf_flatten.h"
+#include "tsdf_meshgrid.h"
+#include "tsdf_meshpost.h"
+
+// ---- state -----------------------------------------------------------------------------------------------------------------
+#define FL_C_FINITE 0  // vertices with three finite coordinates
+#define FL_C_BAD 1     // != 0: a face names a vertex >= n_verts
+#define FL_C_ROUNDS 2  // rounds that found an undecided vertex
+#define FL_C_SEEDS 3
+#define FL_C_KEPT 4
+#define FL_C_LIST 5  // three list lengths in rotation: round r reads r % 3, appends to (r + 1) % 3, zeroes (r + 2) % 3
+#define FL_COUNTERS 8
+#define FL_MAX_ROUNDS 0x7fffffffu  // the state word holds round << 1
+
+struct FlWork {
+  void *buf = nullptr;  // per-vertex and per-face arrays + rocprim's temporary storage
+  size_t cap = 0;
+  void *cells = nullptr;  // per-cell arrays (sized once the number of occupied cells is known)
+  size_t cells_cap = 0;
+  unsigned long long *counters = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+struct FlState {  // per handle: the indexed mesh of tsdf_hip_march_flatten
+  FlWork work;
+  bool valid = false, has_rgb = false;
+  uint64_t n_verts = 0, n_faces = 0;
+  void *out = nullptr;  // one handle: vertices, faces, cell keys, colours (device)
+  size_t out_cap = 0, o_faces = 0, o_cell = 0, o_rgb = 0;
+  std::vector<float> h_verts;  // a multi-GPU set: the same on the host, like its soup
+  std::vector<uint8_t> h_rgb;
+  std::vector<uint32_t> h_faces;
+  std::vector<uint64_t> h_cell;
+};
+
+static std::mutex g_fl_mutex;
+static std::unordered_map<tsdf_hip_volume *, std::unique_ptr<FlState>> g_fl;
+static thread_local uint64_t g_fl_stats[4] = {0, 0, 0, 0};  // tsdf_hip_mesh_flatten_stats
+
+static FlState *fl_state(tsdf_hip_volume *v, bool create) {
+  std::lock_guard<std::mutex> lock(g_fl_mutex);
+  auto it = g_fl.find(v);
+  if (it != g_fl.end()) return it->second.get();
+  if (!create) return nullptr;
+  return (g_fl[v] = std::unique_ptr<FlState>(new FlState())).get();
+}
+
+static void fl_work_free(FlWork &w) {
+  if (w.buf) (void)hipFree(w.buf);
+  if (w.cells) (void)hipFree(w.cells);
+  if (w.counters) (void)hipFree(w.counters);
+  for (hipEvent_t e : w.ev)
+    if (e) (void)hipEventDestroy(e);
+  w = FlWork();
+}
+
+void tsdf_flatten_invalidate(tsdf_hip_volume *v) {
+  if (FlState *st = fl_state(v, false)) st->valid = false;
+}
+
+void tsdf_flatten_release(tsdf_hip_volume *v) {
+  std::unique_ptr<FlState> st;
+  {
+    std::lock_guard<std::mutex> lock(g_fl_mutex);
+    auto it = g_fl.find(v);
+    if (it == g_fl.end()) return;
+    st = std::move(it->second);
+    g_fl.erase(it);
+  }
+  TsdfDeviceScope scope(v->multi ? tsdf_multi_first(v)->device : v->device);
+  fl_work_free(st->work);
+  if (st->out) (void)hipFree(st->out);
+}
+
+// ---- kernels ---------------------------------------------------------------------------------------------------------------
+static __global__ void __launch_bounds__(256)
+k_fl_key(const float *__restrict__ verts, uint32_t n, double cell, uint64_t *__restrict__ keys, uint32_t *__restrict__ idx,
+         unsigned long long *__restrict__ counters) {
+  const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+  bool fin = false;
+  if (v < n) {
+    const float x = verts[3ull * v], y = verts[3ull * v + 1ull], z = verts[3ull * v + 2ull];
+    uint64_t key = MP_NO_KEY;
+    if (isfinite(x) && isfinite(y) && isfinite(z)) {
+      // PointGrid::c / key (mesh_post.h:59-62): floor((double)v / cell), 21 bits per axis.  Cells that alias under the masks
+      // share a bucket, as on the host; the distance test rejects what is far.
+      const long long cx = (long long)floor((double)x / cell), cy = (long long)floor((double)y / cell), cz = (long long)floor((double)z / cell);
+      key = ((uint64_t)(cx & 0x1fffff) << 42) | ((uint64_t)(cy & 0x1fffff) << 21) | (uint64_t)(cz & 0x1fffff);
+      fin = true;
+    }
+    keys[v] = key;
+    idx[v] = v;
+  }
+  const unsigned long long m = __ballot(fin);
+  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[FL_C_FINITE], (unsigned long long)__popcll(m));
+}
+
+// sorted position i -> position of the vertex there, and "first vertex of its cell"
+static __global__ void __launch_bounds__(256)
+k_fl_gather(const float *__restrict__ verts, const uint32_t *__restrict__ order, const uint64_t *__restrict__ keys, uint32_t n,
+            float4 *__restrict__ pos, uint32_t *__restrict__ head) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t key = keys[i];
+  const uint64_t v = order[i];
+  pos[i] = make_float4(verts[3ull * v], verts[3ull * v + 1ull], verts[3ull * v + 2ull], 0.f);
+  head[i] = key != MP_NO_KEY && (i == 0u || keys[i - 1u] != key) ? 1u : 0u;
+}
+
+// State of the vertex at a sorted position: 0 = undecided, else (round that decided it) << 1 | (1 = seed, 0 = merged).
+// Written once, by the thread that owns the vertex; read by others in later launches (and, ignored, in the same one).  The
+// accesses are agent-scope atomics, as in mp_find: a plain load may be served from a line another launch left in a cache.
+static __device__ __forceinline__ uint32_t fl_load(const uint32_t *state, uint32_t i) {
+  return __hip_atomic_load(&state[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Round `round` (1, 2, ..) of rule 1.  list_in == NULL: every finite vertex (round 1); otherwise the cnt[slot_in] positions
+// the round before left undecided.  A vertex that stays undecided goes to list_out.  The grid covers an upper bound of the
+// list's length (the host reads the true one only every few rounds).
+static __global__ void __launch_bounds__(256)
+k_fl_round(const MpGrid g, const uint32_t *__restrict__ order, uint32_t *__restrict__ state, const uint32_t *__restrict__ list_in,
+           uint32_t *__restrict__ list_out, unsigned long long *__restrict__ counters, int slot_in, int slot_out, int slot_zero, uint32_t round) {
+  unsigned long long *cnt = counters + FL_C_LIST;
+  const uint32_t n_in = list_in ? (uint32_t)cnt[slot_in] : g.n_fin;
+  if (blockIdx.x == 0u && threadIdx.x == 0u) {
+    cnt[slot_zero] = 0ull;  // (the next round appends there; nobody touches it in this one)
+    if (n_in) counters[FL_C_ROUNDS] += 1ull;
+  }
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  bool still = false;
+  uint32_t i = 0u;
+  if (t < n_in) {
+    i = list_in ? list_in[t] : t;
+    const uint32_t me = order[i];
+    bool merged = false, pending = false;
+    unsigned tests = 0u;
+    mp_for_links(g, i, tests, [&](uint32_t j) {
+      if (order[j] > me) return true;  // only earlier vertices decide (j != i, so never equal)
+      const uint32_t s = fl_load(state, j);
+      if (s == 0u || (s >> 1) >= round) {
+        pending = true;  // undecided when this round began
+        return true;
+      }
+      merged = (s & 1u) != 0u;
+      return !merged;
+    });
+    if (merged)
+      __hip_atomic_store(&state[i], round << 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if (!pending)
+      __hip_atomic_store(&state[i], (round << 1) | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else
+      still = true;
+  }
+  // one atomic per wave; the order inside the list does not matter
+  const unsigned long long m = __ballot(still);
+  if (m) {
+    const unsigned lane = threadIdx.x & 63u, leader = (unsigned)__ffsll((long long)m) - 1u;
+    uint32_t base = 0u;
+    if (lane == leader) base = (uint32_t)atomicAdd(&cnt[slot_out], (unsigned long long)__popcll(m));
+    base = (uint32_t)__shfl((int)base, (int)leader);
+    if (still) list_out[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
+  }
+}
+
+// Rule 2, per ORIGINAL vertex index: is it a seed, and which seed's output vertex it takes.
+static __global__ void __launch_bounds__(256)
+k_fl_remap(const MpGrid g, uint32_t n, const uint32_t *__restrict__ order, const uint32_t *__restrict__ state, uint8_t *__restrict__ flag,
+           uint32_t *__restrict__ seed_of, unsigned long long *__restrict__ counters) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  bool seed = false;
+  if (i < n) {
+    const uint32_t me = order[i];
+    uint32_t best = me;
+    seed = i >= g.n_fin || (fl_load(state, i) & 1u);  // positions >= n_fin: not finite, no neighbour, not even itself
+    if (!seed) {
+      best = 0u;  // (a merged vertex has a seed among its neighbours: that is what merged it)
+      unsigned tests = 0u;
+      mp_for_links(g, i, tests, [&](uint32_t j) {
+        if (fl_load(state, j) & 1u) best = max(best, order[j]);
+        return true;
+      });
+    }
+    flag[me] = seed ? 1 : 0;
+    seed_of[me] = best;
+  }
+  const unsigned long long m = __ballot(seed);
+  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[FL_C_SEEDS], (unsigned long long)__popcll(m));
+}
+
+// outidx: the exclusive scan of flag (rule 3)
+static __global__ void __launch_bounds__(256)
+k_fl_out(uint32_t n, const uint8_t *__restrict__ flag, const uint32_t *__restrict__ seed_of, const uint32_t *__restrict__ outidx,
+         uint32_t *__restrict__ remap, uint32_t *__restrict__ seeds) {
+  const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+  if (v >= n) return;
+  remap[v] = outidx[seed_of[v]];
+  if (flag[v]) seeds[outidx[v]] = v;
+}
+
+// mesh_post.h:107-115: the corners through remap; a face with two equal corners goes
+static __global__ void __launch_bounds__(256)
+k_fl_faces(const uint32_t *__restrict__ faces, uint32_t n_faces, uint64_t n_verts, const uint32_t *__restrict__ remap,
+           uint32_t *__restrict__ mapped, uint8_t *__restrict__ keep, unsigned long long *__restrict__ counters) {
+  const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+  bool k = false;
+  if (f < n_faces) {
+    uint64_t a = 3ull * f, b = a + 1ull, c = a + 2ull;
+    if (faces) a = faces[3ull * f], b = faces[3ull * f + 1ull], c = faces[3ull * f + 2ull];
+    uint32_t ra = 0u, rb = 0u, rc = 0u;
+    if (a >= n_verts || b >= n_verts || c >= n_verts) {
+      counters[FL_C_BAD] = 1ull;  // (every writer stores the same 1)
+    } else {
+      ra = remap[a], rb = remap[b], rc = remap[c];
+      k = ra != rb && rb != rc && rc != ra;
+    }
+    mapped[3ull * f] = ra, mapped[3ull * f + 1ull] = rb, mapped[3ull * f + 2ull] = rc;
+    keep[f] = k ? 1 : 0;
+  }
+  const unsigned long long m = __ballot(k);
+  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[FL_C_KEPT], (unsigned long long)__popcll(m));
+}
+
+// output vertex o = the seed's position and, on the device-resident path, its colour
+static __global__ void __launch_bounds__(256)
+k_fl_gather_out(const float *__restrict__ verts, const uint8_t *__restrict__ rgb, const uint32_t *__restrict__ seeds, uint32_t m,
+                float *__restrict__ out_verts, uint8_t *__restrict__ out_rgb) {
+  const uint32_t o = blockIdx.x * 256u + threadIdx.x;
+  if (o >= m) return;
+  const uint64_t v = seeds[o];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out_verts[3ull * o + k] = verts[3ull * v + k];
+  if (rgb) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out_rgb[3ull * o + k] = rgb[3ull * v + k];
+  }
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------
+struct FlLayout {  // the arrays inside FlWork::buf
+  size_t key_a, key_b, idx_a, idx_b, pos, cellno, flag, remap, seeds, mapped, faces, keep, offset, tmp, tmp_bytes, total;
+};
+
+static int fl_layout(size_t n, size_t f, hipStream_t s, FlLayout &L) {
+  size_t t_sort = 0, t_scan = 0, t_scan2 = 0;
+  TSDF_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t_sort, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, n,
+                                         0u, 64u, s));
+  TSDF_HIP_TRY(rocprim::inclusive_scan(nullptr, t_scan, (uint32_t *)nullptr, (uint32_t *)nullptr, n, rocprim::plus<uint32_t>(), s));
+  TSDF_HIP_TRY(rocprim::exclusive_scan(nullptr, t_scan2, MpKeepIt(nullptr, MpKeepCount()), (uint32_t *)nullptr, 0u, std::max(n, f),
+                                       rocprim::plus<uint32_t>(), s));
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += mp_up(bytes);
+    return at;
+  };
+  L.key_a = take(n * 8), L.key_b = take(n * 8), L.idx_a = take(n * 4), L.idx_b = take(n * 4), L.pos = take(n * 16);
+  L.cellno = take(n * 4), L.flag = take(n), L.remap = take(n * 4), L.seeds = take(n * 4);
+  L.mapped = take(f * 12), L.faces = take(f * 12), L.keep = take(f), L.offset = take(f * 4);
+  L.tmp_bytes = std::max(t_sort, std::max(t_scan, t_scan2));
+  L.tmp = take(L.tmp_bytes);
+  L.total = o;
+  return TSDF_HIP_OK;
+}
+
+// The whole pass on device arrays.  Leaves in FlWork::buf: remap (n_verts), seeds (*n_out), the surviving faces (L.faces,
+// *n_kept x 3), the faces' keep flags and, when a face went, their offsets; and the stats of the calling thread.  Leaves the
+// stream idle.
+static int fl_core(FlWork &w, hipStream_t s, const float *d_verts, uint64_t n_verts, const uint32_t *d_faces, uint64_t n_faces, float min_dist,
+                   FlLayout &L, uint64_t *n_out, uint64_t *n_kept, const char *who) {
+  const uint32_t n = (uint32_t)n_verts, nf = (uint32_t)n_faces;
+  int rc = fl_layout(n, nf, s, L);
+  if (rc || (rc = mp_reserve(&w.buf, &w.cap, L.total, s, "mesh flatten"))) return rc;
+  if (!w.counters) TSDF_HIP_TRY(hipMalloc(&w.counters, FL_COUNTERS * sizeof(unsigned long long)));
+  for (int i = 0; i < 2; ++i)
+    if (!w.ev[i]) TSDF_HIP_TRY(hipEventCreate(&w.ev[i]));
+  char *b = (char *)w.buf;
+  uint64_t *key_a = (uint64_t *)(b + L.key_a), *key_b = (uint64_t *)(b + L.key_b);
+  uint32_t *idx_a = (uint32_t *)(b + L.idx_a), *order = (uint32_t *)(b + L.idx_b), *cellno = (uint32_t *)(b + L.cellno);
+  float4 *pos = (float4 *)(b + L.pos);
+  uint8_t *flag = (uint8_t *)(b + L.flag), *keep = (uint8_t *)(b + L.keep);
+  uint32_t *remap = (uint32_t *)(b + L.remap), *seeds = (uint32_t *)(b + L.seeds), *mapped = (uint32_t *)(b + L.mapped);
+  uint32_t *faces_out = (uint32_t *)(b + L.faces), *offset = (uint32_t *)(b + L.offset);
+  // free once the sort has run: the unsorted keys' 8 n bytes hold the state and one list, the unsorted indices the run heads
+  // and then the other list; free once the cell table stands: the sorted keys' 8 n bytes hold rule 2's and rule 3's arrays
+  uint32_t *state = (uint32_t *)key_a, *list[2] = {state + n, idx_a}, *head = idx_a;
+  uint32_t *seed_of = (uint32_t *)key_b, *outidx = seed_of + n;
+  const dim3 blk(256), grid_n((n + 255u) / 256u);
+
+  TSDF_HIP_TRY(hipMemsetAsync(w.counters, 0, FL_COUNTERS * sizeof(unsigned long long), s));
+  TSDF_HIP_TRY(hipEventRecord(w.ev[0], s));
+  hipLaunchKernelGGL(k_fl_key, grid_n, blk, 0, s, d_verts, n, (double)min_dist, key_a, idx_a, w.counters);
+  TSDF_HIP_TRY(hipGetLastError());
+  size_t tmp_bytes = L.tmp_bytes;
+  TSDF_HIP_TRY(rocprim::radix_sort_pairs(b + L.tmp, tmp_bytes, key_a, key_b, idx_a, order, (size_t)n, 0u, 64u, s));
+  hipLaunchKernelGGL(k_fl_gather, grid_n, blk, 0, s, d_verts, order, key_b, n, pos, head);
+  TSDF_HIP_TRY(hipGetLastError());
+  tmp_bytes = L.tmp_bytes;
+  TSDF_HIP_TRY(rocprim::inclusive_scan(b + L.tmp, tmp_bytes, head, cellno, (size_t)n, rocprim::plus<uint32_t>(), s));
+  unsigned long long counts[FL_COUNTERS] = {0};
+  uint32_t n_cells = 0;
+  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, sizeof counts, hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipMemcpyAsync(&n_cells, cellno + (n - 1u), sizeof n_cells, hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipStreamSynchronize(s));
+  const uint32_t n_fin = (uint32_t)counts[FL_C_FINITE];
+  MpGrid g{pos, cellno, nullptr, nullptr, n_fin, 0.f};
+  if (n_fin) {
+    const size_t o_start = mp_up((size_t)n_cells * 8), o_nbr = o_start + mp_up(((size_t)n_cells + 1) * 4);
+    if ((rc = mp_reserve(&w.cells, &w.cells_cap, o_nbr + (size_t)n_cells * 27 * 4, s, "mesh flatten"))) return rc;
+    uint64_t *cell_key = (uint64_t *)w.cells;
+    uint32_t *cell_start = (uint32_t *)((char *)w.cells + o_start);
+    int32_t *nbr = (int32_t *)((char *)w.cells + o_nbr);
+    hipLaunchKernelGGL(k_mp_cells, grid_n, blk, 0, s, key_b, head, cellno, n, cell_key, cell_start);
+    TSDF_HIP_TRY(hipGetLastError());
+    TSDF_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(cell_start + n_cells), (int)n_fin, 1, s));
+    hipLaunchKernelGGL(k_mp_cellnbr, dim3((unsigned)((27ull * n_cells + 255ull) / 256ull)), blk, 0, s, cell_key, n_cells, nbr);
+    TSDF_HIP_TRY(hipGetLastError());
+    TSDF_HIP_TRY(hipMemsetAsync(state, 0, (size_t)n * 4, s));
+    // mesh_post.h:96,103: the squared distance is compared with min_dist * min_dist AND with min_dist itself
+    // (integrate.cpp:124), so with the smaller of the two; its root is <= min_dist, so the 27 cells hold every neighbour
+    const float r2 = (float)((double)min_dist * (double)min_dist);
+    g.nbr = nbr, g.cell_start = cell_start, g.r2 = r2 < min_dist ? r2 : min_dist;
+    // rule 1.  The host reads the list's length only once per batch of rounds; the rounds of a batch after the one that
+    // emptied the list find nothing to do.
+    uint32_t undecided = n_fin, round = 0u, batch = 4u;
+    while (undecided) {
+      if (round >= n_fin || round + batch >= FL_MAX_ROUNDS) {
+        tsdf_set_error(std::string(who) + ": " + std::to_string(undecided) + " vertices are undecided after " + std::to_string(round) +
+                       " rounds (every round decides at least the lowest one: this cannot happen)");
+        return TSDF_HIP_E_HIP;
+      }
+      const dim3 grid_u((undecided + 255u) / 256u);
+      for (uint32_t k = 0; k < batch; ++k) {
+        ++round;
+        hipLaunchKernelGGL(k_fl_round, grid_u, blk, 0, s, g, order, state, round == 1u ? nullptr : list[round & 1u], list[(round + 1u) & 1u],
+                           w.counters, (int)(round % 3u), (int)((round + 1u) % 3u), (int)((round + 2u) % 3u), round);
+        TSDF_HIP_TRY(hipGetLastError());
+      }
+      unsigned long long left = 0;
+      TSDF_HIP_TRY(hipMemcpyAsync(&left, w.counters + FL_C_LIST + (round + 1u) % 3u, sizeof left, hipMemcpyDeviceToHost, s));
+      TSDF_HIP_TRY(hipStreamSynchronize(s));
+      undecided = (uint32_t)left;
+      batch = std::min(64u, batch * 2u);
+    }
+  }
+  hipLaunchKernelGGL(k_fl_remap, grid_n, blk, 0, s, g, n, order, state, flag, seed_of, w.counters);
+  TSDF_HIP_TRY(hipGetLastError());
+  tmp_bytes = L.tmp_bytes;
+  TSDF_HIP_TRY(rocprim::exclusive_scan(b + L.tmp, tmp_bytes, MpKeepIt(flag, MpKeepCount()), outidx, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
+  hipLaunchKernelGGL(k_fl_out, grid_n, blk, 0, s, n, flag, seed_of, outidx, remap, seeds);
+  TSDF_HIP_TRY(hipGetLastError());
+  if (nf) {
+    hipLaunchKernelGGL(k_fl_faces, dim3((nf + 255u) / 256u), blk, 0, s, d_faces, nf, n_verts, remap, mapped, keep, w.counters);
+    TSDF_HIP_TRY(hipGetLastError());
+    tmp_bytes = L.tmp_bytes;
+    TSDF_HIP_TRY(rocprim::exclusive_scan(b + L.tmp, tmp_bytes, MpKeepIt(keep, MpKeepCount()), offset, 0u, (size_t)nf, rocprim::plus<uint32_t>(), s));
+    hipLaunchKernelGGL((k_mp_compact<uint32_t, 3>), dim3((unsigned)((3ull * nf + 255ull) / 256ull)), blk, 0, s, mapped, keep, offset, 3ull * nf,
+                       faces_out);
+    TSDF_HIP_TRY(hipGetLastError());
+  }
+  TSDF_HIP_TRY(hipEventRecord(w.ev[1], s));
+  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, sizeof counts, hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipStreamSynchronize(s));
+  if (counts[FL_C_BAD]) {
+    tsdf_set_error(std::string(who) + ": a face names a vertex index >= n_verts");
+    return TSDF_HIP_E_INVALID;
+  }
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, w.ev[0], w.ev[1]);
+  g_fl_stats[0] = n, g_fl_stats[1] = counts[FL_C_SEEDS], g_fl_stats[2] = counts[FL_C_ROUNDS], g_fl_stats[3] = (uint64_t)(ms * 1000.f);
+  *n_out = counts[FL_C_SEEDS];
+  *n_kept = counts[FL_C_KEPT];
+  return TSDF_HIP_OK;
+}
+
+static int fl_check_args(float min_dist, uint64_t n_verts, uint64_t n_faces, const char *who) {
+  if (!(min_dist > 0.f) || !std::isfinite(min_dist)) {
+    tsdf_set_error(std::string(who) + ": min_dist must be finite and positive");
+    return TSDF_HIP_E_INVALID;
+  }
+  if (n_verts > (1ull << 31) || n_faces > (1ull << 31)) {
+    tsdf_set_error(std::string(who) + ": vertex and face indices are 32-bit; more than 2^31 vertices or faces are not accepted");
+    return TSDF_HIP_E_INVALID;
+  }
+  return TSDF_HIP_OK;
+}
+
+static void fl_zero_stats() { g_fl_stats[0] = g_fl_stats[1] = g_fl_stats[2] = g_fl_stats[3] = 0; }
+
+extern "C" int tsdf_hip_mesh_flatten(int device, const float *verts, uint64_t n_verts, const uint32_t *faces, uint64_t n_faces, float min_dist,
+                                     uint32_t *remap, uint32_t *seeds, uint64_t *n_out_verts, uint32_t *out_faces, uint64_t *n_out_faces) {
+  if (n_out_verts) *n_out_verts = 0;
+  if (n_out_faces) *n_out_faces = 0;
+  if (const int rc = fl_check_args(min_dist, n_verts, n_faces, "tsdf_hip_mesh_flatten")) return rc;
+  if (device < 0) return TSDF_HIP_E_INVALID;
+  if ((n_verts && !verts) || (seeds && !n_out_verts) || (out_faces && !n_out_faces)) {
+    tsdf_set_error("tsdf_hip_mesh_flatten: verts must not be NULL, and seeds / out_faces need n_out_verts / n_out_faces");
+    return TSDF_HIP_E_INVALID;
+  }
+  if (!faces && n_verts / 3 < n_faces) {
+    tsdf_set_error("tsdf_hip_mesh_flatten: a triangle soup needs 3 vertices per face");
+    return TSDF_HIP_E_INVALID;
+  }
+  if (n_verts == 0) {
+    if (n_faces) {
+      tsdf_set_error("tsdf_hip_mesh_flatten: a face names a vertex index >= n_verts");
+      return TSDF_HIP_E_INVALID;
+    }
+    fl_zero_stats();
+    return TSDF_HIP_OK;
+  }
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+    (void)hipGetLastError();
+    return TSDF_HIP_E_NODEVICE;
+  }
+  if (device >= n_dev) return TSDF_HIP_E_INVALID;
+  TSDF_ON_DEVICE(device);
+  // everything this call allocates goes when it returns: there is no handle to keep it for
+  struct Call {
+    hipStream_t s = nullptr;
+    void *in = nullptr;
+    FlWork work;
+    MpStage stage;
+    ~Call() {
+      if (s) (void)hipStreamSynchronize(s);
+      fl_work_free(work);
+      if (in) (void)hipFree(in);
+      if (s) (void)hipStreamDestroy(s);
+    }
+  } c;
+  TSDF_HIP_TRY(hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking));
+  const size_t b_verts = mp_up((size_t)n_verts * 12), b_faces = faces ? (size_t)n_faces * 12 : 0;
+  if (hipMalloc(&c.in, b_verts + b_faces) != hipSuccess) {
+    c.in = nullptr;
+    (void)hipGetLastError();
+    tsdf_set_error("tsdf_hip_mesh_flatten: " + std::to_string(b_verts + b_faces) + " bytes of device memory for the mesh are not available");
+    return TSDF_HIP_E_NOMEM;
+  }
+  float *d_verts = (float *)c.in;
+  uint32_t *d_faces = faces && n_faces ? (uint32_t *)((char *)c.in + b_verts) : nullptr;
+  int rc = mp_to_device(c.stage, d_verts, verts, (size_t)n_verts * 12, c.s);
+  if (!rc && d_faces) rc = mp_to_device(c.stage, d_faces, faces, b_faces, c.s);
+  if (rc) return rc;
+  FlLayout L;
+  uint64_t m = 0, kept = 0;
+  if ((rc = fl_core(c.work, c.s, d_verts, n_verts, d_faces, n_faces, min_dist, L, &m, &kept, "tsdf_hip_mesh_flatten"))) return rc;
+  const char *b = (const char *)c.work.buf;
+  if (remap && (rc = mp_to_host(c.stage, remap, b + L.remap, (size_t)n_verts * 4, c.s))) return rc;
+  if (seeds && (rc = mp_to_host(c.stage, seeds, b + L.seeds, (size_t)m * 4, c.s))) return rc;
+  if (out_faces && (rc = mp_to_host(c.stage, out_faces, b + L.faces, (size_t)kept * 12, c.s))) return rc;
+  if (n_out_verts) *n_out_verts = m;
+  if (n_out_faces) *n_out_faces = kept;
+  return TSDF_HIP_OK;
+}
+
+// A set: the merged soup is on the host, so it takes the host-array entry point on the first slab's device, and the indexed
+// mesh stays on the host too -- what one handle holding the whole grid would fetch.
+static int fl_multi(tsdf_handle h, FlState *st, float min_dist) {
+  const uint64_t n = h->mc_ntri;
+  const float *verts = nullptr;
+  const uint8_t *rgb = nullptr;
+  const uint64_t *cell = nullptr;
+  tsdf_multi_mesh(h, &verts, &rgb, &cell);
+  std::vector<uint32_t> remap((size_t)n * 3), seeds((size_t)n * 3);
+  st->h_faces.resize((size_t)n * 3);
+  uint64_t m = 0, kept = 0;
+  const int rc = tsdf_hip_mesh_flatten(tsdf_multi_first(h)->device, verts, 3 * n, nullptr, n, min_dist, remap.data(), seeds.data(), &m,
+                                       st->h_faces.data(), &kept);
+  if (rc) return rc;
+  st->h_faces.resize((size_t)kept * 3);
+  st->h_verts.resize((size_t)m * 3);
+  st->h_rgb.resize(rgb ? (size_t)m * 3 : 0);
+  for (uint64_t o = 0; o < m; ++o) {
+    memcpy(&st->h_verts[3 * o], verts + 3ull * seeds[o], 3 * sizeof(float));
+    if (rgb) memcpy(&st->h_rgb[3 * o], rgb + 3ull * seeds[o], 3);
+  }
+  st->h_cell.clear();
+  for (uint64_t f = 0; f < n; ++f) {
+    const uint32_t a = remap[3 * f], b = remap[3 * f + 1], c = remap[3 * f + 2];
+    if (a != b && b != c && c != a) st->h_cell.push_back(cell[f]);
+  }
+  st->has_rgb = rgb != nullptr;
+  st->n_verts = m, st->n_faces = kept;
+  return TSDF_HIP_OK;
+}
+
+extern "C" int tsdf_hip_march_flatten(tsdf_handle h, float min_dist, uint64_t *n_verts, uint64_t *n_faces) {
+  if (!h) return TSDF_HIP_E_INVALID;
+  if (n_verts) *n_verts = 0;
+  if (n_faces) *n_faces = 0;
+  if (const int rc = fl_check_args(min_dist, 0, 0, "tsdf_hip_march_flatten")) return rc;
+  if (!tsdf_meshpost_marched(h)) {
+    tsdf_set_error("tsdf_hip_march_flatten: the last tsdf_hip_march on this handle did not succeed, or none has run");
+    return TSDF_HIP_E_INVALID;
+  }
+  FlState *st = fl_state(h, true);
+  st->valid = false;
+  const uint64_t n = h->mc_ntri;
+  if (const int rc = fl_check_args(min_dist, 3 * n, n, "tsdf_hip_march_flatten")) return rc;
+  if (!n) {
+    fl_zero_stats();
+    st->n_verts = st->n_faces = 0;
+    st->valid = true;
+    return TSDF_HIP_OK;
+  }
+  if (h->multi) {
+    if (const int rc = fl_multi(h, st, min_dist)) return rc;
+  } else {
+    TSDF_ENTER(h);
+    FlLayout L;
+    uint64_t m = 0, kept = 0;
+    int rc = fl_core(st->work, h->stream, h->mc_verts, 3 * n, nullptr, n, min_dist, L, &m, &kept, "tsdf_hip_march_flatten");
+    if (rc) return rc;
+    // the soup stays as it is: the indexed mesh gets buffers of its own
+    st->o_faces = mp_up((size_t)m * 12), st->o_cell = st->o_faces + mp_up((size_t)kept * 12), st->o_rgb = st->o_cell + mp_up((size_t)kept * 8);
+    if ((rc = mp_reserve(&st->out, &st->out_cap, st->o_rgb + mp_up((size_t)m * 3), h->stream, "mesh flatten"))) return rc;
+    char *b = (char *)st->work.buf, *o = (char *)st->out;
+    const dim3 blk(256);
+    hipLaunchKernelGGL(k_fl_gather_out, dim3((unsigned)((m + 255) / 256)), blk, 0, h->stream, h->mc_verts, h->mc_has_rgb ? h->mc_rgb : nullptr,
+                       (const uint32_t *)(b + L.seeds), (uint32_t)m, (float *)o, (uint8_t *)(o + st->o_rgb));
+    TSDF_HIP_TRY(hipGetLastError());
+    if (kept) {
+      TSDF_HIP_TRY(hipMemcpyAsync(o + st->o_faces, b + L.faces, (size_t)kept * 12, hipMemcpyDeviceToDevice, h->stream));
+      hipLaunchKernelGGL((k_mp_compact<uint64_t, 1>), dim3((unsigned)((n + 255) / 256)), blk, 0, h->stream, h->mc_cell, (const uint8_t *)(b + L.keep),
+                         (const uint32_t *)(b + L.offset), n, (uint64_t *)(o + st->o_cell));
+      TSDF_HIP_TRY(hipGetLastError());
+    }
+    TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
+    st->has_rgb = h->mc_has_rgb;
+    st->n_verts = m, st->n_faces = kept;
+  }
+  st->valid = true;
+  if (n_verts) *n_verts = st->n_verts;
+  if (n_faces) *n_faces = st->n_faces;
+  return TSDF_HIP_OK;
+}
+
+extern "C" int tsdf_hip_march_fetch_indexed(tsdf_handle h, float *verts, uint8_t *rgb, uint32_t *faces, uint64_t *cell) {
+  if (!h) return TSDF_HIP_E_INVALID;
+  FlState *st = fl_state(h, false);
+  if (!st || !st->valid) {
+    tsdf_set_error("tsdf_hip_march_fetch_indexed: no indexed mesh: tsdf_hip_march_flatten has not run since the last tsdf_hip_march / "
+                   "tsdf_hip_march_cleanup");
+    return TSDF_HIP_E_INVALID;
+  }
+  if (rgb && !st->has_rgb && st->n_verts) {
+    tsdf_set_error("the last tsdf_hip_march ran without a colour mode");
+    return TSDF_HIP_E_INVALID;
+  }
+  const size_t m = (size_t)st->n_verts, k = (size_t)st->n_faces;
+  if (h->multi) {
+    if (verts && m) memcpy(verts, st->h_verts.data(), m * 12);
+    if (rgb && m) memcpy(rgb, st->h_rgb.data(), m * 3);
+    if (faces && k) memcpy(faces, st->h_faces.data(), k * 12);
+    if (cell && k) memcpy(cell, st->h_cell.data(), k * 8);
+    return TSDF_HIP_OK;
+  }
+  if (!m) return TSDF_HIP_OK;
+  TSDF_ENTER(h);
+  const char *o = (const char *)st->out;
+  int rc = TSDF_HIP_OK;
+  if (verts && (rc = tsdf_to_host(h, verts, o, m * 12))) return rc;
+  if (rgb && (rc = tsdf_to_host(h, rgb, o + st->o_rgb, m * 3))) return rc;
+  if (faces && k && (rc = tsdf_to_host(h, faces, o + st->o_faces, k * 12))) return rc;
+  if (cell && k && (rc = tsdf_to_host(h, cell, o + st->o_cell, k * 8))) return rc;
+  TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
+  return TSDF_HIP_OK;
+}
+
+extern "C" int tsdf_hip_mesh_flatten_stats(uint64_t out[4]) {
+  if (!out) return TSDF_HIP_E_INVALID;
+  for (int i = 0; i < 4; ++i) out[i] = g_fl_stats[i];
+  return TSDF_HIP_OK;
+}

@@ -10,6 +10,8 @@ void tsdf_meshpost_release(tsdf_hip_volume *v);
 // tsdf_hip_march notes the outcome of every call here: tsdf_hip_march_cleanup refuses a handle that never marched, or whose
 // last march failed (its buffers then hold nothing that call vouches for).
 void tsdf_meshpost_note_march(tsdf_hip_volume *v, bool succeeded);
+// Did the last tsdf_hip_march on this handle succeed?  (tsdf_hip_march_flatten asks: it works on that result too.)
+bool tsdf_meshpost_marched(tsdf_hip_volume *v);
 
 // tsdf_multi.hip: the merged mesh of a multi-GPU set lives on the host; it goes through tsdf_hip_mesh_cleanup on the first
 // slab's device and the host copy is compacted.

@@ -7,7 +7,8 @@
 // exactly:
 //   k_mp_centroid  centroid ((v0 + v1) + v2) / 3.f and the host's cell key per face; non-finite centroids get the key ~0
 //   rocprim sort   (key, face) pairs; k_mp_gather writes the centroids in sorted order and marks run heads, a scan numbers
-//                  the cells, k_mp_cells / k_mp_cellnbr build the cell table and each cell's 27 neighbour cells
+//                  the cells, k_mp_cells / k_mp_cellnbr build the cell table and each cell's 27 neighbour cells (these two,
+//                  mp_for_links and k_mp_compact live in tsdf_meshgrid.h: tsdf_flatten.hip builds the same grid of vertices)
 //   k_mp_degree    links per face, leaving at min_neighbors: a face with that many links is HEAVY -- its group has more than
 //                  min_neighbors faces whatever else it holds.  On a surface nearly every face is heavy after a few tests.
 //   k_mp_link      the LIGHT faces enumerate all their links and join a lock-free union-find (CAS hooking of the larger root
@@ -33,6 +34,8 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
+#include "tsdf_flatten.h"
+#include "tsdf_meshgrid.h"
 #include "tsdf_meshpost.h"
 
 // ---- state -----------------------------------------------------------------------------------------------------------------
@@ -42,7 +45,6 @@
 #define MP_C_KEPT 2
 #define MP_C_TESTS 8
 #define MP_COUNTERS (MP_C_TESTS + MP_TEST_SLOTS)
-#define MP_STAGE (4u << 20)  // bytes per slot of the pinned staging buffer of the host-array entry point
 
 struct MpWork {
   void *buf = nullptr;  // per-face arrays + rocprim's temporary storage
@@ -81,9 +83,16 @@ static void mp_work_free(MpWork &w) {
 
 void tsdf_meshpost_note_march(tsdf_hip_volume *v, bool succeeded) {
   if (MpState *st = mp_state(v, succeeded)) st->marched = succeeded;  // (a failure on a handle without an entry needs none)
+  tsdf_flatten_invalidate(v);  // an indexed mesh of the soup before this march describes nothing any more
+}
+
+bool tsdf_meshpost_marched(tsdf_hip_volume *v) {
+  const MpState *st = mp_state(v, false);
+  return st && st->marched;
 }
 
 void tsdf_meshpost_release(tsdf_hip_volume *v) {
+  tsdf_flatten_release(v);
   std::unique_ptr<MpState> st;
   {
     std::lock_guard<std::mutex> lock(g_mp_mutex);
@@ -97,7 +106,6 @@ void tsdf_meshpost_release(tsdf_hip_volume *v) {
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
-#define MP_NO_KEY (~0ull)  // a face whose centroid is not finite: in no cell (PointGrid skips it), last in the sorted order
 
 // mesh_post.h:124 -- ((v0 + v1) + v2) / 3.f per component (the build keeps -ffp-contract=off and hipcc's correctly rounded
 // float division).  false: the face names a vertex that does not exist.
@@ -147,69 +155,6 @@ k_mp_gather(const float *__restrict__ verts, uint64_t n_verts, const uint32_t *_
   if (key != MP_NO_KEY) (void)mp_centroid(verts, n_verts, faces, order[i], c);
   cen[i] = make_float4(c[0], c[1], c[2], 0.f);
   head[i] = key != MP_NO_KEY && (i == 0u || keys[i - 1u] != key) ? 1u : 0u;
-}
-
-// cellno: the inclusive scan of head (cell of position i = cellno[i] - 1)
-static __global__ void __launch_bounds__(256)
-k_mp_cells(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ head, const uint32_t *__restrict__ cellno, uint32_t n,
-           uint64_t *__restrict__ cell_key, uint32_t *__restrict__ cell_start) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n || !head[i]) return;
-  const uint32_t c = cellno[i] - 1u;
-  cell_key[c] = keys[i];
-  cell_start[c] = i;
-}
-
-// the 27 cells PointGrid::forNeighbours visits (mesh_post.h:39-43), as indices into the cell table (-1: empty); slot
-// (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1), so slot 13 is the cell itself
-static __global__ void __launch_bounds__(256)
-k_mp_cellnbr(const uint64_t *__restrict__ cell_key, uint32_t n_cells, int32_t *__restrict__ nbr) {
-  const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (t >= 27ull * n_cells) return;
-  const uint32_t c = (uint32_t)(t / 27ull), s = (uint32_t)(t - 27ull * c);
-  const uint64_t key = cell_key[c];
-  const int dx = (int)(s % 3u) - 1, dy = (int)((s / 3u) % 3u) - 1, dz = (int)(s / 9u) - 1;
-  const uint64_t want = ((((key >> 42) + (uint64_t)(int64_t)dx) & 0x1fffffull) << 42) | ((((key >> 21) + (uint64_t)(int64_t)dy) & 0x1fffffull) << 21) |
-                        ((key + (uint64_t)(int64_t)dz) & 0x1fffffull);
-  uint32_t lo = 0u, hi = n_cells;  // the keys ascend
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (cell_key[mid] < want)
-      lo = mid + 1u;
-    else
-      hi = mid;
-  }
-  nbr[t] = lo < n_cells && cell_key[lo] == want ? (int32_t)lo : -1;
-}
-
-struct MpGrid {
-  const float4 *cen;
-  const uint32_t *cellno;
-  const int32_t *nbr;
-  const uint32_t *cell_start;  // n_cells + 1 entries
-  uint32_t n_fin;
-  float r2;
-};
-
-// f(j) for every j != i with a link to i (mesh_post.h:44-47: (ex * ex + ey * ey) + ez * ez < r2 in float, strict), the own
-// cell first; f returns false to stop.  The link test is symmetric bit for bit (ex only changes sign).
-template <typename F>
-static __device__ __forceinline__ void mp_for_links(const MpGrid &g, uint32_t i, unsigned &tests, F f) {
-  const float4 p = g.cen[i];
-  const int32_t *nb = g.nbr + 27ull * (g.cellno[i] - 1u);
-  for (int k = 0; k < 27; ++k) {
-    const int32_t c = nb[k < 14 ? 13 - k : k];  // 13, 12 .. 0, 14 .. 26
-    if (c < 0) continue;
-    const uint32_t e = g.cell_start[c + 1];
-    for (uint32_t j = g.cell_start[c]; j < e; ++j) {
-      if (j == i) continue;
-      const float4 q = g.cen[j];
-      const float ex = q.x - p.x, ey = q.y - p.y, ez = q.z - p.z;
-      ++tests;
-      if ((ex * ex + ey * ey) + ez * ez < g.r2)
-        if (!f(j)) return;
-    }
-  }
 }
 
 static __device__ __forceinline__ void mp_add_tests(unsigned tests, unsigned long long *counters) {
@@ -307,42 +252,7 @@ k_mp_keep(uint32_t n, uint32_t n_fin, uint32_t min_nb, const uint32_t *__restric
   if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[MP_C_KEPT], (unsigned long long)__popcll(m));
 }
 
-// stable compaction of per-triangle records of K elements: one thread per input element
-template <typename T, int K>
-static __global__ void __launch_bounds__(256)
-k_mp_compact(const T *__restrict__ src, const uint8_t *__restrict__ keep, const uint32_t *__restrict__ offset, uint64_t n_elems,
-             T *__restrict__ dst) {
-  const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (e >= n_elems) return;
-  const uint64_t t = e / (uint64_t)K;
-  if (keep[t]) dst[(uint64_t)offset[t] * K + (e - t * K)] = src[e];
-}
-
-struct MpKeepCount {
-  __host__ __device__ uint32_t operator()(uint8_t k) const { return k ? 1u : 0u; }
-};
-using MpKeepIt = rocprim::transform_iterator<const uint8_t *, MpKeepCount, uint32_t>;
-
 // ---- host ------------------------------------------------------------------------------------------------------------------
-static int mp_reserve(void **p, size_t *cap, size_t need, hipStream_t s) {
-  if (need <= *cap && *p) return TSDF_HIP_OK;
-  if (*p) {
-    TSDF_HIP_TRY(hipStreamSynchronize(s));
-    TSDF_HIP_TRY(hipFree(*p));
-    *p = nullptr, *cap = 0;
-  }
-  if (hipMalloc(p, need) != hipSuccess) {
-    *p = nullptr;
-    (void)hipGetLastError();
-    tsdf_set_error("mesh cleanup: " + std::to_string(need) + " bytes of device memory for the working set are not available");
-    return TSDF_HIP_E_NOMEM;
-  }
-  *cap = need;
-  return TSDF_HIP_OK;
-}
-
-static inline size_t mp_up(size_t v) { return (v + 255) / 256 * 256; }
-
 struct MpLayout {  // the per-face arrays inside MpWork::buf
   size_t key_a, key_b, idx_a, idx_b, cen, cellno, heavy, any_heavy, keep, tmp, tmp_bytes, total;
 };
@@ -464,69 +374,6 @@ static int mp_check_args(float face_dist, int min_neighbors, uint64_t n_faces, c
   return TSDF_HIP_OK;
 }
 
-// Is `p` host memory the runtime knows as pinned?  (As tsdf_to_host / tsdf_to_device decide: the DMA engine then reads and
-// writes it directly.)
-static bool mp_is_pinned(const void *p) {
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return attr.type == hipMemoryTypeHost;
-}
-
-struct MpStage {  // two pinned slots for pageable caller memory
-  char *pinned = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~MpStage() {
-    if (pinned) (void)hipHostFree(pinned);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  int ready() {
-    if (pinned) return TSDF_HIP_OK;
-    TSDF_HIP_TRY(hipHostMalloc((void **)&pinned, 2 * (size_t)MP_STAGE, hipHostMallocDefault));
-    for (int i = 0; i < 2; ++i) TSDF_HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-    return TSDF_HIP_OK;
-  }
-};
-
-static int mp_to_device(MpStage &st, void *dst, const void *src, size_t bytes, hipStream_t s) {
-  if (!bytes) return TSDF_HIP_OK;
-  if (bytes >= (64u << 10) && mp_is_pinned(src)) {
-    TSDF_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-    return TSDF_HIP_OK;
-  }
-  if (const int rc = st.ready()) return rc;
-  for (size_t off = 0, k = 0; off < bytes; off += MP_STAGE, ++k) {
-    const int slot = (int)(k & 1);
-    if (k >= 2) TSDF_HIP_TRY(hipEventSynchronize(st.ev[slot]));  // the copy that last read this slot has finished
-    const size_t len = std::min((size_t)MP_STAGE, bytes - off);
-    memcpy(st.pinned + (size_t)slot * MP_STAGE, (const char *)src + off, len);
-    TSDF_HIP_TRY(hipMemcpyAsync((char *)dst + off, st.pinned + (size_t)slot * MP_STAGE, len, hipMemcpyHostToDevice, s));
-    TSDF_HIP_TRY(hipEventRecord(st.ev[slot], s));
-  }
-  TSDF_HIP_TRY(hipStreamSynchronize(s));  // (the slots are free again for the way back)
-  return TSDF_HIP_OK;
-}
-
-static int mp_to_host(MpStage &st, void *dst, const void *src, size_t bytes, hipStream_t s) {
-  if (!bytes) return TSDF_HIP_OK;
-  if (bytes >= (64u << 10) && mp_is_pinned(dst)) {
-    TSDF_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
-    TSDF_HIP_TRY(hipStreamSynchronize(s));
-    return TSDF_HIP_OK;
-  }
-  if (const int rc = st.ready()) return rc;
-  for (size_t off = 0; off < bytes; off += MP_STAGE) {
-    const size_t len = std::min((size_t)MP_STAGE, bytes - off);
-    TSDF_HIP_TRY(hipMemcpyAsync(st.pinned, (const char *)src + off, len, hipMemcpyDeviceToHost, s));
-    TSDF_HIP_TRY(hipStreamSynchronize(s));
-    memcpy((char *)dst + off, st.pinned, len);
-  }
-  return TSDF_HIP_OK;
-}
-
 extern "C" int tsdf_hip_mesh_cleanup(int device, const float *verts, uint64_t n_verts, const uint32_t *faces, uint64_t n_faces, float face_dist,
                                      int min_neighbors, uint8_t *keep, uint64_t *n_kept) {
   if (n_kept) *n_kept = 0;
@@ -590,6 +437,7 @@ extern "C" int tsdf_hip_march_cleanup(tsdf_handle h, float face_dist, int min_ne
     tsdf_set_error("tsdf_hip_march_cleanup: the last tsdf_hip_march on this handle did not succeed, or none has run");
     return TSDF_HIP_E_INVALID;
   }
+  tsdf_flatten_invalidate(h);  // (tsdf_flatten.h: the soup is about to change)
   if (h->multi) return tsdf_multi_march_cleanup(h, face_dist, min_neighbors, n_tri);
   TSDF_ENTER(h);
   const uint64_t n = h->mc_ntri;

@@ -26,6 +26,7 @@
 
 #include "tsdf_common.h"
 #include "tsdf_occupied.h"
+#include "tsdf_flatten.h"
 #include "tsdf_meshpost.h"
 
 struct tsdf_hip_multi {
@@ -1176,6 +1177,14 @@ int tsdf_multi_march_cleanup(tsdf_handle h, float face_dist, int min_neighbors, 
   h->mc_ntri = o;
   if (n_tri) *n_tri = o;
   return TSDF_HIP_OK;
+}
+
+// (tsdf_flatten.h) the merged soup, for tsdf_hip_march_flatten on a set
+void tsdf_multi_mesh(tsdf_handle h, const float **verts, const uint8_t **rgb, const uint64_t **cell) {
+  tsdf_hip_multi *m = h->multi;
+  *verts = m->verts.data();
+  *rgb = m->mesh_has_rgb ? m->rgb.data() : nullptr;
+  *cell = m->cell.data();
 }
 
 int tsdf_multi_march_timing(tsdf_handle h, float ms[3], uint64_t *n_cells) {

@@ -624,6 +624,7 @@ class MarchingCubesTSDFOctree:
         self._by_conf = False
         self._vol = None
         self._cleanup = None
+        self._flatten = None
 
     def setCleanup(self, face_dist=0.02, min_neighbors=5):
         """Extension (no reference counterpart on the class): reconstruct() drops the faces in connected groups of at most
@@ -637,6 +638,22 @@ class MarchingCubesTSDFOctree:
 
     def clearCleanup(self):
         self._cleanup = None
+
+    def setFlatten(self, min_dist=0.0001):
+        """Extension (no reference counterpart on the class): reconstruct() merges the vertices closer than `min_dist` -- the
+        `integrate` program's --flatten (src/prog/integrate.cpp:103-150) -- on the GPU, between the march and the fetch
+        (tsdf_hip_march_flatten), and returns the INDEXED mesh.  It acts in the VOLUME frame, before the global transform,
+        and, unlike the program's pass, keeps the colours: an output vertex has the colour of its seed vertex.  With
+        setCleanup as well, the cleanup runs FIRST, on the soup, and flatten second.  The `integrate` program uses the other
+        order, as the reference does (flatten, then cleanup on the indexed mesh), which is why it goes through the
+        host-array entry points (tsdf_hip_mesh_flatten, tsdf_hip_mesh_cleanup) instead."""
+        min_dist = float(min_dist)
+        if not (np.isfinite(min_dist) and min_dist > 0):
+            raise ValueError("setFlatten: min_dist must be finite and positive")
+        self._flatten = min_dist
+
+    def clearFlatten(self):
+        self._flatten = None
 
     def setInputTSDF(self, volume):
         self._vol = volume
@@ -652,7 +669,8 @@ class MarchingCubesTSDFOctree:
 
     def reconstruct(self, want_cells=False):
         """marching_cubes_tsdf_octree.cpp:108-143.  Returns dict(vertices (3n,3) float32 after the global
-        transform, polygons (n,3) int32 = [3i,3i+1,3i+2], rgb (3n,3) uint8 or None, cells)."""
+        transform, polygons (n,3) int32 = [3i,3i+1,3i+2], rgb (3n,3) uint8 or None, cells).  With setFlatten: the indexed
+        mesh -- vertices (m,3), polygons (k,3) int32 into them, rgb (m,3) or None, cells (k,)."""
         vol = self._vol
         vol._cubic_for_queries("MarchingCubesTSDFOctree.reconstruct")
         h = vol._need()
@@ -662,6 +680,8 @@ class MarchingCubesTSDFOctree:
         capi.check(lib.tsdf_hip_march(h, self._w_min, mode, C.byref(n)), "march")
         if self._cleanup is not None:
             capi.check(lib.tsdf_hip_march_cleanup(h, self._cleanup[0], self._cleanup[1], C.byref(n)), "march_cleanup")
+        if self._flatten is not None:
+            return self._fetch_indexed(vol, h, mode, want_cells)
         nt = int(n.value)
         verts = np.empty((nt * 3, 3), dtype=np.float32)
         rgb = np.empty((nt * 3, 3), dtype=np.uint8) if mode else None
@@ -676,6 +696,26 @@ class MarchingCubesTSDFOctree:
             verts = transform_points_f64(verts, g)
         polys = np.arange(nt * 3, dtype=np.int32).reshape(nt, 3)
         return {"vertices": verts, "polygons": polys, "rgb": rgb, "cells": cells}
+
+    def _fetch_indexed(self, vol, h, mode, want_cells):
+        lib = capi.load()
+        m, k = C.c_uint64(0), C.c_uint64(0)
+        capi.check(lib.tsdf_hip_march_flatten(h, self._flatten, C.byref(m), C.byref(k)), "march_flatten")
+        m, k = int(m.value), int(k.value)
+        verts = np.empty((m, 3), dtype=np.float32)
+        rgb = np.empty((m, 3), dtype=np.uint8) if mode else None
+        faces = np.empty((k, 3), dtype=np.uint32)
+        cells = np.empty(k, dtype=np.uint64) if want_cells else None
+        if m:
+            capi.check(
+                lib.tsdf_hip_march_fetch_indexed(h, capi.as_f32p(verts), capi.as_u8p(rgb) if rgb is not None else None,
+                                                 faces.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 cells.ctypes.data_as(C.POINTER(C.c_uint64)) if cells is not None else None),
+                "march_fetch_indexed")
+        g = vol.getGlobalTransform()
+        if not np.array_equal(g, np.eye(4)):
+            verts = transform_points_f64(verts, g)
+        return {"vertices": verts, "polygons": faces.astype(np.int32), "rgb": rgb, "cells": cells}
 
 
 def cleanup_mesh(vertices, polygons=None, face_dist=0.02, min_neighbors=5, device=0):
@@ -694,6 +734,31 @@ def cleanup_mesh(vertices, polygons=None, face_dist=0.02, min_neighbors=5, devic
                                           faces.ctypes.data_as(C.POINTER(C.c_uint32)) if faces is not None else None, n_faces,
                                           float(face_dist), int(min_neighbors), capi.as_u8p(keep), C.byref(kept)), "mesh_cleanup")
     return keep.astype(bool)
+
+
+def flatten_mesh(vertices, polygons=None, min_dist=0.0001, device=0):
+    """The `integrate` program's --flatten (src/prog/integrate.cpp:103-150) computed on the GPU (tsdf_hip_mesh_flatten):
+    vertices closer than min_dist are merged, faces re-indexed, a face with two equal corners dropped.  vertices (n, 3)
+    float32; polygons (k0, 3) vertex indices, or None for a triangle soup (face f = vertices 3f, 3f+1, 3f+2).  Returns
+    dict(vertices (m, 3) float32, polygons (k, 3) int32, remap (n,) uint32: output vertex of each input vertex, seeds (m,)
+    uint32: input vertex of each output vertex)."""
+    verts = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    faces = None if polygons is None else np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
+    if faces is None and len(verts) % 3:
+        raise ValueError("flatten_mesh: a triangle soup needs 3 vertices per face")
+    n_faces = len(verts) // 3 if faces is None else len(faces)
+    u32p = C.POINTER(C.c_uint32)
+    remap = np.zeros(len(verts), dtype=np.uint32)
+    seeds = np.zeros(len(verts), dtype=np.uint32)
+    out_faces = np.zeros((n_faces, 3), dtype=np.uint32)
+    m, k = C.c_uint64(0), C.c_uint64(0)
+    capi.check(
+        capi.load().tsdf_hip_mesh_flatten(int(device), capi.as_f32p(verts), len(verts),
+                                          faces.ctypes.data_as(u32p) if faces is not None else None, n_faces, float(min_dist),
+                                          remap.ctypes.data_as(u32p), seeds.ctypes.data_as(u32p), C.byref(m),
+                                          out_faces.ctypes.data_as(u32p), C.byref(k)), "mesh_flatten")
+    seeds = seeds[:int(m.value)].copy()
+    return {"vertices": verts[seeds], "polygons": out_faces[:int(k.value)].astype(np.int32), "remap": remap, "seeds": seeds}
 
 
 def reference_cull_planes(p, trans):

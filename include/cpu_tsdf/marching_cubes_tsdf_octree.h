@@ -19,7 +19,7 @@ class MarchingCubesTSDFOctree : public pcl::MarchingCubes<pcl::PointXYZ> {
  public:
   MarchingCubesTSDFOctree()
       : pcl::MarchingCubes<pcl::PointXYZ>(), color_by_confidence_(false), color_by_rgb_(false), w_min_(2.5f) {}
-  ~MarchingCubesTSDFOctree() override;  // forgets the object's setCleanup (see there)
+  ~MarchingCubesTSDFOctree() override;  // forgets the object's setCleanup / setFlatten (see there)
 
   // Mirrors the reference (:44-83): remembers the volume and dresses the base class the same way -- grid resolution,
   // the 8-corner "input cloud", no grid extension, iso level 0, bounding box and size_voxel_.
@@ -36,13 +36,21 @@ class MarchingCubesTSDFOctree : public pcl::MarchingCubes<pcl::PointXYZ> {
   // used to; a member read behind them would be whatever the stack held).  A copy of the object does not carry it.
   void setCleanup(float face_dist = 0.02f, int min_neighbors = 5);
   void clearCleanup();
+  // Extension likewise: reconstruct merges the vertices closer than min_dist -- flattenVertices of the `integrate` program
+  // (src/prog/integrate.cpp:103-150) -- on the GPU, after the march (and after setCleanup's pass, which runs FIRST, on the
+  // soup), and fills the PolygonMesh with the INDEXED mesh: the merged vertices, each with the colour of the vertex that
+  // opened it, and polygons that name them; a face with two equal corners is dropped.  The `integrate` program uses the
+  // other order (flatten, then cleanup), as the reference does, and therefore goes through the host-array entry points.
+  // The argument lives in the shell library next to setCleanup's: the class keeps its size.
+  void setFlatten(float min_dist = 0.0001f);
+  void clearFlatten();
 
   using pcl::MarchingCubes<pcl::PointXYZ>::reconstruct;  // reconstruct(PolygonMesh&), reconstruct(points, polygons)
 
  protected:
   void voxelizeData() override {}  // as in the reference (:86-90): nothing to voxelize, the TSDF is the grid
-  // fills output.cloud (PointXYZ, or PointXYZRGB when a colour mode is on) and output.polygons ({3i, 3i+1, 3i+2});
-  // vertices are moved by the volume's global transform (:108-143)
+  // fills output.cloud (PointXYZ, or PointXYZRGB when a colour mode is on) and output.polygons ({3i, 3i+1, 3i+2}, or the
+  // indexed mesh's with setFlatten); vertices are moved by the volume's global transform (:108-143)
   void performReconstruction(pcl::PolygonMesh &output) override;
   void performReconstruction(pcl::PointCloud<pcl::PointXYZ> &points, std::vector<pcl::Vertices> &polygons) override;
 

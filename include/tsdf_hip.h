@@ -433,6 +433,55 @@ int tsdf_hip_march_cleanup(tsdf_handle h, float face_dist, int min_neighbors, ui
  * stream) before and after the host reads the cell count in between; that read and all transfers are excluded. */
 int tsdf_hip_mesh_cleanup_stats(uint64_t out[4]);
 
+/* flattenVertices -- src/prog/integrate.cpp:103-150 (the `integrate` program's --flatten), as
+ * cpu_tsdf::mesh_post::flattenVertices (csrc/prog/mesh_post.h) defines it: the vertices closer than min_dist are merged and
+ * the faces re-indexed.  Two vertices are NEIGHBOURS when both are finite, lie in neighbouring cells (the 27 around a
+ * vertex's own) of a grid of edge min_dist, cell = floor((double)v / (double)min_dist), and
+ * (ex*ex + ey*ey) + ez*ez < min((float)((double)min_dist * min_dist), min_dist) in float, strictly (the reference compares
+ * the SQUARED distance with min_dist once more, :124).  The host pass visits the vertices in index order; its result is a
+ * function of the input alone, by three rules:
+ *   1. vertex i is a SEED -- it opens an output vertex -- iff no earlier seed is its neighbour.  A vertex that is not finite
+ *      has no neighbour, not even itself: always a seed.
+ *   2. remap[j] of a seed is its own output vertex; of any other vertex, the output vertex of the HIGHEST-indexed seed
+ *      among its neighbours (the loop lets every seed overwrite the entry of every neighbour: the last writer wins).
+ *   3. the output index of a seed is the number of seeds before it.
+ * Faces are re-indexed through remap; a face with two equal corners is dropped, face order is kept.  Output vertex o is
+ * input vertex seeds[o], bit for bit.
+ *   verts, faces   HOST arrays (pinned memory is used directly): n_verts x 3 floats, n_faces x 3 vertex indices;
+ *                  faces == NULL = triangle soup, face f using vertices 3f, 3f + 1, 3f + 2.
+ *   remap          n_verts entries: the output vertex of each input vertex; nullable.
+ *   seeds          room for n_verts entries, the first *n_out_verts are filled: the input vertex of each output vertex;
+ *                  nullable.
+ *   out_faces      room for n_faces x 3 entries, the first *n_out_faces x 3 are filled; nullable.
+ * E_INVALID: min_dist not finite or <= 0, device < 0, more than 2^31 vertices or faces (indices are 32-bit), NULL where
+ * data is needed (verts; n_out_verts with seeds, n_out_faces with out_faces), a soup with fewer than 3 * n_faces vertices,
+ * a face naming a vertex >= n_verts.  All of these but the last are checked before any device call.  n_verts == 0 (with no
+ * face) is OK and touches no device.
+ * Cost: rule 1 is iterated to its fixed point -- an undecided vertex is merged as soon as one earlier neighbour is a seed,
+ * and a seed as soon as all earlier neighbours are merged; one kernel launch per round over the still undecided vertices.
+ * Rounds = the depth of the longest index-ordered chain of near vertices: a handful on a marched mesh (its clusters are the
+ * 2-8 exact copies of a shared edge vertex), n for n vertices strung out in index order at just under min_dist. */
+int tsdf_hip_mesh_flatten(int device, const float *verts, uint64_t n_verts, const uint32_t *faces /* NULL = soup */,
+                          uint64_t n_faces, float min_dist, uint32_t *remap, uint32_t *seeds, uint64_t *n_out_verts,
+                          uint32_t *out_faces, uint64_t *n_out_faces);
+/* The same on the DEVICE-RESIDENT result of the last tsdf_hip_march (after an optional tsdf_hip_march_cleanup; an extension:
+ * the reference flattens the final PolygonMesh on the host).  The soup STAYS: the indexed mesh -- *n_verts vertices,
+ * *n_faces faces -- lives in buffers of its own, and tsdf_hip_march_fetch / _fetch_device keep returning the soup.
+ * E_INVALID before the first tsdf_hip_march on the handle, and after one that failed.  A later tsdf_hip_march or
+ * tsdf_hip_march_cleanup invalidates the indexed mesh.  On a multi-GPU handle the merged mesh (host) goes through
+ * tsdf_hip_mesh_flatten on the first slab's device; the result equals one handle holding the whole grid. */
+int tsdf_hip_march_flatten(tsdf_handle h, float min_dist, uint64_t *n_verts, uint64_t *n_faces);
+/* The indexed mesh of the last tsdf_hip_march_flatten (each pointer nullable): verts n_verts x 3 floats (volume frame), rgb
+ * n_verts x 3 bytes -- the colour of the output vertex's SEED vertex; an extension: the reference converts to PointXYZ and
+ * loses the colours -- faces n_faces x 3 vertex indices, cell[f] the cell key of surviving face f.  E_INVALID while there
+ * is no valid indexed mesh, and for rgb after a march without a colour mode. */
+int tsdf_hip_march_fetch_indexed(tsdf_handle h, float *verts, uint8_t *rgb, uint32_t *faces, uint64_t *cell);
+/* Report-only, of the last flatten (either entry point) on the calling thread: out[0] = vertices in, out[1] = vertices out,
+ * out[2] = seed rounds (launches of rule 1 that found an undecided vertex), out[3] = device microseconds from the first
+ * kernel to the last (HIP events on the stream; the host's reads of the undecided count between batches of rounds fall
+ * inside, the transfers of the host-array entry point do not). */
+int tsdf_hip_mesh_flatten_stats(uint64_t out[4]);
+
 /* getOccupiedVoxelIndices -- src/lib/tsdf_volume_octree.cpp:590-609 (+ OctreeNode::getLeaves, src/lib/octree.cpp:99-109):
  * the voxels with w > 0 && fabsf(d) < 1, d and w being the floats tsdf_hip_download returns (PACKED layout:
  * w = min(k, max_weight); a NaN distance is not listed), in the reference's leaf order: ascending key
