@@ -19,6 +19,7 @@ TEST_LIB_PATH = os.path.join(_HERE, "lib", "libtsdf_hip_test.so")
 LIB_PATH = os.environ.get("TSDF_HIP_LIB_PATH") or PRODUCT_LIB_PATH
 
 OK, E_INVALID, E_NOMEM, E_HIP, E_NODEVICE, E_UNSUPPORTED, E_IO = range(7)
+ALIGN_NO_POINTS, ALIGN_RANK_DEFICIENT = 7, 8  # statuses of tsdf_hip_align only
 XFORM_PCL_SSE, XFORM_LEFT_TO_RIGHT = 0, 1
 LAYOUT_AUTO, LAYOUT_F32W, LAYOUT_PACKED = 0, 1, 2
 COLOR_RGB, COLOR_RGB_NORMALIZED, COLOR_LAB = 0, 1, 2
@@ -123,6 +124,11 @@ SIGNATURES = {
     "tsdf_hip_alloc_probe": (C.c_int, [C.c_void_p, _f32p, C.POINTER(C.c_int32)]),
     "tsdf_hip_sample": (C.c_int, [C.c_void_p, _f32p, C.c_size_t, _f32p, _f32p, _f32p, _u8p]),
     "tsdf_hip_lookup_rgb": (C.c_int, [C.c_void_p, _f32p, C.c_size_t, _u8p, _u8p]),
+    "tsdf_hip_align_system": (C.c_int, [C.c_void_p, _f32p, C.c_size_t, _f64p, C.c_float, C.c_float, _f64p, _u8p, _f32p]),
+    "tsdf_hip_align_system_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _f64p, C.c_float, C.c_float, _f64p]),
+    "tsdf_hip_align": (C.c_int, [C.c_void_p, _f32p, C.c_size_t, _f64p, C.c_float, C.c_float, C.c_int, C.c_double, _f64p,
+                                 C.POINTER(C.c_int32), _f64p]),
+    "tsdf_hip_align_stats": (C.c_int, [C.c_void_p, _u64p]),
     "tsdf_hip_march": (C.c_int, [C.c_void_p, C.c_float, C.c_int, _u64p]),
     "tsdf_hip_march_fetch": (C.c_int, [C.c_void_p, _f32p, _u8p, _u64p]),
     "tsdf_hip_march_fetch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

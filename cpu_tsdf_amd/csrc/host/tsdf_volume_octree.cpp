@@ -542,6 +542,35 @@ bool TSDFVolumeOctree::getFxnGradientAndHessian(const pcl::PointXYZ &pt, float &
   return true;
 }
 
+// ---- alignCloud (not in the reference): tsdf_hip_align_system / tsdf_hip_align ---------------------------------------------
+static void pose12(const Eigen::Affine3d &t, double out[12]) {
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 4; ++c) out[4 * r + c] = t.matrix()(r, c);
+}
+bool TSDFVolumeOctree::getAlignmentSystem(const float *xyz, size_t n, const Eigen::Affine3d &trans, double out[29], float min_weight,
+                                          float r_max) const {
+  if (!ready("getAlignmentSystem") || !cubicForQueries("getAlignmentSystem")) return false;
+  double T[12];
+  pose12(trans, T);
+  const int rc = tsdf_hip_align_system(h_, xyz, n, T, min_weight, r_max, out, nullptr, nullptr);
+  if (rc) report("getAlignmentSystem", rc);
+  return rc == 0;
+}
+bool TSDFVolumeOctree::alignPoints(const float *xyz, size_t n, const Eigen::Affine3d &guess, Eigen::Affine3d &refined, int max_iterations,
+                                   float min_weight, float r_max, double min_step) const {
+  if (!ready("alignCloud") || !cubicForQueries("alignCloud")) return false;
+  double T[12], R[12];
+  pose12(guess, T);
+  const int rc = tsdf_hip_align(h_, xyz, n, T, min_weight, r_max, max_iterations, min_step, R, nullptr, nullptr);
+  if (rc == TSDF_HIP_OK || rc == TSDF_HIP_ALIGN_NO_POINTS || rc == TSDF_HIP_ALIGN_RANK_DEFICIENT) {
+    refined = Eigen::Affine3d::Identity();
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 4; ++c) refined.matrix()(r, c) = R[4 * r + c];
+  }
+  if (rc) report("alignCloud", rc);
+  return rc == 0;
+}
+
 // ---- save / load: the reference's .vol format (src/lib/tsdf_volume_octree.cpp:222-275) -----------------------
 // The format and the block streaming live behind the C ABI (tsdf_hip_save / tsdf_hip_load); this class adds
 // what only it knows: max cell size, the empty flag, the weighting flags and the global transform.

@@ -111,6 +111,8 @@ struct tsdf_hip_volume {
   uint64_t mc_ncells = 0;
   uint64_t mc_d_bytes = 0;   // distance bytes the last classify pass requested (tsdf_hip_march_stats)
   bool mc_skipped = false;   // ... with the band flags deciding what to read
+  hipEvent_t align_ev[2] = {nullptr, nullptr};  // tsdf_hip_align_stats: around the system kernels of the last call
+  uint64_t align_stats[4] = {0, 0, 0, 0};       // points, used, iterations, device microseconds
   void *scratch = nullptr;
   size_t scratch_bytes = 0;
 };
@@ -134,6 +136,8 @@ int tsdf_multi_last_count_detail(tsdf_handle h, uint64_t out[2]);
 int tsdf_multi_last_read_detail(tsdf_handle h, uint64_t out[3]);
 int tsdf_multi_block(tsdf_handle h, bool down, int x0, int y0, int z0, int nx, int ny, int nz, float *d, float *w, uint8_t *rgb);
 int tsdf_multi_sample(tsdf_handle h, const float *xyz, size_t n, float *val, float *grad, float *hess, uint8_t *ok);
+int tsdf_multi_align_system(tsdf_handle h, const float *xyz, size_t n, const double vol_from_src[12], float min_weight, float r_max,
+                            double out[29], uint8_t *used, float *xyz_vol);
 int tsdf_multi_lookup_rgb(tsdf_handle h, const float *xyz, size_t n, uint8_t *rgb, uint8_t *found);
 int tsdf_multi_raycast(tsdf_handle h, const float rot[9], const float origin[3], int downsample, const double *inv, float *out);
 int tsdf_multi_march(tsdf_handle h, float w_min, int color_mode, uint64_t *n_tri);

@@ -44,6 +44,8 @@ extern "C" const char *tsdf_hip_error_string(int code) {
     case TSDF_HIP_E_NODEVICE: return "no HIP device";
     case TSDF_HIP_E_UNSUPPORTED: return "unsupported";
     case TSDF_HIP_E_IO: return "file error";
+    case TSDF_HIP_ALIGN_NO_POINTS: return "alignment: no point passed the gate";
+    case TSDF_HIP_ALIGN_RANK_DEFICIENT: return "alignment: the cloud does not constrain all six freedoms";
   }
   return "unknown";
 }
@@ -434,6 +436,8 @@ static void free_volume(tsdf_hip_volume *v) {
   if (v->mc_need) (void)hipFree(v->mc_need);
   for (int i = 0; i < 4; ++i)
     if (v->mc_ev[i]) (void)hipEventDestroy(v->mc_ev[i]);
+  for (int i = 0; i < 2; ++i)
+    if (v->align_ev[i]) (void)hipEventDestroy(v->align_ev[i]);
   if (v->scratch) (void)hipFree(v->scratch);
   delete v;
 }

@@ -876,6 +876,36 @@ int tsdf_multi_sample(tsdf_handle h, const float *xyz, size_t n, float *val, flo
   return TSDF_HIP_OK;
 }
 
+// ---- alignCloud's normal equations (tsdf_align.hip) ----------------------------------------------------------------------
+// Every slab sums the points whose lower-corner plane it owns (k_sample's ownership test: exactly one slab answers for a
+// point); the host adds the 29-double slab sums in slab order, so the result is a function of the input and the partition.
+int tsdf_multi_align_system(tsdf_handle h, const float *xyz, size_t n, const double vol_from_src[12], float min_weight, float r_max,
+                            double out[29], uint8_t *used, float *xyz_vol) {
+  if (const int rc_flush = tsdf_multi_flush(h)) return rc_flush;  // (frame pairing: slabs launch what they hold first)
+  tsdf_hip_multi *m = h->multi;
+  int rc = exchange_halo(h, 1, false);
+  if (rc) return rc;
+  std::vector<uint8_t> u(used ? n : 0);
+  if (used) memset(used, 0, n);
+  for (int k = 0; k < 29; ++k) out[k] = 0.0;
+  uint64_t usec = 0;
+  for (size_t k = 0; k < m->slab.size(); ++k) {
+    double part[29];
+    rc = tsdf_hip_align_system(m->slab[k], xyz, n, vol_from_src, min_weight, r_max, part, used ? u.data() : nullptr,
+                               k == 0 ? xyz_vol : nullptr);
+    if (rc) return rc;
+    for (int t = 0; t < 29; ++t) out[t] += part[t];
+    if (used)
+      for (size_t i = 0; i < n; ++i) used[i] |= u[i];
+    usec += m->slab[k]->align_stats[3];
+  }
+  h->align_stats[0] = n;
+  h->align_stats[1] = (uint64_t)out[28];
+  h->align_stats[2] = 0;
+  h->align_stats[3] = usec;
+  return TSDF_HIP_OK;
+}
+
 int tsdf_multi_lookup_rgb(tsdf_handle h, const float *xyz, size_t n, uint8_t *rgb, uint8_t *found) {
   if (const int rc_flush = tsdf_multi_flush(h)) return rc_flush;  // (frame pairing: slabs launch what they hold first)
   tsdf_hip_multi *m = h->multi;

@@ -17,47 +17,10 @@
 #include <string.h>
 
 #include "tsdf_common.h"
+#include "tsdf_gridview.h"
 #ifdef TSDF_HIP_TEST_HOOKS
 #include "tsdf_hip_test.h"
 #endif
-
-struct GridView {
-  int nx, ny, nz;        // full resolution
-  int z_first, nz_alloc; // allocated plane range
-  int lv[3];             // octree levels per axis (log2 res) or -1
-  float size[3];
-  float nsize[3];        // size the axis' node centres descend from (tsdf_node_size: size_x on an octree grid)
-  float half[3];         // size/2 in float (root bounds test, octree.cpp:630)
-  int64_t pitch;
-  const float *d;
-  PlaneView pv;          // weights (and colour) through tsdf_load_w: layout-independent
-  const float *ctr[3];   // octree node-centre tables
-};
-
-static GridView make_view(const tsdf_hip_volume *v) {
-  GridView g;
-  g.nx = v->nx;
-  g.ny = v->ny;
-  g.nz = v->nz;
-  g.z_first = v->z_first;
-  g.nz_alloc = v->nz_alloc;
-  for (int a = 0; a < 3; ++a) {
-    g.lv[a] = v->levels[a];
-    g.size[a] = v->p.size[a];
-    g.nsize[a] = tsdf_node_size(v->p, a);
-    g.half[a] = v->p.size[a] / 2;
-    g.ctr[a] = v->ctr[a];
-  }
-  g.pitch = v->pitch;
-  g.d = v->d;
-  g.pv = tsdf_plane_view(v);
-  return g;
-}
-
-// x86 cvttsd2si semantics (see tsdf_integrate.hip)
-static __device__ __forceinline__ int cvtt(double v) {
-  return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN;
-}
 
 // One axis of OctreeNode::getContainingVoxel's descent (octree.cpp:112-121): child bit = (x - ctr) > 0.
 static __device__ __forceinline__ int descend_axis(float x, float size, int L) {
@@ -93,20 +56,6 @@ static __device__ __forceinline__ bool containing(const GridView &g, float x, fl
   local = kl >= 0 && kl < g.nz_alloc;
   vi = ((int64_t)(local ? kl : 0) * g.ny + j) * g.pitch + i;
   return true;
-}
-
-// getVoxelCenter (tsdf_volume_octree.cpp:553-560), one axis: double formula rounded to float.
-static __device__ __forceinline__ float voxel_center(const GridView &g, int a, int i) {
-  const int res = a == 0 ? g.nx : a == 1 ? g.ny : g.nz;
-  const float off = g.size[a] / 2.0;
-  return (float)(((size_t)i + 0.5) * g.size[a] / (double)res - off);
-}
-
-// getVoxelIndex (tsdf_volume_octree.cpp:562-574), one axis.
-static __device__ __forceinline__ int voxel_index(const GridView &g, int a, float x) {
-  const int res = a == 0 ? g.nx : a == 1 ? g.ny : g.nz;
-  const double off = (double)g.size[a] / 2.0;
-  return cvtt(floor(((double)x + off) / (double)g.size[a] * (double)res));
 }
 
 // interpolateTrilinearly (tsdf_volume_octree.cpp:486-541).  *valid is only ever AND-ed, as in the
@@ -880,64 +829,16 @@ extern "C" int tsdf_hip_selftest_containing(tsdf_handle h, const float *xyz, siz
 }
 #endif  // TSDF_HIP_TEST_HOOKS
 
-// ---------------------------------------------------------------------------------------------
-// getNeighbors :796-828, getFxn :655-672, getGradient :681-700, getHessian :703-726.
-// Neighbour order: dx outer, dy, dz inner.  getFxn/getGradient read the octree NODE centre
-// (vox->getCenter), getHessian reads getVoxelCenter (`centers[i]`).  Unqualified fabs(float) is
-// double fabs(double), so every term is a double product accumulated into a float.
-static __device__ __forceinline__ int sgn(float x) { return x > 0 ? 1 : -1; }  // :674-678
-
+// getFxn / getGradient / getHessian: the per-point arithmetic is sample_point (tsdf_gridview.h), one thread per point.
 static __global__ void __launch_bounds__(256)
 k_sample(const GridView g, const int own_lo, const int own_hi, const float *__restrict__ xyz, size_t n,
          float *__restrict__ val, float *__restrict__ grad, float *__restrict__ hess, unsigned char *__restrict__ ok) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n) return;
   const float px = xyz[3 * idx], py = xyz[3 * idx + 1], pz = xyz[3 * idx + 2];
-  bool good = true;
-  int xi = voxel_index(g, 0, px), yi = voxel_index(g, 1, py), zi = voxel_index(g, 2, pz);
-  if (!(xi >= 0 && yi >= 0 && zi >= 0 && xi < g.nx && yi < g.ny && zi < g.nz)) good = false;
-  if (good) {
-    if (px < voxel_center(g, 0, xi)) xi -= 1;
-    if (py < voxel_center(g, 1, yi)) yi -= 1;
-    if (pz < voxel_center(g, 2, zi)) zi -= 1;
-    if (xi < 0 || xi >= g.nx - 1 || yi < 0 || yi >= g.ny - 1 || zi < 0 || zi >= g.nz - 1) good = false;
-  }
-  const int kl = zi - g.z_first;
-  // A Z-slab handle answers only for points whose lower-corner plane it OWNS: halo planes are allocated but only
-  // as fresh as the caller's last exchange, and exactly one handle of a partition owns any plane (plane zi + 1
-  // may be the first halo plane: the one-plane exchange marching cubes needs as well).
-  if (good && (zi < own_lo || zi >= own_hi || kl < 0 || kl + 1 >= g.nz_alloc)) good = false;
-  float v = NAN, gr[3] = {NAN, NAN, NAN}, h01 = NAN, h02 = NAN, h12 = NAN;
-  if (good) {
-    const float c = g.size[0] / g.nx;
-    v = 0;
-    gr[0] = gr[1] = gr[2] = 0;
-    h01 = h02 = h12 = 0;
-    for (int dx = 0; dx <= 1; dx++)
-      for (int dy = 0; dy <= 1; dy++)
-        for (int dz = 0; dz <= 1; dz++) {
-          const int i = xi + dx, j = yi + dy, k = zi + dz;
-          const float dv = g.d[((int64_t)(k - g.z_first) * g.ny + j) * g.pitch + i];
-          const float nc[3] = {g.ctr[0][i], g.ctr[1][j], g.ctr[2][k]};
-          const float fc[3] = {voxel_center(g, 0, i), voxel_center(g, 1, j), voxel_center(g, 2, k)};
-          v += (c - fabs((double)(px - nc[0]))) * (c - fabs((double)(py - nc[1]))) *
-               (c - fabs((double)(pz - nc[2]))) * dv;
-          gr[0] += -sgn(px - nc[0]) * (c - fabs((double)(py - nc[1]))) * (c - fabs((double)(pz - nc[2]))) * dv;
-          gr[1] += (c - fabs((double)(px - nc[0]))) * -sgn(py - nc[1]) * (c - fabs((double)(pz - nc[2]))) * dv;
-          gr[2] += (c - fabs((double)(px - nc[0]))) * (c - fabs((double)(py - nc[1]))) * -sgn(pz - nc[2]) * dv;
-          h01 += sgn(px - fc[0]) * sgn(py - fc[1]) * (c - fabs((double)(pz - fc[2]))) * dv;
-          h02 += sgn(px - fc[0]) * (c - fabs((double)(py - fc[1]))) * sgn(pz - fc[2]) * dv;
-          h12 += (c - fabs((double)(px - fc[0]))) * sgn(py - fc[1]) * sgn(pz - fc[2]) * dv;
-        }
-    const float c3 = c * c * c;
-    v /= c3;
-    gr[0] /= c3;
-    gr[1] /= c3;
-    gr[2] /= c3;
-    h01 /= c3;
-    h02 /= c3;
-    h12 /= c3;
-  }
+  float v, gr[3], hs[3];
+  int xi, yi, zi;
+  const bool good = sample_point<true>(g, own_lo, own_hi, px, py, pz, v, gr, hs, xi, yi, zi);
   if (ok) ok[idx] = good ? 1 : 0;
   if (val) val[idx] = v;
   if (grad) {
@@ -949,9 +850,9 @@ k_sample(const GridView g, const int own_lo, const int own_hi, const float *__re
     float *hp = hess + 9 * idx;
     const float z = good ? 0.f : NAN;
     hp[0] = hp[4] = hp[8] = z;
-    hp[1] = hp[3] = h01;
-    hp[2] = hp[6] = h02;
-    hp[5] = hp[7] = h12;
+    hp[1] = hp[3] = hs[0];
+    hp[2] = hp[6] = hs[1];
+    hp[5] = hp[7] = hs[2];
   }
 }
 

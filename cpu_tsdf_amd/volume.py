@@ -21,6 +21,26 @@ class NonCubicQueryWarning(UserWarning):
     TSDFVolumeOctree._cubic_for_queries)."""
 
 
+class AlignmentError(RuntimeError):
+    """alignCloud could not go on: ``code`` is capi.ALIGN_NO_POINTS or capi.ALIGN_RANK_DEFICIENT, ``refined`` the pose of
+    the last good step (the guess, if none), ``iterations`` the steps taken, ``cost_log`` as alignCloud returns it."""
+
+    def __init__(self, code, refined, iterations, cost_log):
+        self.code, self.refined, self.iterations, self.cost_log = code, refined, iterations, cost_log
+        what = "no point passed the gate" if code == capi.ALIGN_NO_POINTS else "the cloud does not constrain all six freedoms"
+        super().__init__(f"alignCloud: {what} (after {iterations} steps)")
+
+
+def backproject(depth, fx, fy, cx, cy):
+    """A depth image (H, W; NaN = no return) as the cloud alignCloud / alignmentSystem take: per pixel
+    ((u - cx) / fx * z, (v - cy) / fy * z, z) in float64, rounded to float32; NaN pixels are dropped."""
+    z = np.asarray(depth, dtype=np.float64)
+    v, u = np.mgrid[0:z.shape[0], 0:z.shape[1]]
+    keep = ~np.isnan(z)
+    z, u, v = z[keep], u[keep].astype(np.float64), v[keep].astype(np.float64)
+    return np.ascontiguousarray(np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], axis=1), dtype=np.float32)
+
+
 class TSDFVolumeOctree:
     """Drop-in for ``cpu_tsdf::TSDFVolumeOctree`` (flat SoA grid in HBM instead of an octree)."""
 
@@ -452,6 +472,64 @@ class TSDFVolumeOctree:
                                         capi.as_f32p(grad) if grad is not None else None,
                                         capi.as_f32p(hess) if hess is not None else None, capi.as_u8p(ok)), "sample")
         return ok.astype(bool), val, grad, (hess.reshape(n, 3, 3) if hess is not None else None)
+
+    # -- alignCloud (not in the reference; include/tsdf_hip.h) ---------------------------------------------------------
+    @staticmethod
+    def _pose12(trans, who):
+        m = np.asarray(trans, dtype=np.float64)
+        if m.shape not in ((4, 4), (3, 4)):
+            raise ValueError(f"{who}: a pose is a 4 x 4 (or 3 x 4) matrix, got shape {m.shape}")
+        return np.ascontiguousarray(m[:3, :4]).reshape(12)
+
+    def alignmentSystem(self, points, trans, min_weight=0.0, r_max=0.9, want_used=False, want_points=False):
+        """The normal equations of  min_xi sum_i getFxn(exp(xi) * trans * p_i)^2  at xi = 0, reduced on the GPU
+        (tsdf_hip_align_system): out (29,) float64 = the 21 upper-triangle entries of sum J J^T (row-major), the 6 of
+        sum J r, sum r^2, the number of used points; J = [q x g, g], q = trans * p, r = getFxn(q), g = getGradient(q).
+        A point is used iff getFxn succeeds, its eight neighbour voxels all have w > min_weight, and |r| < r_max.
+        Returns out, then -- if asked for -- used (n,) bool and the transformed points (n, 3) float32."""
+        self._cubic_for_queries("alignmentSystem")
+        h = self._need()
+        pts = capi.f32c(points).reshape(-1, 3)
+        n = pts.shape[0]
+        T = self._pose12(trans, "alignmentSystem")
+        out = np.empty(29, np.float64)
+        used = np.empty(n, np.uint8) if want_used else None
+        q = np.empty((n, 3), np.float32) if want_points else None
+        f64p = C.POINTER(C.c_double)
+        capi.check(capi.load().tsdf_hip_align_system(h, capi.as_f32p(pts), n, T.ctypes.data_as(f64p), float(min_weight), float(r_max),
+                                                     out.ctypes.data_as(f64p), capi.as_u8p(used) if want_used else None,
+                                                     capi.as_f32p(q) if want_points else None), "align_system")
+        res = (out,)
+        if want_used:
+            res += (used.astype(bool),)
+        if want_points:
+            res += (q,)
+        return res[0] if len(res) == 1 else res
+
+    def alignCloud(self, points, guess, max_iterations=10, min_weight=0.0, r_max=0.9, min_step=1e-7):
+        """Register a cloud to the fused surface: Gauss-Newton on the signed distance field (tsdf_hip_align), starting
+        from `guess` (source -> volume).  Returns (refined 4 x 4, iterations, cost_log (k, 2): sum r^2 and the used count
+        of every system evaluated).  Raises AlignmentError -- carrying the pose of the last good step, the steps taken
+        and the cost log -- where no point is used or the cloud does not constrain all six freedoms."""
+        self._cubic_for_queries("alignCloud")
+        h = self._need()
+        pts = capi.f32c(points).reshape(-1, 3)
+        n = pts.shape[0]
+        T = self._pose12(guess, "alignCloud")
+        max_iterations = int(max_iterations)
+        refined = np.empty(12, np.float64)
+        log = np.full((max(max_iterations, 1), 2), np.nan)
+        it = C.c_int32(0)
+        f64p = C.POINTER(C.c_double)
+        rc = capi.load().tsdf_hip_align(h, capi.as_f32p(pts), n, T.ctypes.data_as(f64p), float(min_weight), float(r_max), max_iterations,
+                                        float(min_step), refined.ctypes.data_as(f64p), C.byref(it), log.ctypes.data_as(f64p))
+        out = np.eye(4)
+        out[:3, :4] = refined.reshape(3, 4)
+        log = log[~np.isnan(log[:, 1])]
+        if rc in (capi.ALIGN_NO_POINTS, capi.ALIGN_RANK_DEFICIENT):
+            raise AlignmentError(rc, out, int(it.value), log)
+        capi.check(rc, "align")
+        return out, int(it.value), log
 
     # -- raw access (parity tests, save) -------------------------------------------------------------
     def download(self, x0=0, y0=0, z0=None, nx=None, ny=None, nz=None, want_rgb=None):

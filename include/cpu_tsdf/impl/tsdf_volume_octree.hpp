@@ -7,6 +7,9 @@
 // PointT needs r,g,b members.
 #pragma once
 
+#include <cmath>
+#include <vector>
+
 namespace cpu_tsdf {
 
 template <typename PointT, typename NormalT>
@@ -39,6 +42,23 @@ bool TSDFVolumeOctree::integrateCloud(const pcl::PointCloud<PointT> &cloud, cons
     for (long i = 0; i < n; ++i) depth[i] = pts[i].z;
   }
   return commitFrame(trans);
+}
+
+// alignCloud: x, y, z of the points with a finite z into one contiguous buffer (as integrateCloud strips its cloud), then
+// the out-of-line forwarder to tsdf_hip_align.
+template <typename PointT>
+bool TSDFVolumeOctree::alignCloud(const pcl::PointCloud<PointT> &cloud, const Eigen::Affine3d &guess, Eigen::Affine3d &refined,
+                                  int max_iterations, float min_weight, float r_max, double min_step) const {
+  std::vector<float> xyz;
+  xyz.reserve(3 * cloud.points.size());
+  for (size_t i = 0; i < cloud.points.size(); ++i) {
+    const PointT &pt = cloud.points[i];
+    if (!std::isfinite(pt.z)) continue;
+    xyz.push_back(pt.x);
+    xyz.push_back(pt.y);
+    xyz.push_back(pt.z);
+  }
+  return alignPoints(xyz.empty() ? nullptr : &xyz[0], xyz.size() / 3, guess, refined, max_iterations, min_weight, r_max, min_step);
 }
 
 }  // namespace cpu_tsdf

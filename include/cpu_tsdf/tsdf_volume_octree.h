@@ -142,6 +142,22 @@ class TSDFVolumeOctree : public TSDFInterface {
   bool getReferenceCull() const { return reference_cull_; }
   // TSDF_LAYOUT_* (include/tsdf_hip.h): how the weight is stored in HBM; default AUTO
   void setLayout(int layout) { p_.layout = layout; }
+  // Register a cloud to the fused surface (tsdf_hip_align): Gauss-Newton on getFxn over the whole cloud, on the GPU --
+  // what getFxn / getGradient exist for in the reference, which leaves the loop to the caller, one point per call.
+  // guess / refined: cloud -> volume.  Points with a non-finite z are skipped.  A point counts iff getFxn succeeds, its
+  // eight neighbour voxels have weight > min_weight and |getFxn| < r_max (d units).  Stops after max_iterations steps or
+  // when the step's norm falls below min_step.  false (and a PCL_ERROR) where no point counts or the cloud leaves a
+  // freedom unconstrained; refined then holds the last good step.  Refuses on a non-cubic grid like getFxn.
+  template <typename PointT>
+  bool alignCloud(const pcl::PointCloud<PointT> &cloud, const Eigen::Affine3d &guess, Eigen::Affine3d &refined,
+                  int max_iterations = 10, float min_weight = 0.f, float r_max = 0.9f, double min_step = 1e-7) const;
+  // The normal equations of one such step at `trans` (tsdf_hip_align_system): out = 21 upper-triangle entries of
+  // sum J J^T, 6 of sum J r, sum r^2, the number of points that count; xyz = n x 3 floats.
+  bool getAlignmentSystem(const float *xyz, size_t n, const Eigen::Affine3d &trans, double out[29], float min_weight = 0.f,
+                          float r_max = 0.9f) const;
+  // out-of-line half of the alignCloud template: xyz = n x 3 floats
+  bool alignPoints(const float *xyz, size_t n, const Eigen::Affine3d &guess, Eigen::Affine3d &refined, int max_iterations,
+                   float min_weight, float r_max, double min_step) const;
 
   const float UNOBSERVED_VOXEL;
 

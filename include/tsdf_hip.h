@@ -39,7 +39,10 @@ enum {
   TSDF_HIP_E_HIP = 3,         /* any other HIP runtime error (see tsdf_hip_last_error) */
   TSDF_HIP_E_NODEVICE = 4,    /* no gfx950 device visible */
   TSDF_HIP_E_UNSUPPORTED = 5,
-  TSDF_HIP_E_IO = 6           /* file missing, unreadable, unwritable or not a .vol (see tsdf_hip_last_error) */
+  TSDF_HIP_E_IO = 6,          /* file missing, unreadable, unwritable or not a .vol (see tsdf_hip_last_error) */
+  /* statuses of tsdf_hip_align only: not failures of the library, the cloud cannot be aligned */
+  TSDF_HIP_ALIGN_NO_POINTS = 7,      /* no point passed the gate at the current pose */
+  TSDF_HIP_ALIGN_RANK_DEFICIENT = 8  /* the used points do not constrain all six freedoms (Cholesky failed) */
 };
 
 /* Summation order of the rigid transform g = T * (c,1), which decides the last ulp of the
@@ -379,6 +382,45 @@ int tsdf_hip_sample(tsdf_handle h, const float *xyz, size_t n, float *val, float
  * Octree::getContainingVoxel returns (src/lib/octree.cpp:112-133,628-643) and its RGBNode colour (r,g,b; zeros
  * if the volume stores no colour).  found[i] = 0 where the reference gets NULL. */
 int tsdf_hip_lookup_rgb(tsdf_handle h, const float *xyz, size_t n, uint8_t *rgb, uint8_t *found);
+
+/* alignCloud -- NOT IN THE REFERENCE.  The reference has getFxn / getGradient so that a caller can optimise a pose against
+ * the signed distance field; these entry points do that for a whole cloud on the device.
+ *
+ * tsdf_hip_align_system: the normal equations of  min_xi  sum_i getFxn(exp(xi) * T * p_i)^2  at xi = 0.
+ *   xyz n x 3 floats (source frame); vol_from_src the rows of T = [R | t], cast to float as the reference casts poses
+ *   (trans.cast<float>(), hpp:76).  Per point: q = R p + t in fp32, each row ((R0*p.x + R1*p.y) + R2*p.z) + t; val, g and
+ *   ok are getFxnAndGradient of q, bit for bit what tsdf_hip_sample returns.
+ *   GATE (an extension: the reference's getFxn ignores weights, so never-observed voxels -- d = -1, w = 0 -- would pull
+ *   on the pose): a point is USED iff ok, all eight neighbour voxels have weight > min_weight (strictly; any layout), and
+ *   fabsf(val) < r_max (a NaN fails).
+ *   Terms, in fp64 from the float inputs: J = [q x g, g], the left-multiplied twist (omega, v) in the volume frame
+ *   (r(exp(xi) q) ~ r + omega . (q x g) + v . g), r = val.  out[0..20] = the upper triangle of sum J J^T, row-major;
+ *   out[21..26] = sum J r; out[27] = sum r^2; out[28] = the number of used points.
+ *   used (n bytes, nullable) and xyz_vol (n x 3 floats, nullable) receive the gate's verdict and q per point.
+ *   The summation order is a function of n alone (no floating-point atomics): two calls return identical bytes, and so
+ *   do the host-pointer and the _device form.  A multi-GPU set exchanges the one-plane halo, every slab sums the points
+ *   whose lower-corner plane it owns, the host adds the slab sums in slab order; `used` is the OR.
+ * tsdf_hip_align_system_device: the cloud is already on the handle's device; synchronises the handle's stream for `out`.
+ *   TSDF_HIP_E_UNSUPPORTED on a multi-GPU set.
+ * tsdf_hip_align: Gauss-Newton around it.  Uploads the cloud once; per iteration runs the system kernels (232 bytes come
+ *   back), solves the 6 x 6 by Cholesky in fp64 on the host, and updates T <- exp(delta) * T with the closed-form SE(3)
+ *   exponential (Rodrigues; series below |omega| = 1e-12).  Stops after max_iterations steps or when |delta|_2 < min_step.
+ *   iterations (nullable) receives the number of steps taken; cost_log (nullable, 2 * max_iterations doubles) sum r^2
+ *   and the used count of every system it evaluated (entries beyond that are left alone).
+ *   Returns TSDF_HIP_E_INVALID for n = 0, a NULL xyz / guess / refined, r_max <= 0 or NaN, a NaN min_weight,
+ *   max_iterations < 1, min_step < 0 or NaN -- before any device is touched.  Returns TSDF_HIP_ALIGN_NO_POINTS where no
+ *   point is used and TSDF_HIP_ALIGN_RANK_DEFICIENT where the factorisation fails (a pivot not above 1e-10 of the largest
+ *   diagonal entry: a single plane); refined then holds the pose of the last good step (the guess, if none).
+ * tsdf_hip_align_stats: report-only, of the last of the calls above on this handle: points, used (of the last system),
+ *   iterations (steps; 0 for the system calls), device microseconds of the system kernels (handle's stream events).
+ * Like every entry point that reads the volume, all of them first launch a frame held back by frame pairing. */
+int tsdf_hip_align_system(tsdf_handle h, const float *xyz, size_t n, const double vol_from_src[12],
+                          float min_weight, float r_max, double out[29], uint8_t *used, float *xyz_vol);
+int tsdf_hip_align_system_device(tsdf_handle h, const float *d_xyz, size_t n, const double vol_from_src[12],
+                                 float min_weight, float r_max, double out[29]);
+int tsdf_hip_align(tsdf_handle h, const float *xyz, size_t n, const double guess[12], float min_weight, float r_max,
+                   int max_iterations, double min_step, double refined[12], int32_t *iterations, double *cost_log);
+int tsdf_hip_align_stats(tsdf_handle h, uint64_t out[4]);
 
 /* MarchingCubesTSDFOctree::reconstruct -- src/lib/marching_cubes_tsdf_octree.cpp:108-236
  * (+ pcl::MarchingCubes::createSurface).  color_mode: 0 none, 1 setColorByRGB, 2 setColorByConfidence.
