@@ -12,6 +12,10 @@
 
 struct tsdf_hip_pipeline;  // tsdf_integrate.hip: pinned staging ring of tsdf_hip_integrate_async
 struct tsdf_hip_multi;     // tsdf_multi.hip: the Z-slab handles of a multi-GPU volume
+// per-handle state of one feature each, defined in its own translation unit and created by the first call that needs it
+struct tsdf_occ_state;       // tsdf_occupied.hip: the sorted key list of tsdf_hip_occupied, a set's merged list
+struct tsdf_meshpost_state;  // tsdf_meshpost.hip: the working set of tsdf_hip_march_cleanup
+struct tsdf_flatten_state;   // tsdf_flatten.hip: the indexed mesh of tsdf_hip_march_flatten and its working set
 
 struct tsdf_hip_volume {
   // non-null: this handle is a SET of Z-slab handles on several GPUs (tsdf_hip_create_multi) and owns no voxel plane
@@ -100,6 +104,7 @@ struct tsdf_hip_volume {
   uint8_t *mc_rgb = nullptr;
   uint64_t *mc_cell = nullptr;
   uint64_t mc_ntri = 0;
+  bool mc_valid = false;   // the last tsdf_hip_march on this handle succeeded (tsdf_hip_march_cleanup / _flatten work on its result)
   size_t mc_cap = 0;       // triangles the output buffers hold
   bool mc_has_rgb = false;
   uint64_t *mc_keys = nullptr, *mc_vals = nullptr;  // active-cell list (Morton key, packed cell)
@@ -111,10 +116,14 @@ struct tsdf_hip_volume {
   uint64_t mc_ncells = 0;
   uint64_t mc_d_bytes = 0;   // distance bytes the last classify pass requested (tsdf_hip_march_stats)
   bool mc_skipped = false;   // ... with the band flags deciding what to read
+  bool mc_counts_pass = false;  // ... and the corner weights not gathered: their test could not fail (tsdf_march.hip counts_pass)
   hipEvent_t align_ev[2] = {nullptr, nullptr};  // tsdf_hip_align_stats: around the system kernels of the last call
   uint64_t align_stats[4] = {0, 0, 0, 0};       // points, used, iterations, device microseconds
   void *scratch = nullptr;
   size_t scratch_bytes = 0;
+  tsdf_occ_state *occ = nullptr;
+  tsdf_meshpost_state *mp = nullptr;
+  tsdf_flatten_state *fl = nullptr;
 };
 
 // Multi-GPU forwarding targets (tsdf_multi.hip); `h` is a handle with h->multi != nullptr.
@@ -145,6 +154,11 @@ int tsdf_multi_march_fetch(tsdf_handle h, float *verts, uint8_t *rgb, uint64_t *
 int tsdf_multi_march_timing(tsdf_handle h, float ms[3], uint64_t *n_cells);
 int tsdf_multi_march_stats(tsdf_handle h, uint64_t out[4]);
 tsdf_handle tsdf_multi_first(tsdf_handle h);
+tsdf_handle tsdf_multi_slab(tsdf_handle h, int k);  // slab k of the set, nullptr when k is out of range
+// the merged mesh of a set lives on the host: cleanup runs tsdf_hip_mesh_cleanup on the first slab's device and compacts the
+// host copy; flatten reads the soup (h->mc_ntri triangles; rgb NULL without a colour mode) through tsdf_multi_mesh
+int tsdf_multi_march_cleanup(tsdf_handle h, float face_dist, int min_neighbors, uint64_t *n_tri);
+void tsdf_multi_mesh(tsdf_handle h, const float **verts, const uint8_t **rgb, const uint64_t **cell);
 // frame pairing on a set (round 6): the slabs pair the frames of their own rings; tsdf_multi_flush lets them launch what they hold
 int tsdf_multi_flush(tsdf_handle h);
 int tsdf_multi_set_frame_pairing(tsdf_handle h, int on);
@@ -290,6 +304,14 @@ int tsdf_ensure_scratch(tsdf_hip_volume *v, size_t bytes);
 int tsdf_to_host(tsdf_hip_volume *v, void *dst, const void *dev_src, size_t bytes);
 int tsdf_to_device(tsdf_hip_volume *v, void *dev_dst, const void *src, size_t bytes);
 void tsdf_pipeline_destroy(tsdf_hip_volume *v);
+// Free v->occ / v->mp / v->fl and null them (free_volume; a handle that never ran the feature has none).  The mesh passes
+// of a set keep their device memory on the first slab's device, so these run before tsdf_multi_free.
+void tsdf_occupied_release(tsdf_hip_volume *v);
+void tsdf_meshpost_release(tsdf_hip_volume *v);
+void tsdf_flatten_release(tsdf_hip_volume *v);
+// The indexed mesh tsdf_hip_march_flatten left on a handle describes the soup it was made from: a later tsdf_hip_march or
+// tsdf_hip_march_cleanup makes tsdf_hip_march_fetch_indexed refuse until flatten has run again.
+void tsdf_flatten_invalidate(tsdf_hip_volume *v);
 
 // Launch-shape knobs, overridable from the environment for A/B runs (TSDF_HIP_ROWS_PER_BLOCK,
 // TSDF_HIP_BLOCKS_PER_CU, TSDF_HIP_FAST_PROJECTION, TSDF_HIP_MC_FLUSH_AT, TSDF_HIP_CULL, TSDF_HIP_VOL_CHUNK, TSDF_HIP_ALLIN); read once, changeable

@@ -10,11 +10,7 @@
 #include <thread>
 #include <string.h>
 
-#include <mutex>
-
 #include "tsdf_common.h"
-#include "tsdf_occupied.h"
-#include "tsdf_meshpost.h"
 #ifdef TSDF_HIP_TEST_HOOKS
 #include "tsdf_hip_test.h"
 #endif
@@ -404,6 +400,9 @@ int tsdf_to_device(tsdf_hip_volume *v, void *dev_dst, const void *src, size_t by
 
 static void free_volume(tsdf_hip_volume *v) {
   if (!v) return;
+  tsdf_occupied_release(v);
+  tsdf_meshpost_release(v);
+  tsdf_flatten_release(v);
   if (v->multi) tsdf_multi_free(v);
   TsdfDeviceScope scope(v->device);
   tsdf_pipeline_destroy(v);
@@ -766,8 +765,6 @@ extern "C" int tsdf_hip_destroy(tsdf_handle h) {
   if (!h) return TSDF_HIP_E_INVALID;
   TsdfDeviceScope scope(h->device);
   (void)hipStreamSynchronize(h->stream);
-  tsdf_occupied_release(h);  // the state tsdf_occupied.hip keeps for this handle, if any
-  tsdf_meshpost_release(h);  // ... and tsdf_meshpost.hip
   free_volume(h);
   return TSDF_HIP_OK;
 }

@@ -26,19 +26,14 @@
 
 #include <algorithm>
 #include <cmath>
-#include <memory>
-#include <mutex>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "tsdf_flatten.h"
 #include "tsdf_meshgrid.h"
-#include "tsdf_meshpost.h"
 
 // ---- state -----------------------------------------------------------------------------------------------------------------
 #define FL_C_FINITE 0  // vertices with three finite coordinates
@@ -50,17 +45,8 @@
 #define FL_COUNTERS 8
 #define FL_MAX_ROUNDS 0x7fffffffu  // the state word holds round << 1
 
-struct FlWork {
-  void *buf = nullptr;  // per-vertex and per-face arrays + rocprim's temporary storage
-  size_t cap = 0;
-  void *cells = nullptr;  // per-cell arrays (sized once the number of occupied cells is known)
-  size_t cells_cap = 0;
-  unsigned long long *counters = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-};
-
-struct FlState {  // per handle: the indexed mesh of tsdf_hip_march_flatten
-  FlWork work;
+struct tsdf_flatten_state {  // per handle (tsdf_hip_volume::fl): the indexed mesh of tsdf_hip_march_flatten
+  MpWork work;
   bool valid = false, has_rgb = false;
   uint64_t n_verts = 0, n_faces = 0;
   void *out = nullptr;  // one handle: vertices, faces, cell keys, colours (device)
@@ -71,43 +57,19 @@ struct FlState {  // per handle: the indexed mesh of tsdf_hip_march_flatten
   std::vector<uint64_t> h_cell;
 };
 
-static std::mutex g_fl_mutex;
-static std::unordered_map<tsdf_hip_volume *, std::unique_ptr<FlState>> g_fl;
 static thread_local uint64_t g_fl_stats[4] = {0, 0, 0, 0};  // tsdf_hip_mesh_flatten_stats
 
-static FlState *fl_state(tsdf_hip_volume *v, bool create) {
-  std::lock_guard<std::mutex> lock(g_fl_mutex);
-  auto it = g_fl.find(v);
-  if (it != g_fl.end()) return it->second.get();
-  if (!create) return nullptr;
-  return (g_fl[v] = std::unique_ptr<FlState>(new FlState())).get();
-}
-
-static void fl_work_free(FlWork &w) {
-  if (w.buf) (void)hipFree(w.buf);
-  if (w.cells) (void)hipFree(w.cells);
-  if (w.counters) (void)hipFree(w.counters);
-  for (hipEvent_t e : w.ev)
-    if (e) (void)hipEventDestroy(e);
-  w = FlWork();
-}
-
 void tsdf_flatten_invalidate(tsdf_hip_volume *v) {
-  if (FlState *st = fl_state(v, false)) st->valid = false;
+  if (v->fl) v->fl->valid = false;
 }
 
 void tsdf_flatten_release(tsdf_hip_volume *v) {
-  std::unique_ptr<FlState> st;
-  {
-    std::lock_guard<std::mutex> lock(g_fl_mutex);
-    auto it = g_fl.find(v);
-    if (it == g_fl.end()) return;
-    st = std::move(it->second);
-    g_fl.erase(it);
-  }
-  TsdfDeviceScope scope(v->multi ? tsdf_multi_first(v)->device : v->device);
-  fl_work_free(st->work);
-  if (st->out) (void)hipFree(st->out);
+  if (!v->fl) return;
+  TsdfDeviceScope scope(v->device);  // (a set keeps its indexed mesh on the host: work and out are empty)
+  mp_work_free(v->fl->work);
+  if (v->fl->out) (void)hipFree(v->fl->out);
+  delete v->fl;
+  v->fl = nullptr;
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
@@ -274,7 +236,7 @@ k_fl_gather_out(const float *__restrict__ verts, const uint8_t *__restrict__ rgb
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-struct FlLayout {  // the arrays inside FlWork::buf
+struct FlLayout {  // the arrays inside MpWork::buf
   size_t key_a, key_b, idx_a, idx_b, pos, cellno, flag, remap, seeds, mapped, faces, keep, offset, tmp, tmp_bytes, total;
 };
 
@@ -300,10 +262,10 @@ static int fl_layout(size_t n, size_t f, hipStream_t s, FlLayout &L) {
   return TSDF_HIP_OK;
 }
 
-// The whole pass on device arrays.  Leaves in FlWork::buf: remap (n_verts), seeds (*n_out), the surviving faces (L.faces,
+// The whole pass on device arrays.  Leaves in MpWork::buf: remap (n_verts), seeds (*n_out), the surviving faces (L.faces,
 // *n_kept x 3), the faces' keep flags and, when a face went, their offsets; and the stats of the calling thread.  Leaves the
 // stream idle.
-static int fl_core(FlWork &w, hipStream_t s, const float *d_verts, uint64_t n_verts, const uint32_t *d_faces, uint64_t n_faces, float min_dist,
+static int fl_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_verts, const uint32_t *d_faces, uint64_t n_faces, float min_dist,
                    FlLayout &L, uint64_t *n_out, uint64_t *n_kept, const char *who) {
   const uint32_t n = (uint32_t)n_verts, nf = (uint32_t)n_faces;
   int rc = fl_layout(n, nf, s, L);
@@ -457,11 +419,11 @@ extern "C" int tsdf_hip_mesh_flatten(int device, const float *verts, uint64_t n_
   struct Call {
     hipStream_t s = nullptr;
     void *in = nullptr;
-    FlWork work;
+    MpWork work;
     MpStage stage;
     ~Call() {
       if (s) (void)hipStreamSynchronize(s);
-      fl_work_free(work);
+      mp_work_free(work);
       if (in) (void)hipFree(in);
       if (s) (void)hipStreamDestroy(s);
     }
@@ -493,7 +455,7 @@ extern "C" int tsdf_hip_mesh_flatten(int device, const float *verts, uint64_t n_
 
 // A set: the merged soup is on the host, so it takes the host-array entry point on the first slab's device, and the indexed
 // mesh stays on the host too -- what one handle holding the whole grid would fetch.
-static int fl_multi(tsdf_handle h, FlState *st, float min_dist) {
+static int fl_multi(tsdf_handle h, tsdf_flatten_state *st, float min_dist) {
   const uint64_t n = h->mc_ntri;
   const float *verts = nullptr;
   const uint8_t *rgb = nullptr;
@@ -527,11 +489,12 @@ extern "C" int tsdf_hip_march_flatten(tsdf_handle h, float min_dist, uint64_t *n
   if (n_verts) *n_verts = 0;
   if (n_faces) *n_faces = 0;
   if (const int rc = fl_check_args(min_dist, 0, 0, "tsdf_hip_march_flatten")) return rc;
-  if (!tsdf_meshpost_marched(h)) {
+  if (!h->mc_valid) {
     tsdf_set_error("tsdf_hip_march_flatten: the last tsdf_hip_march on this handle did not succeed, or none has run");
     return TSDF_HIP_E_INVALID;
   }
-  FlState *st = fl_state(h, true);
+  if (!h->fl) h->fl = new tsdf_flatten_state();
+  tsdf_flatten_state *st = h->fl;
   st->valid = false;
   const uint64_t n = h->mc_ntri;
   if (const int rc = fl_check_args(min_dist, 3 * n, n, "tsdf_hip_march_flatten")) return rc;
@@ -575,7 +538,7 @@ extern "C" int tsdf_hip_march_flatten(tsdf_handle h, float min_dist, uint64_t *n
 
 extern "C" int tsdf_hip_march_fetch_indexed(tsdf_handle h, float *verts, uint8_t *rgb, uint32_t *faces, uint64_t *cell) {
   if (!h) return TSDF_HIP_E_INVALID;
-  FlState *st = fl_state(h, false);
+  tsdf_flatten_state *st = h->fl;
   if (!st || !st->valid) {
     tsdf_set_error("tsdf_hip_march_fetch_indexed: no indexed mesh: tsdf_hip_march_flatten has not run since the last tsdf_hip_march / "
                    "tsdf_hip_march_cleanup");

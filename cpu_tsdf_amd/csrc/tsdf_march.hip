@@ -23,7 +23,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "tsdf_common.h"
-#include "tsdf_meshpost.h"
+#include "tsdf_morton.h"
 #ifdef TSDF_HIP_TEST_HOOKS
 #include "tsdf_hip_test.h"
 #endif
@@ -53,34 +53,14 @@ struct McArgs {
   int need_gx, need_rows, need_by;
 };
 
-static __device__ __forceinline__ uint64_t spread3(uint64_t v) {  // 21 bits -> every third bit
-  v &= 0x1fffffull;
-  v = (v | v << 32) & 0x1f00000000ffffull;
-  v = (v | v << 16) & 0x1f0000ff0000ffull;
-  v = (v | v << 8) & 0x100f00f00f00f00full;
-  v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-  v = (v | v << 2) & 0x1249249249249249ull;
-  return v;
-}
-
-static __device__ __forceinline__ uint32_t compact3(uint64_t v) {  // every third bit -> 21 bits (spread3's inverse)
-  v &= 0x1249249249249249ull;
-  v = (v | v >> 2) & 0x10c30c30c30c30c3ull;
-  v = (v | v >> 4) & 0x100f00f00f00f00full;
-  v = (v | v >> 8) & 0x1f0000ff0000ffull;
-  v = (v | v >> 16) & 0x1f00000000ffffull;
-  v = (v | v >> 32) & 0x1fffffull;
-  return (uint32_t)v;
-}
 // An active cell is ONE 64-bit word since round 6: (Morton key << MC_KEY_SHIFT) | triangle count.  The key IS the cell's
 // coordinates (x the high bit of every triple: octree.cpp:119,257-264), so the (key, packed cell) PAIRS of rounds 1-5 carried them
 // twice; sorting words instead of pairs halves what the radix sort moves (the count's bits take no part in it).  mc_unpack
 // gives the packed form the rest of the file reads: x | y << 20 | z << 40 | count << 60.
 #define MC_KEY_SHIFT 4
-#define MC_STAT_COUNTS_PASS (1ull << 63)  // in tsdf_hip_volume::mc_d_bytes, see tsdf_hip_march
 static __device__ __forceinline__ uint64_t mc_unpack(uint64_t word) {
   const uint64_t key = word >> MC_KEY_SHIFT;
-  return (uint64_t)compact3(key >> 2) | ((uint64_t)compact3(key >> 1) << 20) | ((uint64_t)compact3(key) << 40) | ((word & 15ull) << 60);
+  return (uint64_t)tsdf_compact3(key >> 2) | ((uint64_t)tsdf_compact3(key >> 1) << 20) | ((uint64_t)tsdf_compact3(key) << 40) | ((word & 15ull) << 60);
 }
 
 static __device__ __forceinline__ int cube_index(const float leaf[8]) {
@@ -304,10 +284,10 @@ k_mc_classify(const McArgs a, uint64_t *__restrict__ keys, uint64_t capacity,
   if (a.need_blk && !a.need_blk[((int64_t)blockIdx.z * a.need_by + by) * a.need_gx + bx]) return;
   const int zs = a.z_lo + (int)blockIdx.z * a.zb;
   const int ze = min(zs + a.zb, a.z_hi);                       // cell planes [zs, ze); plane ze is read
-  s_xkey[tid] = (uint32_t)(spread3((uint64_t)tid) << 2);
-  const uint64_t xkey_hi = spread3((uint64_t)bx * 256u) << 2;
-  if (tid < 4u * MC_R) s_ykey[tid] = spread3((uint64_t)(1u + by * 4u * MC_R + tid)) << 1;
-  if (tid < (unsigned)MC_ZB) s_zkey[tid] = spread3((uint64_t)(zs + (int)tid));
+  s_xkey[tid] = (uint32_t)(tsdf_spread3((uint64_t)tid) << 2);
+  const uint64_t xkey_hi = tsdf_spread3((uint64_t)bx * 256u) << 2;
+  if (tid < 4u * MC_R) s_ykey[tid] = tsdf_spread3((uint64_t)(1u + by * 4u * MC_R + tid)) << 1;
+  if (tid < (unsigned)MC_ZB) s_zkey[tid] = tsdf_spread3((uint64_t)(zs + (int)tid));
   __syncthreads();
   const int64_t sz = (int64_t)a.ny * a.pitch;
   // k_mc_need's verdicts on this wave's part of planes zs .. ze, one per lane, fetched once: a load per plane step
@@ -709,7 +689,8 @@ static int march_single(tsdf_handle h, float w_min, int color_mode, uint64_t *n_
 extern "C" int tsdf_hip_march(tsdf_handle h, float w_min, int color_mode, uint64_t *n_tri) {
   if (!h || color_mode < 0 || color_mode > 2) return TSDF_HIP_E_INVALID;
   const int rc = h->multi ? tsdf_multi_march(h, w_min, color_mode, n_tri) : march_single(h, w_min, color_mode, n_tri);
-  tsdf_meshpost_note_march(h, rc == TSDF_HIP_OK);  // tsdf_hip_march_cleanup refuses a handle whose last march did not succeed
+  h->mc_valid = rc == TSDF_HIP_OK;  // tsdf_hip_march_cleanup / _flatten refuse a handle whose last march did not succeed
+  tsdf_flatten_invalidate(h);       // an indexed mesh of the soup before this march describes nothing any more
   return rc;
 }
 
@@ -860,11 +841,9 @@ static int march_single(tsdf_handle h, float w_min, int color_mode, uint64_t *n_
     }
     need_bytes = per_plane * (uint64_t)((a.z_hi - a.z_lo) + (int)grid.z);
   }
-  // (bit 63 carries "the weight test could not fail and was not evaluated" to tsdf_hip_march_stats: the handle struct lives
-  //  in tsdf_common.h, one of the sources whose hash stamps the committed k_integrate profiles -- bench.py kernel_sha16 --
-  //  and a report-only flag is not worth invalidating them)
-  h->mc_d_bytes = need_bytes | (counts_pass ? MC_STAT_COUNTS_PASS : 0ull);
+  h->mc_d_bytes = need_bytes;
   h->mc_skipped = a.need != nullptr;
+  h->mc_counts_pass = counts_pass;
   if (n_cells == 0) return TSDF_HIP_OK;
   if (n_cells > 0xffffffffull || ntri > 0xffffffffull) {
     tsdf_set_error("mesh too large (more than 2^32 cells or triangles)");
@@ -964,8 +943,8 @@ extern "C" int tsdf_hip_march_stats(tsdf_handle h, uint64_t out[4]) {
   if (h->multi) return tsdf_multi_march_stats(h, out);
   out[0] = h->mc_ncells;
   out[1] = h->mc_ntri;
-  out[2] = h->mc_d_bytes & ~MC_STAT_COUNTS_PASS;
-  out[3] = (h->mc_skipped ? 1u : 0u) | ((h->mc_d_bytes & MC_STAT_COUNTS_PASS) ? 2u : 0u);
+  out[2] = h->mc_d_bytes;
+  out[3] = (h->mc_skipped ? 1u : 0u) | (h->mc_counts_pass ? 2u : 0u);
   return TSDF_HIP_OK;
 }
 

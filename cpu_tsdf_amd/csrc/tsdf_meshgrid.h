@@ -5,9 +5,8 @@
 //   k_mp_cellnbr   each cell's 27 neighbour cells as indices into that table
 //   mp_for_links   the points strictly within the radius of point i, from those 27 cells: the host's forNeighbours
 //   k_mp_compact   stable compaction of per-face records behind a scan of the keep flags
-//   mp_reserve / mp_to_device / mp_to_host   the working set, and caller memory (pinned: direct; pageable: staged)
-// Everything here is static: each translation unit compiles its own copy.  Kept out of tsdf_common.h for the reason
-// tsdf_occupied.h gives.
+//   MpWork / mp_reserve / mp_to_device / mp_to_host   the working set, and caller memory (pinned: direct; pageable: staged)
+// Everything here is static: each translation unit compiles its own copy.
 #pragma once
 
 #include <string.h>
@@ -102,6 +101,24 @@ struct MpKeepCount {
   __host__ __device__ uint32_t operator()(uint8_t k) const { return k ? 1u : 0u; }
 };
 using MpKeepIt = rocprim::transform_iterator<const uint8_t *, MpKeepCount, uint32_t>;
+
+struct MpWork {  // the working set of one pass: a handle's, or a handle-less call's
+  void *buf = nullptr;  // per-point and per-face arrays + rocprim's temporary storage
+  size_t cap = 0;
+  void *cells = nullptr;  // per-cell arrays (sized once the number of occupied cells is known)
+  size_t cells_cap = 0;
+  unsigned long long *counters = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // timed intervals on the stream (cleanup: two; flatten: one, ev[0 .. 1])
+};
+
+static void mp_work_free(MpWork &w) {
+  if (w.buf) (void)hipFree(w.buf);
+  if (w.cells) (void)hipFree(w.cells);
+  if (w.counters) (void)hipFree(w.counters);
+  for (hipEvent_t e : w.ev)
+    if (e) (void)hipEventDestroy(e);
+  w = MpWork();
+}
 
 static int mp_reserve(void **p, size_t *cap, size_t need, hipStream_t s, const char *who = "mesh cleanup") {
   if (need <= *cap && *p) return TSDF_HIP_OK;

@@ -23,20 +23,14 @@
 
 #include <algorithm>
 #include <cmath>
-#include <memory>
-#include <mutex>
 #include <string>
-#include <unordered_map>
-#include <vector>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
-#include "tsdf_flatten.h"
 #include "tsdf_meshgrid.h"
-#include "tsdf_meshpost.h"
 
 // ---- state -----------------------------------------------------------------------------------------------------------------
 #define MP_TEST_SLOTS 64  // counters[MP_C_TESTS ..]: link tests, striped (one address for every wave costs milliseconds)
@@ -46,63 +40,18 @@
 #define MP_C_TESTS 8
 #define MP_COUNTERS (MP_C_TESTS + MP_TEST_SLOTS)
 
-struct MpWork {
-  void *buf = nullptr;  // per-face arrays + rocprim's temporary storage
-  size_t cap = 0;
-  void *cells = nullptr;  // per-cell arrays (sized once the number of occupied cells is known)
-  size_t cells_cap = 0;
-  unsigned long long *counters = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // the device work before / after the host reads the counts
-};
-
-struct MpState {  // per handle
-  bool marched = false;
+struct tsdf_meshpost_state {  // per handle (tsdf_hip_volume::mp); a set has none: its mesh goes through tsdf_hip_mesh_cleanup
   MpWork work;
 };
 
-static std::mutex g_mp_mutex;
-static std::unordered_map<tsdf_hip_volume *, std::unique_ptr<MpState>> g_mp;
 static thread_local uint64_t g_mp_stats[4] = {0, 0, 0, 0};  // tsdf_hip_mesh_cleanup_stats
 
-static MpState *mp_state(tsdf_hip_volume *v, bool create) {
-  std::lock_guard<std::mutex> lock(g_mp_mutex);
-  auto it = g_mp.find(v);
-  if (it != g_mp.end()) return it->second.get();
-  if (!create) return nullptr;
-  return (g_mp[v] = std::unique_ptr<MpState>(new MpState())).get();
-}
-
-static void mp_work_free(MpWork &w) {
-  if (w.buf) (void)hipFree(w.buf);
-  if (w.cells) (void)hipFree(w.cells);
-  if (w.counters) (void)hipFree(w.counters);
-  for (hipEvent_t e : w.ev)
-    if (e) (void)hipEventDestroy(e);
-  w = MpWork();
-}
-
-void tsdf_meshpost_note_march(tsdf_hip_volume *v, bool succeeded) {
-  if (MpState *st = mp_state(v, succeeded)) st->marched = succeeded;  // (a failure on a handle without an entry needs none)
-  tsdf_flatten_invalidate(v);  // an indexed mesh of the soup before this march describes nothing any more
-}
-
-bool tsdf_meshpost_marched(tsdf_hip_volume *v) {
-  const MpState *st = mp_state(v, false);
-  return st && st->marched;
-}
-
 void tsdf_meshpost_release(tsdf_hip_volume *v) {
-  tsdf_flatten_release(v);
-  std::unique_ptr<MpState> st;
-  {
-    std::lock_guard<std::mutex> lock(g_mp_mutex);
-    auto it = g_mp.find(v);
-    if (it == g_mp.end()) return;
-    st = std::move(it->second);
-    g_mp.erase(it);
-  }
-  TsdfDeviceScope scope(v->multi ? tsdf_multi_first(v)->device : v->device);
-  mp_work_free(st->work);
+  if (!v->mp) return;
+  TsdfDeviceScope scope(v->device);
+  mp_work_free(v->mp->work);
+  delete v->mp;
+  v->mp = nullptr;
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
@@ -432,12 +381,11 @@ extern "C" int tsdf_hip_march_cleanup(tsdf_handle h, float face_dist, int min_ne
   if (!h) return TSDF_HIP_E_INVALID;
   if (n_tri) *n_tri = 0;
   if (const int rc = mp_check_args(face_dist, min_neighbors, 0, "tsdf_hip_march_cleanup")) return rc;
-  MpState *st = mp_state(h, false);
-  if (!st || !st->marched) {
+  if (!h->mc_valid) {
     tsdf_set_error("tsdf_hip_march_cleanup: the last tsdf_hip_march on this handle did not succeed, or none has run");
     return TSDF_HIP_E_INVALID;
   }
-  tsdf_flatten_invalidate(h);  // (tsdf_flatten.h: the soup is about to change)
+  tsdf_flatten_invalidate(h);  // (the soup is about to change)
   if (h->multi) return tsdf_multi_march_cleanup(h, face_dist, min_neighbors, n_tri);
   TSDF_ENTER(h);
   const uint64_t n = h->mc_ntri;
@@ -446,6 +394,8 @@ extern "C" int tsdf_hip_march_cleanup(tsdf_handle h, float face_dist, int min_ne
     g_mp_stats[0] = g_mp_stats[1] = g_mp_stats[2] = g_mp_stats[3] = 0;
     return TSDF_HIP_OK;
   }
+  if (!h->mp) h->mp = new tsdf_meshpost_state();
+  tsdf_meshpost_state *st = h->mp;
   MpLayout L;
   uint64_t kept = 0;
   int rc = mp_core(st->work, h->stream, h->mc_verts, 3 * n, nullptr, n, face_dist, min_neighbors, L, &kept);

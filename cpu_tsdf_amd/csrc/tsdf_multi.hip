@@ -25,9 +25,7 @@
 #include <vector>
 
 #include "tsdf_common.h"
-#include "tsdf_occupied.h"
-#include "tsdf_flatten.h"
-#include "tsdf_meshpost.h"
+#include "tsdf_morton.h"
 
 struct tsdf_hip_multi {
   std::vector<tsdf_handle> slab;
@@ -1072,17 +1070,8 @@ extern "C" int tsdf_hip_multi_link_stats(tsdf_handle h, uint64_t out[3]) {
 }
 
 // ---- marching cubes ------------------------------------------------------------------------------------------------------
-static inline uint64_t spread3_host(uint64_t v) {
-  v &= 0x1fffffull;
-  v = (v | v << 32) & 0x1f00000000ffffull;
-  v = (v | v << 16) & 0x1f0000ff0000ffull;
-  v = (v | v << 8) & 0x100f00f00f00f00full;
-  v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-  v = (v | v << 2) & 0x1249249249249249ull;
-  return v;
-}
 static inline uint64_t morton_of_cell(uint64_t c) {  // cell = x<<42 | y<<21 | z; the reference's order: x is the high bit
-  return (spread3_host(c >> 42) << 2) | (spread3_host((c >> 21) & 0x1fffff) << 1) | spread3_host(c & 0x1fffff);
+  return tsdf_morton_key(c >> 42, (c >> 21) & 0x1fffff, c & 0x1fffff);
 }
 
 int tsdf_multi_march(tsdf_handle h, float w_min, int color_mode, uint64_t *n_tri) {
@@ -1209,7 +1198,7 @@ int tsdf_multi_march_cleanup(tsdf_handle h, float face_dist, int min_neighbors, 
   return TSDF_HIP_OK;
 }
 
-// (tsdf_flatten.h) the merged soup, for tsdf_hip_march_flatten on a set
+// the merged soup, for tsdf_hip_march_flatten on a set
 void tsdf_multi_mesh(tsdf_handle h, const float **verts, const uint8_t **rgb, const uint64_t **cell) {
   tsdf_hip_multi *m = h->multi;
   *verts = m->verts.data();
@@ -1236,7 +1225,7 @@ int tsdf_multi_march_stats(tsdf_handle h, uint64_t out[4]) {  // sums over the s
 
 tsdf_handle tsdf_multi_first(tsdf_handle h) { return h->multi->slab[0]; }
 
-// (tsdf_occupied.h) slab k of the set, for the per-slab scans of tsdf_hip_occupied
+// slab k of the set, for the per-slab scans of tsdf_hip_occupied
 tsdf_handle tsdf_multi_slab(tsdf_handle h, int k) {
   return h && h->multi && k >= 0 && k < (int)h->multi->slab.size() ? h->multi->slab[k] : nullptr;
 }

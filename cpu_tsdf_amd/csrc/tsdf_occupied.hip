@@ -11,23 +11,21 @@
 #include <string.h>
 
 #include <algorithm>
-#include <memory>
-#include <mutex>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "tsdf_occupied.h"
+#include "tsdf_common.h"
+#include "tsdf_morton.h"
 
-// ---- per-handle state ----------------------------------------------------------------------------------------------------
-// Lives here, not in tsdf_hip_volume (tsdf_occupied.h says why).  What a call leaves behind is the SORTED key list in a
-// buffer of its own: the unsorted keys borrow tsdf_hip_march's cell buffer (mc_keys) and the sort's temporary storage the
-// handle's scratch, both free again when tsdf_hip_occupied returns, so neither a download nor a march disturbs the result.
-struct OccState {
+// ---- per-handle state (tsdf_hip_volume::occ) ------------------------------------------------------------------------------
+// What a call leaves behind is the SORTED key list in a buffer of its own: the unsorted keys borrow tsdf_hip_march's cell
+// buffer (mc_keys) and the sort's temporary storage the handle's scratch, both free again when tsdf_hip_occupied returns, so
+// neither a download nor a march disturbs the result.
+struct tsdf_occ_state {
   bool valid = false;      // a tsdf_hip_occupied has completed on this handle
   uint64_t n = 0;
   uint64_t *keys = nullptr;  // sorted Morton keys (device)
@@ -40,56 +38,26 @@ struct OccState {
   // a multi-GPU set: the merged list (host) and where each entry came from (slab << 48 | index in the slab's list)
   std::vector<int32_t> m_idx;
   std::vector<uint64_t> m_src;
-  std::vector<uint64_t> m_n;  // per slab: entries it contributed (0: the box misses it, its own state is not ours)
+  std::vector<uint64_t> m_n;    // per slab: entries it contributed
+  std::vector<uint8_t> m_used;  // per slab: the box touches it (else its own state is not ours)
 };
 
-static std::mutex g_occ_mutex;
-static std::unordered_map<tsdf_hip_volume *, std::unique_ptr<OccState>> g_occ;
-
-static OccState *occ_state(tsdf_hip_volume *v, bool create) {
-  std::lock_guard<std::mutex> lock(g_occ_mutex);
-  auto it = g_occ.find(v);
-  if (it != g_occ.end()) return it->second.get();
-  if (!create) return nullptr;
-  return (g_occ[v] = std::unique_ptr<OccState>(new OccState())).get();
+static tsdf_occ_state *occ_state(tsdf_hip_volume *v) {  // created by the first tsdf_hip_occupied on the handle
+  if (!v->occ) v->occ = new tsdf_occ_state();
+  return v->occ;
 }
 
 void tsdf_occupied_release(tsdf_hip_volume *v) {
-  std::unique_ptr<OccState> st;
-  {
-    std::lock_guard<std::mutex> lock(g_occ_mutex);
-    auto it = g_occ.find(v);
-    if (it == g_occ.end()) return;
-    st = std::move(it->second);
-    g_occ.erase(it);
-  }
+  if (!v->occ) return;
   TsdfDeviceScope scope(v->device);
-  if (st->keys) (void)hipFree(st->keys);
-  for (hipEvent_t e : st->ev)
+  if (v->occ->keys) (void)hipFree(v->occ->keys);
+  for (hipEvent_t e : v->occ->ev)
     if (e) (void)hipEventDestroy(e);
+  delete v->occ;
+  v->occ = nullptr;
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
-static __device__ __forceinline__ uint64_t occ_spread3(uint64_t v) {  // 21 bits -> every third bit (tsdf_march.hip spread3)
-  v &= 0x1fffffull;
-  v = (v | v << 32) & 0x1f00000000ffffull;
-  v = (v | v << 16) & 0x1f0000ff0000ffull;
-  v = (v | v << 8) & 0x100f00f00f00f00full;
-  v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-  v = (v | v << 2) & 0x1249249249249249ull;
-  return v;
-}
-
-static __device__ __forceinline__ uint32_t occ_compact3(uint64_t v) {  // its inverse
-  v &= 0x1249249249249249ull;
-  v = (v | v >> 2) & 0x10c30c30c30c30c3ull;
-  v = (v | v >> 4) & 0x100f00f00f00f00full;
-  v = (v | v >> 8) & 0x1f0000ff0000ffull;
-  v = (v | v >> 16) & 0x1f00000000ffffull;
-  v = (v | v >> 32) & 0x1fffffull;
-  return (uint32_t)v;
-}
-
 struct OccArgs {
   int x0, y0, z0, x1, y1, z1;  // the box [x0, x1) x [y0, y1) x [z0, z1), global voxel indices, inside the owned planes
   int xb, yb;                  // tile origin: x0 rounded down to a flag cell (64), y0 to a row group (4)
@@ -228,7 +196,7 @@ k_occ_scan(const OccArgs a, uint64_t *__restrict__ keys, uint64_t capacity, unsi
   unsigned long long slot = s_base + rank;
   for (unsigned k = 0; k < wave; ++k) slot += s_cnt[k];
   // x4 and yw are multiples of 4: the two low bits of x and y are the voxel's place in the tile, no carry
-  const uint64_t kxy = (occ_spread3((uint64_t)x4) << 2) | (occ_spread3((uint64_t)yw) << 1);
+  const uint64_t kxy = (tsdf_spread3((uint64_t)x4) << 2) | (tsdf_spread3((uint64_t)yw) << 1);
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
     unsigned long long m = half ? m_hi : m_lo;
@@ -237,7 +205,7 @@ k_occ_scan(const OccArgs a, uint64_t *__restrict__ keys, uint64_t capacity, unsi
       m &= m - 1ull;
       const unsigned zi = (bit >> 4) + 4u * (unsigned)half, r = (bit >> 2) & 3u, j = bit & 3u;
       if (slot < capacity)
-        keys[slot] = kxy | (occ_spread3((uint64_t)j) << 2) | (occ_spread3((uint64_t)r) << 1) | occ_spread3((uint64_t)(zs + (int)zi));
+        keys[slot] = kxy | (tsdf_spread3((uint64_t)j) << 2) | (tsdf_spread3((uint64_t)r) << 1) | tsdf_spread3((uint64_t)(zs + (int)zi));
       ++slot;
     }
   }
@@ -262,7 +230,7 @@ k_occ_emit(const OccEmitArgs a, const uint64_t *__restrict__ keys, uint64_t n, i
   const uint64_t c0 = (uint64_t)blockIdx.x * 256u, i = c0 + threadIdx.x;
   if (i < n) {
     const uint64_t key = keys[i];
-    const int x = (int)occ_compact3(key >> 2), y = (int)occ_compact3(key >> 1), z = (int)occ_compact3(key);
+    const int x = (int)tsdf_compact3(key >> 2), y = (int)tsdf_compact3(key >> 1), z = (int)tsdf_compact3(key);
     const int64_t vi = tsdf_index(a.pitch, a.ny, a.z_first, x, y, z);
     s_xyz[3 * threadIdx.x] = x, s_xyz[3 * threadIdx.x + 1] = y, s_xyz[3 * threadIdx.x + 2] = z;
     if (d) d[i] = a.d[vi];
@@ -308,7 +276,7 @@ extern "C" int tsdf_hip_occupied(tsdf_handle h, const int32_t box[6], uint64_t *
   if (n) *n = 0;
   if (h->multi) return occ_multi(h, box, n);
   TSDF_ENTER(h);
-  OccState *st = occ_state(h, true);
+  tsdf_occ_state *st = occ_state(h);
   st->valid = false;
   st->n = 0;
   if (h->nx >= (1 << 21) || h->ny >= (1 << 21) || h->nz >= (1 << 21)) return TSDF_HIP_E_UNSUPPORTED;
@@ -420,7 +388,7 @@ static OccEmitArgs occ_emit_args(tsdf_handle h) {
   return e;
 }
 
-static void occ_collect_emit_time(OccState *st) {
+static void occ_collect_emit_time(tsdf_occ_state *st) {
   if (!st->emit_pending) return;
   float ms = 0.f;
   if (hipEventSynchronize(st->ev[4]) == hipSuccess && hipEventElapsedTime(&ms, st->ev[3], st->ev[4]) == hipSuccess) st->ms[2] += ms;
@@ -431,7 +399,7 @@ extern "C" int tsdf_hip_occupied_fetch(tsdf_handle h, int32_t *idx, float *d, fl
   if (!h) return TSDF_HIP_E_INVALID;
   if (h->multi) return occ_multi_fetch(h, idx, d, w, rgb);
   TSDF_ENTER(h);
-  OccState *st = occ_state(h, false);
+  tsdf_occ_state *st = h->occ;
   if (!st || !st->valid) {
     tsdf_set_error("tsdf_hip_occupied_fetch: no tsdf_hip_occupied has completed on this handle");
     return TSDF_HIP_E_INVALID;
@@ -474,7 +442,7 @@ extern "C" int tsdf_hip_occupied_fetch_device(tsdf_handle h, int32_t *d_idx, flo
   if (!h) return TSDF_HIP_E_INVALID;
   TSDF_NOT_ON_MULTI(h, "tsdf_hip_occupied_fetch_device (the merged list of a multi-GPU set lives on the host)");
   TSDF_ENTER(h);
-  OccState *st = occ_state(h, false);
+  tsdf_occ_state *st = h->occ;
   if (!st || !st->valid) {
     tsdf_set_error("tsdf_hip_occupied_fetch_device: no tsdf_hip_occupied has completed on this handle");
     return TSDF_HIP_E_INVALID;
@@ -496,13 +464,13 @@ extern "C" int tsdf_hip_occupied_fetch_device(tsdf_handle h, int32_t *d_idx, flo
 extern "C" int tsdf_hip_occupied_stats(tsdf_handle h, uint64_t out[4]) {
   if (!h || !out) return TSDF_HIP_E_INVALID;
   out[0] = out[1] = out[2] = out[3] = 0;
-  OccState *st = occ_state(h, false);
+  tsdf_occ_state *st = h->occ;
   if (!st || !st->valid) return TSDF_HIP_OK;
   if (h->multi) {  // sums over the slabs the box touched; "flags decided" only if they did on every one; the slowest slab's time
     out[2] = 1;
     for (size_t k = 0; k < st->m_n.size(); ++k) {
-      OccState *ss = occ_state(tsdf_multi_slab(h, (int)k), false);
-      if (!ss || !ss->valid || !(st->m_n[k] >> 63)) continue;  // (bit 63 clear: the box misses this slab)
+      const tsdf_occ_state *ss = tsdf_multi_slab(h, (int)k)->occ;
+      if (!ss || !ss->valid || !st->m_used[k]) continue;  // (the box misses this slab)
       out[1] += ss->d_bytes;
       out[2] &= ss->used_flags ? 1u : 0u;
       out[3] = std::max<uint64_t>(out[3], (uint64_t)((ss->ms[0] + ss->ms[1]) * 1000.f));
@@ -523,15 +491,15 @@ extern "C" int tsdf_hip_occupied_timing(tsdf_handle h, float ms[3]) {
   if (!h || !ms) return TSDF_HIP_E_INVALID;
   ms[0] = ms[1] = ms[2] = 0.f;
   if (h->multi) {  // the slowest slab, phase by phase
-    OccState *st = occ_state(h, false);
+    tsdf_occ_state *st = h->occ;
     for (size_t k = 0; st && k < st->m_n.size(); ++k) {
       float m[3];
-      if (!(st->m_n[k] >> 63) || tsdf_hip_occupied_timing(tsdf_multi_slab(h, (int)k), m)) continue;
+      if (!st->m_used[k] || tsdf_hip_occupied_timing(tsdf_multi_slab(h, (int)k), m)) continue;
       for (int i = 0; i < 3; ++i) ms[i] = std::max(ms[i], m[i]);
     }
     return TSDF_HIP_OK;
   }
-  OccState *st = occ_state(h, false);
+  tsdf_occ_state *st = h->occ;
   if (!st || !st->valid) return TSDF_HIP_OK;
   TSDF_ON_DEVICE(h->device);
   occ_collect_emit_time(st);
@@ -543,24 +511,12 @@ extern "C" int tsdf_hip_occupied_timing(tsdf_handle h, float ms[3]) {
 // Every slab scans the part of the box it owns, on its own stream, from a host thread of its own (as tsdf_multi_march runs
 // the slabs' meshes); the sorted slab lists are merged by key on the host.  z is the LOW bit of every key triple, so the
 // slabs interleave: runs are taken from the slab with the smallest key up to the smallest key of the others.
-static inline uint64_t occ_spread3_host(uint64_t v) {
-  v &= 0x1fffffull;
-  v = (v | v << 32) & 0x1f00000000ffffull;
-  v = (v | v << 16) & 0x1f0000ff0000ffull;
-  v = (v | v << 8) & 0x100f00f00f00f00full;
-  v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-  v = (v | v << 2) & 0x1249249249249249ull;
-  return v;
-}
-static inline uint64_t occ_key_host(const int32_t *p) {
-  return (occ_spread3_host((uint64_t)p[0]) << 2) | (occ_spread3_host((uint64_t)p[1]) << 1) | occ_spread3_host((uint64_t)p[2]);
-}
-#define OCC_SLAB_USED (1ull << 63)  // in OccState::m_n: the box touches the slab (its count in the low bits)
+static inline uint64_t occ_key_host(const int32_t *p) { return tsdf_morton_key((uint64_t)p[0], (uint64_t)p[1], (uint64_t)p[2]); }
 
 static int occ_multi(tsdf_handle h, const int32_t box[6], uint64_t *n_out) {
   if (const int rc = tsdf_multi_flush(h)) return rc;  // (frame pairing: slabs launch what they hold first)
   const int n = tsdf_hip_slab_count(h);
-  OccState *st = occ_state(h, true);
+  tsdf_occ_state *st = occ_state(h);
   st->valid = false;
   st->n = 0;
   int32_t b[6] = {0, 0, 0, h->nx, h->ny, h->nz};
@@ -600,13 +556,15 @@ static int occ_multi(tsdf_handle h, const int32_t box[6], uint64_t *n_out) {
   for (auto &t : th) t.join();
   uint64_t total = 0;
   st->m_n.assign(n, 0);
+  st->m_used.assign(n, 0);
   for (int k = 0; k < n; ++k) {
     if (part[k].rc) {
       tsdf_set_error(part[k].err);
       return part[k].rc;
     }
     total += part[k].n;
-    st->m_n[k] = part[k].n | (part[k].used ? OCC_SLAB_USED : 0ull);
+    st->m_n[k] = part[k].n;
+    st->m_used[k] = part[k].used ? 1 : 0;
   }
   st->m_idx.resize(total * 3);
   st->m_src.resize(total);
@@ -637,7 +595,7 @@ static int occ_multi(tsdf_handle h, const int32_t box[6], uint64_t *n_out) {
 }
 
 static int occ_multi_fetch(tsdf_handle h, int32_t *idx, float *d, float *w, uint8_t *rgb) {
-  OccState *st = occ_state(h, false);
+  tsdf_occ_state *st = h->occ;
   if (!st || !st->valid) {
     tsdf_set_error("tsdf_hip_occupied_fetch: no tsdf_hip_occupied has completed on this handle");
     return TSDF_HIP_E_INVALID;
@@ -657,7 +615,7 @@ static int occ_multi_fetch(tsdf_handle h, int32_t *idx, float *d, float *w, uint
   std::vector<Part> part(n);
   std::vector<std::thread> th;
   for (int k = 0; k < n; ++k) {
-    const uint64_t nk = st->m_n[k] & ~OCC_SLAB_USED;
+    const uint64_t nk = st->m_n[k];
     if (!nk) continue;
     th.emplace_back([&part, h, k, nk, d, w, rgb]() {
       Part &p = part[k];
