@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "tsdf_common.h"
 #include "tsdf_div.h"
@@ -2358,6 +2359,52 @@ static IntegrateHost make_args(tsdf_handle h, const float T[12]) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// The plain kernels (k_integrate_rgbn, k_integrate_lab, k_integrate_plain): one thread per voxel, grid = (x blocks of 256,
+// rows, planes).  They share updateVoxel up to addObservation (plain_observe) and the observation count (plain_count);
+// each kernel's own part is its voxel class's addObservation.
+struct PlainObs {
+  int pix;     // the pixel the voxel projects to
+  float z;     // its raw depth (weight_by_depth_ needs it)
+  float dn;    // the hinged, normalised distance handed to addObservation
+  int64_t vi;  // the voxel's index in the planes
+};
+
+// Does this thread's voxel reach addObservation?  If so, *o says with what.
+template <int ORDER>
+static __device__ __forceinline__ bool plain_observe(const IntegrateArgs &a, const double *__restrict__ cam,
+                                                     const float *__restrict__ ctrx, const float *__restrict__ ctry,
+                                                     const float *__restrict__ ctrz, const float *__restrict__ depth, PlainObs *o) {
+  const int x = (int)(blockIdx.x * 256u + threadIdx.x);
+  const int y = (int)blockIdx.y, zl = (int)blockIdx.z;
+  if (!(x < (int)a.pitch)) return false;  // the x centre table is NaN beyond nx: those lanes fail the range test
+  const float cx = ctrx[x], cy = ctry[y], cz = ctrz[a.z_global0 + zl];
+  float g[3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q)  // pcl::transformPoint (hpp:145) in the summation order of this PCL build
+    g[q] = ORDER == TSDF_XFORM_PCL_SSE ? cx * a.m[4 * q] + (cy * a.m[4 * q + 1] + (cz * a.m[4 * q + 2] + a.m[4 * q + 3]))
+                                       : ((a.m[4 * q] * cx + a.m[4 * q + 1] * cy) + a.m[4 * q + 2] * cz) + a.m[4 * q + 3];
+  const bool in = !(g[2] < a.zmin || g[2] > a.zmax) && g[2] > 0.f &&  // hpp:146, .cpp:616
+                  (!a.ref_cull || reference_cull_keeps(a, cx, cy, cz));  // hpp:93-94 (replication mode)
+  o->pix = in ? project_exact(a, cam, g[0], g[1], g[2]) : -1;
+  if (o->pix < 0) return false;
+  o->z = depth[o->pix];
+  const float dn = o->z - g[2];  // hpp:159
+  if (isnan(o->z) || dn < -a.neg) return false;  // hpp:152, :193-196
+  o->dn = dn > a.pos ? a.pos_over_neg : dn / a.neg;  // hpp:189-198
+  o->vi = ((int64_t)(a.zl0 + zl) * a.plane_rows + y) * a.pitch + x;
+  return true;
+}
+
+// n_obs (NULL: no count): 1024 striped counters of the voxels that reached addObservation, one atomic per wave
+static __device__ __forceinline__ void plain_count(bool observed, unsigned long long *__restrict__ n_obs) {
+  if (!n_obs) return;
+  const unsigned long long m = __ballot(observed);
+  if ((threadIdx.x & 63u) == 0u && m)
+    atomicAdd(n_obs + ((blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * gridDim.x * gridDim.y) & 1023u),
+              (unsigned long long)__popcll(m));
+}
+
+// ---------------------------------------------------------------------------------------------
 // TSDF_COLOR_RGB_NORMALIZED: updateVoxel with RGBNormalized::addObservation (src/lib/octree.cpp:380-393).
 // A plain kernel -- one thread per voxel, exact fp64 projection, the compiler's IEEE divisions and square
 // root, every operation in the reference's order -- because this voxel class is a setter away from the
@@ -2370,57 +2417,34 @@ k_integrate_rgbn(const IntegrateArgs a, float *__restrict__ D, float *__restrict
                  const float *__restrict__ depth, const uint32_t *__restrict__ bgra, const double *__restrict__ cam,
                  const float *__restrict__ ctrx, const float *__restrict__ ctry, const float *__restrict__ ctrz,
                  unsigned long long *__restrict__ n_obs) {
-  const int x = (int)(blockIdx.x * 256u + threadIdx.x);
-  const int y = (int)blockIdx.y, zl = (int)blockIdx.z;
-  bool observed = false;
-  if (x < (int)a.pitch) {  // the x centre table is NaN beyond nx: those lanes fail the range test
-    const float cx = ctrx[x], cy = ctry[y], cz = ctrz[a.z_global0 + zl];
-    float g[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q)  // pcl::transformPoint (hpp:145) in the summation order of this PCL build
-      g[q] = ORDER == TSDF_XFORM_PCL_SSE ? cx * a.m[4 * q] + (cy * a.m[4 * q + 1] + (cz * a.m[4 * q + 2] + a.m[4 * q + 3]))
-                                         : ((a.m[4 * q] * cx + a.m[4 * q + 1] * cy) + a.m[4 * q + 2] * cz) + a.m[4 * q + 3];
-    const bool in = !(g[2] < a.zmin || g[2] > a.zmax) && g[2] > 0.f &&  // hpp:146, .cpp:616
-                    (!a.ref_cull || reference_cull_keeps(a, cx, cy, cz));  // hpp:93-94 (replication mode)
-    const int pix = in ? project_exact(a, cam, g[0], g[1], g[2]) : -1;
-    if (pix >= 0) {
-      const float z = depth[pix];
-      float dn = z - g[2];  // hpp:159
-      if (!isnan(z) && !(dn < -a.neg)) {  // hpp:152, :193-196
-        dn = dn > a.pos ? a.pos_over_neg : dn / a.neg;  // hpp:189-198
-        const int64_t vi = ((int64_t)(a.zl0 + zl) * a.plane_rows + y) * a.pitch + x;
-        const uint32_t c = bgra[pix];  // PCL memory order b, g, r, a
-        const float r = (float)((c >> 16) & 255u), gch = (float)((c >> 8) & 255u), b = (float)(c & 255u);
-        float w = Wt[vi], d = D[vi];
-        const float wn = 1.f;
-        const float wsum = w + wn;
-        const float i = sqrtf(r * r + gch * gch + b * b);  // octree.cpp:384 (products and sums are exact)
-        const float rf = r / i, gf = gch / i, bf = b / i;   // a black pixel makes these NaN, as in the reference
-        const float rn = (w * RN[vi] + wn * rf) / wsum;
-        const float gn = (w * GN[vi] + wn * gf) / wsum;
-        const float bn = (w * BN[vi] + wn * bf) / wsum;
-        const float im = (w * IN[vi] + wn * i) / wsum;
-        RN[vi] = rn;
-        GN[vi] = gn;
-        BN[vi] = bn;
-        IN[vi] = im;
-        // getRGB (octree.cpp:396-402): uint8_t = float, i.e. cvttss2si and the low byte (NaN -> 0)
-        RGB[vi] = ((uint32_t)(int)(rn * im) & 255u) | (((uint32_t)(int)(gn * im) & 255u) << 8) |
-                  (((uint32_t)(int)(bn * im) & 255u) << 16);
-        uint32_t unused = 0;
-        add_observation_ieee<false>(d, w, unused, dn, 0u, a.wmax);
-        D[vi] = d;
-        Wt[vi] = w;
-        observed = true;
-      }
-    }
+  PlainObs o;
+  const bool observed = plain_observe<ORDER>(a, cam, ctrx, ctry, ctrz, depth, &o);
+  if (observed) {
+    const int64_t vi = o.vi;
+    const uint32_t c = bgra[o.pix];  // PCL memory order b, g, r, a
+    const float r = (float)((c >> 16) & 255u), gch = (float)((c >> 8) & 255u), b = (float)(c & 255u);
+    float w = Wt[vi], d = D[vi];
+    const float wn = 1.f;
+    const float wsum = w + wn;
+    const float i = sqrtf(r * r + gch * gch + b * b);  // octree.cpp:384 (products and sums are exact)
+    const float rf = r / i, gf = gch / i, bf = b / i;   // a black pixel makes these NaN, as in the reference
+    const float rn = (w * RN[vi] + wn * rf) / wsum;
+    const float gn = (w * GN[vi] + wn * gf) / wsum;
+    const float bn = (w * BN[vi] + wn * bf) / wsum;
+    const float im = (w * IN[vi] + wn * i) / wsum;
+    RN[vi] = rn;
+    GN[vi] = gn;
+    BN[vi] = bn;
+    IN[vi] = im;
+    // getRGB (octree.cpp:396-402): uint8_t = float, i.e. cvttss2si and the low byte (NaN -> 0)
+    RGB[vi] = ((uint32_t)(int)(rn * im) & 255u) | (((uint32_t)(int)(gn * im) & 255u) << 8) |
+              (((uint32_t)(int)(bn * im) & 255u) << 16);
+    uint32_t unused = 0;
+    add_observation_ieee<false>(d, w, unused, o.dn, 0u, a.wmax);
+    D[vi] = d;
+    Wt[vi] = w;
   }
-  if (n_obs) {
-    const unsigned long long m = __ballot(observed);
-    if ((threadIdx.x & 63u) == 0u && m)
-      atomicAdd(n_obs + ((blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * gridDim.x * gridDim.y) & 1023u),
-                (unsigned long long)__popcll(m));
-  }
+  plain_count(observed, n_obs);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2488,50 +2512,27 @@ k_integrate_lab(const IntegrateArgs a, float *__restrict__ D, float *__restrict_
                 const float *__restrict__ depth, const float4 *__restrict__ lab, const double *__restrict__ cam,
                 const float *__restrict__ ctrx, const float *__restrict__ ctry, const float *__restrict__ ctrz,
                 unsigned long long *__restrict__ n_obs) {
-  const int x = (int)(blockIdx.x * 256u + threadIdx.x);
-  const int y = (int)blockIdx.y, zl = (int)blockIdx.z;
-  bool observed = false;
-  if (x < (int)a.pitch) {  // the x centre table is NaN beyond nx: those lanes fail the range test
-    const float cx = ctrx[x], cy = ctry[y], cz = ctrz[a.z_global0 + zl];
-    float g[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q)  // pcl::transformPoint (hpp:145) in the summation order of this PCL build
-      g[q] = ORDER == TSDF_XFORM_PCL_SSE ? cx * a.m[4 * q] + (cy * a.m[4 * q + 1] + (cz * a.m[4 * q + 2] + a.m[4 * q + 3]))
-                                         : ((a.m[4 * q] * cx + a.m[4 * q + 1] * cy) + a.m[4 * q + 2] * cz) + a.m[4 * q + 3];
-    const bool in = !(g[2] < a.zmin || g[2] > a.zmax) && g[2] > 0.f &&  // hpp:146, .cpp:616
-                    (!a.ref_cull || reference_cull_keeps(a, cx, cy, cz));  // hpp:93-94 (replication mode)
-    const int pix = in ? project_exact(a, cam, g[0], g[1], g[2]) : -1;
-    if (pix >= 0) {
-      const float z = depth[pix];
-      float dn = z - g[2];  // hpp:159
-      if (!isnan(z) && !(dn < -a.neg)) {  // hpp:152, :193-196
-        dn = dn > a.pos ? a.pos_over_neg : dn / a.neg;  // hpp:189-198
-        const int64_t vi = ((int64_t)(a.zl0 + zl) * a.plane_rows + y) * a.pitch + x;
-        const float4 n = lab[pix];  // RGB2LAB of the pixel (octree.cpp:537)
-        float w = Wt[vi], d = D[vi];
-        const float wn = 1.f;
-        const float wsum = w + wn;  // octree.cpp:535
-        const float lm = (w * LM[vi] + wn * n.x) / wsum;  // :540-542
-        const float am = (w * AM[vi] + wn * n.y) / wsum;
-        const float bm = (w * BM[vi] + wn * n.z) / wsum;
-        LM[vi] = lm;
-        AM[vi] = am;
-        BM[vi] = bm;
-        RGB[vi] = lab_to_rgb(lm, am, bm);  // getRGB (octree.cpp:547-551)
-        uint32_t unused = 0;
-        add_observation_ieee<false>(d, w, unused, dn, 0u, a.wmax);
-        D[vi] = d;
-        Wt[vi] = w;
-        observed = true;
-      }
-    }
+  PlainObs o;
+  const bool observed = plain_observe<ORDER>(a, cam, ctrx, ctry, ctrz, depth, &o);
+  if (observed) {
+    const int64_t vi = o.vi;
+    const float4 n = lab[o.pix];  // RGB2LAB of the pixel (octree.cpp:537)
+    float w = Wt[vi], d = D[vi];
+    const float wn = 1.f;
+    const float wsum = w + wn;  // octree.cpp:535
+    const float lm = (w * LM[vi] + wn * n.x) / wsum;  // :540-542
+    const float am = (w * AM[vi] + wn * n.y) / wsum;
+    const float bm = (w * BM[vi] + wn * n.z) / wsum;
+    LM[vi] = lm;
+    AM[vi] = am;
+    BM[vi] = bm;
+    RGB[vi] = lab_to_rgb(lm, am, bm);  // getRGB (octree.cpp:547-551)
+    uint32_t unused = 0;
+    add_observation_ieee<false>(d, w, unused, o.dn, 0u, a.wmax);
+    D[vi] = d;
+    Wt[vi] = w;
   }
-  if (n_obs) {
-    const unsigned long long m = __ballot(observed);
-    if ((threadIdx.x & 63u) == 0u && m)
-      atomicAdd(n_obs + ((blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * gridDim.x * gridDim.y) & 1023u),
-                (unsigned long long)__popcll(m));
-  }
+  plain_count(observed, n_obs);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2550,92 +2551,108 @@ k_integrate_plain(const IntegrateArgs a, float *__restrict__ D, float *__restric
                   const float *__restrict__ depth, const uint32_t *__restrict__ bgra, const double *__restrict__ cam,
                   const float *__restrict__ ctrx, const float *__restrict__ ctry, const float *__restrict__ ctrz,
                   unsigned long long *__restrict__ n_obs) {
-  const int x = (int)(blockIdx.x * 256u + threadIdx.x);
-  const int y = (int)blockIdx.y, zl = (int)blockIdx.z;
-  bool observed = false;
-  if (x < (int)a.pitch) {  // the x centre table is NaN beyond nx: those lanes fail the range test
-    const float cx = ctrx[x], cy = ctry[y], cz = ctrz[a.z_global0 + zl];
-    float g[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q)  // pcl::transformPoint (hpp:145) in the summation order of this PCL build
-      g[q] = ORDER == TSDF_XFORM_PCL_SSE ? cx * a.m[4 * q] + (cy * a.m[4 * q + 1] + (cz * a.m[4 * q + 2] + a.m[4 * q + 3]))
-                                         : ((a.m[4 * q] * cx + a.m[4 * q + 1] * cy) + a.m[4 * q + 2] * cz) + a.m[4 * q + 3];
-    const bool in = !(g[2] < a.zmin || g[2] > a.zmax) && g[2] > 0.f &&  // hpp:146, .cpp:616
-                    (!a.ref_cull || reference_cull_keeps(a, cx, cy, cz));  // hpp:93-94 (replication mode)
-    const int pix = in ? project_exact(a, cam, g[0], g[1], g[2]) : -1;
-    if (pix >= 0) {
-      const float z = depth[pix];
-      float dn = z - g[2];  // hpp:159
-      if (!isnan(z) && !(dn < -a.neg)) {  // hpp:152, :193-196
-        dn = dn > a.pos ? a.pos_over_neg : dn / a.neg;  // hpp:189-198
-        float wn = 1.f;
-        if (BY_DEPTH) {  // hpp:201-202; std::min(a, b) = (b < a) ? b : a
-          const double q = (double)z / 10.;
-          wn = (float)((double)wn * (1. - ((1. < q) ? 1. : q)));
-        }
-        const int64_t vi = ((int64_t)(a.zl0 + zl) * a.plane_rows + y) * a.pitch + x;
-        unsigned k_old = 0u;
-        float w, d = D[vi];
-        // weight_by_variance_ (hpp:203-204; VM / VN = OctreeNode::M_ / nsample_, non-NULL only then): once a voxel has
-        // more than five samples, w_new *= std::exp(logNormal(d_new, d_, getVariance())) with logNormal (hpp:106-110)
-        // = -std::pow(x - mean, 2) / (2 * var) -- the double pow of a float difference (an exact square), a double
-        // quotient stored in a float -- getVariance (octree.cpp:281-287) = (M_ / w_) * (nsample_ / (nsample_ - 1)) with
-        // an INTEGER quotient, and std::exp(float) = the host libm's expf (tsdf_expf_glibc)
-        int ns_old = 0;
-        if (!PACKED && VM) {
-          ns_old = VN[vi];
-          if (ns_old > 5) {
-            const float var = (VM[vi] / Wt[vi]) * (float)(ns_old / (ns_old - 1));
-            const double dx = (double)(dn - d);
-            const float ln = (float)(-(dx * dx) / (double)(2 * var));
-            wn *= tsdf_expf_glibc(ln, a.expf_fused_r != 0);
-          }
-        }
-        if (PACKED) {
-          k_old = COLOR ? RGB[vi] >> 24 : (unsigned)K8[vi];
-          w = tsdf_decode_w(k_old, a.wmax);
-        } else {
-          w = Wt[vi];
-        }
-        const float wsum = w + wn;  // (wn: after both weightings)
-        if (COLOR) {  // RGBNode::addObservation, octree.cpp:331-335: the OLD w, static_cast<uint8_t> = cvttss2si & 255
-          const uint32_t c = bgra[pix], old = RGB[vi];  // PCL memory order b, g, r, a (byte 3 of `old`: the PACKED count)
-          uint32_t out = 0u;
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) {
-            const float c_old = (float)((old >> (8 * ch)) & 255u);
-            const float c_new = (float)((c >> (16 - 8 * ch)) & 255u);
-            const float qv = (w * c_old + wn * c_new) / wsum;
-            // x86: NaN and anything outside int32 give INT_MIN, whose low byte is 0; v_cvt_i32_f32 gives 0 for NaN
-            const bool in_range = qv > -2147483904.f && qv < 2147483648.f;
-            out |= (in_range ? ((uint32_t)(int)qv & 255u) : 0u) << (8 * ch);
-          }
-          RGB[vi] = PACKED ? out | (min(k_old + 1u, a.kmax) << 24) : out;
-        }
-        const float d_old = d;
-        d = (d * w + dn * wn) / wsum;  // octree.cpp:156
-        w = wsum;                      // :157
-        if (w > a.wmax) w = a.wmax;    // :158-159
-        D[vi] = d;
-        if (!PACKED && VM) {
-          VM[vi] += wn * (dn - d) * (dn - d_old);  // octree.cpp:160
-          VN[vi] = ns_old + 1;                      // :161
-        }
-        if (PACKED) {
-          if (!COLOR) K8[vi] = (uint8_t)min(k_old + 1u, a.kmax);
-        } else {
-          Wt[vi] = w;
-        }
-        observed = true;
+  PlainObs o;
+  const bool observed = plain_observe<ORDER>(a, cam, ctrx, ctry, ctrz, depth, &o);
+  if (observed) {
+    const float dn = o.dn;
+    const int64_t vi = o.vi;
+    float wn = 1.f;
+    if (BY_DEPTH) {  // hpp:201-202; std::min(a, b) = (b < a) ? b : a
+      const double q = (double)o.z / 10.;
+      wn = (float)((double)wn * (1. - ((1. < q) ? 1. : q)));
+    }
+    unsigned k_old = 0u;
+    float w, d = D[vi];
+    // weight_by_variance_ (hpp:203-204; VM / VN = OctreeNode::M_ / nsample_, non-NULL only then): once a voxel has
+    // more than five samples, w_new *= std::exp(logNormal(d_new, d_, getVariance())) with logNormal (hpp:106-110)
+    // = -std::pow(x - mean, 2) / (2 * var) -- the double pow of a float difference (an exact square), a double
+    // quotient stored in a float -- getVariance (octree.cpp:281-287) = (M_ / w_) * (nsample_ / (nsample_ - 1)) with
+    // an INTEGER quotient, and std::exp(float) = the host libm's expf (tsdf_expf_glibc)
+    int ns_old = 0;
+    if (!PACKED && VM) {
+      ns_old = VN[vi];
+      if (ns_old > 5) {
+        const float var = (VM[vi] / Wt[vi]) * (float)(ns_old / (ns_old - 1));
+        const double dx = (double)(dn - d);
+        const float ln = (float)(-(dx * dx) / (double)(2 * var));
+        wn *= tsdf_expf_glibc(ln, a.expf_fused_r != 0);
       }
     }
+    if (PACKED) {
+      k_old = COLOR ? RGB[vi] >> 24 : (unsigned)K8[vi];
+      w = tsdf_decode_w(k_old, a.wmax);
+    } else {
+      w = Wt[vi];
+    }
+    const float wsum = w + wn;  // (wn: after both weightings)
+    if (COLOR) {  // RGBNode::addObservation, octree.cpp:331-335: the OLD w, static_cast<uint8_t> = cvttss2si & 255
+      const uint32_t c = bgra[o.pix], old = RGB[vi];  // PCL memory order b, g, r, a (byte 3 of `old`: the PACKED count)
+      uint32_t out = 0u;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const float c_old = (float)((old >> (8 * ch)) & 255u);
+        const float c_new = (float)((c >> (16 - 8 * ch)) & 255u);
+        const float qv = (w * c_old + wn * c_new) / wsum;
+        // x86: NaN and anything outside int32 give INT_MIN, whose low byte is 0; v_cvt_i32_f32 gives 0 for NaN
+        const bool in_range = qv > -2147483904.f && qv < 2147483648.f;
+        out |= (in_range ? ((uint32_t)(int)qv & 255u) : 0u) << (8 * ch);
+      }
+      RGB[vi] = PACKED ? out | (min(k_old + 1u, a.kmax) << 24) : out;
+    }
+    const float d_old = d;
+    d = (d * w + dn * wn) / wsum;  // octree.cpp:156
+    w = wsum;                      // :157
+    if (w > a.wmax) w = a.wmax;    // :158-159
+    D[vi] = d;
+    if (!PACKED && VM) {
+      VM[vi] += wn * (dn - d) * (dn - d_old);  // octree.cpp:160
+      VN[vi] = ns_old + 1;                      // :161
+    }
+    if (PACKED) {
+      if (!COLOR) K8[vi] = (uint8_t)min(k_old + 1u, a.kmax);
+    } else {
+      Wt[vi] = w;
+    }
   }
-  if (n_obs) {
-    const unsigned long long m = __ballot(observed);
-    if ((threadIdx.x & 63u) == 0u && m)
-      atomicAdd(n_obs + ((blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * gridDim.x * gridDim.y) & 1023u),
-                (unsigned long long)__popcll(m));
-  }
+  plain_count(observed, n_obs);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Host side.
+// Runtime flags -> template arguments: with_consts(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, ...), and a generic
+// lambda f uses its arguments as constants.  The launch sites drop the instances that are never built with `if constexpr`.
+template <class F>
+static void with_consts(F &&f) {
+  f();
+}
+template <class F, class... Rest>
+static void with_consts(F &&f, bool b, Rest... rest) {
+  if (b)
+    with_consts([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else
+    with_consts([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+constexpr int xform_order_of(bool pcl_sse) {  // (tsdf_hip_create admits these two orders only)
+  return pcl_sse ? TSDF_XFORM_PCL_SSE : TSDF_XFORM_LEFT_TO_RIGHT;
+}
+
+// A pose with a non-finite (or absurdly large) entry makes g.x/g.y/g.z non-finite or out of sensor
+// range for every voxel, and the reference then observes nothing (u/v become INT_MIN or g.z fails
+// hpp:146 / .cpp:616).  Same here, without launching: the kernels may assume finite arithmetic.
+static bool pose_is_finite(const float T[12]) {
+  for (int i = 0; i < 12; ++i)
+    if (!(std::isfinite(T[i]) && fabsf(T[i]) <= 1e15f)) return false;
+  return true;
+}
+
+// The camera members CullArgs and RowArgs share: pose, intrinsics, sensor range, image size.
+template <class Args>
+static void fill_camera(Args &c, const tsdf_params &p, const float T[12]) {
+  for (int i = 0; i < 12; ++i) c.m[i] = T[i];
+  c.fx = p.fx, c.fy = p.fy, c.cx = p.cx, c.cy = p.cy;
+  c.zlo = p.min_sensor_dist > 0 ? p.min_sensor_dist : 0;
+  c.zmax = p.max_sensor_dist;
+  c.W = p.image_width, c.H = p.image_height;
 }
 
 static bool fast_projection_ok(const IntegrateHost &a, bool color, bool force = false) {
@@ -2799,24 +2816,326 @@ static bool slab_all_inside(const tsdf_hip_volume *h, const float T[12]) {
   return all_inside;
 }
 
-// Asynchronous half: queues the launch on the handle's stream.  `count` selects the counting instance, whose striped
-// counters stay in h->counter until tsdf_integrate_collect reads them (a multi-GPU set launches every slab first and
-// collects afterwards, so the slabs count concurrently).
-int tsdf_integrate_launch(tsdf_handle h, const float *d_depth, const uint32_t *d_bgra, const float T[12], bool count) {
+// The fast kernels read the frame through ONE buffer descriptor based at the depth image, with the colour image at a
+// 32-bit byte offset from it.  True, and *off (0 without colour), when the caller's buffers already lie so: the colour
+// image behind the depth image, within 2 GB.
+static bool frame_bgra_offset(const tsdf_params &p, const float *d_depth, const uint32_t *d_bgra, unsigned *off) {
+  *off = 0;
+  if (!p.integrate_color) return true;
+  const size_t npx = (size_t)p.image_width * p.image_height;
+  const char *zd = (const char *)d_depth, *cb = (const char *)d_bgra;
+  if (!(cb >= zd + npx * 4 && (size_t)(cb - zd) + npx * 4 < (1ull << 31))) return false;
+  *off = (unsigned)(cb - zd);
+  return true;
+}
+
+// Frame staging: caller buffers laid out otherwise are copied into the handle's [depth | bgra] allocation first (two
+// device copies of 1.2 MB each at 640x480), and *d_depth then points there.
+static int stage_frame(tsdf_handle h, const float **d_depth, const uint32_t *d_bgra, unsigned *bgra_off) {
+  if (frame_bgra_offset(h->p, *d_depth, d_bgra, bgra_off)) return TSDF_HIP_OK;
+  const size_t npx = (size_t)h->p.image_width * h->p.image_height;
+  if (*d_depth != h->frame_depth)
+    TSDF_HIP_TRY(hipMemcpyAsync(h->frame_depth, *d_depth, npx * 4, hipMemcpyDeviceToDevice, h->stream));
+  if (d_bgra != h->frame_bgra)
+    TSDF_HIP_TRY(hipMemcpyAsync(h->frame_bgra, d_bgra, npx * 4, hipMemcpyDeviceToDevice, h->stream));
+  *d_depth = h->frame_depth;
+  *bgra_off = (unsigned)(npx * 4);
+  return TSDF_HIP_OK;
+}
+
+// planes fastest when the frame outgrows an XCD's L2 (knob zfast: -1 auto, 0 / 1 force)
+static int zfast_for(const tsdf_params &p, unsigned gx) {
+  const size_t frame_bytes = (size_t)p.image_width * p.image_height * (p.integrate_color ? 8 : 4);
+  return tsdf_tuning().zfast < 0 ? (frame_bytes > (3u << 20) && gx <= 65535u) : (tsdf_tuning().zfast != 0 && gx <= 65535u);
+}
+
+// The kernels keep the "band seen" flags per block in LDS with block-local row groups: they are the volume's row groups
+// only if every block starts on a multiple of 4 rows (always, unless the rows_per_block knob was turned below 4);
+// otherwise this launch keeps no flags (NULL) and marching cubes reads everything until the next reset.
+static uint8_t *band_flags_for(tsdf_handle h, const IntegrateArgs &a) {
+  uint8_t *band = h->band_exact && ((a.rpb * a.TY) & 3) == 0 && (a.y_abs0 & 3) == 0 ? h->band : nullptr;
+  if (!band) h->band_exact = false;
+  return band;
+}
+
+// The software-pipelined row loop (k_integrate_p / k_integrate_pc): ALLIN, PACKED, every block's rows present, resting
+// hinge (knob pipe: bit 0 = without colour, k_integrate_p; bit 1 = with colour, k_integrate_pc).
+static bool pipelined_rows_apply(tsdf_handle h, const IntegrateArgs &a, bool color, bool fastproj, bool allin, bool live) {
+  return (tsdf_tuning().pipe & (color ? 2 : 1)) && fastproj && allin && !live && h->packed && a.hinge_fixed && a.neg_in_window &&
+         a.ny % a.TY == 0;
+}
+
+// The plain family: k_integrate_plain (plain_mode 1-4) or, plain_mode 0, the kernels of the handle's own colour mode
+// (TSDF_COLOR_RGB_NORMALIZED / TSDF_COLOR_LAB: h->cn[0]).  One thread per voxel of the whole slab; they count
+// observations only (no changed-byte slots).
+static int launch_plain_family(tsdf_handle h, const IntegrateArgs &a, unsigned gz, int plain_mode, const float *d_depth,
+                               const uint32_t *d_bgra, const float T[12], bool count) {
   const tsdf_params &p = h->p;
-  h->count_slots = 0;
-  h->count_ran = false;
-  const IntegrateHost hh = make_args(h, T);
-  IntegrateArgs a = hh.a;
-  unsigned gx = (unsigned)((a.qpr + a.TX - 1) / a.TX);
-  unsigned gy = (unsigned)((a.ny + a.rpb * a.TY - 1) / (a.rpb * a.TY));
-  unsigned gz = (unsigned)hh.planes;
-  if (gy > 65535u || gz > 65535u) {
+  if (plain_mode && ((h->packed && plain_mode != 3) || h->cn[0])) {  // (2 and 4 need float weights)
+    tsdf_set_error("weight_by_depth needs the F32W layout and TSDF_COLOR_RGB");
+    return TSDF_HIP_E_UNSUPPORTED;
+  }
+  if (count) TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, 1024 * sizeof(unsigned long long), h->stream));
+  const bool pose_ok = pose_is_finite(T);
+  if (pose_ok) {
+    const dim3 grid((unsigned)((h->pitch + 255) / 256), (unsigned)h->ny, gz), block(256);
+    if (grid.y > 65535u) {
+      tsdf_set_error("grid too large for one launch");
+      return TSDF_HIP_E_UNSUPPORTED;
+    }
+    unsigned long long *n_obs = count ? h->counter : nullptr;
+    const bool sse = p.xform_order == TSDF_XFORM_PCL_SSE, by_depth = plain_mode == 2;
+    if (plain_mode) {
+      float *vm = h->weight_by_variance ? h->vm : nullptr;
+      int32_t *vn = h->weight_by_variance ? h->vn : nullptr;
+      with_consts(
+          [&](auto SSE, auto COLOR, auto BY_DEPTH, auto PACKED) {
+            if constexpr (!(BY_DEPTH && PACKED))  // (never built: weight_by_depth_ needs float weights)
+              hipLaunchKernelGGL((k_integrate_plain<xform_order_of(SSE), COLOR, BY_DEPTH, PACKED>), grid, block, 0, h->stream, a,
+                                 h->d, h->w, h->rgb, h->k8, vm, vn, d_depth, d_bgra, h->cam64, h->ctr[0], h->ctr[1], h->ctr[2], n_obs);
+          },
+          sse, p.integrate_color != 0, by_depth, !by_depth && h->packed);
+    } else if (h->lab_img) {  // TSDF_COLOR_LAB: convert the frame's pixels once, then the per-voxel kernel
+      const int npx = p.image_width * p.image_height;
+      hipLaunchKernelGGL(k_lab_image, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, d_bgra, h->lab_lut, h->lab_img, npx);
+      with_consts(
+          [&](auto SSE) {
+            hipLaunchKernelGGL((k_integrate_lab<xform_order_of(SSE)>), grid, block, 0, h->stream, a, h->d, h->w, h->rgb, h->cn[0],
+                               h->cn[1], h->cn[2], d_depth, h->lab_img, h->cam64, h->ctr[0], h->ctr[1], h->ctr[2], n_obs);
+          },
+          sse);
+    } else {
+      with_consts(
+          [&](auto SSE) {
+            hipLaunchKernelGGL((k_integrate_rgbn<xform_order_of(SSE)>), grid, block, 0, h->stream, a, h->d, h->w, h->rgb, h->cn[0],
+                               h->cn[1], h->cn[2], h->cn[3], d_depth, d_bgra, h->cam64, h->ctr[0], h->ctr[1], h->ctr[2], n_obs);
+          },
+          sse);
+    }
+    TSDF_HIP_TRY(hipGetLastError());
+  }
+  h->count_slots = count ? 1024 : 0;
+  h->count_ran = pose_ok;
+  return TSDF_HIP_OK;
+}
+
+// What one launch of the fast kernels covers.  whole_slab_plan: the handle's own planes and centre tables.  A LIVE
+// launch (plan_live) shrinks that to the blocks that meet the observable index box -- host only: pointers, centre tables
+// and `a` are offset to the box's first block, the kernel does not know -- and adds the block flags.
+struct LaunchPlan {
+  IntegrateArgs a;
+  unsigned gx, gy, gz;  // blocks along x, row groups, planes
+  float *D, *Wt;
+  uint32_t *RGB;
+  uint8_t *K8;
+  const float *ctrx, *ctry;
+  const uint8_t *live;      // k_cull's block flags (NULL: not a LIVE launch)
+  bool nothing_observable;  // the index box is empty: nothing to launch
+};
+
+static LaunchPlan whole_slab_plan(tsdf_handle h, const IntegrateHost &hh) {
+  LaunchPlan pl;
+  const IntegrateArgs &a = pl.a = hh.a;
+  pl.gx = (unsigned)((a.qpr + a.TX - 1) / a.TX);
+  pl.gy = (unsigned)((a.ny + a.rpb * a.TY - 1) / (a.rpb * a.TY));
+  pl.gz = (unsigned)hh.planes;
+  pl.D = h->d, pl.Wt = h->w, pl.RGB = h->rgb, pl.K8 = h->k8;
+  pl.ctrx = h->ctr[0], pl.ctry = h->ctr[1];
+  pl.live = nullptr;
+  pl.nothing_observable = false;
+  return pl;
+}
+
+// Launch kind.  Cull (TSDF_HIP_CULL: 1 on when useful, 0 off, 2 always) is skipped when the whole slab is provably inside
+// the frustum and sensor range (convex frustum: test the slab's 8 corners), the turntable case: then the ALLIN instance
+// runs if the grid and the weights allow it, else the general one.  Otherwise the launch is LIVE (plan_live).
+struct LaunchKind {
+  bool all_inside;  // the slab's corners are inside, and the cull knob allows the shortcut
+  bool allin;       // every voxel of the launch in sensor range and a pixel inside the image: the ALLIN instance
+  bool live;        // the frame cannot see the whole slab (or the reference's cull bites): row intervals + block flags
+};
+
+static LaunchKind launch_kind(tsdf_handle h, const float T[12], const IntegrateArgs &a, bool rc, bool rc_rows) {
+  LaunchKind k = {false, false, false};
+  if (tsdf_tuning().cull) {
+    k.all_inside = tsdf_tuning().cull != 2 && slab_all_inside(h, T);
+    k.allin = k.all_inside && tsdf_tuning().allin && (h->nx & 3) == 0 && zlo_margin_ok(T, h) &&
+              (!h->packed || (a.wmax_is_int && (float)h->kmax == h->p.max_weight));
+  }
+  if (rc) k.allin = false;  // (the ALLIN instance knows no row intervals; measured: an ALLIN pass over the blocks the cull leaves
+                            // whole + an interval pass over the rest took 16.0 + 3.8 ms where ONE interval pass takes 18 ms)
+  k.live = (tsdf_tuning().cull && !k.all_inside && row_intervals_usable(h, false)) || rc_rows;
+  return k;
+}
+
+// LIVE, step 1: narrow blocks, 32 quads (128 voxels) by 8 rows per pass, 64 rows per block, so that the flags and a wave's
+// row skip follow the frustum's outline (a block of a whole 1024-voxel row group is mostly outside it when the camera sits
+// inside the volume).
+static void narrow_live_blocks(LaunchPlan &pl) {
+  IntegrateArgs &a = pl.a;
+  const int ltx = std::max(4, std::min(8, tsdf_tuning().live_log2tx));  // 32 quads by default (a knob for A/B runs: 16 .. 256)
+  if (a.TX <= (1 << ltx)) return;
+  a.TX = 1 << ltx, a.log2TX = ltx, a.TY = 256 >> ltx;
+  // (twice the rows of a full-width block: 128 voxels x 64 rows, eight passes -- Scene B at 2048^3: 0.43 / 0.36 / 0.34 /
+  // 0.36 ms per frame with 16 / 32 / 64 / 128 rows)
+  a.rpb = std::max(1, std::min(2 * tsdf_tuning().rows_per_block, 64) / a.TY);  // (64 rows: the default knob's own value since round 6)
+  pl.gx = (unsigned)((a.qpr + a.TX - 1) / a.TX);
+  pl.gy = (unsigned)((a.ny + a.rpb * a.TY - 1) / (a.rpb * a.TY));
+}
+
+// LIVE, step 2: the launch shrinks to the blocks that meet the index box of the observable pyramid (observable_index_box).
+// Conservative, so results do not change.
+static void shrink_to_index_box(tsdf_handle h, const float T[12], LaunchPlan &pl) {
+  IntegrateArgs &a = pl.a;
+  int lo[3], hi[3];
+  bool empty = false;
+  if (!observable_index_box(h, T, lo, hi, &empty)) return;
+  lo[2] = std::max(lo[2], h->z_begin);
+  hi[2] = std::min(hi[2], h->z_end - 1);
+  if (empty || lo[2] > hi[2]) {
+    pl.nothing_observable = true;
+    return;
+  }
+  const int bxv = a.TX * 4, byr = a.rpb * a.TY;  // voxels / rows per block
+  const int bx0 = lo[0] / bxv, bx1 = hi[0] / bxv, by0 = lo[1] / byr, by1 = hi[1] / byr;
+  const int x_off = bx0 * bxv, y_off = by0 * byr, z_off = lo[2] - h->z_begin;
+  const int64_t e_off = (int64_t)y_off * h->pitch + x_off;
+  pl.D += e_off;
+  if (pl.Wt) pl.Wt += e_off;
+  if (pl.RGB) pl.RGB += e_off;
+  if (pl.K8) pl.K8 += e_off;
+  pl.ctrx += x_off;
+  pl.ctry += y_off;
+  a.qpr -= x_off / 4;
+  a.ny -= y_off;
+  a.x_abs0 = x_off;
+  a.y_abs0 = y_off;
+  a.z_global0 += z_off;
+  a.zl0 += z_off;
+  pl.gx = (unsigned)(bx1 - bx0 + 1);
+  pl.gy = (unsigned)(by1 - by0 + 1);
+  pl.gz = (unsigned)(hi[2] - lo[2] + 1);
+}
+
+// the handle's scratch for a LIVE launch: nb block flags, nrows interval words
+static int grow_live_scratch(tsdf_handle h, size_t nb, size_t nrows) {
+  if (nb <= h->live_cap && nrows <= h->row_iv_cap) return TSDF_HIP_OK;
+  TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
+  if (nb > h->live_cap) {
+    if (h->live) TSDF_HIP_TRY(hipFree(h->live));
+    h->live = nullptr, h->live_cap = 0;
+    TSDF_HIP_TRY(hipMalloc(&h->live, nb));
+    h->live_cap = nb;
+  }
+  if (nrows > h->row_iv_cap) {
+    if (h->row_iv) TSDF_HIP_TRY(hipFree(h->row_iv));
+    h->row_iv = nullptr, h->row_iv_cap = 0;
+    TSDF_HIP_TRY(hipMalloc(&h->row_iv, nrows * sizeof(uint32_t)));
+    h->row_iv_cap = nrows;
+  }
+  return TSDF_HIP_OK;
+}
+
+// LIVE, step 3: k_rows writes every row's interval, k_cull flags, inside the box, the blocks none of whose voxels can be
+// observed.
+static int launch_rows_and_cull(tsdf_handle h, const float T[12], bool rc_rows, LaunchPlan &pl) {
+  IntegrateArgs &a = pl.a;
+  // the rows the launch's blocks cover (the last row group may reach past the box, never past the grid)
+  const int rows = a.ny = std::min(a.ny, (int)pl.gy * a.rpb * a.TY);
+  CullArgs c;
+  fill_camera(c, h->p, T);
+  c.nx = h->nx - (int)(pl.ctrx - h->ctr[0]), c.ny = rows, c.z_global0 = a.z_global0;
+  c.bx_vox = a.TX * 4, c.by_rows = a.rpb * a.TY;
+  c.gx = (int)pl.gx, c.gy = (int)pl.gy, c.gz = (int)pl.gz;
+  RowArgs ra;
+  fill_camera(ra, h->p, T);
+  ra.nx = std::min(c.nx, (int)pl.gx * a.TX * 4), ra.ny = rows, ra.nz = (int)pl.gz, ra.z_global0 = a.z_global0;
+  ra.rc = rc_rows ? 1 : 0;
+  for (int i = 0; i < 24; ++i) ra.cull[i] = rc_rows ? h->cull_planes[i] : 0.f;
+  const size_t nb = (size_t)pl.gx * pl.gy * pl.gz, nrows = (size_t)rows * pl.gz;
+  if (const int e = grow_live_scratch(h, nb, nrows)) return e;
+  const dim3 row_grid((unsigned)((nrows + 255) / 256)), block(256);
+  if (ra.nx <= TSDF_ROWS_LDS_NX)
+    hipLaunchKernelGGL(k_rows<true>, row_grid, block, 0, h->stream, ra, pl.ctrx, pl.ctry, h->ctr[2], h->row_iv);
+  else
+    hipLaunchKernelGGL(k_rows<false>, row_grid, block, 0, h->stream, ra, pl.ctrx, pl.ctry, h->ctr[2], h->row_iv);
+  hipLaunchKernelGGL(k_cull, dim3((unsigned)((nb + 255) / 256)), block, 0, h->stream, c, pl.ctrx, pl.ctry, h->ctr[2], h->row_iv, h->live);
+  TSDF_HIP_TRY(hipGetLastError());
+  pl.live = h->live;
+  return TSDF_HIP_OK;
+}
+
+// The LIVE plan.  (A slab that is wholly in view -- only the reference's cull decides anything -- keeps the streaming
+// block shape and the whole grid.)
+static int plan_live(tsdf_handle h, const float T[12], bool all_inside, bool rc_rows, LaunchPlan &pl) {
+  if (!all_inside) narrow_live_blocks(pl);
+  if (tsdf_tuning().cull && !all_inside) shrink_to_index_box(h, T, pl);
+  if (pl.gy > 65535u) {
     tsdf_set_error("grid too large for one launch");
     return TSDF_HIP_E_UNSUPPORTED;
   }
-  const bool color = p.integrate_color != 0;
-  if (color && !d_bgra) {
+  return pl.nothing_observable ? TSDF_HIP_OK : launch_rows_and_cull(h, T, rc_rows, pl);
+}
+
+// Dispatch: the instance of k_integrate (or, `pipe`, of the pipelined kernels) for this launch.
+static void dispatch_fast(tsdf_handle h, const LaunchPlan &pl, const float *d_depth, bool count, bool fastproj, bool allin,
+                          bool pipe, uint8_t *band_arg) {
+  const IntegrateArgs &a = pl.a;
+  const dim3 grid(a.zfast ? pl.gz : pl.gx, pl.gy, a.zfast ? pl.gx : pl.gz), block(256);
+  const bool sse = h->p.xform_order == TSDF_XFORM_PCL_SSE, color = h->p.integrate_color != 0;
+  if (pipe) {
+    with_consts(
+        [&](auto SSE, auto COUNT) {
+          if (color)
+            hipLaunchKernelGGL((k_integrate_pc<xform_order_of(SSE), COUNT>), grid, block, 0, h->stream, a, pl.D, pl.RGB, d_depth,
+                               h->cam64, pl.ctrx, pl.ctry, h->ctr[2], h->counter, band_arg);
+          else
+            hipLaunchKernelGGL((k_integrate_p<xform_order_of(SSE), COUNT>), grid, block, 0, h->stream, a, pl.D, pl.K8, d_depth,
+                               h->cam64, pl.ctrx, pl.ctry, h->ctr[2], h->counter, band_arg);
+        },
+        sse, count);
+    return;
+  }
+  with_consts(
+      [&](auto SSE, auto COLOR, auto FASTPROJ, auto COUNT, auto PACKED, auto ALLIN, auto LIVE) {
+        if constexpr (!(ALLIN && (!FASTPROJ || LIVE)))  // (never built: ALLIN without the fast projection, ALLIN with LIVE)
+          hipLaunchKernelGGL((k_integrate<xform_order_of(SSE), COLOR, FASTPROJ, COUNT, PACKED, ALLIN, LIVE>), grid, block, 0,
+                             h->stream, a, pl.D, pl.Wt, pl.RGB, pl.K8, d_depth, h->cam64, pl.ctrx, pl.ctry, h->ctr[2], h->counter,
+                             pl.live, band_arg, h->row_iv);
+      },
+      sse, color, fastproj, count, h->packed, allin, pl.live != nullptr);
+}
+
+#if TSDF_PHASE_TIMER
+// diagnostic build: the phase accumulators of THIS launch, appended to $TSDF_HIP_PHASE_FILE and cleared
+static int dump_phase_timers(tsdf_handle h, bool count, bool allin, bool live) {
+  const char *pf = getenv("TSDF_HIP_PHASE_FILE");
+  if (!pf) return TSDF_HIP_OK;
+  TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
+  static unsigned long long host_ph[1024 * TSDF_NPHASE];
+  TSDF_HIP_TRY(hipMemcpyFromSymbol(host_ph, HIP_SYMBOL(g_phase), sizeof host_ph));
+  unsigned long long sum[TSDF_NPHASE] = {0};
+  for (int i = 0; i < 1024; ++i)
+    for (int k = 0; k < TSDF_NPHASE; ++k) sum[k] += host_ph[i * TSDF_NPHASE + k];
+  memset(host_ph, 0, sizeof host_ph);
+  TSDF_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_phase), host_ph, sizeof host_ph));
+  if (FILE *f = fopen(pf, "a")) {
+    fprintf(f, "{\"color\": %d, \"count\": %d, \"allin\": %d, \"live\": %d, \"packed\": %d, \"blocks\": %d, \"phase\": [",
+            (int)(h->p.integrate_color != 0), (int)count, (int)allin, (int)live, (int)h->packed, h->last_launch[3]);
+    for (int k = 0; k < TSDF_NPHASE; ++k) fprintf(f, "%llu%s", sum[k], k + 1 < TSDF_NPHASE ? ", " : "]}\n");
+    fclose(f);
+  }
+  return TSDF_HIP_OK;
+}
+#endif
+
+// Validation of a launch, in the order the errors have always been reported.
+static int validate_launch(tsdf_handle h, const LaunchPlan &pl, const uint32_t *d_bgra) {
+  if (pl.gy > 65535u || pl.gz > 65535u) {
+    tsdf_set_error("grid too large for one launch");
+    return TSDF_HIP_E_UNSUPPORTED;
+  }
+  if (h->p.integrate_color && !d_bgra) {
     tsdf_set_error("integrate_color is set but no colour image was given");
     return TSDF_HIP_E_INVALID;
   }
@@ -2824,358 +3143,61 @@ int tsdf_integrate_launch(tsdf_handle h, const float *d_depth, const uint32_t *d
     tsdf_set_error("weight_by_variance_ (hpp:203-204) needs the per-voxel M_ / nsample_ planes: F32W layout, TSDF_COLOR_RGB");
     return TSDF_HIP_E_UNSUPPORTED;
   }
-  // the plain per-voxel kernel: weight_by_depth_ (2), the test knob "plain_kernel" (1), or the reference-cull replication
-  // mode (3: any layout; the fast kernels know nothing about the six planes)
+  return TSDF_HIP_OK;
+}
+
+// Asynchronous half: queues the launch on the handle's stream.  `count` selects the counting instance, whose striped
+// counters stay in h->counter until tsdf_integrate_collect reads them (a multi-GPU set launches every slab first and
+// collects afterwards, so the slabs count concurrently).
+int tsdf_integrate_launch(tsdf_handle h, const float *d_depth, const uint32_t *d_bgra, const float T[12], bool count) {
+  h->count_slots = 0;
+  h->count_ran = false;
+  const IntegrateHost hh = make_args(h, T);
+  LaunchPlan pl = whole_slab_plan(h, hh);
+  IntegrateArgs &a = pl.a;
+  if (const int e = validate_launch(h, pl, d_bgra)) return e;
   // The reference's frustum cull (tsdf_hip_set_reference_cull): nothing to do when the six planes provably keep every
   // voxel of this slab (ordinary cameras: the cull is a no-op and the launch is the usual one); otherwise the fast kernel
   // applies it through the row intervals (k_rows), or -- planes that are not finite, a grid too wide for the interval
   // words, the `refcull_plain` knob -- the plain per-voxel kernel tests the six planes itself.
   const bool rc = h->ref_cull && !reference_cull_keeps_whole_slab(h, h->cull_planes);
   const bool rc_rows = rc && !h->cn[0] && !tsdf_tuning().refcull_plain && row_intervals_usable(h, true);
+  // the plain per-voxel kernel: weight_by_depth_ (2), weight_by_variance_ (4), the test knob "plain_kernel" (1), or the
+  // reference-cull replication mode (3: any layout; the fast kernels know nothing about the six planes)
   const int plain_mode = h->weight_by_depth ? 2 : h->weight_by_variance ? 4 : (rc && !rc_rows && !h->cn[0]) ? 3 : (tsdf_tuning().plain_kernel && !h->packed && !h->cn[0] ? 1 : 0);
   a.ref_cull = rc ? 1 : 0;  // (the plain kernels test the planes per voxel only when they can bite)
-  if (plain_mode || h->cn[0]) h->band_exact = false;  // the plain kernels keep no "band seen" flags: marching cubes reads everything
-  if (plain_mode) {
-    if ((h->packed && plain_mode != 3) || h->cn[0]) {  // (2 and 4 need float weights)
-      tsdf_set_error("weight_by_depth needs the F32W layout and TSDF_COLOR_RGB");
-      return TSDF_HIP_E_UNSUPPORTED;
-    }
-    if (count) TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, 1024 * sizeof(unsigned long long), h->stream));
-    bool pose_ok = true;
-    for (int i = 0; i < 12; ++i) pose_ok &= std::isfinite(T[i]) && fabsf(T[i]) <= 1e15f;
-    if (pose_ok) {
-      const dim3 grid((unsigned)((h->pitch + 255) / 256), (unsigned)h->ny, gz), block(256);
-      if (grid.y > 65535u) {
-        tsdf_set_error("grid too large for one launch");
-        return TSDF_HIP_E_UNSUPPORTED;
-      }
-#define LAUNCH_PLAIN(ORDER, COLOR, BYD, PK)                                                                             \
-  hipLaunchKernelGGL((k_integrate_plain<ORDER, COLOR, BYD, PK>), grid, block, 0, h->stream, a, h->d, h->w, h->rgb, h->k8, \
-                     h->weight_by_variance ? h->vm : nullptr, h->weight_by_variance ? h->vn : nullptr, d_depth, d_bgra,   \
-                     h->cam64, h->ctr[0], h->ctr[1], h->ctr[2], count ? h->counter : nullptr)
-#define LP2(ORDER, COLOR)                      \
-  do {                                         \
-    if (plain_mode == 2)                       \
-      LAUNCH_PLAIN(ORDER, COLOR, true, false); \
-    else if (h->packed)                        \
-      LAUNCH_PLAIN(ORDER, COLOR, false, true); \
-    else                                       \
-      LAUNCH_PLAIN(ORDER, COLOR, false, false); \
-  } while (0)
-      if (p.xform_order == TSDF_XFORM_PCL_SSE) {
-        if (color)
-          LP2(TSDF_XFORM_PCL_SSE, true);
-        else
-          LP2(TSDF_XFORM_PCL_SSE, false);
-      } else {
-        if (color)
-          LP2(TSDF_XFORM_LEFT_TO_RIGHT, true);
-        else
-          LP2(TSDF_XFORM_LEFT_TO_RIGHT, false);
-      }
-#undef LP2
-#undef LAUNCH_PLAIN
-      TSDF_HIP_TRY(hipGetLastError());
-    }
-    h->count_slots = count ? 1024 : 0;  // these kernels count observations only (no changed-byte slots)
-    h->count_ran = pose_ok;
-    return TSDF_HIP_OK;
+  if (plain_mode || h->cn[0]) {
+    h->band_exact = false;  // the plain kernels keep no "band seen" flags: marching cubes reads everything
+    return launch_plain_family(h, a, pl.gz, plain_mode, d_depth, d_bgra, T, count);
   }
-  if (h->cn[0]) {  // TSDF_COLOR_RGB_NORMALIZED / TSDF_COLOR_LAB: their own plain kernels
-    if (count) TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, 1024 * sizeof(unsigned long long), h->stream));
-    bool pose_ok = true;
-    for (int i = 0; i < 12; ++i) pose_ok &= std::isfinite(T[i]) && fabsf(T[i]) <= 1e15f;
-    if (pose_ok) {
-      const dim3 grid((unsigned)((h->pitch + 255) / 256), (unsigned)h->ny, gz), block(256);
-      if (grid.y > 65535u) {
-        tsdf_set_error("grid too large for one launch");
-        return TSDF_HIP_E_UNSUPPORTED;
-      }
-      if (h->lab_img) {  // TSDF_COLOR_LAB: convert the frame's pixels once, then the per-voxel kernel
-        const int npx = p.image_width * p.image_height;
-        hipLaunchKernelGGL(k_lab_image, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, d_bgra,
-                           h->lab_lut, h->lab_img, npx);
-      }
-#define LAUNCH_RGBN(ORDER)                                                                                        \
-  do {                                                                                                            \
-    if (h->lab_img)                                                                                               \
-      hipLaunchKernelGGL((k_integrate_lab<ORDER>), grid, block, 0, h->stream, a, h->d, h->w, h->rgb, h->cn[0],    \
-                         h->cn[1], h->cn[2], d_depth, h->lab_img, h->cam64, h->ctr[0], h->ctr[1], h->ctr[2],      \
-                         count ? h->counter : nullptr);                                                           \
-    else                                                                                                          \
-      hipLaunchKernelGGL((k_integrate_rgbn<ORDER>), grid, block, 0, h->stream, a, h->d, h->w, h->rgb, h->cn[0],   \
-                         h->cn[1], h->cn[2], h->cn[3], d_depth, d_bgra, h->cam64, h->ctr[0], h->ctr[1], h->ctr[2], \
-                         count ? h->counter : nullptr);                                                           \
-  } while (0)
-      if (p.xform_order == TSDF_XFORM_PCL_SSE)
-        LAUNCH_RGBN(TSDF_XFORM_PCL_SSE);
-      else
-        LAUNCH_RGBN(TSDF_XFORM_LEFT_TO_RIGHT);
-#undef LAUNCH_RGBN
-      TSDF_HIP_TRY(hipGetLastError());
-    }
-    h->count_slots = count ? 1024 : 0;  // these kernels count observations only (no changed-byte slots)
-    h->count_ran = pose_ok;
-    return TSDF_HIP_OK;
-  }
-  // The kernel reads the frame through ONE buffer descriptor based at the depth image, with the colour
-  // image at a 32-bit byte offset from it.  Caller buffers laid out otherwise are staged into the handle's
-  // [depth | bgra] allocation first (two device copies of 1.2 MB each at 640x480).
-  const size_t npx = (size_t)p.image_width * p.image_height;
-  a.bgra_off = 0;
-  if (color) {
-    const char *zd = (const char *)d_depth, *cb = (const char *)d_bgra;
-    if (cb >= zd + npx * 4 && (size_t)(cb - zd) + npx * 4 < (1ull << 31)) {
-      a.bgra_off = (unsigned)(cb - zd);
-    } else {
-      if (d_depth != h->frame_depth)
-        TSDF_HIP_TRY(hipMemcpyAsync(h->frame_depth, d_depth, npx * 4, hipMemcpyDeviceToDevice, h->stream));
-      if (d_bgra != h->frame_bgra)
-        TSDF_HIP_TRY(hipMemcpyAsync(h->frame_bgra, d_bgra, npx * 4, hipMemcpyDeviceToDevice, h->stream));
-      d_depth = h->frame_depth;
-      a.bgra_off = (unsigned)(npx * 4);
-    }
-  }
-  // Cull (TSDF_HIP_CULL: 1 on when useful, 0 off, 2 always): skipped when the whole slab is provably inside the
-  // frustum and sensor range (convex frustum: test the slab's 8 corners), the turntable case.  Otherwise
-  //  (1) the launch shrinks to the blocks that meet the index box of the observable pyramid
-  //      (observable_index_box; host only -- pointers, centre tables and limits are offset to the box's first
-  //      block, the kernel does not know), and
-  //  (2) k_cull flags, inside that box, the blocks none of whose voxels can be observed.
-  // Neither changes results: both are conservative.
-  const uint8_t *live = nullptr;
-  float *D = h->d, *Wt = h->w;
-  uint32_t *RGB = h->rgb;
-  uint8_t *K8 = h->k8;
-  const float *ctrx = h->ctr[0], *ctry = h->ctr[1];
-  bool nothing_observable = false;
-  bool allin = false;  // every voxel of the launch in sensor range and a pixel inside the image: the ALLIN instance
-  bool all_inside = false;
-  if (tsdf_tuning().cull) {
-    all_inside = tsdf_tuning().cull != 2 && slab_all_inside(h, T);
-    allin = all_inside && tsdf_tuning().allin && (h->nx & 3) == 0 && zlo_margin_ok(T, h) &&
-            (!h->packed || (a.wmax_is_int && (float)h->kmax == p.max_weight));
-  }
-  if (rc) allin = false;  // (the ALLIN instance knows no row intervals; measured: an ALLIN pass over the blocks the cull leaves
-                          // whole + an interval pass over the rest took 16.0 + 3.8 ms where ONE interval pass takes 18 ms)
-  // LIVE launch: the frame cannot see the whole slab (or the reference's cull bites): row intervals + block flags
-  const bool want_live = (tsdf_tuning().cull && !all_inside && row_intervals_usable(h, false)) || rc_rows;
-  if (want_live) {
-    // narrow blocks: 32 quads (128 voxels) by 8 rows per pass, 64 rows per block, so that the flags and a wave's row skip follow the frustum's outline (a block
-    // of a whole 1024-voxel row group is mostly outside it when the camera sits inside the volume)
-    // (a slab that is wholly in view -- only the reference's cull decides anything -- keeps the streaming shape)
-    const int ltx = std::max(4, std::min(8, tsdf_tuning().live_log2tx));  // 32 quads by default (a knob for A/B runs: 16 .. 256)
-    if (a.TX > (1 << ltx) && !all_inside) {
-      a.TX = 1 << ltx, a.log2TX = ltx, a.TY = 256 >> ltx;
-      // (twice the rows of a full-width block: 128 voxels x 64 rows, eight passes -- Scene B at 2048^3: 0.43 / 0.36 / 0.34 /
-      // 0.36 ms per frame with 16 / 32 / 64 / 128 rows)
-      a.rpb = std::max(1, std::min(2 * tsdf_tuning().rows_per_block, 64) / a.TY);  // (64 rows: the default knob's own value since round 6)
-      gx = (unsigned)((a.qpr + a.TX - 1) / a.TX);
-      gy = (unsigned)((a.ny + a.rpb * a.TY - 1) / (a.rpb * a.TY));
-    }
-    int lo[3], hi[3];
-    bool empty = false;
-    if (tsdf_tuning().cull && !all_inside && observable_index_box(h, T, lo, hi, &empty)) {
-      lo[2] = std::max(lo[2], h->z_begin);
-      hi[2] = std::min(hi[2], h->z_end - 1);
-      if (empty || lo[2] > hi[2]) {
-        nothing_observable = true;
-      } else {
-        const int bxv = a.TX * 4, byr = a.rpb * a.TY;  // voxels / rows per block
-        const int bx0 = lo[0] / bxv, bx1 = hi[0] / bxv, by0 = lo[1] / byr, by1 = hi[1] / byr;
-        const int x_off = bx0 * bxv, y_off = by0 * byr, z_off = lo[2] - h->z_begin;
-        const int64_t e_off = (int64_t)y_off * h->pitch + x_off;
-        D += e_off;
-        if (Wt) Wt += e_off;
-        if (RGB) RGB += e_off;
-        if (K8) K8 += e_off;
-        ctrx += x_off;
-        ctry += y_off;
-        a.qpr -= x_off / 4;
-        a.ny -= y_off;
-        a.x_abs0 = x_off;
-        a.y_abs0 = y_off;
-        a.z_global0 += z_off;
-        a.zl0 += z_off;
-        gx = (unsigned)(bx1 - bx0 + 1);
-        gy = (unsigned)(by1 - by0 + 1);
-        gz = (unsigned)(hi[2] - lo[2] + 1);
-      }
-    }
-    if (gy > 65535u) {
-      tsdf_set_error("grid too large for one launch");
-      return TSDF_HIP_E_UNSUPPORTED;
-    }
-    if (!nothing_observable) {
-      CullArgs c;
-      for (int i = 0; i < 12; ++i) c.m[i] = T[i];
-      c.fx = p.fx, c.fy = p.fy, c.cx = p.cx, c.cy = p.cy;
-      c.zlo = p.min_sensor_dist > 0 ? p.min_sensor_dist : 0;
-      c.zmax = p.max_sensor_dist;
-      c.W = p.image_width, c.H = p.image_height;
-      c.nx = h->nx - (int)(ctrx - h->ctr[0]), c.ny = a.ny, c.z_global0 = a.z_global0;
-      c.bx_vox = a.TX * 4, c.by_rows = a.rpb * a.TY;
-      c.gx = (int)gx, c.gy = (int)gy, c.gz = (int)gz;
-      // the rows the launch's blocks cover (the last row group may reach past the box, never past the grid)
-      const int rows = std::min(a.ny, (int)gy * a.rpb * a.TY);
-      a.ny = rows;
-      c.ny = rows;
-      RowArgs ra;
-      for (int i = 0; i < 12; ++i) ra.m[i] = T[i];
-      ra.fx = p.fx, ra.fy = p.fy, ra.cx = p.cx, ra.cy = p.cy;
-      ra.zlo = c.zlo, ra.zmax = c.zmax;
-      ra.W = c.W, ra.H = c.H;
-      ra.nx = std::min(c.nx, (int)gx * a.TX * 4), ra.ny = rows, ra.nz = (int)gz, ra.z_global0 = a.z_global0;
-      ra.rc = rc_rows ? 1 : 0;
-      for (int i = 0; i < 24; ++i) ra.cull[i] = rc_rows ? h->cull_planes[i] : 0.f;
-      const size_t nb = (size_t)gx * gy * gz, nrows = (size_t)rows * gz;
-      if (nb > h->live_cap || nrows > h->row_iv_cap) {
-        TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
-        if (nb > h->live_cap) {
-          if (h->live) TSDF_HIP_TRY(hipFree(h->live));
-          h->live = nullptr, h->live_cap = 0;
-          TSDF_HIP_TRY(hipMalloc(&h->live, nb));
-          h->live_cap = nb;
-        }
-        if (nrows > h->row_iv_cap) {
-          if (h->row_iv) TSDF_HIP_TRY(hipFree(h->row_iv));
-          h->row_iv = nullptr, h->row_iv_cap = 0;
-          TSDF_HIP_TRY(hipMalloc(&h->row_iv, nrows * sizeof(uint32_t)));
-          h->row_iv_cap = nrows;
-        }
-      }
-      if (ra.nx <= TSDF_ROWS_LDS_NX)
-        hipLaunchKernelGGL(k_rows<true>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, h->stream, ra, ctrx, ctry, h->ctr[2], h->row_iv);
-      else
-        hipLaunchKernelGGL(k_rows<false>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, h->stream, ra, ctrx, ctry, h->ctr[2], h->row_iv);
-      hipLaunchKernelGGL(k_cull, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, h->stream, c, ctrx, ctry, h->ctr[2], h->row_iv, h->live);
-      TSDF_HIP_TRY(hipGetLastError());
-      live = h->live;
-    }
-  }
+  if (const int e = stage_frame(h, &d_depth, d_bgra, &a.bgra_off)) return e;
+  const LaunchKind kind = launch_kind(h, T, a, rc, rc_rows);
+  if (kind.live)
+    if (const int e = plan_live(h, T, kind.all_inside, rc_rows, pl)) return e;
   if (count) TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, 4096 * sizeof(unsigned long long), h->stream));
-  // A pose with a non-finite (or absurdly large) entry makes g.x/g.y/g.z non-finite or out of sensor
-  // range for every voxel, and the reference then observes nothing (u/v become INT_MIN or g.z fails
-  // hpp:146 / .cpp:616).  Same here, without launching: the kernel may assume finite arithmetic.
-  bool pose_ok = true;
-  for (int i = 0; i < 12; ++i) pose_ok &= std::isfinite(T[i]) && fabsf(T[i]) <= 1e15f;
-  const bool fastproj = fast_projection_ok(hh, p.integrate_color != 0);
+  const bool pose_ok = pose_is_finite(T);
+  const bool fastproj = fast_projection_ok(hh, h->p.integrate_color != 0);
   h->last_launch[0] = h->last_launch[1] = h->last_launch[2] = h->last_launch[3] = 0;
-  // the kernel keeps the "band seen" flags per block in LDS with block-local row groups: they are the volume's row groups
-  // only if every block starts on a multiple of 4 rows (always, unless the rows_per_block knob was turned below 4);
-  // otherwise this launch keeps no flags and marching cubes reads everything until the next reset
-  uint8_t *band_arg = h->band_exact && ((a.rpb * a.TY) & 3) == 0 && (a.y_abs0 & 3) == 0 ? h->band : nullptr;
-  if (!band_arg) h->band_exact = false;
+  uint8_t *band_arg = band_flags_for(h, a);
   a.implied_d = implied_distances(h, a, band_arg != nullptr);
   h->last_implied_on = a.implied_d != 0;
-  if (pose_ok && !nothing_observable) {
-    // planes fastest when the frame outgrows an XCD's L2 (knob zfast: -1 auto, 0 / 1 force)
-    const size_t frame_bytes = npx * (color ? 8 : 4);
-    a.zfast = tsdf_tuning().zfast < 0 ? (frame_bytes > (3u << 20) && gx <= 65535u) : (tsdf_tuning().zfast != 0 && gx <= 65535u);
-    const dim3 grid(a.zfast ? gz : gx, gy, a.zfast ? gx : gz), block(256);
-    h->last_launch[0] = fastproj && allin && !live;
+  if (pose_ok && !pl.nothing_observable) {
+    const bool live = pl.live != nullptr, allin = fastproj && kind.allin && !live;
+    const bool pipe = pipelined_rows_apply(h, a, h->p.integrate_color != 0, fastproj, kind.allin, live);
+    a.zfast = zfast_for(h->p, pl.gx);
+    h->last_launch[0] = (allin ? 1 : 0) | (pipe ? 0x100 : 0);  // bit 8: the pipelined row loop
     h->last_launch[1] = fastproj;
     h->last_launch[2] = live ? (rc_rows ? 2 : 1) : 0;
-    h->last_launch[3] = (int)std::min<uint64_t>((uint64_t)gx * gy * gz, 0x7fffffffu);
-#define LAUNCH(ORDER, COLOR, FP, COUNT, PK, AI, LV)                                                                  \
-  hipLaunchKernelGGL((k_integrate<ORDER, COLOR, FP, COUNT, PK, AI, LV>), grid, block, 0, h->stream, a, D, Wt, RGB, K8, \
-                     d_depth, h->cam64, ctrx, ctry, h->ctr[2], h->counter, live, band_arg, h->row_iv)
-#define L6(ORDER, COLOR, FP, COUNT, PK)                  \
-  do {                                                   \
-    if (live)                                            \
-      LAUNCH(ORDER, COLOR, FP, COUNT, PK, false, true);  \
-    else if (FP && allin)                                \
-      LAUNCH(ORDER, COLOR, FP, COUNT, PK, FP, false);    \
-    else                                                 \
-      LAUNCH(ORDER, COLOR, FP, COUNT, PK, false, false); \
-  } while (0)
-#define L5(ORDER, COLOR, FP, COUNT)     \
-  do {                                  \
-    if (h->packed)                      \
-      L6(ORDER, COLOR, FP, COUNT, true);  \
-    else                                \
-      L6(ORDER, COLOR, FP, COUNT, false); \
-  } while (0)
-#define L4(ORDER, COLOR, FP) \
-  do {                       \
-    if (count)               \
-      L5(ORDER, COLOR, FP, true);  \
-    else                     \
-      L5(ORDER, COLOR, FP, false); \
-  } while (0)
-#define L2(ORDER, COLOR) \
-  do {                   \
-    if (fastproj)        \
-      L4(ORDER, COLOR, true);  \
-    else                 \
-      L4(ORDER, COLOR, false); \
-  } while (0)
-    // the software-pipelined instance (k_integrate_p): ALLIN, PACKED, no colour, every block's rows present, resting hinge
-    // (knob pipe: bit 0 = without colour, k_integrate_p; bit 1 = with colour, k_integrate_pc)
-    const bool pipe = (tsdf_tuning().pipe & (color ? 2 : 1)) && fastproj && allin && !live && h->packed && a.hinge_fixed && a.neg_in_window &&
-                      a.ny % a.TY == 0;
-    if (pipe) {
-      h->last_launch[0] |= 0x100;  // bit 8: the pipelined row loop
-#define LAUNCH_P(ORDER, COUNT)                                                                                                           \
-  do {                                                                                                                                   \
-    if (color)                                                                                                                           \
-      hipLaunchKernelGGL((k_integrate_pc<ORDER, COUNT>), grid, block, 0, h->stream, a, D, RGB, d_depth, h->cam64, ctrx, ctry, h->ctr[2], \
-                         h->counter, band_arg);                                                                                          \
-    else                                                                                                                                 \
-      hipLaunchKernelGGL((k_integrate_p<ORDER, COUNT>), grid, block, 0, h->stream, a, D, K8, d_depth, h->cam64, ctrx, ctry, h->ctr[2],   \
-                         h->counter, band_arg);                                                                                          \
-  } while (0)
-      if (p.xform_order == TSDF_XFORM_PCL_SSE) {
-        if (count)
-          LAUNCH_P(TSDF_XFORM_PCL_SSE, true);
-        else
-          LAUNCH_P(TSDF_XFORM_PCL_SSE, false);
-      } else {
-        if (count)
-          LAUNCH_P(TSDF_XFORM_LEFT_TO_RIGHT, true);
-        else
-          LAUNCH_P(TSDF_XFORM_LEFT_TO_RIGHT, false);
-      }
-#undef LAUNCH_P
-    } else if (p.xform_order == TSDF_XFORM_PCL_SSE) {
-      if (color)
-        L2(TSDF_XFORM_PCL_SSE, true);
-      else
-        L2(TSDF_XFORM_PCL_SSE, false);
-    } else {
-      if (color)
-        L2(TSDF_XFORM_LEFT_TO_RIGHT, true);
-      else
-        L2(TSDF_XFORM_LEFT_TO_RIGHT, false);
-    }
-#undef L2
-#undef L4
-#undef L5
-#undef L6
-#undef LAUNCH
+    h->last_launch[3] = (int)std::min<uint64_t>((uint64_t)pl.gx * pl.gy * pl.gz, 0x7fffffffu);
+    dispatch_fast(h, pl, d_depth, count, fastproj, allin, pipe, band_arg);
     TSDF_HIP_TRY(hipGetLastError());
 #if TSDF_PHASE_TIMER
-    if (const char *pf = getenv("TSDF_HIP_PHASE_FILE")) {  // diagnostic build: the phase accumulators of THIS launch
-      TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
-      static unsigned long long host_ph[1024 * TSDF_NPHASE];
-      TSDF_HIP_TRY(hipMemcpyFromSymbol(host_ph, HIP_SYMBOL(g_phase), sizeof host_ph));
-      unsigned long long sum[TSDF_NPHASE] = {0};
-      for (int i = 0; i < 1024; ++i)
-        for (int k = 0; k < TSDF_NPHASE; ++k) sum[k] += host_ph[i * TSDF_NPHASE + k];
-      memset(host_ph, 0, sizeof host_ph);
-      TSDF_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_phase), host_ph, sizeof host_ph));
-      if (FILE *f = fopen(pf, "a")) {
-        fprintf(f, "{\"color\": %d, \"count\": %d, \"allin\": %d, \"live\": %d, \"packed\": %d, \"blocks\": %d, \"phase\": [", (int)color, (int)count,
-                (int)(fastproj && allin && !live), (int)(live != nullptr), (int)h->packed, h->last_launch[3]);
-        for (int k = 0; k < TSDF_NPHASE; ++k) fprintf(f, "%llu%s", sum[k], k + 1 < TSDF_NPHASE ? ", " : "]}\n");
-        fclose(f);
-      }
-    }
+    if (const int e = dump_phase_timers(h, count, allin, live)) return e;
 #endif
   }
   h->count_slots = count ? 4096 : 0;  // slots 1024.. hold the bytes of voxel words whose value changed, 2048.. the observed
                                       // voxels whose distance word was not read, 3072.. the plane bytes requested
-  h->count_ran = pose_ok && !nothing_observable;
+  h->count_ran = pose_ok && !pl.nothing_observable;
   return TSDF_HIP_OK;
 }
 
@@ -3217,8 +3239,7 @@ static int launch_integrate(tsdf_handle h, const float *d_depth, const uint32_t 
 // the handle keeps frame B's afterwards.  *fused says which way it went.  With `count`, tsdf_integrate_collect2 reads
 // the per-frame observation counts (identical to two separate launches) and the detail of the pair.
 static bool fusable_pose(tsdf_handle h, const IntegrateHost &hh, const float T[12], const float *planes) {
-  for (int i = 0; i < 12; ++i)
-    if (!(std::isfinite(T[i]) && fabsf(T[i]) <= 1e15f)) return false;
+  if (!pose_is_finite(T)) return false;
   if (planes && !reference_cull_keeps_whole_slab(h, planes)) return false;
   return slab_all_inside(h, T) && zlo_margin_ok(T, h) && fast_projection_ok(hh, h->p.integrate_color != 0);
 }
@@ -3238,29 +3259,24 @@ int tsdf_integrate_launch2(tsdf_handle h, const float *dA, const uint32_t *cA, c
     return TSDF_HIP_E_INVALID;
   }
   const IntegrateHost hh = make_args(h, TA);
-  IntegrateArgs a = hh.a;
-  const size_t npx = (size_t)p.image_width * p.image_height;
-  auto bgra_offset = [&](const float *d, const uint32_t *c, unsigned *off) {  // the colour image behind the depth image, within 2 GB
-    *off = 0;
-    if (!color) return true;
-    const char *zd = (const char *)d, *cb = (const char *)c;
-    if (!(cb >= zd + npx * 4 && (size_t)(cb - zd) + npx * 4 < (1ull << 31))) return false;
-    *off = (unsigned)(cb - zd);
-    return true;
-  };
+  LaunchPlan pl = whole_slab_plan(h, hh);
+  IntegrateArgs &a = pl.a;
   Frame2 fb;
   for (int i = 0; i < 12; ++i) fb.m[i] = TB[i];
-  const unsigned gx = (unsigned)((a.qpr + a.TX - 1) / a.TX), gy = (unsigned)((a.ny + a.rpb * a.TY - 1) / (a.rpb * a.TY)),
-                 gz = (unsigned)hh.planes;
   // Without colour two frames through the pipelined single-frame kernel beat one shared sweep since round 6 (k_integrate_p 7.1 ms per
   // frame against k_integrate2's 7.6 at 2048^3: profiles/r06_cpp_path_timing.json), so knob fuse2 = 1 (the default) pairs only where
   // the sweep wins: with colour, or where k_integrate_p does not apply; fuse2 = 2 always shares the sweep (the tests' k_integrate2
   // coverage), 0 never.
-  const bool pipe_wins = !color && (tsdf_tuning().pipe & 1) && tsdf_tuning().fuse2 == 1 && a.hinge_fixed && a.neg_in_window && a.ny % a.TY == 0;
+  // "k_integrate_p applies" is the single-frame launcher's own predicate with fastproj = allin = true, live = false.
+  // pipe_wins only decides anything where every other term of `ok` holds, and there these three hold by construction:
+  // both poses pass fusable_pose (fast projection; the slab all inside with its margins; a reference cull that keeps the
+  // whole slab, so no row intervals) on a PACKED handle whose grid and weights admit ALLIN under cull = 1 -- which is
+  // launch_kind's allin && !live.  (The predicate also asks for h->packed, which `ok` requires anyway.)
+  const bool pipe_wins = !color && tsdf_tuning().fuse2 == 1 && pipelined_rows_apply(h, a, color, true, true, false);
   const bool ok = tsdf_tuning().fuse2 && !pipe_wins && tsdf_tuning().cull == 1 && tsdf_tuning().allin && h->packed && !h->cn[0] && !h->weight_by_depth &&
                   !h->weight_by_variance && !tsdf_tuning().plain_kernel && (h->nx & 3) == 0 && a.wmax_is_int && (float)h->kmax == p.max_weight &&
-                  gy <= 65535u && gz <= 65535u && gz > 0 && bgra_offset(dA, cA, &a.bgra_off) && bgra_offset(dB, cB, &fb.bgra_off) &&
-                  fusable_pose(h, hh, TA, planesA) && fusable_pose(h, hh, TB, planesB);
+                  pl.gy <= 65535u && pl.gz <= 65535u && pl.gz > 0 && frame_bgra_offset(p, dA, cA, &a.bgra_off) &&
+                  frame_bgra_offset(p, dB, cB, &fb.bgra_off) && fusable_pose(h, hh, TA, planesA) && fusable_pose(h, hh, TB, planesB);
   if (fused) *fused = ok;
   if (!ok) {  // two launches, each with its own planes; with `count` the first one's counters are read before the second runs
     int rc = tsdf_hip_set_reference_cull(h, planesA);
@@ -3281,38 +3297,20 @@ int tsdf_integrate_launch2(tsdf_handle h, const float *dA, const uint32_t *cA, c
   h->count_slots = 0;
   h->count_ran = false;
   if (count) TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, 3072 * sizeof(unsigned long long), h->stream));
-  uint8_t *band_arg = h->band_exact && ((a.rpb * a.TY) & 3) == 0 ? h->band : nullptr;
-  if (!band_arg) h->band_exact = false;
+  uint8_t *band_arg = band_flags_for(h, a);
   (void)implied_distances(h, a, band_arg != nullptr);  // the record every flag-keeping launch keeps (rest_state); k_integrate2
   a.implied_d = 0;                                      // itself reads every distance word (see the kernel)
   h->last_implied_on = false;
   h->last_launch[0] = 2, h->last_launch[1] = 1, h->last_launch[2] = 0;
-  h->last_launch[3] = (int)std::min<uint64_t>((uint64_t)gx * gy * gz, 0x7fffffffu);
-  a.zfast = tsdf_tuning().zfast < 0 ? (npx * (color ? 8 : 4) > (3u << 20) && gx <= 65535u) : (tsdf_tuning().zfast != 0 && gx <= 65535u);
-  const dim3 grid(a.zfast ? gz : gx, gy, a.zfast ? gx : gz), block(256);
-#define LAUNCH2(ORDER, COLOR, COUNT)                                                                                    \
-  hipLaunchKernelGGL((k_integrate2<ORDER, COLOR, COUNT>), grid, block, 0, h->stream, a, fb, h->d, h->rgb, h->k8, dA, dB, \
-                     h->cam64, h->ctr[0], h->ctr[1], h->ctr[2], h->counter, band_arg)
-#define L2B(ORDER, COLOR)         \
-  do {                            \
-    if (count)                    \
-      LAUNCH2(ORDER, COLOR, true);  \
-    else                          \
-      LAUNCH2(ORDER, COLOR, false); \
-  } while (0)
-  if (p.xform_order == TSDF_XFORM_PCL_SSE) {
-    if (color)
-      L2B(TSDF_XFORM_PCL_SSE, true);
-    else
-      L2B(TSDF_XFORM_PCL_SSE, false);
-  } else {
-    if (color)
-      L2B(TSDF_XFORM_LEFT_TO_RIGHT, true);
-    else
-      L2B(TSDF_XFORM_LEFT_TO_RIGHT, false);
-  }
-#undef L2B
-#undef LAUNCH2
+  h->last_launch[3] = (int)std::min<uint64_t>((uint64_t)pl.gx * pl.gy * pl.gz, 0x7fffffffu);
+  a.zfast = zfast_for(p, pl.gx);
+  const dim3 grid(a.zfast ? pl.gz : pl.gx, pl.gy, a.zfast ? pl.gx : pl.gz), block(256);
+  with_consts(
+      [&](auto SSE, auto COLOR, auto COUNT) {
+        hipLaunchKernelGGL((k_integrate2<xform_order_of(SSE), COLOR, COUNT>), grid, block, 0, h->stream, a, fb, h->d, h->rgb, h->k8,
+                           dA, dB, h->cam64, h->ctr[0], h->ctr[1], h->ctr[2], h->counter, band_arg);
+      },
+      p.xform_order == TSDF_XFORM_PCL_SSE, color, count);
   TSDF_HIP_TRY(hipGetLastError());
   h->count_slots = count ? 3072 : 0;
   h->count_ran = true;
@@ -3886,16 +3884,22 @@ extern "C" int tsdf_hip_selftest_read_sweep(tsdf_handle h, int stride_bytes, uin
   return TSDF_HIP_OK;
 }
 
+// The centre tables of the three host-only hooks below: what tsdf_hip_create builds for these parameters.
+static bool selftest_centers(const tsdf_params &p, std::vector<float> ctr[3], int levels[3]) {
+  for (int a = 0; a < 3; ++a) {
+    if (p.res[a] <= 0 || !(p.size[a] > 0.f)) return false;
+    tsdf_build_centers(p.res[a], tsdf_node_size(p, a), ctr[a], &levels[a]);
+  }
+  return true;
+}
+
 // Test hook, host only (no device needed): the index box launch_integrate would restrict a frame's launch to.
 // rc 0 and box = {lo x,y,z, hi x,y,z} (inclusive); *state = 0 box valid, 1 nothing observable, 2 no claim.
 extern "C" int tsdf_hip_selftest_index_box(const tsdf_params *p, const float cam_from_vol[12], int32_t box[6], int32_t *state) {
   if (!p || !cam_from_vol || !box || !state) return TSDF_HIP_E_INVALID;
   tsdf_hip_volume v;
   v.p = *p;
-  for (int a = 0; a < 3; ++a) {
-    if (p->res[a] <= 0 || !(p->size[a] > 0.f)) return TSDF_HIP_E_INVALID;
-    tsdf_build_centers(p->res[a], tsdf_node_size(*p, a), v.h_ctr[a], &v.levels[a]);
-  }
+  if (!selftest_centers(*p, v.h_ctr, v.levels)) return TSDF_HIP_E_INVALID;
   int lo[3], hi[3];
   bool empty = false;
   if (!observable_index_box(&v, cam_from_vol, lo, hi, &empty)) {
@@ -3917,17 +3921,11 @@ extern "C" int tsdf_hip_selftest_block_flags(const tsdf_params *p, const float c
                                              uint8_t *flags) {
   if (!p || !cam_from_vol || !flags || bx_vox < 1 || by_rows < 1) return TSDF_HIP_E_INVALID;
   std::vector<float> ctr[3];
-  for (int a = 0; a < 3; ++a) {
-    int levels;
-    if (p->res[a] <= 0 || !(p->size[a] > 0.f)) return TSDF_HIP_E_INVALID;
-    tsdf_build_centers(p->res[a], tsdf_node_size(*p, a), ctr[a], &levels);
-  }
+  int levels[3];
+  if (!selftest_centers(*p, ctr, levels)) return TSDF_HIP_E_INVALID;
   CullArgs c;
-  for (int i = 0; i < 12; ++i) c.m[i] = cam_from_vol[i];
-  c.fx = p->fx, c.fy = p->fy, c.cx = p->cx, c.cy = p->cy;
-  c.zlo = p->min_sensor_dist > 0 ? p->min_sensor_dist : 0;
-  c.zmax = p->max_sensor_dist;
-  c.W = p->image_width, c.H = p->image_height, c.nx = p->res[0], c.ny = p->res[1], c.z_global0 = 0;
+  fill_camera(c, *p, cam_from_vol);
+  c.nx = p->res[0], c.ny = p->res[1], c.z_global0 = 0;
   c.bx_vox = bx_vox, c.by_rows = by_rows;
   c.gx = (p->res[0] + bx_vox - 1) / bx_vox, c.gy = (p->res[1] + by_rows - 1) / by_rows, c.gz = p->res[2];
   for (int bz = 0; bz < c.gz; ++bz)
@@ -3947,18 +3945,12 @@ extern "C" int tsdf_hip_selftest_row_intervals(const tsdf_params *p, const float
                                                uint32_t *words) {
   if (!p || !cam_from_vol || !words) return TSDF_HIP_E_INVALID;
   std::vector<float> ctr[3];
-  for (int a = 0; a < 3; ++a) {
-    int levels;
-    if (p->res[a] <= 0 || !(p->size[a] > 0.f)) return TSDF_HIP_E_INVALID;
-    tsdf_build_centers(p->res[a], tsdf_node_size(*p, a), ctr[a], &levels);
-  }
+  int levels[3];
+  if (!selftest_centers(*p, ctr, levels)) return TSDF_HIP_E_INVALID;
   if (p->res[0] > 0xfff0) return TSDF_HIP_E_UNSUPPORTED;
   RowArgs c;
-  for (int i = 0; i < 12; ++i) c.m[i] = cam_from_vol[i];
-  c.fx = p->fx, c.fy = p->fy, c.cx = p->cx, c.cy = p->cy;
-  c.zlo = p->min_sensor_dist > 0 ? p->min_sensor_dist : 0;
-  c.zmax = p->max_sensor_dist;
-  c.W = p->image_width, c.H = p->image_height, c.nx = p->res[0], c.ny = p->res[1], c.nz = p->res[2], c.z_global0 = 0;
+  fill_camera(c, *p, cam_from_vol);
+  c.nx = p->res[0], c.ny = p->res[1], c.nz = p->res[2], c.z_global0 = 0;
   c.rc = planes ? 1 : 0;
   for (int i = 0; i < 24; ++i) c.cull[i] = planes ? planes[i] : 0.f;
   for (int z = 0; z < c.nz; ++z)

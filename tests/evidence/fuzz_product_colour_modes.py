@@ -255,7 +255,8 @@ def run_case(c, check_cull=False):
             if not (np.array_equal(ok, ook) and same(val[ok], oval[ok]) and same(grad[ok], ograd[ok]) and same(hess[ok], ohess[ok])):
                 what.append("getFxn")
     v.close()
-    info = dict(observed=int((ov.w[zb:ze] != 0).sum()), nan=int(np.isnan(ov.d).sum()), frac=float(((ov.w % 1) != 0).mean()))
+    info = dict(observed=int((ov.w[zb:ze] != 0).sum()), nan=int(np.isnan(ov.d).sum()), frac=float(((ov.w % 1) != 0).mean()),
+                observed_x256=int((ov.w[zb:ze, :, 256:] != 0).sum()))   # (voxels of a row's second 256-thread block)
     if ov_plain is not None:
         info["cull_removed"] = not (np.array_equal(ov.w.view(np.uint32), ov_plain.w.view(np.uint32))
                                     and np.array_equal(ov.d.view(np.uint32), ov_plain.d.view(np.uint32)))

@@ -71,6 +71,18 @@ def test_rows_padded_to_the_pitch(gpu, mode, nx):
     assert info["observed"] > 1000
 
 
+@pytest.mark.parametrize("mode", MODES)
+def test_rows_wider_than_one_block(gpu, mode):
+    """260 voxels along x: the plain kernels' second x block (blockIdx.x = 1) with four live lanes.  The camera was chosen
+    on the CPU against the oracle alone so that it observes voxels there (336-376 of the 1920, by mode); the default
+    camera of `case` observes none, and the test would pass without testing anything."""
+    c = case(mode, res3=(260, 24, 20), color=True, seed=2, fx=0.5 * 80, fy=0.5 * 80, zmax=8.0, eye=(7, 11), n_poses=3,
+             n_frames=7 if "by_variance" in mode else 3)
+    what, info = hunt.run_case(c)
+    assert not what, what
+    assert info["observed_x256"] >= 300, "the case must observe voxels at x >= 256"
+
+
 @pytest.mark.parametrize("handle", ["one", "multi"])
 def test_weight_by_depth_past_ten_metres(gpu, handle):
     """A 12 m volume seen from 6-11 m: every voxel observed past 10 m gets w_new = 0 -- a fresh voxel d = 0/0 = NaN,
