@@ -571,6 +571,24 @@ bool TSDFVolumeOctree::alignPoints(const float *xyz, size_t n, const Eigen::Affi
   return rc == 0;
 }
 
+// ---- shiftVolume (not in the reference): tsdf_hip_shift ----------------------------------------------------------------------
+bool TSDFVolumeOctree::shiftVolume(int sx, int sy, int sz, Eigen::Vector3d *moved) {
+  if (!ready("shiftVolume")) return false;
+  const int32_t s[3] = {sx, sy, sz};
+  const int rc = tsdf_hip_shift(h_, s);
+  if (rc) {
+    report("shiftVolume", rc);
+    return false;
+  }
+  Eigen::Vector3d t;
+  for (int a = 0; a < 3; ++a) t[a] = s[a] * (double)p_.size[a] / p_.res[a];
+  Eigen::Affine3d step = Eigen::Affine3d::Identity();  // Translation(t)
+  for (int a = 0; a < 3; ++a) step.matrix()(a, 3) = t[a];
+  global_transform_ = global_transform_ * step;
+  if (moved) *moved = t;
+  return true;
+}
+
 // ---- save / load: the reference's .vol format (src/lib/tsdf_volume_octree.cpp:222-275) -----------------------
 // The format and the block streaming live behind the C ABI (tsdf_hip_save / tsdf_hip_load); this class adds
 // what only it knows: max cell size, the empty flag, the weighting flags and the global transform.

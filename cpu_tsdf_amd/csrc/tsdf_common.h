@@ -119,6 +119,9 @@ struct tsdf_hip_volume {
   bool mc_counts_pass = false;  // ... and the corner weights not gathered: their test could not fail (tsdf_march.hip counts_pass)
   hipEvent_t align_ev[2] = {nullptr, nullptr};  // tsdf_hip_align_stats: around the system kernels of the last call
   uint64_t align_stats[4] = {0, 0, 0, 0};       // points, used, iterations, device microseconds
+  hipEvent_t shift_ev[2] = {nullptr, nullptr};  // tsdf_hip_shift_stats: around the work of the last tsdf_hip_shift (tsdf_shift.hip)
+  bool shift_timed = false;                     // ... both have been recorded
+  uint64_t shift_stats[3] = {0, 0, 0};          // voxels that kept a value, voxels reset, 1 if the band flags were carried over
   void *scratch = nullptr;
   size_t scratch_bytes = 0;
   tsdf_occ_state *occ = nullptr;
@@ -162,6 +165,7 @@ void tsdf_multi_mesh(tsdf_handle h, const float **verts, const uint8_t **rgb, co
 // frame pairing on a set (round 6): the slabs pair the frames of their own rings; tsdf_multi_flush lets them launch what they hold
 int tsdf_multi_flush(tsdf_handle h);
 int tsdf_multi_set_frame_pairing(tsdf_handle h, int on);
+int tsdf_multi_shift(tsdf_handle h, const int32_t shift[3]);
 int tsdf_multi_integrate_device2(tsdf_handle h, const float *da, const uint32_t *ca, const float TA[12], const float *planes_a, const float *db,
                                  const uint32_t *cb, const float TB[12], const float *planes_b, uint64_t *n_observed, int32_t *fused);
 #define TSDF_NOT_ON_MULTI(h, what)                                                                          \
@@ -312,6 +316,17 @@ void tsdf_flatten_release(tsdf_hip_volume *v);
 // The indexed mesh tsdf_hip_march_flatten left on a handle describes the soup it was made from: a later tsdf_hip_march or
 // tsdf_hip_march_cleanup makes tsdf_hip_march_fetch_indexed refuse until flatten has run again.
 void tsdf_flatten_invalidate(tsdf_hip_volume *v);
+// A list made by tsdf_hip_occupied names voxels by index: after tsdf_hip_shift the fetches refuse until the next scan.
+void tsdf_occupied_invalidate(tsdf_hip_volume *v);
+// The pieces of tsdf_hip_shift (tsdf_shift.hip) a multi-GPU set puts together per slab (tsdf_multi.hip), all asynchronous on
+// the handle's stream: every voxel array of the allocated planes [dz0, dz1) <- the voxels at (+sx, +sy, +sz), the reset state
+// where that lies outside the allocated planes; the band flags of all allocated planes likewise (only while band_exact);
+// the event pair of tsdf_hip_shift_stats; the shift clamped to +-res; the voxels of an nx x ny x nz grid that keep a value.
+int tsdf_shift_planes(tsdf_hip_volume *v, int sx, int sy, int sz, int dz0, int dz1);
+int tsdf_shift_band(tsdf_hip_volume *v, int sx, int sy, int sz);
+int tsdf_shift_mark(tsdf_hip_volume *v, int which);
+void tsdf_shift_clamp(const tsdf_hip_volume *v, const int32_t shift[3], int s[3]);
+void tsdf_shift_count(int nx, int ny, int nz, const int s[3], uint64_t *kept, uint64_t *reset);
 
 // Launch-shape knobs, overridable from the environment for A/B runs (TSDF_HIP_ROWS_PER_BLOCK,
 // TSDF_HIP_BLOCKS_PER_CU, TSDF_HIP_FAST_PROJECTION, TSDF_HIP_MC_FLUSH_AT, TSDF_HIP_CULL, TSDF_HIP_VOL_CHUNK, TSDF_HIP_ALLIN); read once, changeable

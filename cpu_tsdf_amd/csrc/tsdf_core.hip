@@ -437,6 +437,8 @@ static void free_volume(tsdf_hip_volume *v) {
     if (v->mc_ev[i]) (void)hipEventDestroy(v->mc_ev[i]);
   for (int i = 0; i < 2; ++i)
     if (v->align_ev[i]) (void)hipEventDestroy(v->align_ev[i]);
+  for (int i = 0; i < 2; ++i)
+    if (v->shift_ev[i]) (void)hipEventDestroy(v->shift_ev[i]);
   if (v->scratch) (void)hipFree(v->scratch);
   delete v;
 }

@@ -804,6 +804,139 @@ static int exchange_halo(tsdf_handle h, int planes, bool both) {
   return TSDF_HIP_OK;
 }
 
+// ---- tsdf_hip_shift on a set ---------------------------------------------------------------------------------------------
+// Global planes [zs, zs + nz) of slab `src` (owned there, not shifted yet) become planes [zd, zd + nz) of slab `dst`: every
+// array copy_planes moves plus vm / vn, and the band flags when they are being carried.  Ordered like copy_planes.
+static int pull_planes(tsdf_hip_multi *m, int src, int dst, int zs, int zd, int nz, bool with_band) {
+  tsdf_handle a = m->slab[src], b = m->slab[dst];
+  const int64_t plane = a->pitch * a->ny;
+  const int64_t oa = (int64_t)(zs - a->z_first) * plane, ob = (int64_t)(zd - b->z_first) * plane;
+  {
+    TSDF_ON_DEVICE(a->device);
+    TSDF_HIP_TRY(hipEventRecord(m->ev[src], a->stream));
+  }
+  TSDF_ON_DEVICE(b->device);
+  TSDF_HIP_TRY(hipStreamWaitEvent(b->stream, m->ev[src], 0));
+  auto cp = [&](void *dst_p, const void *src_p, size_t bytes) -> int {
+    return tsdf_multi_copy(m, dst_p, b->device, src_p, a->device, bytes, b->stream);
+  };
+  const size_t n = (size_t)(plane * nz);
+  int rc = cp(b->d + ob, a->d + oa, n * 4);
+  if (!rc && a->w) rc = cp(b->w + ob, a->w + oa, n * 4);
+  if (!rc && a->rgb) rc = cp(b->rgb + ob, a->rgb + oa, n * 4);
+  if (!rc && a->k8) rc = cp(b->k8 + ob, a->k8 + oa, n);
+  for (int c = 0; c < 4 && !rc; ++c)
+    if (a->cn[c]) rc = cp(b->cn[c] + ob, a->cn[c] + oa, n * 4);
+  if (!rc && a->vm && b->vm) rc = cp(b->vm + ob, a->vm + oa, n * 4);
+  if (!rc && a->vn && b->vn) rc = cp(b->vn + ob, a->vn + oa, n * 4);
+  if (!rc && with_band) {
+    const size_t cells = (size_t)a->band_fx * a->band_fy;
+    rc = cp(b->band + (size_t)(zd - b->z_first) * cells, a->band + (size_t)(zs - a->z_first) * cells, cells * nz);
+  }
+  return rc;
+}
+
+// The z part on slab k: its owned planes [zb, ze) <- global planes z + sz.  Sources the slab owns itself move in place
+// (tsdf_shift_planes, whose batches keep a source from being overwritten before it is read), sources of slabs that have not
+// shifted yet are pulled over the link, sources outside the grid give the reset state.  The flags move as whole planes.
+static int shift_slab_z(tsdf_hip_multi *m, int k, int sz, int nz_grid, bool with_band) {
+  tsdf_handle s = m->slab[k];
+  const int zb = s->z_begin, ze = s->z_end;
+  // destination planes whose source lies in this slab / beyond it in the direction of the shift
+  const int own0 = sz > 0 ? zb : std::min(ze, zb - sz), own1 = sz > 0 ? std::max(zb, ze - sz) : ze;
+  const int far0 = sz > 0 ? own1 : zb, far1 = sz > 0 ? ze : own0;
+  const size_t cells = (size_t)s->band_fx * s->band_fy;
+  {
+    TSDF_ON_DEVICE(s->device);
+    if (own0 < own1) {
+      if (const int rc = tsdf_shift_planes(s, 0, 0, sz, own0 - s->z_first, own1 - s->z_first)) return rc;
+      if (with_band) {  // through a copy: the two plane ranges overlap
+        const size_t n = cells * (size_t)(own1 - own0);
+        if (const int rc = tsdf_ensure_scratch(s, n)) return rc;
+        TSDF_HIP_TRY(hipMemcpyAsync(s->scratch, s->band + (size_t)(own0 + sz - s->z_first) * cells, n, hipMemcpyDeviceToDevice, s->stream));
+        TSDF_HIP_TRY(hipMemcpyAsync(s->band + (size_t)(own0 - s->z_first) * cells, s->scratch, n, hipMemcpyDeviceToDevice, s->stream));
+      }
+    }
+  }
+  for (int z = far0; z < far1;) {
+    const int zs = z + sz;
+    if (zs < 0 || zs >= nz_grid) {  // the rest of the range is outside the grid (sz > 0) / this part is (sz < 0)
+      const int run = sz > 0 ? far1 - z : std::min(far1, -sz) - z;
+      TSDF_ON_DEVICE(s->device);
+      if (const int rc = tsdf_shift_planes(s, 0, 0, 2 * nz_grid, z - s->z_first, z + run - s->z_first)) return rc;  // no source: reset state
+      if (with_band) TSDF_HIP_TRY(hipMemsetAsync(s->band + (size_t)(z - s->z_first) * cells, 0, cells * run, s->stream));
+      z += run;
+      continue;
+    }
+    const int o = owner_of(m, zs);
+    if (o < 0) return TSDF_HIP_E_INVALID;
+    const int run = std::min(far1 - z, m->slab[o]->z_end - zs);
+    if (const int rc = pull_planes(m, o, k, zs, z, run, with_band)) return rc;
+    z += run;
+  }
+  return TSDF_HIP_OK;
+}
+
+int tsdf_multi_shift(tsdf_handle h, const int32_t shift[3]) {
+  if (const int rc_flush = tsdf_multi_flush(h)) return rc_flush;  // (frame pairing: slabs launch what they hold first)
+  tsdf_hip_multi *m = h->multi;
+  const int n = (int)m->slab.size();
+  int s[3];
+  tsdf_shift_clamp(h, shift, s);
+  bool carried = true;
+  for (tsdf_handle sl : m->slab) carried = carried && sl->band_exact;
+  for (tsdf_handle sl : m->slab) {
+    TSDF_ON_DEVICE(sl->device);
+    if (const int rc = tsdf_shift_mark(sl, 0)) return rc;
+  }
+  m->halo1_fresh = m->halo_all_fresh = false;
+  auto fail = [&](int rc) {
+    for (tsdf_handle sl : m->slab) sl->band_exact = false;
+    return rc;
+  };
+  if (s[2]) {
+    // planes change slabs: what the slabs' records say about their planes has to hold for the planes they receive
+    int rest = 0;
+    uint32_t bits = 0;
+    for (tsdf_handle sl : m->slab) {
+      if (sl->rest_state == 2 || (sl->rest_state == 1 && rest == 1 && sl->rest_bits != bits)) rest = 2;
+      if (sl->rest_state == 1 && rest == 0) rest = 1, bits = sl->rest_bits;
+    }
+    for (tsdf_handle sl : m->slab) {
+      if (rest) sl->rest_state = rest, sl->rest_bits = bits;
+      if (!carried) sl->band_exact = false;
+    }
+    // ascending for sz > 0: a slab pulls from the slabs above it, which shift after it and wait for its pulls
+    for (int i = 0; i < n; ++i) {
+      const int k = s[2] > 0 ? i : n - 1 - i;
+      tsdf_handle sl = m->slab[k];
+      {
+        TSDF_ON_DEVICE(sl->device);
+        for (int j = 0; j < i; ++j) TSDF_HIP_TRY(hipStreamWaitEvent(sl->stream, m->ev2[s[2] > 0 ? j : n - 1 - j], 0));
+      }
+      if (const int rc = shift_slab_z(m, k, s[2], h->nz, carried)) return fail(rc);
+      TSDF_ON_DEVICE(sl->device);
+      TSDF_HIP_TRY(hipEventRecord(m->ev2[k], sl->stream));
+    }
+  }
+  for (tsdf_handle sl : m->slab) {  // the x / y part, every slab by itself (halo planes included: they are stale anyway)
+    TSDF_ON_DEVICE(sl->device);
+    int rc = TSDF_HIP_OK;
+    if (s[0] || s[1]) {
+      rc = tsdf_shift_planes(sl, s[0], s[1], 0, 0, sl->nz_alloc);
+      if (!rc) rc = tsdf_shift_band(sl, s[0], s[1], 0);
+    }
+    if (!rc) rc = tsdf_shift_mark(sl, 1);
+    if (rc) return fail(rc);
+    tsdf_occupied_invalidate(sl);
+  }
+  tsdf_occupied_invalidate(h);
+  if (const int rc = all_wait_all(m)) return fail(rc);
+  tsdf_shift_count(h->nx, h->ny, h->nz, s, &h->shift_stats[0], &h->shift_stats[1]);
+  h->shift_stats[2] = carried ? 1u : 0u;
+  return TSDF_HIP_OK;
+}
+
 // ---- raw voxel blocks --------------------------------------------------------------------------------------------------
 int tsdf_multi_block(tsdf_handle h, bool down, int x0, int y0, int z0, int nx, int ny, int nz, float *d, float *w, uint8_t *rgb) {
   if (const int rc_flush = tsdf_multi_flush(h)) return rc_flush;  // (frame pairing: slabs launch what they hold first)

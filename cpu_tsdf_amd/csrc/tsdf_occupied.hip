@@ -57,6 +57,10 @@ void tsdf_occupied_release(tsdf_hip_volume *v) {
   v->occ = nullptr;
 }
 
+void tsdf_occupied_invalidate(tsdf_hip_volume *v) {
+  if (v->occ) v->occ->valid = false;
+}
+
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
 struct OccArgs {
   int x0, y0, z0, x1, y1, z1;  // the box [x0, x1) x [y0, y1) x [z0, z1), global voxel indices, inside the owned planes

@@ -581,6 +581,31 @@ class TSDFVolumeOctree:
         capi.check(capi.load().tsdf_hip_occupied_stats(self._need(), out), "occupied_stats")
         return tuple(int(v) for v in out)
 
+    def shiftVolume(self, sx, sy, sz):
+        """Not in the reference: move the volume's window by whole voxels along +x, +y, +z of the volume frame, in place on
+        the GPU (tsdf_hip_shift).  Afterwards voxel (x, y, z) holds what (x + sx, y + sy, z + sz) held, or the reset state
+        where that lies outside the grid; the band flags move along, so reconstruct / getOccupiedVoxelIndices /
+        integrateCloud keep their skips.  Returns ``moved`` (3 float64): the translation of the volume frame in its own
+        coordinates, s * size / res.  The world stays where it is: the global transform becomes G * Translation(moved),
+        so reconstruct() returns the surviving surface where it was.  What the caller owes in return: a pose handed to
+        integrateCloud / renderView / alignCloud afterwards is Translation(-moved) * trans_old.  Works on setDevices
+        volumes; a setZSlab volume shifts along x and y only."""
+        h = self._need()
+        s = (C.c_int32 * 3)(int(sx), int(sy), int(sz))
+        capi.check(capi.load().tsdf_hip_shift(h, s), "shift")
+        moved = np.array([int(s[a]) * float(self._p.size[a]) / int(self._p.res[a]) for a in range(3)], dtype=np.float64)
+        t = np.eye(4)
+        t[:3, 3] = moved
+        self._global_transform = self._global_transform @ t
+        return moved
+
+    def shiftStats(self):
+        """Report-only, of the last shiftVolume: (voxels that kept a value, voxels reset, 1 if the band flags were carried
+        over, device microseconds).  Waits for the shift to finish."""
+        out = (C.c_uint64 * 4)()
+        capi.check(capi.load().tsdf_hip_shift_stats(self._need(), out), "shift_stats")
+        return tuple(int(v) for v in out)
+
     def occupiedTiming(self):
         """Report-only: device milliseconds (scan, sort, gather) of the last getOccupiedVoxelIndices."""
         ms = (C.c_float * 3)()

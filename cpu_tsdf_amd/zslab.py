@@ -305,7 +305,11 @@ class ZSlabVolume:
     """One logical TSDF volume, Z-slab partitioned over the ranks of `group`.
 
     configure(vol) applies the usual setters (setResolution, setGridSize, ...) to a volume object; it is
-    called once per rank.  All methods are collective: every rank calls them in the same order."""
+    called once per rank.  All methods are collective: every rank calls them in the same order.
+
+    There is no shiftVolume here: a shift along z would move planes between the ranks, and a rank's handle refuses it
+    (tsdf_hip_shift, E_UNSUPPORTED for sz != 0 on a handle that owns part of the grid).  The one-process multi-GPU
+    volume (TSDFVolumeOctree.setDevices) shifts along every axis."""
 
     def __init__(self, configure, resolution_z, group=None, slab_factory=None, halo=None):
         """halo: planes kept on each side of the slab; None = enough for renderView across slabs

@@ -158,6 +158,15 @@ class TSDFVolumeOctree : public TSDFInterface {
   // out-of-line half of the alignCloud template: xyz = n x 3 floats
   bool alignPoints(const float *xyz, size_t n, const Eigen::Affine3d &guess, Eigen::Affine3d &refined, int max_iterations,
                    float min_weight, float r_max, double min_step) const;
+  // Not in the reference: move the volume's window by whole voxels along +x, +y, +z of the volume frame, in place on the
+  // GPU (tsdf_hip_shift), so that the dense grid can follow the camera.  Afterwards voxel (x, y, z) holds what voxel
+  // (x + sx, y + sy, z + sz) held, or the reset state where that lies outside the grid.  *moved (optional) receives the
+  // translation of the volume frame in its own coordinates, s * size / res per axis.  The world stays where it is:
+  // global_transform_ becomes global_transform_ * Translation(moved), so MarchingCubesTSDFOctree::reconstruct returns the
+  // surviving surface where it was (up to float rounding of the voxel-centre tables).  What the caller owes in return: a
+  // pose handed to integrateCloud / renderView / alignCloud afterwards is Translation(-moved) * trans_old.
+  // false (and a PCL_ERROR) before reset(), or when the call fails (a setZSlab volume with sz != 0).
+  bool shiftVolume(int sx, int sy, int sz, Eigen::Vector3d *moved = nullptr);
 
   const float UNOBSERVED_VOXEL;
 

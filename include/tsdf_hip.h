@@ -563,6 +563,40 @@ int tsdf_hip_occupied_stats(tsdf_handle h, uint64_t out[4]);
  * ms[2] the gather kernel of the fetches since that call. */
 int tsdf_hip_occupied_timing(tsdf_handle h, float ms[3]);
 
+/* shiftVolume -- NOT IN THE REFERENCE (its octree has a fixed root, like this grid).  Moves the volume's window by whole
+ * voxels, in place on the device, so that a dense grid can follow the camera.
+ *   shift  (sx, sy, sz): the window moves by that many voxels along +x, +y, +z of the volume frame.  Afterwards voxel
+ *          (x, y, z) holds what voxel (x + sx, y + sy, z + sz) held before, if that index lies in the grid, and the reset
+ *          state, exactly as tsdf_hip_reset writes it, otherwise.  Everything a voxel owns moves with it: d, the weight (w, or
+ *          the count in byte 3 of the colour word / the count plane of the PACKED layout), rgb, the float colour state of
+ *          RGB_NORMALIZED / LAB, and M / nsample where allocated.  Pitch padding is not part of the contract.
+ * A zero shift returns OK without touching the device.  |s| >= res on any axis is legal and leaves every voxel in the reset
+ * state.  E_INVALID for a NULL handle or shift.  Like every entry point that reads or writes the planes, the call first
+ * launches a frame held back by frame pairing.  Asynchronous on the handle's stream, like tsdf_hip_integrate_device without
+ * n_observed.  No second copy of the volume is made: the planes are moved in batches whose sources a launch never writes
+ * (DESIGN.md 3.15); the only scratch is one copy of the band flags (1/256 byte per voxel).
+ * The "band seen" flags move with the data (a cell's new flag is the OR of the flags of the cells its voxels came from), so
+ * what tsdf_hip_march, tsdf_hip_occupied and the PACKED integrate launches skip because of them they still skip afterwards.
+ * A list made by tsdf_hip_occupied before the shift names old indices: tsdf_hip_occupied_fetch* return E_INVALID until the
+ * next tsdf_hip_occupied.  The mesh of the last tsdf_hip_march is plain data and stays: it describes the volume BEFORE the
+ * shift.
+ * The caller's bookkeeping: the volume frame has moved by t = (sx * size[0] / res[0], sy * size[1] / res[1],
+ * sz * size[2] / res[2]) in its own coordinates.  A camera pose `trans` (camera -> volume) that was right before the shift
+ * is Translation(-t) * trans afterwards, and a global transform G (volume -> world) becomes G * Translation(t);
+ * cpu_tsdf::TSDFVolumeOctree::shiftVolume does the latter.
+ * A handle that owns part of the grid (z_begin / z_end, with its halo) shifts every allocated plane, halo included, when
+ * sz == 0, and returns E_UNSUPPORTED when sz != 0: planes would have to cross processes (cpu_tsdf_amd/zslab.py has no shift).
+ * On a multi-GPU set the result equals one handle holding the whole grid: the z part moves planes between the slabs (each
+ * slab pulls from slabs that have not shifted yet, ascending for sz > 0), the x / y part runs on every slab by itself, and
+ * the halos are stale afterwards (refreshed by the next call that needs them).
+ * tsdf_hip_shift_stats: report-only, of the last tsdf_hip_shift on the handle: out[0] = voxels that kept a value, out[1] =
+ * voxels reset (of the allocated planes: out[0] + out[1] = nx * ny * planes), out[2] = 1 if the band flags were carried over
+ * (they described the planes before and do after), out[3] = device microseconds (HIP events on the handle's stream; the call
+ * waits for the second event, i.e. for the shift to finish).  Multi-GPU: counts of the whole grid, flags only if every slab
+ * carried them, the slowest slab's time. */
+int tsdf_hip_shift(tsdf_handle h, const int32_t shift[3]);
+int tsdf_hip_shift_stats(tsdf_handle h, uint64_t out[4]);
+
 /* Block transfer of raw voxels (parity tests, save/load, halo exchange).  Coordinates are global
  * grid indices; the block must lie inside the handle's slab + halo.  Any pointer may be NULL.
  * rgb is 3 bytes per voxel (r,g,b).  *_device variants take device pointers (rgb then 4 bytes). */
