@@ -117,6 +117,8 @@ struct tsdf_hip_volume {
   uint64_t mc_d_bytes = 0;   // distance bytes the last classify pass requested (tsdf_hip_march_stats)
   bool mc_skipped = false;   // ... with the band flags deciding what to read
   bool mc_counts_pass = false;  // ... and the corner weights not gathered: their test could not fail (tsdf_march.hip counts_pass)
+  bool mc_halo_vouched = false;  // a slab of a set, during tsdf_multi_march: halo plane z_end is a fresh copy of a plane of the
+                                 // neighbour, and every slab's planes hold only what integrate launches wrote (band_exact)
   hipEvent_t align_ev[2] = {nullptr, nullptr};  // tsdf_hip_align_stats: around the system kernels of the last call
   uint64_t align_stats[4] = {0, 0, 0, 0};       // points, used, iterations, device microseconds
   hipEvent_t shift_ev[2] = {nullptr, nullptr};  // tsdf_hip_shift_stats: around the work of the last tsdf_hip_shift (tsdf_shift.hip)

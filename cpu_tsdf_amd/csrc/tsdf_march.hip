@@ -734,7 +734,9 @@ static int march_single(tsdf_handle h, float w_min, int color_mode, uint64_t *n_
   // this handle's own integrate launches wrote since the reset (band_exact) and no halo plane is among the corners: a
   // listed cell has all eight |d| < 1 (:98), a distance leaves the reset value -1 only with an observation, and every
   // observation counts (octree.cpp:157-159: w + 1) -- so all eight counts are >= 1.  The 8 gathers per listed cell go.
-  const bool counts_pass = h->packed && h->band_exact && tsdf_tuning().mc_skip && a.z_hi < h->z_end &&
+  // A halo plane nobody vouches for may hold anything (an upload into the halo does not end band_exact); a set vouches for
+  // its slabs' plane z_end while the same holds of EVERY slab's planes and the halo was just refreshed (tsdf_multi_march).
+  const bool counts_pass = h->packed && h->band_exact && tsdf_tuning().mc_skip && (a.z_hi < h->z_end || h->mc_halo_vouched) &&
                            w_min <= 1.f && w_min <= a.pv.wmax;
   if (counts_pass) a.check_w = 0;
   a.flush_at = std::min(MC_WAVE_BUF, std::max(0, tsdf_tuning().mc_flush_at));

@@ -55,6 +55,7 @@ struct tsdf_hip_multi {
   bool timing = false;
   std::vector<std::vector<hipEvent_t>> t_ev;  // per slab: start, stop, start, stop, ...
   std::vector<size_t> t_used;
+  std::vector<int> t_launches;  // per slab: sweeps inside the recorded brackets (a bracket around an unfused pair holds two)
   // Copies between two slabs' devices: hipMemcpyPeerAsync where the driver grants peer access (xGMI), else -- access
   // refused, or TSDF_HIP_NO_PEER=1, which routes EVERY cross-slab copy this way so that a one-GPU box can test it --
   // through a pinned relay buffer on the host: device -> host on a relay stream of the source device, host -> device on
@@ -253,6 +254,7 @@ extern "C" int tsdf_hip_create_multi(const tsdf_params *p, const int32_t *device
   m->ray_counters.resize(n_devices, nullptr);
   m->t_ev.resize(n_devices);
   m->t_used.resize(n_devices, 0);
+  m->t_launches.resize(n_devices, 0);
   for (int k = 0; k < n_devices; ++k) {
     TsdfDeviceScope scope(devices[k]);
     if (hipEventCreateWithFlags(&m->ev[k], hipEventDisableTiming) != hipSuccess ||
@@ -313,13 +315,47 @@ static int copy_thunk(void *ctx, void *dst, int dst_dev, const void *src, int sr
   return tsdf_multi_copy(static_cast<tsdf_hip_multi *>(ctx), dst, dst_dev, src, src_dev, bytes, st, true);
 }
 
+// tsdf_hip_multi_timing: an event pair on slab k's stream around a stretch of its launches.  timing_begin records the
+// start and hands out the stop event (nullptr while timing is off); timing_end records it and books the `launches` sweeps
+// the stretch ran -- none (the frame is held back for a partner) leaves the pair for the next stretch.
+static int timing_begin(tsdf_hip_multi *m, size_t k, hipEvent_t *stop) {
+  *stop = nullptr;
+  if (!m->timing) return TSDF_HIP_OK;
+  tsdf_handle s = m->slab[k];
+  TSDF_ON_DEVICE(s->device);
+  std::vector<hipEvent_t> &ev = m->t_ev[k];
+  while (ev.size() < m->t_used[k] + 2) {
+    hipEvent_t e = nullptr;
+    TSDF_HIP_TRY(hipEventCreate(&e));
+    ev.push_back(e);
+  }
+  TSDF_HIP_TRY(hipEventRecord(ev[m->t_used[k]], s->stream));
+  *stop = ev[m->t_used[k] + 1];
+  return TSDF_HIP_OK;
+}
+
+static int timing_end(tsdf_hip_multi *m, size_t k, hipEvent_t stop, int launches) {
+  if (!stop || launches <= 0) return TSDF_HIP_OK;
+  tsdf_handle s = m->slab[k];
+  TSDF_ON_DEVICE(s->device);
+  TSDF_HIP_TRY(hipEventRecord(stop, s->stream));
+  m->t_used[k] += 2;
+  m->t_launches[k] += launches;
+  return TSDF_HIP_OK;
+}
+
 int tsdf_multi_flush(tsdf_handle h) {
-  for (tsdf_handle s : h->multi->slab)
-    if (s->pair_pending) {
-      TSDF_ON_DEVICE(s->device);
-      const int rc = tsdf_pipeline_flush(s);
-      if (rc) return rc;
-    }
+  tsdf_hip_multi *m = h->multi;
+  for (size_t k = 0; k < m->slab.size(); ++k) {
+    tsdf_handle s = m->slab[k];
+    if (!s->pair_pending) continue;
+    TSDF_ON_DEVICE(s->device);
+    hipEvent_t t1 = nullptr;
+    int rc = timing_begin(m, k, &t1);
+    if (!rc) rc = tsdf_pipeline_flush(s);
+    if (!rc) rc = timing_end(m, k, t1, 1);
+    if (rc) return rc;
+  }
   return TSDF_HIP_OK;
 }
 
@@ -363,21 +399,11 @@ static int integrate_all(tsdf_handle h, const float T[12], uint64_t *n_observed)
   for (size_t k = 0; k < m->slab.size(); ++k) {
     tsdf_handle s = m->slab[k];
     TSDF_ON_DEVICE(s->device);
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (m->timing) {
-      std::vector<hipEvent_t> &ev = m->t_ev[k];
-      while (ev.size() < m->t_used[k] + 2) {
-        hipEvent_t e = nullptr;
-        TSDF_HIP_TRY(hipEventCreate(&e));
-        ev.push_back(e);
-      }
-      t0 = ev[m->t_used[k]], t1 = ev[m->t_used[k] + 1];
-      m->t_used[k] += 2;
-      TSDF_HIP_TRY(hipEventRecord(t0, s->stream));
-    }
-    const int rc = tsdf_integrate_launch(s, s->frame_depth, s->p.integrate_color ? s->frame_bgra : nullptr, T, n_observed != nullptr);
+    hipEvent_t t1 = nullptr;
+    int rc = timing_begin(m, k, &t1);
+    if (!rc) rc = tsdf_integrate_launch(s, s->frame_depth, s->p.integrate_color ? s->frame_bgra : nullptr, T, n_observed != nullptr);
+    if (!rc) rc = timing_end(m, k, t1, 1);
     if (rc) return rc;
-    if (t1) TSDF_HIP_TRY(hipEventRecord(t1, s->stream));
   }
   if (n_observed) {
     unsigned long long total = 0, changed = 0, implied = 0, read_bytes = 0;
@@ -405,11 +431,13 @@ static int integrate_all(tsdf_handle h, const float T[12], uint64_t *n_observed)
 
 // Per-slab k_integrate time (bench.py --host inprocess): while enabled, every slab's launches are bracketed by HIP events
 // on the slab's own stream.  tsdf_hip_multi_kernel_ms synchronises and returns the summed milliseconds and the
-// number of launches of slab k since timing was enabled (or last read), then forgets them.
+// number of launches of slab k since timing was enabled (or last read), then forgets them.  The paired paths count the
+// sweeps a slab really ran: one for a pair it fused, two for one it did not, one for a frame launched on its own, none
+// while a frame waits for its partner.
 extern "C" int tsdf_hip_multi_timing(tsdf_handle h, int enable) {
   if (!h || !h->multi) return TSDF_HIP_E_INVALID;
   h->multi->timing = enable != 0;
-  for (size_t k = 0; k < h->multi->t_used.size(); ++k) h->multi->t_used[k] = 0;
+  for (size_t k = 0; k < h->multi->t_used.size(); ++k) h->multi->t_used[k] = 0, h->multi->t_launches[k] = 0;
   return TSDF_HIP_OK;
 }
 
@@ -425,8 +453,9 @@ extern "C" int tsdf_hip_multi_kernel_ms(tsdf_handle h, int k, float *ms_sum, int
     sum += ms;
   }
   *ms_sum = sum;
-  if (launches) *launches = (int32_t)(m->t_used[k] / 2);
+  if (launches) *launches = (int32_t)m->t_launches[k];
   m->t_used[k] = 0;
+  m->t_launches[k] = 0;
   return TSDF_HIP_OK;
 }
 
@@ -472,7 +501,13 @@ int tsdf_multi_frame_commit(tsdf_handle h, const float T[12]) {
     }
     m->halo1_fresh = m->halo_all_fresh = false;
     for (size_t k = 0; k < m->slab.size(); ++k) {
-      const int rc = tsdf_pipeline_commit_from(m->slab[k], m->pinned[slot], -1, T, true, m->uploaded[slot][k], copy_thunk, m);
+      tsdf_handle s = m->slab[k];
+      const bool held = s->pair_pending;
+      hipEvent_t t1 = nullptr;
+      int rc = timing_begin(m, k, &t1);
+      if (!rc) rc = tsdf_pipeline_commit_from(s, m->pinned[slot], -1, T, true, m->uploaded[slot][k], copy_thunk, m);
+      // a frame with nobody waiting is held back (no sweep); the partner of a held frame gives one sweep or two
+      if (!rc) rc = timing_end(m, k, t1, held ? (s->pair_pending || s->pair_fused ? 1 : 2) : (s->pair_pending ? 0 : 1));
       if (rc) return rc;
     }
     m->frames++;
@@ -511,11 +546,15 @@ int tsdf_multi_integrate_device2(tsdf_handle h, const float *da, const uint32_t 
     if (!rc) rc = tsdf_multi_integrate_device(h, db, cb, TB, n_observed ? n_observed + 1 : nullptr);
     return rc;
   }
+  if (const int rc_flush = tsdf_multi_flush(h)) return rc_flush;  // (a frame the slabs were holding back goes first)
   m->halo1_fresh = m->halo_all_fresh = false;
   bool all_fused = true;
-  for (tsdf_handle s : m->slab) {
+  for (size_t k = 0; k < m->slab.size(); ++k) {
     bool f = false;
-    const int rc = tsdf_pipeline_pair_from(s, da, db, src_dev, TA, planes_a, TB, planes_b, n_observed != nullptr, &f, copy_thunk, m);
+    hipEvent_t t1 = nullptr;
+    int rc = timing_begin(m, k, &t1);
+    if (!rc) rc = tsdf_pipeline_pair_from(m->slab[k], da, db, src_dev, TA, planes_a, TB, planes_b, n_observed != nullptr, &f, copy_thunk, m);
+    if (!rc) rc = timing_end(m, k, t1, f ? 1 : 2);
     if (rc) return rc;
     all_fused = all_fused && f;
   }
@@ -523,6 +562,7 @@ int tsdf_multi_integrate_device2(tsdf_handle h, const float *da, const uint32_t 
   if (n_observed) {
     n_observed[0] = n_observed[1] = 0;
     unsigned long long observed = 0, changed = 0, implied = 0, read_bytes = 0;
+    bool implied_on = true;
     for (tsdf_handle s : m->slab) {
       TSDF_ON_DEVICE(s->device);
       uint64_t n2[2] = {0, 0};
@@ -530,8 +570,10 @@ int tsdf_multi_integrate_device2(tsdf_handle h, const float *da, const uint32_t 
       if (rc) return rc;
       n_observed[0] += n2[0], n_observed[1] += n2[1];
       observed += s->last_observed, changed += s->last_changed_bytes, implied += s->last_implied, read_bytes += s->last_read_bytes;
+      implied_on = implied_on && s->last_implied_on;  // (a fused sweep reads every distance word: off)
     }
     h->last_observed = observed, h->last_changed_bytes = changed, h->last_implied = implied, h->last_read_bytes = read_bytes;
+    h->last_implied_on = implied_on;
   }
   return TSDF_HIP_OK;
 }
@@ -1215,6 +1257,11 @@ int tsdf_multi_march(tsdf_handle h, float w_min, int color_mode, uint64_t *n_tri
   int rc = exchange_halo(h, 1, false);
   if (rc) return rc;
   if ((rc = tsdf_multi_synchronize(h))) return rc;
+  // the weight test of cells that end on a halo plane (tsdf_march.hip counts_pass): plane z_end of every slab is now a copy
+  // of its owner's, counts included, so what band_exact says of the owner's planes holds for the copy
+  bool vouch = true;
+  for (tsdf_handle s : m->slab) vouch = vouch && s->packed && s->band_exact;
+  for (tsdf_handle s : m->slab) s->mc_halo_vouched = vouch;
   struct Part {
     std::vector<float> verts;
     std::vector<uint8_t> rgb;
@@ -1242,6 +1289,7 @@ int tsdf_multi_march(tsdf_handle h, float w_min, int color_mode, uint64_t *n_tri
       (void)tsdf_hip_march_timing(s, p.ms, &p.cells);
     });
   for (auto &t : th) t.join();
+  for (tsdf_handle s : m->slab) s->mc_halo_vouched = false;
   uint64_t total = 0;
   m->mc_ms[0] = m->mc_ms[1] = m->mc_ms[2] = 0.f;
   m->mc_ncells = 0;
@@ -1345,8 +1393,8 @@ int tsdf_multi_march_timing(tsdf_handle h, float ms[3], uint64_t *n_cells) {
   return TSDF_HIP_OK;
 }
 
-int tsdf_multi_march_stats(tsdf_handle h, uint64_t out[4]) {  // sums over the slabs; "skipped" only if every slab did
-  out[0] = out[1] = out[2] = 0, out[3] = 1;
+int tsdf_multi_march_stats(tsdf_handle h, uint64_t out[4]) {  // sums over the slabs; a bit of out[3] only if every slab set it
+  out[0] = out[1] = out[2] = 0, out[3] = ~0ull;
   for (tsdf_handle s : h->multi->slab) {
     uint64_t o[4];
     const int rc = tsdf_hip_march_stats(s, o);

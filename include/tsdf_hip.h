@@ -153,7 +153,9 @@ int tsdf_hip_multi_render_stats(tsdf_handle h, uint64_t out[4]);
 int tsdf_hip_multi_link_stats(tsdf_handle h, uint64_t out[3]);
 /* Report-only, multi-GPU handles: per-slab k_integrate time.  While enabled, every slab's integrate launch is bracketed
  * by HIP events on that slab's stream; tsdf_hip_multi_kernel_ms synchronises slab k and returns the summed milliseconds
- * and the number of launches since timing was enabled (or last read). */
+ * and the number of launches since timing was enabled (or last read).  With frame pairing and tsdf_hip_integrate_device2
+ * the launches are the sweeps slab k really ran: 1 for a pair it fused, 2 for a pair it did not, 1 for a frame launched
+ * on its own, none while a frame waits for its partner (the brackets then include the wait for the frame's copy). */
 int tsdf_hip_multi_timing(tsdf_handle h, int enable);
 int tsdf_hip_multi_kernel_ms(tsdf_handle h, int k, float *ms_sum, int32_t *launches);
 int tsdf_hip_slab_info(tsdf_handle h, int k, int32_t *device, int32_t *z_begin, int32_t *z_end, int32_t *halo);
@@ -439,7 +441,10 @@ int tsdf_hip_march_timing(tsdf_handle h, float ms[3], uint64_t *n_cells);
  * in use (0: every plane was read -- after an upload / load the flags say nothing until reset); out[3] bit 1: the
  * weight test (marching_cubes_tsdf_octree.cpp:98, w < w_min) was not evaluated because it could not fail -- PACKED counts,
  * planes written only by integrateCloud since the reset, no halo plane, w_min <= min(1, max_weight): a corner with
- * |d| < 1 has been observed, and an observation counts. */
+ * |d| < 1 has been observed, and an observation counts.  On a multi-GPU set out[0..2] are the sums over the slabs and
+ * out[3] is combined bit by bit: a bit is set when EVERY slab set it.  (The slabs of a set leave the weight test out on
+ * their halo plane too, while all slabs' planes were written only by integrateCloud since the reset: the halo is then a
+ * fresh copy of such a plane.) */
 int tsdf_hip_march_stats(tsdf_handle h, uint64_t out[4]);
 /* The same copies into DEVICE buffers of the caller, asynchronous on the handle's stream (multi-GPU mesh merge:
  * the buffers go straight to RCCL). */

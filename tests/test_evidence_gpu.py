@@ -23,6 +23,7 @@ import torch
 from cpu_tsdf_amd import capi, synth
 from oracle.oracle import OracleVolume
 from tests.common import assert_same_f32, make_volume
+from tests.sequence_model import Record, compare
 from tests.test_fused2_gpu import device_frame
 from tests.test_implied_d_gpu import holes, open_scene, read_detail
 
@@ -47,39 +48,6 @@ def test_dropin_vs_compiled_reference_hunt_slice(gpu):
     rc, out, err = run_script(["tests/evidence/fuzz_dropin_vs_reference.py", "--cases", "20", "--seed", "502", "--ref-cull", "0.5"])
     assert rc == 0, (out[-3000:], err[-2000:])
     assert "20 cases, seed 502: 0 with differences" in out, out[-1500:]
-
-
-class Record:
-    """The host's record of what the planes may hold (tsdf_hip_volume::band_exact / rest_state), restated."""
-
-    def __init__(self, packed, fixed, kmax):
-        self.can = bool(packed and fixed and kmax >= 1)
-        self.reset()
-
-    def reset(self):
-        self.flags_describe_planes, self.rest = True, 0
-
-    def foreign_write(self):  # upload, set_planes_device on owned planes, device_planes, load, a plain-kernel launch
-        self.flags_describe_planes = False
-
-    def fast_launch(self):
-        """A flag-keeping launch (k_integrate / k_integrate2): returns whether it may rebuild distances from counts."""
-        if not self.flags_describe_planes:
-            return False
-        if not self.can:
-            self.rest = 2
-        elif self.rest == 0:
-            self.rest = 1
-        return self.rest == 1
-
-
-def compare(vol, ov, what):
-    d, w, rgb = vol.download()
-    assert_same_f32(d, ov.d, f"d {what}")
-    assert_same_f32(w, ov.w, f"w {what}")
-    if ov.rgb is not None:
-        assert np.array_equal(rgb, ov.rgb), f"rgb {what}"
-    return d, w, rgb
 
 
 @pytest.mark.parametrize("seed", range(12))

@@ -125,8 +125,9 @@ def test_march_flags_of_a_set_read_as_before(gpu):
         h, n = vol._need(), C.c_uint64(0)
         capi.check(gpu.tsdf_hip_march(h, 0.0, 1, C.byref(n)), "march")
         st = march_stats(gpu, h)
-        # 1 is what commit 606da28 returns here (measured on its build): tsdf_multi_march_stats ANDs the slabs' words into an initial 1, so "skipped
-        # on every slab" survives and bit 1 never does
-        assert st[3] == 1 and 0 < st[2] < 2 ** 63 and st[1] == n.value > 1000
+        # a bit of out[3] on a set means EVERY slab set it: the flags decided what each slab's classify read (bit 0), and no slab
+        # gathered corner weights (bit 1) -- the lower slab neither, whose top cells end on a halo plane: that plane is a fresh
+        # copy of a plane the upper slab's own integrate launches wrote.  The single-handle twin above reads 3 as well
+        assert st[3] == 3 and 0 < st[2] < 2 ** 63 and st[1] == n.value > 1000
     finally:
         vol.close()

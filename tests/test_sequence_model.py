@@ -1,0 +1,116 @@
+"""CPU tier: the model of tests/sequence_model.py checked without the product.  Its shift + integrate composition against an
+OracleVolume that integrates the same frame on arrays rolled beforehand by other means (np.roll and index masks, not
+tests/shift_cases), the pose rule against the geometry it stands for, the in-place uploads, and the record's shift rule."""
+import numpy as np
+import pytest
+
+from cpu_tsdf_amd import capi, synth
+from oracle.oracle import OracleVolume
+from tests.common import assert_same_f32, make_volume
+from tests.sequence_model import Model, clamp_shift, record_for
+
+RES = 32
+
+
+def rolled(a, s, fill):
+    """out[z, y, x] = a[z + sz, y + sy, x + sx] or `fill`: np.roll, then everything that wrapped around is overwritten."""
+    out = np.roll(a, (-s[2], -s[1], -s[0]), axis=(0, 1, 2))
+    for axis, v in zip((2, 1, 0), s):
+        n = a.shape[axis]
+        idx = np.arange(n)
+        wrapped = (idx + v < 0) | (idx + v >= n)
+        sl = [slice(None)] * a.ndim
+        sl[axis] = wrapped
+        out[tuple(sl)] = fill
+    return out
+
+
+def fused_model(color):
+    vol, sc = make_volume(RES, 80, 60, color=color)
+    m = Model(vol._p)
+    for i in range(3):
+        tr = synth.turntable_pose(i, 8, sc.size)
+        assert m.integrate(sc.depth(tr), sc.bgra(i) if color else None, m.pose(tr)) > 0
+    return vol, sc, m
+
+
+@pytest.mark.parametrize("color", [True, False])
+@pytest.mark.parametrize("s", [(3, -2, 1), (0, 0, -12), (-33, 1, 0), (1, 0, 0)])
+def test_shift_then_integrate_equals_integrate_on_rolled_arrays(color, s):
+    vol, sc, m = fused_model(color)
+    before = (m.ov.d.copy(), m.ov.w.copy(), m.ov.rgb.copy() if color else None)
+    moved = np.array(s, np.float64) * sc.size / RES   # what shiftVolume returns: s * size / res
+    m.shift(s, moved)
+    c = clamp_shift(s, (RES,) * 3)
+    want = OracleVolume(vol._p, adopt=(np.ascontiguousarray(rolled(before[0], c, np.float32(-1))),
+                                       np.ascontiguousarray(rolled(before[1], c, np.float32(0))),
+                                       np.ascontiguousarray(rolled(before[2], c, np.uint8(0))) if color else None))
+    assert_same_f32(m.ov.d, want.d, f"rolled d, shift {s}")
+    assert_same_f32(m.ov.w, want.w, f"rolled w, shift {s}")
+    assert (m.ov.w > 0).sum() < (before[1] > 0).sum() or s == (1, 0, 0)
+    tr = synth.turntable_pose(3, 8, sc.size)
+    dep, col = sc.depth(tr), sc.bgra(3) if color else None
+    posed = m.pose(tr)
+    assert np.array_equal(posed[:3, :3], tr[:3, :3]) and np.array_equal(posed[:3, 3], tr[:3, 3] - moved)
+    n = m.integrate(dep, col, posed)
+    assert n == want.integrate(dep, col, synth.cam_from_vol_f32(posed))
+    assert_same_f32(m.ov.d, want.d, "d after one more frame")
+    assert_same_f32(m.ov.w, want.w, "w after one more frame")
+    if color:
+        assert np.array_equal(m.ov.rgb, want.rgb)
+    g = np.eye(4)
+    g[:3, 3] = moved
+    assert np.array_equal(m.G, g)
+
+
+def test_the_posed_camera_sees_every_surviving_voxel_where_it_was():
+    """Voxel (x, y, z) after the shift is voxel (x + sx, y + sy, z + sz) before it: seen from Model.pose(trans) its centre
+    has the camera coordinates the old voxel's centre had from `trans`."""
+    vol, sc, m = fused_model(False)
+    s = (3, -2, 5)
+    ctr = [m.ov.centers(a).astype(np.float64) for a in range(3)]
+    m.shift(s, np.array(s, np.float64) * sc.size / RES)
+    tr = synth.turntable_pose(1, 8, sc.size, tilt=0.2)
+    new_cam, old_cam = np.linalg.inv(m.pose(tr)), np.linalg.inv(tr)
+    for x, y, z in [(0, 2, 0), (10, 20, 5), (28, 31, 26)]:
+        new = new_cam @ np.array([ctr[0][x], ctr[1][y], ctr[2][z], 1.0])
+        old = old_cam @ np.array([ctr[0][x + s[0]], ctr[1][y + s[1]], ctr[2][z + s[2]], 1.0])
+        assert np.abs(new - old).max() < 1e-12
+    verts = np.array([[ctr[0][4], ctr[1][5], ctr[2][6]]], np.float32)   # ... and reconstruct() puts it back where it was
+    assert_same_f32(m.to_world(verts), np.array([[ctr[0][4 + s[0]], ctr[1][5 + s[1]], ctr[2][6 + s[2]]]], np.float32), "to_world")
+
+
+def test_uploads_write_the_box_and_nothing_else():
+    vol, sc, m = fused_model(True)
+    d0, w0, rgb0 = m.ov.d.copy(), m.ov.w.copy(), m.ov.rgb.copy()
+    box = (3, 5, 9, 20, 11, 4)
+    d, w, rgb = (a.copy() for a in m.box(*box))
+    m.upload(d=d - np.float32(0.25), x0=3, y0=5, z0=9)
+    m.upload(w=w + 1, x0=3, y0=5, z0=9)
+    sl = (slice(9, 13), slice(5, 16), slice(3, 23))
+    assert_same_f32(m.ov.d[sl], d0[sl] - np.float32(0.25), "d in the box")
+    assert_same_f32(m.ov.w[sl], w0[sl] + 1, "w in the box")
+    outside = np.ones(d0.shape, bool)
+    outside[sl] = False
+    assert np.array_equal(m.ov.d[outside], d0[outside]) and np.array_equal(m.ov.w[outside], w0[outside])
+    assert np.array_equal(m.ov.rgb, rgb0)
+    idx, dd, ww, cc = m.occupied(box)
+    assert len(idx) > 0 and (idx >= box[:3]).all() and (idx < np.add(box[:3], box[3:])).all()
+    assert np.array_equal(dd, m.ov.d[idx[:, 2], idx[:, 1], idx[:, 0]]) and np.array_equal(cc, m.ov.rgb[idx[:, 2], idx[:, 1], idx[:, 0]])
+    m.reset()
+    assert (m.ov.d == -1).all() and not m.ov.w.any()
+
+
+def test_a_shift_leaves_the_record_as_it_was():
+    for packed, trunc, wmax, can in ((True, (0.03, 0.03), 100.0, True), (True, (0.01, 0.03), 100.0, False),
+                                     (True, (0.03, 0.03), 2.5, False), (False, (0.03, 0.03), 4.0, False)):
+        rec = record_for(packed, trunc, wmax)
+        assert rec.can == can
+        assert rec.fast_launch() == can
+        state = dict(rec.__dict__)
+        rec.shift()
+        assert rec.__dict__ == state and rec.fast_launch() == can
+        rec.foreign_write()
+        rec.shift()
+        assert not rec.flags_describe_planes and not rec.fast_launch()
+    assert capi.LAYOUT_PACKED != capi.LAYOUT_F32W
