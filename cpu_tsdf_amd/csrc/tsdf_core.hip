@@ -928,6 +928,9 @@ static int block_transfer(tsdf_handle h, int x0, int y0, int z0, int nx, int ny,
     tsdf_set_error("RGB_NORMALIZED / LAB colour state cannot be set from r,g,b bytes");
     return TSDF_HIP_E_UNSUPPORTED;
   }
+  // arbitrary distances arrive: the "band seen" flags no longer describe the planes.  (Only here, behind the refusals
+  // above: a call that is refused before it writes anything leaves the record as it was.)
+  if (!DOWN) h->band_exact = false;
   TSDF_ENTER(h);
   const int64_t plane = (int64_t)nx * ny;
   int64_t max_planes = (int64_t)(64 << 20) / plane;  // <= 64 Mi voxels (256 MiB of floats) per chunk
@@ -1098,7 +1101,6 @@ extern "C" int tsdf_hip_upload(tsdf_handle h, int x0, int y0, int z0, int nx, in
   if (h && h->multi)
     return tsdf_multi_block(h, false, x0, y0, z0, nx, ny, nz, const_cast<float *>(d), const_cast<float *>(w),
                             const_cast<uint8_t *>(rgb));
-  if (h) h->band_exact = false;  // arbitrary distances arrive: the "band seen" flags no longer describe the planes
   return block_transfer<false>(h, x0, y0, z0, nx, ny, nz, const_cast<float *>(d), const_cast<float *>(w),
                                const_cast<uint8_t *>(rgb));
 }

@@ -239,9 +239,14 @@ int tsdf_hip_last_read_detail(tsdf_handle h, uint64_t out[3]);
  *                       fp64 projection, IEEE divisions), every operation in the reference's order.
  *   weight_by_variance  w_new *= exp(logNormal(d_new, d, variance)) once a voxel has more than 5 samples (:203-204),
  *                       from OctreeNode::M_ / nsample_ (src/lib/octree.cpp:160-161,281-287): two more planes per voxel
- *                       (float M, int32 nsample), allocated when the flag is set, zero like a fresh octree's, updated by
- *                       every observation from then on, carried by tsdf_hip_save / tsdf_hip_load in the node records the
- *                       reference keeps them in, and readable / writable through tsdf_hip_*_variance_state.  Needs
+ *                       (float M, int32 nsample), allocated when the flag is first set, zero like a fresh octree's,
+ *                       updated by every observation integrated WHILE THE FLAG IS ON, carried by tsdf_hip_save /
+ *                       tsdf_hip_load in the node records the reference keeps them in, and readable / writable through
+ *                       tsdf_hip_*_variance_state.  A handle that has the planes and is switched back
+ *                       (tsdf_hip_set_weighting(h, x, 0)) keeps them -- reset, shift and the block transfers go on
+ *                       moving them; tsdf_hip_save writes them only while the flag is on -- but its frames no longer
+ *                       update them: M / nsample stay what they were until the flag is set again.  (The reference updates them on every observation whatever
+ *                       the flag says; it has no setter, so no sequence of its calls reaches this state.)  Needs
  *                       the F32W layout and TSDF_COLOR_RGB like weight_by_depth (tsdf_hip_load with AUTO picks F32W);
  *                       integrated by the same plain kernel.  std::exp(float) is the host libm's expf restated on the
  *                       device (glibc's table algorithm, in the FMA or the plain build's form, whichever this host

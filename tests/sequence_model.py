@@ -71,20 +71,60 @@ def clamp_shift(s, res):
     return tuple(int(max(-r, min(r, v))) for v, r in zip(s, res))
 
 
+def slab_starts(res, n=3):
+    """First plane of every slab of tsdf_hip_create_multi's partition of `res` planes over n devices, and res."""
+    base, extra = res // n, res % n
+    return [k * base + min(k, extra) for k in range(n + 1)]
+
+
+def draw_shift(rng, cum, thick):
+    """A random shift of the sequence tests: pure and mixed, +-1 / +-3 / a whole flag cell / one more along x, past a row
+    cell along y, past a whole slab along z; `cum` (the sum so far) keeps the window near the scene."""
+    t = thick + 1
+    s = [int(rng.choice([0, 0, 1, -1, 3, -3, 64, -64, 65, -65])), int(rng.choice([0, 0, 1, -1, 4, -4, 5, -5])),
+         int(rng.choice([0, 0, 1, -1, 2, -2, t, -t]))]
+    for a, limit in enumerate((65, 5, t)):   # the window stays near the scene: a shift that would leave turns back
+        if abs(cum[a] + s[a]) > limit:
+            s[a] = -s[a]
+    return tuple(s)
+
+
 class Model:
     """An OracleVolume that follows shifts, uploads and resets.  `moved` is the sum of what shiftVolume returned, `G` the
     global transform the product's class keeps (reset() keeps it, like the class)."""
 
-    def __init__(self, params):
-        self.params = params
-        self.ov = OracleVolume(params)
+    def __init__(self, params, mode=None, cull=False):
+        """mode: None (TSDF_COLOR_RGB, no weighting: OracleVolume.integrate) or one of tests/evidence/
+        fuzz_product_colour_modes.MODES -- the oracle form that integrates, and the per-voxel state that goes with it
+        (ov.cn of the colour modes, ov.M / ov.nsample of the variance weighting).  cull: every frame is integrated with the
+        reference's frustum cull for the pose the product is handed (the product applies it on every frame; it only
+        decides voxels under narrow off-centre cameras)."""
+        if mode is not None:
+            from tests.evidence.fuzz_product_colour_modes import MODES
+            assert mode in MODES, mode
+        self.params, self.mode, self.cull = params, mode, bool(cull)
+        self.reset()
         self.color = self.ov.rgb is not None
         self.moved = np.zeros(3)
         self.G = np.eye(4)
 
     # ---- writers -------------------------------------------------------------------------------------------------------
     def reset(self):
-        self.ov = OracleVolume(self.params)
+        """A fresh volume that keeps its mode (and with it the state planes, zero like tsdf_hip_reset leaves them)."""
+        self.ov = ov = OracleVolume(self.params)
+        planes = {"RGBNormalized": 4, "LAB": 3}.get(self.mode, 0)
+        if planes:
+            ov.cn = np.zeros((planes,) + ov.d.shape, np.float32)
+        if self.mode and "by_variance" in self.mode:
+            ov.M, ov.nsample = np.zeros_like(ov.d), np.zeros(ov.d.shape, np.int32)
+
+    def state_arrays(self):
+        """The per-voxel state beyond d, w, rgb as (name, [z][y][x] array) pairs."""
+        ov = self.ov
+        out = [(f"cn[{k}]", ov.cn[k]) for k in range(len(ov.cn))] if hasattr(ov, "cn") else []
+        if getattr(ov, "M", None) is not None:
+            out += [("M", ov.M), ("nsample", ov.nsample)]
+        return out
 
     def pose(self, trans):
         """The pose to hand to the product for a camera that stands at `trans` in the frame the volume started in."""
@@ -94,7 +134,17 @@ class Model:
 
     def integrate(self, depth, bgra, trans):
         """`trans`: the pose as handed to the product (Model.pose applied by the caller)."""
-        return self.ov.integrate(depth, bgra if self.color else None, synth.cam_from_vol_f32(trans))
+        ov, col, T = self.ov, bgra if self.color else None, synth.cam_from_vol_f32(trans)
+        planes = ov.reference_cull_planes(trans) if self.cull else None
+        if self.mode is None:
+            return ov.integrate(depth, col, T, planes=planes) if self.cull else ov.integrate(depth, col, T)
+        if self.mode == "RGBNormalized":
+            return ov.integrate_rgbn(depth, col, T, planes=planes)
+        if self.mode == "LAB":
+            return ov.integrate_lab(depth, col, T, planes=planes)
+        if "by_variance" in self.mode:
+            return ov.integrate_variance(depth, col, T, "by_depth" in self.mode, planes=planes)
+        return ov.integrate(depth, col, T, weight_by_depth=True, planes=planes)
 
     def shift(self, s, moved):
         """s: the voxels asked for; moved: what shiftVolume returned for them."""
@@ -104,6 +154,8 @@ class Model:
         ov.d[...], ov.w[...] = d, w
         if rgb is not None:
             ov.rgb[...] = rgb
+        for _, a in self.state_arrays():
+            a[...] = shift_cases.shifted(a, clamp_shift(s, res), shift_cases.FILL_STATE)
         self.moved = self.moved + np.asarray(moved, np.float64)
         t = np.eye(4)
         t[:3, 3] = np.asarray(moved, np.float64)
@@ -123,6 +175,20 @@ class Model:
             bw[...] = w
         if rgb is not None:
             brgb[...] = rgb
+
+    def variance_box(self, box):
+        """(M, nsample) views of box = (x0, y0, z0, nx, ny, nz)."""
+        x0, y0, z0, nx, ny, nz = box
+        sl = (slice(z0, z0 + nz), slice(y0, y0 + ny), slice(x0, x0 + nx))
+        return self.ov.M[sl], self.ov.nsample[sl]
+
+    def upload_variance(self, M, ns, box):
+        """tsdf_hip_upload_variance_state: either array may be None."""
+        bM, bns = self.variance_box(box)
+        if M is not None:
+            bM[...] = M
+        if ns is not None:
+            bns[...] = ns
 
     # ---- readers -------------------------------------------------------------------------------------------------------
     def to_world(self, verts):

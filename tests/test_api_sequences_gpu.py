@@ -22,7 +22,7 @@ from cpu_tsdf_amd import capi, synth
 from cpu_tsdf_amd.volume import MarchingCubesTSDFOctree, backproject
 from tests import align_cases, flatten_cases
 from tests.common import assert_same_f32, make_volume
-from tests.sequence_model import Model, assert_same_mesh, compare, record_for
+from tests.sequence_model import Model, assert_same_mesh, compare, draw_shift, record_for, slab_starts  # noqa: F401
 from tests.test_fused2_gpu import device_frame
 from tests.test_implied_d_gpu import holes, open_scene, read_detail
 from tests.test_occupied_gpu import check as check_occupied
@@ -46,11 +46,6 @@ READING = ["mesh", "mesh", "occupied", "render", "render", "sample", "align"]
 SINGLE_ONLY = ("set_planes", "device_planes")
 TALLY = {shape: collections.Counter() for shape in SHAPES}
 RAN, SECONDS = set(), {}
-
-
-def slab_starts(res, n=3):
-    base, extra = res // n, res % n
-    return [k * base + min(k, extra) for k in range(n + 1)]
 
 
 def march_stats(vol):
@@ -99,6 +94,11 @@ class Driver:
         self.pairing, self.held = False, False
         self.stale = None   # single handle: (idx of an occupied list, whether a later step invalidated it)
         self.lib = capi.load()
+
+    mutating, tally = MUTATING, TALLY   # (what a subclass with other operations replaces)
+
+    def compare(self, what):
+        compare(self.vol, self.model.ov, what)
 
     def close(self):
         self.vol.close()
@@ -211,13 +211,7 @@ class Driver:
             self.held = not self.held
 
     def draw_shift(self):
-        rng, t = self.rng, self.thick + 1
-        s = [int(rng.choice([0, 0, 1, -1, 3, -3, 64, -64, 65, -65])), int(rng.choice([0, 0, 1, -1, 4, -4, 5, -5])),
-             int(rng.choice([0, 0, 1, -1, 2, -2, t, -t]))]
-        for a, limit in enumerate((65, 5, t)):   # the window stays near the scene: a shift that would leave turns back
-            if abs(self.cum[a] + s[a]) > limit:
-                s[a] = -s[a]
-        return tuple(s)
+        return draw_shift(self.rng, self.cum, self.thick)
 
     def op_shift(self, what, s=None):
         s = self.draw_shift() if s is None else s
@@ -346,8 +340,11 @@ class Driver:
         assert got.shape == want.shape == (120 // ds, 160 // ds, 8), what
         hit = np.isfinite(want[..., 0])
         assert np.array_equal(np.isfinite(got[..., 0]), hit), f"{what} ds {ds}: hit mask"
-        assert np.array_equal(got[hit].view(np.uint32), want[hit].view(np.uint32)), f"{what} ds {ds}: hits"
+        self.assert_same_hits(got[hit], want[hit], f"{what} ds {ds}: hits")
         return got, int(hit.sum())
+
+    def assert_same_hits(self, got, want, what):
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), what
 
     def op_sample(self, what):
         rng, S = self.rng, self.sc.size
@@ -399,18 +396,18 @@ class Driver:
 
     # ---- one step ---------------------------------------------------------------------------------------------------------
     def step(self, op, what, **kw):
-        mutating = op in MUTATING
+        mutating = op in self.mutating
         if self.single and mutating and op != "ring" and not self.pairing and self.rng.rand() < 0.5:
             self.make_list()
         if op != "ring":
             self.before(op)
         out = getattr(self, "op_" + op)(what, **kw)
         self.after(op)
-        TALLY[self.shape][op] += 1
+        self.tally[self.shape][op] += 1
         if self.stale and mutating:
             self.check_list(what)
         if not self.held:   # (download() is a call like any other: it would launch the frame that waits for the NEXT operation)
-            compare(self.vol, self.model.ov, what)
+            self.compare(what)
         return out
 
     def random_steps(self, n, tag):

@@ -1,12 +1,17 @@
 """CPU tier: the model of tests/sequence_model.py checked without the product.  Its shift + integrate composition against an
 OracleVolume that integrates the same frame on arrays rolled beforehand by other means (np.roll and index masks, not
-tests/shift_cases), the pose rule against the geometry it stands for, the in-place uploads, and the record's shift rule."""
+tests/shift_cases) -- also per colour mode and weighting, state planes included --, the pose rule against the geometry it
+stands for, the in-place uploads, the record's shift rule, and a replay of every case of tests/test_mode_sequences_gpu.py
+through the model alone: the conditions its inputs must meet (tests/mode_cases.CONDITIONS) and its tally of operations."""
+import collections
+
 import numpy as np
 import pytest
 
 from cpu_tsdf_amd import capi, synth
 from oracle.oracle import OracleVolume
 from tests.common import assert_same_f32, make_volume
+from tests import mode_cases
 from tests.sequence_model import Model, clamp_shift, record_for
 
 RES = 32
@@ -114,3 +119,117 @@ def test_a_shift_leaves_the_record_as_it_was():
         rec.shift()
         assert not rec.flags_describe_planes and not rec.fast_launch()
     assert capi.LAYOUT_PACKED != capi.LAYOUT_F32W
+
+
+# ---- the colour modes and the weightings ----------------------------------------------------------------------------------
+MODE_VARIANTS = [("RGBNormalized", True), ("LAB", True), ("by_depth", True), ("by_depth", False), ("by_variance", True),
+                 ("by_variance", False), ("by_depth+by_variance", True), ("by_depth+by_variance", False)]
+
+
+def integrate_directly(ov, mode, dep, col, T):
+    """The oracle form of a mode, called as tests/evidence/fuzz_product_colour_modes.oracle_step calls it (no cull)."""
+    if mode == "RGBNormalized":
+        return ov.integrate_rgbn(dep, col, T)
+    if mode == "LAB":
+        return ov.integrate_lab(dep, col, T)
+    if "by_variance" in mode:
+        return ov.integrate_variance(dep, col, T, "by_depth" in mode)
+    return ov.integrate(dep, col, T, weight_by_depth=True)
+
+
+def arrays_of(ov):
+    out = {"d": ov.d, "w": ov.w}
+    if ov.rgb is not None:
+        out["rgb"] = ov.rgb
+    for k in range(len(getattr(ov, "cn", ()))):
+        out[f"cn[{k}]"] = ov.cn[k]
+    if getattr(ov, "M", None) is not None:
+        out["M"], out["nsample"] = ov.M, ov.nsample
+    return out
+
+
+def assert_same_arrays(got, want, what):
+    assert got.keys() == want.keys(), (what, sorted(got), sorted(want))
+    for name in want:
+        if want[name].dtype == np.float32:
+            assert_same_f32(got[name], want[name], f"{name} {what}")
+        else:
+            assert np.array_equal(got[name], want[name]), f"{name} {what}"
+
+
+@pytest.mark.parametrize("mode,color", MODE_VARIANTS)
+@pytest.mark.parametrize("s", [(3, -2, 1), (0, 0, -12), (1, 0, 0)])
+def test_shift_then_integrate_equals_integrate_on_rolled_arrays_in_every_mode(mode, color, s):
+    vol, sc = make_volume(RES, 80, 60, color=color)
+    m = Model(vol._p, mode)
+    for i in range(7):   # two poses revisited: nsample passes 5 and the variance weighting acts
+        tr = synth.turntable_pose(i % 2, 8, sc.size)
+        assert m.integrate(sc.depth(tr, noise_seed=40 + i), sc.bgra(i) if color else None, m.pose(tr)) > 0
+    before = {k: a.copy() for k, a in arrays_of(m.ov).items()}
+    state = [k for k in before if k not in ("d", "w", "rgb")]
+    assert len(state) == {"RGBNormalized": 4, "LAB": 3, "by_depth": 0}.get(mode, 2)
+    assert all(before[k].any() for k in state)
+    if "by_variance" in mode:
+        assert ((before["nsample"] > 5) & (before["w"] % 1 != 0)).sum() > 1000
+    if "by_depth" in mode:
+        assert (before["w"] % 1 != 0).sum() > 1000
+    m.shift(s, np.array(s, np.float64) * sc.size / RES)
+    c = clamp_shift(s, (RES,) * 3)
+    fill = {"d": np.float32(-1), "w": np.float32(0), "rgb": np.uint8(0), "nsample": np.int32(0)}
+    r = {k: np.ascontiguousarray(rolled(a, c, fill.get(k, np.float32(0)))) for k, a in before.items()}
+    want = OracleVolume(vol._p, adopt=(r["d"], r["w"], r.get("rgb")))
+    if mode in ("RGBNormalized", "LAB"):
+        want.cn = np.ascontiguousarray(np.stack([r[k] for k in state]))
+    if "by_variance" in mode:
+        want.M, want.nsample = r["M"], r["nsample"]
+    assert_same_arrays(arrays_of(m.ov), arrays_of(want), f"rolled, {mode}, shift {s}")
+    tr = synth.turntable_pose(1, 8, sc.size)
+    dep, col = sc.depth(tr, noise_seed=60), sc.bgra(9) if color else None
+    posed = m.pose(tr)
+    assert m.integrate(dep, col, posed) == integrate_directly(want, mode, dep, col, synth.cam_from_vol_f32(posed)) > 0
+    assert_same_arrays(arrays_of(m.ov), arrays_of(want), f"one more frame, {mode}, shift {s}")
+    m.reset()
+    assert m.mode == mode and [k for k in arrays_of(m.ov)] == list(before) and not any(arrays_of(m.ov)[k].any() for k in state)
+
+
+def test_variance_box_upload_writes_the_box_and_nothing_else():
+    vol, sc = make_volume(RES, 80, 60)
+    m = Model(vol._p, "by_variance")
+    rng = np.random.RandomState(3)
+    m.ov.M[...], m.ov.nsample[...] = rng.uniform(0, 2, m.ov.M.shape), rng.randint(0, 9, m.ov.M.shape)
+    M0, n0 = m.ov.M.copy(), m.ov.nsample.copy()
+    box, sl = (3, 5, 9, 20, 11, 4), (slice(9, 13), slice(5, 16), slice(3, 23))
+    bM, bn = (a.copy() for a in m.variance_box(box))
+    assert np.array_equal(bM, M0[sl]) and np.array_equal(bn, n0[sl])
+    m.upload_variance(bM + 1, None, box)
+    m.upload_variance(None, bn + 2, box)
+    M0[sl] += 1
+    n0[sl] += 2
+    assert np.array_equal(m.ov.M, M0) and np.array_equal(m.ov.nsample, n0) and m.ov.nsample.dtype == np.int32
+
+
+@pytest.mark.parametrize("case", mode_cases.CASES, ids=mode_cases.case_id)
+def test_the_replay_of_every_mode_case_meets_the_conditions(case):
+    """The plan of every case of tests/test_mode_sequences_gpu.py through the model alone: tests/mode_cases.CONDITIONS."""
+    model, tally = mode_cases.replay(case)
+    print(mode_cases.case_id(case), model.assert_conditions(mode_cases.case_id(case)), dict(tally))
+
+
+def test_the_plans_run_every_legal_operation_three_times_per_mode_and_shape():
+    tally = collections.defaultdict(collections.Counter)
+    for c in mode_cases.CASES:
+        for e in mode_cases.Setup(c).plan[:-2]:
+            assert e["op"] in mode_cases.legal_ops(c)
+            tally[c.shape, c.mode][e["op"]] += 1
+        plan = mode_cases.Setup(c).plan   # a frame held back by pairing meets a shift in every case
+        assert any(a["op"] == "ring" and a["n"] % 2 == 1 and b["op"] == "shift" for a, b in zip(plan, plan[1:])), mode_cases.case_id(c)
+    assert len(tally) == 10
+    for (shape, mode), t in tally.items():
+        legal = set().union(*[mode_cases.legal_ops(c) for c in mode_cases.CASES if (c.shape, c.mode) == (shape, mode)])
+        assert ("upload_variance" in legal) == ("by_variance" in mode) and ("save_load" in legal) == ("by_" in mode)
+        for op in legal:
+            assert t[op] >= 3, (shape, mode, op, dict(t))
+    for grid in mode_cases.GRIDS:   # pure x shifts of the register path, of whole flag cells and of a cell and one more, on both grids
+        x = {e["s"][0] for c in mode_cases.CASES if c.grid == grid for e in mode_cases.Setup(c).plan
+             if e["op"] == "shift" and not (e["s"][1] or e["s"][2])}
+        assert x >= set(mode_cases.PURE_X), (grid, x)

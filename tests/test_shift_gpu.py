@@ -110,6 +110,64 @@ def test_variance_state_moves_with_the_voxels(gpu):
     vol.close()
 
 
+@pytest.mark.parametrize("devices", [None, [0, 0, 0]], ids=["one_handle", "set_0_0_0"])
+def test_variance_state_moves_over_the_whole_shift_list(gpu, devices):
+    """M and nsample on RES3 (three flag cells in x, pitch != nx), fresh random values before every shift: every path of the
+    shift kernels moves the float and the int32 plane and fills with zeros.  On a set (slabs of 3, 2, 2 planes) the z
+    shifts pull both planes between the slabs."""
+    vol, _ = make_volume(RES3[0], 80, 60, res3=RES3, max_weight=9.0)
+    vol.setLayout(capi.LAYOUT_F32W)
+    vol.setWeighting(False, True)
+    vol.setDevices(devices)
+    vol.reset()
+    rng = np.random.RandomState(23)
+    shape = RES3[::-1]
+    for s in (SHIFTS if devices is None else MULTI_SHIFTS):
+        M, ns = rng.uniform(0.5, 2, shape).astype(np.float32), rng.randint(1, 20, shape).astype(np.int32)
+        vol.uploadVarianceState(M, ns)
+        vol.shiftVolume(*s)
+        gM, gns = vol.downloadVarianceState()
+        assert_same_f32(gM, sc_.shifted(M, s, sc_.FILL_STATE), f"M, shift {s}")
+        assert np.array_equal(gns, sc_.shifted(ns, s, sc_.FILL_STATE)), f"nsample, shift {s}"
+    vol.close()
+
+
+FLAT3 = (70, 36, 45)  # pitch 72 != nx, a partial second flag cell in x, ny no multiple of the 4-row cell
+COLOUR_STATE_SHIFTS = [(1, 0, 0), (-1, 0, 0), (64, 0, 0), (-64, 0, 0), (65, 0, 0), (0, -5, 0), (0, 0, 16), (3, -2, 1), (-65, 4, -2),
+                       (5, 3, 2), (0, 4, -1)]
+
+
+@pytest.mark.parametrize("mode", ["RGBNormalized", "LAB"])
+def test_float_colour_state_moves_on_a_flat_grid(gpu, mode):
+    """The float colour planes (no upload exists for them: three fused frames) over pure x shifts of +-1, +-64 and 65, a pure
+    y, a pure z and mixed shifts, on a grid whose pitch is not nx; re-fused after a reset() where a shift emptied the grid."""
+    size = synth.scene_a(FLAT3[0], 80, 60).size
+    vol, sc = make_volume(FLAT3[0], 80, 60, color=True, res3=FLAT3, size3=tuple(size * r / FLAT3[0] for r in FLAT3))
+    vol.setColorMode(mode)
+
+    def fuse():
+        vol.reset()
+        for i, tr, dep, col in frames(sc, 3, 8):
+            vol.integrateCloud(dep, col, tr)
+    fuse()
+    fused, full = 1, int((vol.download()[1] > 0).sum())
+    for s in COLOUR_STATE_SHIFTS:
+        before, state = vol.download(), vol.downloadColorState()
+        if (before[1] > 0).sum() < full // 2:   # (the shifts by a whole flag cell and back left six columns)
+            fuse()
+            fused += 1
+            before, state = vol.download(), vol.downloadColorState()
+        assert (before[1] > 0).sum() > 1000 and all(plane.any() for plane in state)
+        vol.shiftVolume(*s)
+        same_volume(vol.download(), sc_.shifted_volume(*before, s), f"{mode}, shift {s}")
+        got = vol.downloadColorState()
+        assert got.shape == state.shape == ({"RGBNormalized": 4, "LAB": 3}[mode],) + FLAT3[::-1]
+        for c in range(len(state)):
+            assert_same_f32(got[c], sc_.shifted(state[c], s, sc_.FILL_STATE), f"{mode} state plane {c}, shift {s}")
+    assert fused >= 2
+    vol.close()
+
+
 # ---- 3. the flags survive and still mean something ------------------------------------------------------------------------
 SIDE = dict(first=8, total=44)  # the frames of tests/test_occupied_gpu.py: from one side, so that cells stay without a flag
 
