@@ -139,6 +139,10 @@ SIGNATURES = {
     "tsdf_hip_march_flatten": (C.c_int, [C.c_void_p, C.c_float, _u64p, _u64p]),
     "tsdf_hip_march_fetch_indexed": (C.c_int, [C.c_void_p, _f32p, _u8p, _u32p, _u64p]),
     "tsdf_hip_mesh_flatten_stats": (C.c_int, [_u64p]),
+    "tsdf_hip_mesh_decimate": (C.c_int, [C.c_int, _f32p, _u8p, C.c_uint64, _u32p, C.c_uint64, C.c_float, _u32p, _f32p, _u8p, _u32p, _u64p, _u32p,
+                                         _u64p]),
+    "tsdf_hip_march_decimate": (C.c_int, [C.c_void_p, C.c_float, _u64p, _u64p]),
+    "tsdf_hip_mesh_decimate_stats": (C.c_int, [_u64p]),
     "tsdf_hip_occupied": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), _u64p]),
     "tsdf_hip_occupied_fetch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), _f32p, _f32p, _u8p]),
     "tsdf_hip_occupied_fetch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -2,7 +2,7 @@
 // Mirrors performReconstruction of the reference (src/lib/marching_cubes_tsdf_octree.cpp:108-143): build
 // the vertex cloud (3 vertices per triangle, no sharing), move it by the volume's global transform,
 // pack it into the PolygonMesh blob, polygons = {3i, 3i+1, 3i+2}.  With setFlatten (an extension) the vertex cloud and the
-// polygons are the indexed mesh of tsdf_hip_march_flatten instead.
+// polygons are the indexed mesh of tsdf_hip_march_flatten instead, with setDecimate that of tsdf_hip_march_decimate.
 #include <cpu_tsdf/marching_cubes_tsdf_octree.h>
 #include <pcl/common/transforms.h>
 #include <pcl/console/print.h>
@@ -73,9 +73,31 @@ void MarchingCubesTSDFOctree::clearFlatten() {
   g_flatten.erase(this);
 }
 
+// setDecimate's argument per object, kept likewise
+static std::map<const MarchingCubesTSDFOctree *, float> g_decimate;
+
+void MarchingCubesTSDFOctree::setDecimate(float cell_size) {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  g_decimate[this] = cell_size;
+}
+
+void MarchingCubesTSDFOctree::clearDecimate() {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  g_decimate.erase(this);
+}
+
 MarchingCubesTSDFOctree::~MarchingCubesTSDFOctree() {
   clearCleanup();
   clearFlatten();
+  clearDecimate();
+}
+
+static bool decimate_of(const MarchingCubesTSDFOctree *mc, float &out) {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  const auto it = g_decimate.find(mc);
+  if (it == g_decimate.end()) return false;
+  out = it->second;
+  return true;
 }
 
 static bool flatten_of(const MarchingCubesTSDFOctree *mc, float &out) {
@@ -96,8 +118,9 @@ static bool cleanup_of(const MarchingCubesTSDFOctree *mc, CleanupArgs &out) {
 
 // cleanup: NULL, or the arguments of setCleanup -- tsdf_hip_march_cleanup between the march and the fetch.  flatten: NULL,
 // or setFlatten's min_dist -- tsdf_hip_march_flatten after that, and the INDEXED mesh is fetched: `indexed` is set and
-// `faces` holds its polygons (otherwise the soup: polygon i = {3i, 3i + 1, 3i + 2}).
-static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mode, const CleanupArgs *cleanup, const float *flatten,
+// `faces` holds its polygons (otherwise the soup: polygon i = {3i, 3i + 1, 3i + 2}).  decimate: NULL, or setDecimate's
+// cell_size -- tsdf_hip_march_decimate in flatten's place (with both set, flatten is skipped), fetched the same way.
+static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mode, const CleanupArgs *cleanup, const float *flatten, const float *decimate,
                       std::vector<float> &verts, std::vector<unsigned char> &rgb, std::vector<uint32_t> &faces, bool &indexed) {
   verts.clear();
   rgb.clear();
@@ -111,9 +134,10 @@ static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mo
   uint64_t n_tri = 0;
   int rc = tsdf_hip_march(vol->handle(), w_min, mode, &n_tri);
   if (rc == 0 && cleanup) rc = tsdf_hip_march_cleanup(vol->handle(), cleanup->face_dist, cleanup->min_neighbors, &n_tri);
-  if (rc == 0 && flatten) {
+  if (rc == 0 && (flatten || decimate)) {
     uint64_t n_verts = 0, n_faces = 0;
-    rc = tsdf_hip_march_flatten(vol->handle(), *flatten, &n_verts, &n_faces);
+    rc = decimate ? tsdf_hip_march_decimate(vol->handle(), *decimate, &n_verts, &n_faces)
+                  : tsdf_hip_march_flatten(vol->handle(), *flatten, &n_verts, &n_faces);
     if (rc == 0) {
       indexed = true;
       verts.resize((size_t)n_verts * 3);
@@ -157,9 +181,9 @@ void MarchingCubesTSDFOctree::performReconstruction(pcl::PolygonMesh &output) {
   std::vector<uint32_t> faces;
   bool indexed = false;
   CleanupArgs cleanup;
-  float flatten = 0.f;
-  run_march(tsdf_volume_, w_min_, mode, cleanup_of(this, cleanup) ? &cleanup : nullptr, flatten_of(this, flatten) ? &flatten : nullptr, verts, rgb,
-            faces, indexed);
+  float flatten = 0.f, decimate = 0.f;
+  run_march(tsdf_volume_, w_min_, mode, cleanup_of(this, cleanup) ? &cleanup : nullptr, flatten_of(this, flatten) ? &flatten : nullptr,
+            decimate_of(this, decimate) ? &decimate : nullptr, verts, rgb, faces, indexed);
   const size_t n = verts.size() / 3;
   const Eigen::Affine3d g = tsdf_volume_ ? tsdf_volume_->getGlobalTransform() : Eigen::Affine3d::Identity();
   if (mode) {
@@ -202,9 +226,9 @@ void MarchingCubesTSDFOctree::performReconstruction(pcl::PointCloud<pcl::PointXY
   std::vector<uint32_t> faces;
   bool indexed = false;
   CleanupArgs cleanup;
-  float flatten = 0.f;
-  run_march(tsdf_volume_, w_min_, 0, cleanup_of(this, cleanup) ? &cleanup : nullptr, flatten_of(this, flatten) ? &flatten : nullptr, verts, rgb,
-            faces, indexed);
+  float flatten = 0.f, decimate = 0.f;
+  run_march(tsdf_volume_, w_min_, 0, cleanup_of(this, cleanup) ? &cleanup : nullptr, flatten_of(this, flatten) ? &flatten : nullptr,
+            decimate_of(this, decimate) ? &decimate : nullptr, verts, rgb, faces, indexed);
   const size_t n = verts.size() / 3;
   points.points.resize(n);
   points.width = (uint32_t)n;

@@ -13,6 +13,7 @@
 //   frame pose = poses[0]^-1 * poses[i]                                                            :650
 //   --organized: the cloud must already have the image size                                        :585-592
 //   mesh: min weight, colour by RGB when --color, --flatten, --cleanup, PLY ascii/binary           :685-716
+//   --decimate <cell size in metres> (an extension): vertex clustering, applied last
 // Not reproduced: --visualize (PCLVisualizer) and the reference's PCL_INFO chatter.  --cloud-only works but
 // its VoxelGrid thinning needs real PCL.
 #include <cpu_tsdf/marching_cubes_tsdf_octree.h>
@@ -47,7 +48,9 @@ struct Settings {
   bool verbose = false, flatten = false, cleanup = false, invert = false, organized = false, world_frame = false,
        zero_nans = false, save_ascii = false, save_tsdf = false, cloud_only = false, color = false;
   float cloud_units = 1.f, pose_units = 1.f, max_sensor_dist = 3.0f, min_sensor_dist = 0.f, min_weight = 0.f,
-        trunc_pos = 0.03f, trunc_neg = 0.03f, volume_size = 12.f, cell_size = 0.006f, max_cell_size = 0.5f;
+        trunc_pos = 0.03f, trunc_neg = 0.03f, volume_size = 12.f, cell_size = 0.006f, max_cell_size = 0.5f,
+        decimate = 0.f;
+  bool decimate_on = false;
   int width = 640, height = 480, num_random_splits = 1;
   float fx = 525.f, fy = 525.f, cx = 319.5f, cy = 239.5f;
   bool limit_frames = false;
@@ -80,7 +83,8 @@ int parseCommandLine(int argc, char **argv, Settings &s) {
       "min-sensor-dist", bpo::value<float>(), "Minimum distance data can be from the sensor")(
       "trunc-dist-pos", bpo::value<float>(), "Positive truncation distance")(
       "trunc-dist-neg", bpo::value<float>(), "Negative truncation distance")("min-weight", bpo::value<float>(), "Minimum weight to render")(
-      "cloud-only", "Save aggregate cloud rather than actually running TSDF");
+      "cloud-only", "Save aggregate cloud rather than actually running TSDF")(
+      "decimate", bpo::value<float>(), "Decimate the mesh by vertex clustering: cell size in metres (applied last)");
   bpo::variables_map vm;
   bpo::store(bpo::parse_command_line(argc, argv, d, bpo::command_line_style::unix_style ^ bpo::command_line_style::allow_short), vm);
   bool bad = false;
@@ -109,6 +113,8 @@ int parseCommandLine(int argc, char **argv, Settings &s) {
   s.save_tsdf = vm.count("save-tsdf");
   s.cloud_only = vm.count("cloud-only");
   s.color = vm.count("color");
+  s.decimate_on = vm.count("decimate");
+  take(vm, "decimate", s.decimate);
   take(vm, "cloud-units", s.cloud_units);
   take(vm, "pose-units", s.pose_units);
   take(vm, "num-random-splits", s.num_random_splits);
@@ -315,6 +321,13 @@ int main(int argc, char **argv) {
   if (s.cleanup) {  // on the GPU (tsdf_hip_mesh_cleanup); TSDF_HIP_HOST_MESH_POST=1 keeps the host pass
     if (const int rc = cpu_tsdf::mesh_post::cleanupMeshAuto(mesh)) {
       PCL_ERROR("--cleanup: %s: %s\n", tsdf_hip_error_string(rc), tsdf_hip_last_error());
+      return 1;
+    }
+  }
+  if (s.decimate_on) {  // an extension, last: on the GPU (tsdf_hip_mesh_decimate); TSDF_HIP_HOST_MESH_POST=1 keeps the host pass
+    std::string why;
+    if (const int rc = cpu_tsdf::mesh_post::decimateMeshAuto(mesh, s.decimate, &why)) {
+      PCL_ERROR("--decimate: %s: %s\n", tsdf_hip_error_string(rc), why.c_str());
       return 1;
     }
   }

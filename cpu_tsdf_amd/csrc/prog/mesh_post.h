@@ -13,6 +13,11 @@
 //     below face_dist) of at most min_neighbors faces are removed; vertices no face uses are removed; vertex
 //     and face order are kept.  Colours are lost likewise.  cleanupMeshGpu gets the same face set from the GPU
 //     (tsdf_hip_mesh_cleanup); the host pass stays: it defines the result.
+// An extension with no counterpart in the reference:
+//   decimateMesh: vertex clustering (Rossignac-Borrel) on a grid of edge cell_size -- every occupied cell keeps one vertex,
+//     the mean of its members; faces are re-indexed, degenerate and duplicate faces dropped.  decimateArrays below states the
+//     rules; decimateMeshGpu gets the same arrays from the GPU (tsdf_hip_mesh_decimate); the host pass stays: it defines the
+//     result.
 #pragma once
 
 #include <pcl/PolygonMesh.h>
@@ -21,10 +26,14 @@
 
 #include <tsdf_hip.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
+#include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 namespace cpu_tsdf {
@@ -260,6 +269,239 @@ inline int flattenVerticesAuto(pcl::PolygonMesh &mesh, float min_dist = 0.0001f)
     return 0;
   }
   return flattenVerticesGpu(mesh, min_dist);
+}
+
+// ---- decimateMesh: vertex clustering -------------------------------------------------------------------------------------------
+struct Decimated {
+  std::vector<std::uint32_t> remap;   // n: the output vertex of each input vertex
+  std::vector<float> verts;           // m x 3
+  std::vector<std::uint8_t> rgb;      // m x 3, or empty without colours
+  std::vector<std::uint32_t> counts;  // m: members of each output vertex
+  std::vector<std::uint32_t> faces;   // k x 3
+  std::uint64_t duplicates = 0;       // faces dropped by the duplicate rule (the degenerate ones went before)
+};
+
+// The definition, as one sequential pass over the vertices in index order and one over the faces.
+//   1. A finite vertex belongs to the cell floor((double)v / (double)cell_size) per axis (PointGrid::c); the vertices of one
+//      cell are one cluster.  A vertex with a component that is not finite is a cluster of its own.  A cell index outside
+//      [-2^20, 2^20) would alias under PointGrid::key's 21-bit masks: the call is refused and nothing is written.
+//   2. Clusters are numbered by their lowest member: the first vertex of a new cell opens the next output vertex.
+//   3. A cluster of one member keeps that vertex bit for bit.  Otherwise, per component, a double sum that starts at +0.0 takes
+//      the members one add at a time in ascending index, is divided by (double)count and rounded to float once.  The order
+//      is part of the definition: double addition is not associative, and the GPU pass performs exactly these adds.
+//   4. The colour is the rounded integer mean per channel, (2 * sum + count) / (2 * count).
+//   5. Faces go through remap; a face with two equal corners is dropped; of the remaining faces with the same three corners,
+//      in whatever orientation, the one with the lowest index survives, as it is.  Face order is kept.
+// xyz n x 3, rgb n x 3 or NULL, faces nf x 3 or NULL for a soup (face f = vertices 3f, 3f + 1, 3f + 2).  0, or
+// TSDF_HIP_E_INVALID with the reason in *error.
+inline int decimateArrays(const float *xyz, const std::uint8_t *rgb, size_t n, const std::uint32_t *faces, size_t nf, float cell_size,
+                          Decimated &out, std::string *error = nullptr) {
+  const auto refuse = [&](const std::string &why) {
+    if (error) *error = why;
+    return (int)TSDF_HIP_E_INVALID;
+  };
+  if (!(cell_size > 0.f) || !std::isfinite(cell_size)) return refuse("decimateMesh: cell_size must be finite and positive");
+  if (n > ((size_t)1 << 31) || nf > ((size_t)1 << 31)) return refuse("decimateMesh: more than 2^31 vertices or faces");
+  if (!faces && n / 3 < nf) return refuse("decimateMesh: a triangle soup needs 3 vertices per face");
+  if (faces)
+    for (size_t e = 0; e < 3 * nf; ++e)
+      if (faces[e] >= n) return refuse("decimateMesh: a face names a vertex index >= n_verts");
+  const double cell = (double)cell_size;
+  std::vector<std::uint64_t> key(n);
+  for (size_t i = 0; i < n; ++i) {
+    key[i] = ~(std::uint64_t)0;  // not finite: in no cell
+    if (!std::isfinite(xyz[3 * i]) || !std::isfinite(xyz[3 * i + 1]) || !std::isfinite(xyz[3 * i + 2])) continue;
+    std::uint64_t k = 0;
+    for (int a = 0; a < 3; ++a) {
+      const double c = std::floor((double)xyz[3 * i + a] / cell);
+      if (!(c >= -1048576.0 && c < 1048576.0))
+        return refuse("decimateMesh: a vertex lies outside the 2^21 cells per axis the cell key holds: |coordinate| must stay below 2^20 * "
+                      "cell_size = " + std::to_string(1048576.0 * cell));
+      k = (k << 21) | (std::uint64_t)((long)c & 0x1fffff);
+    }
+    key[i] = k;
+  }
+  struct Acc {
+    double s[3];
+    std::uint64_t c[3];
+    std::uint32_t count, first;
+  };
+  std::vector<Acc> acc;
+  std::unordered_map<std::uint64_t, std::uint32_t> cluster_of;
+  out = Decimated();
+  out.remap.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    std::uint32_t o = (std::uint32_t)acc.size();
+    if (key[i] != ~(std::uint64_t)0) {
+      const auto it = cluster_of.emplace(key[i], o);
+      o = it.first->second;
+    }
+    if (o == acc.size()) acc.push_back(Acc{{0.0, 0.0, 0.0}, {0, 0, 0}, 0u, (std::uint32_t)i});
+    Acc &a = acc[o];
+    for (int k = 0; k < 3; ++k) {
+      a.s[k] += (double)xyz[3 * i + k];
+      if (rgb) a.c[k] += rgb[3 * i + k];
+    }
+    ++a.count;
+    out.remap[i] = o;
+  }
+  const size_t m = acc.size();
+  out.verts.resize(3 * m);
+  out.counts.resize(m);
+  if (rgb) out.rgb.resize(3 * m);
+  for (size_t o = 0; o < m; ++o) {
+    const Acc &a = acc[o];
+    out.counts[o] = a.count;
+    if (a.count == 1)
+      std::memcpy(&out.verts[3 * o], xyz + 3 * (size_t)a.first, 3 * sizeof(float));
+    else
+      for (int k = 0; k < 3; ++k) out.verts[3 * o + k] = (float)(a.s[k] / (double)a.count);
+    if (rgb)
+      for (int k = 0; k < 3; ++k) out.rgb[3 * o + k] = (std::uint8_t)((2 * a.c[k] + a.count) / (2 * (std::uint64_t)a.count));
+  }
+  struct Triple {
+    std::uint32_t v[3];
+    bool operator==(const Triple &t) const { return v[0] == t.v[0] && v[1] == t.v[1] && v[2] == t.v[2]; }
+  };
+  struct TripleHash {
+    size_t operator()(const Triple &t) const {
+      std::uint64_t h = 0x9e3779b97f4a7c15ull;
+      for (int k = 0; k < 3; ++k) h = (h ^ t.v[k]) * 0xff51afd7ed558ccdull, h ^= h >> 32;
+      return (size_t)h;
+    }
+  };
+  std::unordered_set<Triple, TripleHash> seen;
+  for (size_t f = 0; f < nf; ++f) {
+    std::uint32_t r[3];
+    for (int k = 0; k < 3; ++k) r[k] = out.remap[faces ? faces[3 * f + k] : 3 * f + k];
+    if (r[0] == r[1] || r[1] == r[2] || r[2] == r[0]) continue;
+    Triple t{{r[0], r[1], r[2]}};
+    if (t.v[0] > t.v[1]) std::swap(t.v[0], t.v[1]);
+    if (t.v[1] > t.v[2]) std::swap(t.v[1], t.v[2]);
+    if (t.v[0] > t.v[1]) std::swap(t.v[0], t.v[1]);
+    if (!seen.insert(t).second) {
+      ++out.duplicates;
+      continue;
+    }
+    out.faces.insert(out.faces.end(), r, r + 3);
+  }
+  return 0;
+}
+
+inline bool hasColourField(const pcl::PolygonMesh &mesh) {
+  for (const auto &f : mesh.cloud.fields)
+    if (f.name == "rgb" || f.name == "rgba") return true;
+  return false;
+}
+
+// positions and, when the cloud has an rgb field, colours (r, g, b) of the mesh's vertices
+inline void vertexArrays(const pcl::PolygonMesh &mesh, std::vector<float> &xyz, std::vector<std::uint8_t> &rgb) {
+  rgb.clear();
+  if (!hasColourField(mesh)) {
+    xyz = vertexPositions(mesh);
+    return;
+  }
+  pcl::PointCloud<pcl::PointXYZRGB> v;
+  pcl::fromPCLPointCloud2(mesh.cloud, v);
+  xyz.resize(3 * v.points.size());
+  rgb.resize(3 * v.points.size());
+  for (size_t i = 0; i < v.points.size(); ++i) {
+    xyz[3 * i] = v.points[i].x, xyz[3 * i + 1] = v.points[i].y, xyz[3 * i + 2] = v.points[i].z;
+    rgb[3 * i] = v.points[i].r, rgb[3 * i + 1] = v.points[i].g, rgb[3 * i + 2] = v.points[i].b;
+  }
+}
+
+// the tail both decimate passes share: the vertex blob (with an rgb field when colours came along) and the polygons
+inline void storeDecimated(const std::vector<float> &xyz, const std::vector<std::uint8_t> &rgb, size_t m, const std::uint32_t *faces, size_t k,
+                           pcl::PolygonMesh &mesh) {
+  if (!rgb.empty()) {
+    pcl::PointCloud<pcl::PointXYZRGB> out;
+    for (size_t o = 0; o < m; ++o) {
+      pcl::PointXYZRGB p;
+      p.x = xyz[3 * o], p.y = xyz[3 * o + 1], p.z = xyz[3 * o + 2];
+      p.r = rgb[3 * o], p.g = rgb[3 * o + 1], p.b = rgb[3 * o + 2];
+      out.push_back(p);
+    }
+    pcl::toPCLPointCloud2(out, mesh.cloud);
+  } else {
+    pcl::PointCloud<pcl::PointXYZ> out;
+    for (size_t o = 0; o < m; ++o) {
+      pcl::PointXYZ p;
+      p.x = xyz[3 * o], p.y = xyz[3 * o + 1], p.z = xyz[3 * o + 2];
+      out.push_back(p);
+    }
+    pcl::toPCLPointCloud2(out, mesh.cloud);
+  }
+  mesh.polygons.resize(k);
+  for (size_t f = 0; f < k; ++f) {
+    mesh.polygons[f].vertices.resize(3);
+    for (int j = 0; j < 3; ++j) mesh.polygons[f].vertices[j] = faces[3 * f + j];
+  }
+}
+
+// false: a polygon is not a triangle (such a mesh is left alone by both decimate passes: the rules speak of triangles)
+inline bool triangleIndices(const pcl::PolygonMesh &mesh, std::vector<std::uint32_t> &faces) {
+  faces.resize(3 * mesh.polygons.size());
+  for (size_t f = 0; f < mesh.polygons.size(); ++f) {
+    if (mesh.polygons[f].vertices.size() != 3) return false;
+    for (int k = 0; k < 3; ++k) faces[3 * f + k] = mesh.polygons[f].vertices[k];
+  }
+  return true;
+}
+
+// The host pass on a PolygonMesh; it keeps an rgb field when the cloud has one.  0, or TSDF_HIP_E_INVALID (the reason in
+// *error) with the mesh untouched.
+inline int decimateMesh(pcl::PolygonMesh &mesh, float cell_size, std::string *error = nullptr) {
+  std::vector<float> xyz;
+  std::vector<std::uint8_t> rgb;
+  std::vector<std::uint32_t> faces;
+  if (!triangleIndices(mesh, faces)) {
+    if (error) *error = "decimateMesh: a polygon is not a triangle";
+    return (int)TSDF_HIP_E_INVALID;
+  }
+  vertexArrays(mesh, xyz, rgb);
+  Decimated d;
+  const int rc = decimateArrays(xyz.data(), rgb.empty() ? nullptr : rgb.data(), xyz.size() / 3, faces.data(), faces.size() / 3, cell_size, d, error);
+  if (rc) return rc;
+  storeDecimated(d.verts, d.rgb, d.counts.size(), d.faces.data(), d.faces.size() / 3, mesh);
+  return 0;
+}
+
+// The same result from the GPU (tsdf_hip_mesh_decimate, which reproduces the pass above bit for bit); the blob is built by
+// the same tail.  0, or the library's error code (its text in tsdf_hip_last_error) with the mesh untouched.
+inline int decimateMeshGpu(pcl::PolygonMesh &mesh, float cell_size, int device = 0) {
+  std::vector<float> xyz;
+  std::vector<std::uint8_t> rgb;
+  std::vector<std::uint32_t> faces;
+  if (!triangleIndices(mesh, faces)) return (int)TSDF_HIP_E_INVALID;
+  vertexArrays(mesh, xyz, rgb);
+  const size_t n = xyz.size() / 3, nf = faces.size() / 3;
+  std::vector<float> out_xyz(3 * n);
+  std::vector<std::uint8_t> out_rgb(rgb.empty() ? 0 : 3 * n);
+  std::uint64_t m = 0, k = 0;
+  // (the re-indexed faces come back in place of the ones handed over: the library has read those before it writes)
+  const int rc = tsdf_hip_mesh_decimate(device, xyz.data(), rgb.empty() ? nullptr : rgb.data(), n, faces.data(), nf, cell_size, nullptr,
+                                        out_xyz.data(), rgb.empty() ? nullptr : out_rgb.data(), nullptr, &m, faces.data(), &k);
+  if (rc) return rc;
+  if (!rgb.empty()) out_rgb.resize(3 * (size_t)m);
+  storeDecimated(out_xyz, out_rgb, (size_t)m, faces.data(), (size_t)k, mesh);
+  return 0;
+}
+
+// Vertices up to which --decimate keeps the host pass: the largest prefix at which tools/time_decimate.py measured the
+// GPU-backed pass (upload, device pass, download, this file's tail) slower than decimateMesh
+// (profiles/decimate_timing.json, "gpu_backed_pass_loses_up_to_vertices": 300000 at 512^3 with a cell of 2 voxels -- 11.4 ms
+// against 9.4 ms; the next prefix, 3000000, wins with 58.9 ms against 124.8 ms).
+constexpr size_t kDecimateHostBelowVertices = 300000;
+
+// --decimate of the programs: the GPU pass from the crossover up, the host pass below it, or always with
+// TSDF_HIP_HOST_MESH_POST=1 (A/B runs, tools/time_decimate.py).  The result does not depend on the choice.
+inline int decimateMeshAuto(pcl::PolygonMesh &mesh, float cell_size, std::string *error = nullptr) {
+  const char *host = std::getenv("TSDF_HIP_HOST_MESH_POST");
+  if ((host && host[0] == '1') || (size_t)mesh.cloud.width * mesh.cloud.height <= kDecimateHostBelowVertices) return decimateMesh(mesh, cell_size, error);
+  const int rc = decimateMeshGpu(mesh, cell_size);
+  if (rc && error) *error = tsdf_hip_last_error();
+  return rc;
 }
 
 }  // namespace mesh_post

@@ -1,6 +1,8 @@
 // `tsdf2mesh` -- the reference's volume-to-mesh program (src/prog/tsdf2mesh.cpp:50-74) on the MI355X path:
 // `tsdf2mesh foo.vol foo.ply` loads a volume written by TSDFVolumeOctree::save (either implementation's),
 // runs marching cubes on the GPU with the class defaults (min weight 2.5, no colour) and writes a binary PLY.
+// An extension: `tsdf2mesh foo.vol foo.ply --decimate <cell size in metres>` decimates the mesh by vertex clustering before
+// it is written (cpu_tsdf::mesh_post::decimateMeshAuto); without the option the output is what it was.
 #include <cpu_tsdf/marching_cubes_tsdf_octree.h>
 #include <cpu_tsdf/tsdf_interface.h>
 #include <cpu_tsdf/tsdf_volume_octree.h>
@@ -8,12 +10,28 @@
 #include <pcl/console/print.h>
 #include <pcl/io/ply_io.h>
 
+#include <cstdlib>
+#include <cstring>
 #include <string>
+
+#include "mesh_post.h"
 
 int main(int argc, char **argv) {
   if (argc < 3) {
-    PCL_INFO("Renders a mesh from a TSDF volume saved with TSDFVolumeOctree::save.\nUsage: %s foo.vol foo.ply\n", argv[0]);
+    PCL_INFO("Renders a mesh from a TSDF volume saved with TSDFVolumeOctree::save.\nUsage: %s foo.vol foo.ply [--decimate <cell size in metres>]\n",
+             argv[0]);
     return 1;
+  }
+  bool decimate_on = false;
+  float decimate = 0.f;
+  for (int i = 3; i < argc; ++i) {
+    if (!strcmp(argv[i], "--decimate") && i + 1 < argc) {
+      decimate_on = true;
+      decimate = (float)atof(argv[++i]);
+    } else {
+      PCL_ERROR("unknown option %s\n", argv[i]);
+      return 1;
+    }
   }
   cpu_tsdf::TSDFVolumeOctree::Ptr tsdf(new cpu_tsdf::TSDFVolumeOctree);
   tsdf->load(argv[1]);
@@ -24,5 +42,12 @@ int main(int argc, char **argv) {
   mc.setColorByRGB(false);
   pcl::PolygonMesh mesh;
   mc.reconstruct(mesh);
+  if (decimate_on) {
+    std::string why;
+    if (const int rc = cpu_tsdf::mesh_post::decimateMeshAuto(mesh, decimate, &why)) {
+      PCL_ERROR("--decimate: %s: %s\n", tsdf_hip_error_string(rc), why.c_str());
+      return 1;
+    }
+  }
   return pcl::io::savePLYFileBinary(argv[2], mesh);
 }

@@ -42,20 +42,10 @@
 #define FL_C_SEEDS 3
 #define FL_C_KEPT 4
 #define FL_C_LIST 5  // three list lengths in rotation: round r reads r % 3, appends to (r + 1) % 3, zeroes (r + 2) % 3
-#define FL_COUNTERS 8
+#define FL_COUNTERS MP_IDX_COUNTERS
 #define FL_MAX_ROUNDS 0x7fffffffu  // the state word holds round << 1
 
-struct tsdf_flatten_state {  // per handle (tsdf_hip_volume::fl): the indexed mesh of tsdf_hip_march_flatten
-  MpWork work;
-  bool valid = false, has_rgb = false;
-  uint64_t n_verts = 0, n_faces = 0;
-  void *out = nullptr;  // one handle: vertices, faces, cell keys, colours (device)
-  size_t out_cap = 0, o_faces = 0, o_cell = 0, o_rgb = 0;
-  std::vector<float> h_verts;  // a multi-GPU set: the same on the host, like its soup
-  std::vector<uint8_t> h_rgb;
-  std::vector<uint32_t> h_faces;
-  std::vector<uint64_t> h_cell;
-};
+// (tsdf_flatten_state, the indexed mesh of a handle, is in tsdf_meshgrid.h: tsdf_decimate.hip writes it too)
 
 static thread_local uint64_t g_fl_stats[4] = {0, 0, 0, 0};  // tsdf_hip_mesh_flatten_stats
 

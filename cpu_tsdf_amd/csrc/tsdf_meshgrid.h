@@ -6,6 +6,8 @@
 //   mp_for_links   the points strictly within the radius of point i, from those 27 cells: the host's forNeighbours
 //   k_mp_compact   stable compaction of per-face records behind a scan of the keep flags
 //   MpWork / mp_reserve / mp_to_device / mp_to_host   the working set, and caller memory (pinned: direct; pageable: staged)
+//   tsdf_flatten_state   the indexed mesh of a handle, which tsdf_hip_march_flatten and tsdf_hip_march_decimate
+//                  (tsdf_decimate.hip: vertex clustering, on the same cell keys, sort and compaction) both write
 // Everything here is static: each translation unit compiles its own copy.
 #pragma once
 
@@ -13,6 +15,7 @@
 
 #include <algorithm>
 #include <string>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/iterator/transform_iterator.hpp>
@@ -201,3 +204,17 @@ static int mp_to_host(MpStage &st, void *dst, const void *src, size_t bytes, hip
   }
   return TSDF_HIP_OK;
 }
+
+#define MP_IDX_COUNTERS 8  // MpWork::counters of the passes that share a handle's tsdf_flatten_state (flatten, decimate)
+
+struct tsdf_flatten_state {  // per handle (tsdf_hip_volume::fl): the indexed mesh of tsdf_hip_march_flatten / _decimate
+  MpWork work;
+  bool valid = false, has_rgb = false;
+  uint64_t n_verts = 0, n_faces = 0;
+  void *out = nullptr;  // one handle: vertices, faces, cell keys, colours (device)
+  size_t out_cap = 0, o_faces = 0, o_cell = 0, o_rgb = 0;
+  std::vector<float> h_verts;  // a multi-GPU set: the same on the host, like its soup
+  std::vector<uint8_t> h_rgb;
+  std::vector<uint32_t> h_faces;
+  std::vector<uint64_t> h_cell;
+};

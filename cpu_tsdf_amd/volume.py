@@ -728,6 +728,7 @@ class MarchingCubesTSDFOctree:
         self._vol = None
         self._cleanup = None
         self._flatten = None
+        self._decimate = None
 
     def setCleanup(self, face_dist=0.02, min_neighbors=5):
         """Extension (no reference counterpart on the class): reconstruct() drops the faces in connected groups of at most
@@ -758,6 +759,21 @@ class MarchingCubesTSDFOctree:
     def clearFlatten(self):
         self._flatten = None
 
+    def setDecimate(self, cell_size):
+        """Extension (no reference counterpart): reconstruct() decimates the mesh by vertex clustering on a grid of edge
+        `cell_size` (metres, VOLUME frame, before the global transform) -- on the GPU, between the march and the fetch
+        (tsdf_hip_march_decimate) -- and returns the INDEXED mesh: one vertex per occupied cell, the mean of the cell's
+        vertices (colours: the rounded mean), faces re-indexed, degenerate and duplicate faces dropped (include/tsdf_hip.h
+        states the rules).  With setCleanup as well, the cleanup runs FIRST, on the soup.  With setFlatten as well,
+        decimate runs and flatten is skipped: clustering already merges what flatten would."""
+        cell_size = float(cell_size)
+        if not (np.isfinite(cell_size) and cell_size > 0):
+            raise ValueError("setDecimate: cell_size must be finite and positive")
+        self._decimate = cell_size
+
+    def clearDecimate(self):
+        self._decimate = None
+
     def setInputTSDF(self, volume):
         self._vol = volume
 
@@ -773,7 +789,7 @@ class MarchingCubesTSDFOctree:
     def reconstruct(self, want_cells=False):
         """marching_cubes_tsdf_octree.cpp:108-143.  Returns dict(vertices (3n,3) float32 after the global
         transform, polygons (n,3) int32 = [3i,3i+1,3i+2], rgb (3n,3) uint8 or None, cells).  With setFlatten: the indexed
-        mesh -- vertices (m,3), polygons (k,3) int32 into them, rgb (m,3) or None, cells (k,)."""
+        mesh -- vertices (m,3), polygons (k,3) int32 into them, rgb (m,3) or None, cells (k,); with setDecimate likewise."""
         vol = self._vol
         vol._cubic_for_queries("MarchingCubesTSDFOctree.reconstruct")
         h = vol._need()
@@ -783,7 +799,7 @@ class MarchingCubesTSDFOctree:
         capi.check(lib.tsdf_hip_march(h, self._w_min, mode, C.byref(n)), "march")
         if self._cleanup is not None:
             capi.check(lib.tsdf_hip_march_cleanup(h, self._cleanup[0], self._cleanup[1], C.byref(n)), "march_cleanup")
-        if self._flatten is not None:
+        if self._decimate is not None or self._flatten is not None:
             return self._fetch_indexed(vol, h, mode, want_cells)
         nt = int(n.value)
         verts = np.empty((nt * 3, 3), dtype=np.float32)
@@ -803,7 +819,10 @@ class MarchingCubesTSDFOctree:
     def _fetch_indexed(self, vol, h, mode, want_cells):
         lib = capi.load()
         m, k = C.c_uint64(0), C.c_uint64(0)
-        capi.check(lib.tsdf_hip_march_flatten(h, self._flatten, C.byref(m), C.byref(k)), "march_flatten")
+        if self._decimate is not None:
+            capi.check(lib.tsdf_hip_march_decimate(h, self._decimate, C.byref(m), C.byref(k)), "march_decimate")
+        else:
+            capi.check(lib.tsdf_hip_march_flatten(h, self._flatten, C.byref(m), C.byref(k)), "march_flatten")
         m, k = int(m.value), int(k.value)
         verts = np.empty((m, 3), dtype=np.float32)
         rgb = np.empty((m, 3), dtype=np.uint8) if mode else None
@@ -862,6 +881,41 @@ def flatten_mesh(vertices, polygons=None, min_dist=0.0001, device=0):
                                           out_faces.ctypes.data_as(u32p), C.byref(k)), "mesh_flatten")
     seeds = seeds[:int(m.value)].copy()
     return {"vertices": verts[seeds], "polygons": out_faces[:int(k.value)].astype(np.int32), "remap": remap, "seeds": seeds}
+
+
+def decimate_mesh(vertices, polygons=None, colors=None, cell_size=None, device=0):
+    """Vertex clustering on the GPU (tsdf_hip_mesh_decimate; include/tsdf_hip.h states the rules): one output vertex per
+    occupied cell of a grid of edge `cell_size` -- the mean of the cell's vertices, and of their colours -- faces re-indexed,
+    degenerate and duplicate faces dropped.  vertices (n, 3) float32; polygons (k0, 3) vertex indices, or None for a triangle
+    soup (face f = vertices 3f, 3f+1, 3f+2); colors (n, 3) uint8 or None.  Returns dict(vertices (m, 3) float32, polygons
+    (k, 3) int32, rgb (m, 3) uint8 or None, remap (n,) uint32: output vertex of each input vertex, counts (m,) uint32:
+    members of each output vertex)."""
+    if cell_size is None:
+        raise ValueError("decimate_mesh: cell_size is required")
+    verts = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    faces = None if polygons is None else np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
+    rgb = None if colors is None else np.ascontiguousarray(colors, dtype=np.uint8).reshape(-1, 3)
+    if faces is None and len(verts) % 3:
+        raise ValueError("decimate_mesh: a triangle soup needs 3 vertices per face")
+    if rgb is not None and len(rgb) != len(verts):
+        raise ValueError("decimate_mesh: one colour per vertex")
+    n_faces = len(verts) // 3 if faces is None else len(faces)
+    u32p = C.POINTER(C.c_uint32)
+    remap = np.zeros(len(verts), dtype=np.uint32)
+    out_verts = np.zeros((len(verts), 3), dtype=np.float32)
+    out_rgb = np.zeros((len(verts), 3), dtype=np.uint8) if rgb is not None else None
+    counts = np.zeros(len(verts), dtype=np.uint32)
+    out_faces = np.zeros((n_faces, 3), dtype=np.uint32)
+    m, k = C.c_uint64(0), C.c_uint64(0)
+    capi.check(
+        capi.load().tsdf_hip_mesh_decimate(int(device), capi.as_f32p(verts), capi.as_u8p(rgb) if rgb is not None else None, len(verts),
+                                           faces.ctypes.data_as(u32p) if faces is not None else None, n_faces, float(cell_size),
+                                           remap.ctypes.data_as(u32p), capi.as_f32p(out_verts),
+                                           capi.as_u8p(out_rgb) if out_rgb is not None else None, counts.ctypes.data_as(u32p), C.byref(m),
+                                           out_faces.ctypes.data_as(u32p), C.byref(k)), "mesh_decimate")
+    m, k = int(m.value), int(k.value)
+    return {"vertices": out_verts[:m].copy(), "polygons": out_faces[:k].astype(np.int32), "rgb": out_rgb[:m].copy() if out_rgb is not None else None,
+            "remap": remap, "counts": counts[:m].copy()}
 
 
 def reference_cull_planes(p, trans):

@@ -19,7 +19,7 @@ class MarchingCubesTSDFOctree : public pcl::MarchingCubes<pcl::PointXYZ> {
  public:
   MarchingCubesTSDFOctree()
       : pcl::MarchingCubes<pcl::PointXYZ>(), color_by_confidence_(false), color_by_rgb_(false), w_min_(2.5f) {}
-  ~MarchingCubesTSDFOctree() override;  // forgets the object's setCleanup / setFlatten (see there)
+  ~MarchingCubesTSDFOctree() override;  // forgets the object's setCleanup / setFlatten / setDecimate (see there)
 
   // Mirrors the reference (:44-83): remembers the volume and dresses the base class the same way -- grid resolution,
   // the 8-corner "input cloud", no grid extension, iso level 0, bounding box and size_voxel_.
@@ -44,13 +44,21 @@ class MarchingCubesTSDFOctree : public pcl::MarchingCubes<pcl::PointXYZ> {
   // The argument lives in the shell library next to setCleanup's: the class keeps its size.
   void setFlatten(float min_dist = 0.0001f);
   void clearFlatten();
+  // Extension likewise: reconstruct decimates the mesh by vertex clustering on a grid of edge cell_size (metres, VOLUME
+  // frame) -- on the GPU, after the march and after setCleanup's pass, which runs FIRST, on the soup
+  // (tsdf_hip_march_decimate; include/tsdf_hip.h states the rules) -- and fills the PolygonMesh with the INDEXED mesh: one
+  // vertex per occupied cell, the mean of the cell's vertices and colours; degenerate and duplicate faces are dropped.
+  // With BOTH setFlatten and setDecimate, decimate runs and flatten is SKIPPED: clustering already merges what flatten
+  // would.  The argument lives in the shell library next to setFlatten's: the class keeps its size.
+  void setDecimate(float cell_size);
+  void clearDecimate();
 
   using pcl::MarchingCubes<pcl::PointXYZ>::reconstruct;  // reconstruct(PolygonMesh&), reconstruct(points, polygons)
 
  protected:
   void voxelizeData() override {}  // as in the reference (:86-90): nothing to voxelize, the TSDF is the grid
   // fills output.cloud (PointXYZ, or PointXYZRGB when a colour mode is on) and output.polygons ({3i, 3i+1, 3i+2}, or the
-  // indexed mesh's with setFlatten); vertices are moved by the volume's global transform (:108-143)
+  // indexed mesh's with setFlatten / setDecimate); vertices are moved by the volume's global transform (:108-143)
   void performReconstruction(pcl::PolygonMesh &output) override;
   void performReconstruction(pcl::PointCloud<pcl::PointXYZ> &points, std::vector<pcl::Vertices> &polygons) override;
 

@@ -534,6 +534,53 @@ int tsdf_hip_march_fetch_indexed(tsdf_handle h, float *verts, uint8_t *rgb, uint
  * inside, the transfers of the host-array entry point do not). */
 int tsdf_hip_mesh_flatten_stats(uint64_t out[4]);
 
+/* decimateMesh -- vertex clustering (Rossignac-Borrel); an extension with no counterpart in the reference.  A grid of edge
+ * cell_size is laid over the mesh, every occupied cell keeps ONE vertex, and the faces are re-indexed.  The result is
+ * defined by the sequential host pass cpu_tsdf::mesh_post::decimateArrays (csrc/prog/mesh_post.h) and equals it bit for bit:
+ *   1. a finite vertex belongs to the cell floor((double)v / (double)cell_size) per axis; the vertices of one cell are one
+ *      cluster.  A vertex with a component that is not finite is a cluster of its own.  A finite vertex in a cell outside
+ *      [-2^20, 2^20) on any axis (the 21-bit cell key would alias) refuses the call: E_INVALID, the text names the extent,
+ *      nothing is written.
+ *   2. clusters are ordered by their lowest-indexed member; remap[i] is the output index of the cluster of vertex i.
+ *   3. the output vertex of a cluster of one is that vertex, bit for bit (NaN payloads survive).  Otherwise, per component, a
+ *      double sum starting at +0.0 takes the members one add at a time in ascending input index, is divided by
+ *      (double)count and rounded to float once.
+ *   4. the colour is (2 * sum + count) / (2 * count) per channel, in integers.
+ *   5. faces are re-indexed through remap; a face with two equal corners is dropped; of the remaining faces whose sorted
+ *      corner triples are equal, whatever their orientation, only the one with the lowest index survives, as it is.  Face
+ *      order is kept.
+ *   verts, rgb, faces   HOST arrays (pinned memory is used directly, pageable memory is staged): n_verts x 3 floats,
+ *                  n_verts x 3 bytes or NULL, n_faces x 3 vertex indices; faces == NULL = triangle soup, face f using vertices
+ *                  3f, 3f + 1, 3f + 2.
+ *   remap          n_verts entries; nullable.
+ *   out_verts, out_rgb, counts   room for n_verts entries (x 3 floats, x 3 bytes, x 1), the first *n_out_verts are filled:
+ *                  position, colour and number of members of each output vertex; each nullable.
+ *   out_faces      room for n_faces x 3 entries, the first *n_out_faces x 3 are filled; nullable; may be `faces` itself.
+ * E_INVALID: cell_size not finite or <= 0, device < 0, more than 2^31 vertices or faces (indices are 32-bit), NULL where data
+ * is needed (verts; rgb with out_rgb; n_out_verts with out_verts / out_rgb / counts; n_out_faces with out_faces), a soup with
+ * fewer than 3 * n_faces vertices, a face naming a vertex >= n_verts, the extent of rule 1.  All of these but the last two are
+ * checked before any device call.  n_verts == 0 (with no face) is OK and touches no device.  E_NOMEM, with the bytes in
+ * tsdf_hip_last_error, when the working set does not fit.
+ * Cost: two radix sorts of the faces, one of the vertices, and the reduction of rule 3, in which ONE lane walks each cluster
+ * so that the adds keep the host's order: tens to a few hundred members on a marched mesh, but a cell_size that puts all
+ * vertices into one cell makes one lane walk the whole mesh in one kernel launch, as slow as the host pass. */
+int tsdf_hip_mesh_decimate(int device, const float *verts, const uint8_t *rgb /* nullable */, uint64_t n_verts,
+                           const uint32_t *faces /* NULL = soup */, uint64_t n_faces, float cell_size, uint32_t *remap,
+                           float *out_verts, uint8_t *out_rgb, uint32_t *counts, uint64_t *n_out_verts, uint32_t *out_faces,
+                           uint64_t *n_out_faces);
+/* The same on the DEVICE-RESIDENT soup of the last tsdf_hip_march (after an optional tsdf_hip_march_cleanup).  It writes the
+ * indexed-mesh buffers tsdf_hip_march_flatten uses: tsdf_hip_march_fetch_indexed then returns the decimated mesh, rgb being
+ * rule 4's mean and cell[f] the cell key of surviving face f.  The soup STAYS.  A later tsdf_hip_march, _march_cleanup,
+ * _march_flatten or _march_decimate replaces or invalidates the indexed mesh, as documented for flatten.  E_INVALID before
+ * the first tsdf_hip_march on the handle, and after one that failed.  On a multi-GPU handle the merged mesh (host) goes
+ * through the host-array route on the first slab's device; the result equals one handle holding the whole grid. */
+int tsdf_hip_march_decimate(tsdf_handle h, float cell_size, uint64_t *n_verts, uint64_t *n_faces);
+/* Report-only, of the last decimate (either entry point) on the calling thread: out[0] = vertices in, out[1] = vertices out,
+ * out[2] = faces dropped as duplicates (the degenerate drops are faces in - faces out - out[2]), out[3] = device
+ * microseconds from the first kernel to the last (HIP events on the stream; the host's read of the cluster count falls
+ * inside, the transfers of the host-array entry point do not). */
+int tsdf_hip_mesh_decimate_stats(uint64_t out[4]);
+
 /* getOccupiedVoxelIndices -- src/lib/tsdf_volume_octree.cpp:590-609 (+ OctreeNode::getLeaves, src/lib/octree.cpp:99-109):
  * the voxels with w > 0 && fabsf(d) < 1, d and w being the floats tsdf_hip_download returns (PACKED layout:
  * w = min(k, max_weight); a NaN distance is not listed), in the reference's leaf order: ascending key
