@@ -29,13 +29,49 @@
 #include "tsdf_hip_test.h"
 #endif
 
-// (compile-time switch used by add_observation_fast below: its default has to come first)
-#ifndef TSDF_COLOR_PK
-#define TSDF_COLOR_PK 2  // 2: colour bytes through v_cvt_pk_u8_f32 (one convert-and-pack per channel, rounds to nearest even:
-                         // tests/test_div_gpu.py pins that).  Round 2 measured it 2 % SLOWER in a kernel that waited for memory;
-                         // in round 5's issue-bound kernels it is the faster form (k_integrate2 11.76 -> 11.53 ms per frame, the
-                         // configs[4] slab 13.37 -> 13.10, k_integrate 13.6 either way: profiles/r05_ab_diet_call2.txt).  0 = three
-                         // truncating conversions + shifts and ors; 1 assumed truncation of the packed form and is WRONG.
+// Compile-time PARAMETERS: each carries a number into an attribute or a builtin and selects no alternative code (A/B builds:
+// tools/build_variant.py).  The alternatives that were built, measured and rejected in earlier rounds are recorded in
+// profiles/README.md ("Removed compile-time switches").
+#ifndef TSDF_WPE_MAX
+#define TSDF_WPE_MAX 8  // cap on resident waves per SIMD
+#endif
+#ifndef TSDF_WPE_PACKED
+#define TSDF_WPE_PACKED 7  // waves per SIMD the non-counting ALLIN instances of k_integrate ask for: 72 VGPRs, reachable since the x
+                           // products are redone per row (see the row loop)
+#endif
+#ifndef TSDF_WPE_PACKED_COLOR
+#define TSDF_WPE_PACKED_COLOR 8  // ... and the timed colour instance (ALLIN, PACKED, colour, certified projection): 64 VGPRs.  Round 4
+                                 // measured 8 waves at 21.4 ms (spills on the row path); after round 5's diet the row body fits
+                                 // (no spill reload on the row path, tools/isa_guard.py) and the eighth wave buys 1.5-2 %: 13.31 / 13.48
+                                 // against 13.63 / 13.65 ms, the configs[4] slab 13.11 against 13.25 (profiles/r05_ab_eight_waves_call19.txt).
+                                 // The colourless instance stays at TSDF_WPE_PACKED: it fits 8 waves as it is (49 VGPRs), and asking
+                                 // for them shrinks its scalar budget (9.51 against 9.07 ms)
+#endif
+#ifndef TSDF_WPE_GENERAL
+#define TSDF_WPE_GENERAL 7  // ... and every other instance (general, row intervals, counting): 72 VGPRs + two dozen SGPRs spilled into
+                            // VGPR lanes + 30-60 B of scratch, 17.7 against 18.7 ms at 2048^3 + colour (round 4).  Round 3 kept these at 6
+                            // because ONE run of a 7-wave build "gave wrong voxels".  Round 4 rebuilt that configuration (and 8 waves, and
+                            // SGPR spills to scratch instead of lanes), audited its ISA (spill register only ever touched by lane
+                            // accesses; no VALU-writes-SGPR -> VMEM hazard) and ran the bisect script and the integrate / fused test
+                            // modules on it on three GPU boxes: no voxel differs (profiles/r04_wave7_bisect.txt).  Not reproducible;
+                            // tests/test_integrate_gpu.py::test_every_reachable_k_integrate_instance_equals_the_oracle now gates every
+                            // instance of the shipped build
+#endif
+#ifndef TSDF_WPE_PIPE
+#define TSDF_WPE_PIPE 8  // k_integrate_p: 63 VGPRs, no scratch.  (LLVM grants 8 waves 80 SGPRs, 7 waves 96+: at 8 the loop's rare blocks
+                         // carry scalar spills in VGPR lanes, at 7 -- 65 VGPRs, seven waves -- hardly any; measured by alternation,
+                         // 2048^3 without colour: 7.61 ms at 8 against 7.81 at 7, 8.98 for k_integrate's own row loop:
+                         // profiles/r06_ab_pipe_c0_call02.txt)
+#endif
+#ifndef TSDF_WPE_PIPEC
+#define TSDF_WPE_PIPEC 5  // k_integrate_pc: 91 VGPRs, no scratch (six waves: 80 VGPRs + ten spill operations in the row loop, whose
+                          // waits undo the pipeline)
+#endif
+#ifndef TSDF_WPE_K2
+#define TSDF_WPE_K2 5  // k_integrate2: issue + retire of a row back to back
+#endif
+#ifndef TSDF_GATHER_AUX
+#define TSDF_GATHER_AUX 0  // cache policy of the ALLIN instance's frame gather (A/B: the default keeps the frame in L2)
 #endif
 
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -284,10 +320,10 @@ static __device__ __forceinline__ void add_observation_ieee(float &d, float &w, 
 //    the 1/D that separates a non-integer N/D from the next integer.  floor(N/D) is computed as
 //    trunc(fma(N, y, y/2)) = trunc((N + 1/2) * y): the true value lies >= 1/(2D) >= 4.8e-4 from the integers
 //    on either side, the two roundings and y's error move it by < 256 * 2^-23 = 3.1e-5.
-//    With TSDF_COLOR_PK the conversion and the packing are one v_cvt_pk_u8_f32 per channel (it writes one byte of a
-//    word and keeps the others: `base` carries byte 3, the PACKED layout's count).  That instruction rounds to nearest
-//    even (tsdf_hip_selftest_cvt_pk_u8 / tests/test_div_gpu.py), so the value converted is (N + 1/2) * y - 1/2, which
-//    lies within 1/2 - 1/(2D) of floor(N/D).
+//    The conversion and the packing are one v_cvt_pk_u8_f32 per channel (it writes one byte of a word and keeps the
+//    others: `base` carries byte 3, the PACKED layout's count; in the issue-bound kernels this is the faster form).  That
+//    instruction rounds to nearest even (tsdf_hip_selftest_cvt_pk_u8 / tests/test_div_gpu.py), so the value converted is
+//    (N + 1/2) * y - 1/2, which lies within 1/2 - 1/(2D) of floor(N/D).
 template <bool COLOR, bool DIST = true>
 static __device__ __forceinline__ void add_observation_fast(float &d, float &w, uint32_t &rgb, float dn,
                                                             uint32_t bgra, float wmax, const Rcp32 &rs, uint32_t base = 0u,
@@ -295,49 +331,17 @@ static __device__ __forceinline__ void add_observation_fast(float &d, float &w, 
   // [phase: colour update (octree.cpp:328-337)]
   const float wsum = w + 1.f;  // rs = rcp32_prepare(wsum) (nb and y are all that is used)
   if (COLOR) {
-#if TSDF_COLOR_PK
     // hy_tab: the offset comes with the count's table entry (KEntry) instead of being derived from y per voxel
-    const float hy = hy_tab ? *hy_tab : TSDF_COLOR_PK == 2 ? __builtin_fmaf(0.5f, rs.y, -0.5f) : 0.5f * rs.y;
+    const float hy = hy_tab ? *hy_tab : __builtin_fmaf(0.5f, rs.y, -0.5f);
     const float t0 = __builtin_fmaf(__builtin_fmaf(w, (float)(rgb & 255u), (float)((bgra >> 16) & 255u)), rs.y, hy);
     const float t1 = __builtin_fmaf(__builtin_fmaf(w, (float)((rgb >> 8) & 255u), (float)((bgra >> 8) & 255u)), rs.y, hy);
     const float t2 = __builtin_fmaf(__builtin_fmaf(w, (float)((rgb >> 16) & 255u), (float)(bgra & 255u)), rs.y, hy);
     rgb = __builtin_amdgcn_cvt_pk_u8_f32(t0, 0u, __builtin_amdgcn_cvt_pk_u8_f32(t1, 1u, __builtin_amdgcn_cvt_pk_u8_f32(t2, 2u, base)));
-#else
-    const float hy = hy_tab ? *hy_tab : 0.5f * rs.y;
-    const uint32_t q0 = (uint32_t)__builtin_fmaf(__builtin_fmaf(w, (float)(rgb & 255u), (float)((bgra >> 16) & 255u)), rs.y, hy);
-    const uint32_t q1 = (uint32_t)__builtin_fmaf(__builtin_fmaf(w, (float)((rgb >> 8) & 255u), (float)((bgra >> 8) & 255u)), rs.y, hy);
-    const uint32_t q2 = (uint32_t)__builtin_fmaf(__builtin_fmaf(w, (float)((rgb >> 16) & 255u), (float)(bgra & 255u)), rs.y, hy);
-    rgb = q0 | (q1 << 8) | (q2 << 16) | base;
-#endif
   }
   // [phase: d update (octree.cpp:152-163)]
   if (DIST) d = div32_fast(d * w + dn, rs);
   w = wsum;
   if (w > wmax) w = wmax;
-}
-
-// The colour half of add_observation_fast for a PAIR of voxels on float pairs -- (0, 1), then (2, 3), one channel at a time:
-// the same two fmas per channel and voxel (N = fma(w, c_old, c_new), t = fma(N, y, hy): v_pk_fma_f32 rounds each half like
-// v_fma_f32, as in project_quad_allin), in half the instructions -- 12 packed fmas instead of 24 (round 6).  y / hy: Rcp32(k + 1).y
-// and the rounding offset of each voxel's divisor (s_rcp); base: the word v_cvt_pk_u8_f32 packs into (byte 3 = the new count).
-// MEASURED and left OFF (profiles/r06_ab_color_f2_call14.txt, five alternations at 2048^3 + colour): the pairs do not fit the 64
-// registers of the eight-wave instance (spills on the row path: 18.7 ms); at seven waves (72 VGPRs, -12 vector instructions per
-// wave-row, no scalar spills) 13.09 against 13.20 ms without it and 13.03 for the shipped eight-wave instance, 12.88 against 12.37 on a
-// configs[4] slab -- a twelfth fewer vector instructions buy nothing: with colour this kernel is gated by its 58.6 GB per launch.
-#ifndef TSDF_COLOR_F2
-#define TSDF_COLOR_F2 0
-#endif
-static __device__ __forceinline__ void colour_pair_pk(const f2 w, const uint32_t c0a, const uint32_t c0b, const uint32_t csa, const uint32_t csb,
-                                                      const f2 y, const f2 hy, const uint32_t base_a, const uint32_t base_b, uint32_t &cva, uint32_t &cvb) {
-  f2 t[3];
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const f2 o = {(float)((c0a >> (8 * ch)) & 255u), (float)((c0b >> (8 * ch)) & 255u)};
-    const f2 n = {(float)((csa >> (16 - 8 * ch)) & 255u), (float)((csb >> (16 - 8 * ch)) & 255u)};  // PCL b,g,r,a -> r,g,b
-    t[ch] = __builtin_elementwise_fma(__builtin_elementwise_fma(w, o, n), y, hy);
-  }
-  cva = __builtin_amdgcn_cvt_pk_u8_f32(t[0].x, 0u, __builtin_amdgcn_cvt_pk_u8_f32(t[1].x, 1u, __builtin_amdgcn_cvt_pk_u8_f32(t[2].x, 2u, base_a)));
-  cvb = __builtin_amdgcn_cvt_pk_u8_f32(t[0].y, 0u, __builtin_amdgcn_cvt_pk_u8_f32(t[1].y, 1u, __builtin_amdgcn_cvt_pk_u8_f32(t[2].y, 2u, base_b)));
 }
 
 static __device__ __forceinline__ bool update_is_safe(float d, float w, float dn) {
@@ -409,203 +413,39 @@ static __device__ __forceinline__ uint64_t tsdf_quiet_passes(const IntegrateArgs
   return __builtin_amdgcn_ballot_w64(q);
 }
 
-#ifndef TSDF_GUARD_ON_RESULT
-#define TSDF_GUARD_ON_RESULT 1  // PACKED update: guard the divider on its result (v_cmp_class) instead of on its numerator
-#endif
-#ifndef TSDF_EARLY_VOXEL_LOADS
-#define TSDF_EARLY_VOXEL_LOADS 2  // 1: a quad's voxel words are requested together with the frame gather (one memory round trip per
-                                  // row instead of two, a fifth more traffic: measured in round 4, left off); 2 (round 5, ON): only
-                                  // by the quads PREDICTED to be observed (their own outcome one row earlier) -- 13.8 -> 13.45 ms at
-                                  // 2048^3 + colour, 9.96 -> 9.27 without, the configs[4] slab 12.87 -> 12.60, for 0.8 % more traffic
-                                  // (58.19 -> 58.63 GB; plain early loads: 71.1 GB for 13.6 ms); profiles/r05_ab_diet_call3.txt
-#endif
-
-// Round 5 instruction diet of the PACKED instances (profiles/r05_isa_phase_mix.txt has the per-phase counts):
-#ifndef TSDF_KTAB
-#define TSDF_KTAB 0  // 1: everything addObservation derives from the count k alone -- the decoded weight, the refined reciprocal of
-                     // k + 1, the colour rounding offset, the count after the observation -- comes from ONE 16-byte LDS entry per
-                     // voxel (ds_read_b128) instead of an 8-byte entry + five VALU operations per voxel.  Measured in k_integrate
-                     // (profiles/r05_ab_diet_call1.txt): 14.15 against 13.87 ms without it -- sixteen registers of table values
-                     // in flight cost more than the operations they save (and with the v_cvt_pk_u8 colour path on top they spill:
-                     // 16.3 ms).  OFF there; k_integrate2, which runs at 5 waves and has the registers, keeps its table.
-#endif
-#ifndef TSDF_LEAN_K
-#define TSDF_LEAN_K 1  // (without TSDF_KTAB) the count's decode without its v_min, the next count without its mask: see the decode step
-#endif
-#ifndef TSDF_SWAR_K
-#define TSDF_SWAR_K 1  // PACKED without colour: the quad's four count bytes are updated in one word (see k4n in k_integrate)
-#endif
-#ifndef TSDF_LEAN_BAND
-#define TSDF_LEAN_BAND 1  // the in-band test of a quad behind one compare of the least raw distance (see there)
-#endif
-#ifndef TSDF_AMB_UNROLL
-#define TSDF_AMB_UNROLL 1  // the exact fp64 re-projection of uncertified voxels: four straight copies, one per voxel of the quad,
-                           // each under its own exec mask (an empty one is a skipped branch), instead of ONE copy in a loop that
-                           // selects its operands by voxel index through ~90 exec-mask instructions per trip
-#endif
-#ifndef TSDF_PROJ_F2
-#define TSDF_PROJ_F2 1  // ALLIN: transform + projection written on explicit float pairs (v_pk_mul / v_pk_add / v_pk_fma_f32 with
-                        // the pairs (0,1), (2,3) throughout: no register shuffles), the x centres re-read from LDS per row
-#endif
+// Everything addObservation derives from the count k alone.  k_integrate2, which runs at 5 waves and has the registers, reads
+// whole entries from LDS (one ds_read_b128 per voxel); the other kernels keep only {y, hy} there (s_rcp) and work out the rest
+// per voxel: sixteen registers of table values in flight cost them more than the operations they save.
 struct __attribute__((aligned(16))) KEntry {
   float w;      // tsdf_decode_w(k) = min(k, max_weight)
   float y;      // Rcp32(k + 1).y: the refined reciprocal of the divisor k + 1
-  float hy;     // the colour average's rounding offset: y / 2 before a truncating conversion, y / 2 - 1 / 2 before v_cvt_pk_u8_f32
+  float hy;     // the colour average's rounding offset: y / 2 - 1 / 2, for v_cvt_pk_u8_f32's round-to-nearest (add_observation_fast)
   uint32_t k1;  // min(k + 1, kmax) << 24: the count after this observation, in byte 3 of a word
 };
 static __device__ __forceinline__ KEntry tsdf_ktab_entry(const IntegrateArgs &a, unsigned k) {
   KEntry e;
   e.w = __builtin_fminf((float)k, a.wmax);
   e.y = rcp32_prepare((float)(k + 1u)).y;
-  e.hy = TSDF_COLOR_PK == 2 ? __builtin_fmaf(0.5f, e.y, -0.5f) : 0.5f * e.y;
+  e.hy = __builtin_fmaf(0.5f, e.y, -0.5f);
   e.k1 = min(k << 24, a.kcap) + a.kinc;  // saturate BEFORE adding (kmax == 255 would wrap byte 3); both 0 when kmax == 0
   return e;
 }
-#ifndef TSDF_SKIP_FIXED_HINGE
-#define TSDF_SKIP_FIXED_HINGE 1  // PACKED: waves whose observed voxels all stay at the hinge value skip the d ladder
-#endif
-// Timing-only experiment switches (WRONG results; tools/ab_bound.sh builds them to find what binds the kernel):
-//   TSDF_EXP_NO_STORE   no voxel plane is written back          TSDF_EXP_NO_GATHER  the frame is not read (constant far depth)
-//   TSDF_EXP_NO_VLOAD   no voxel plane is read (hinge / zero)   TSDF_WPE_MAX        cap on resident waves per SIMD
-#ifndef TSDF_EXP_NO_STORE
-#define TSDF_EXP_NO_STORE 0
-#endif
-#ifndef TSDF_EXP_NO_GATHER
-#define TSDF_EXP_NO_GATHER 0
-#endif
-#ifndef TSDF_EXP_NO_VLOAD
-#define TSDF_EXP_NO_VLOAD 0
-#endif
-#if TSDF_EXP_NO_VLOAD && TSDF_EARLY_VOXEL_LOADS
-#error "TSDF_EXP_NO_VLOAD declares the voxel words itself: build it with -DTSDF_EARLY_VOXEL_LOADS=0 (tools/ab_bound.sh does)"
-#endif
-#if !TSDF_GUARD_ON_RESULT && TSDF_EARLY_VOXEL_LOADS
-#error "TSDF_GUARD_ON_RESULT=0 tests the numerator d0 * w0 + dn BEFORE unread distance words are rebuilt from the counts, and with TSDF_EARLY_VOXEL_LOADS those words have no initial value: build that A/B with -DTSDF_EARLY_VOXEL_LOADS=0"
-#endif
-#ifndef TSDF_GATHER_AUX
-#define TSDF_GATHER_AUX 0  // cache policy of the ALLIN instance's frame gather (A/B: the default keeps the frame in L2)
-#endif
-#ifndef TSDF_WPE_MAX
-#define TSDF_WPE_MAX 8
-#endif
-#ifndef TSDF_NO_BAND
-#define TSDF_NO_BAND 0  // A/B: compile the "band seen" flag store out of k_integrate
-#endif
-#ifndef TSDF_BAND_PER_WAVE
-#define TSDF_BAND_PER_WAVE 1  // the block's "band seen" flags are collected per WAVE (four private LDS sets) and each wave writes its own
-                              // out when it is done: no barrier at the block's end.  The row loop timing itself (profiles/r06_phase_c0.txt)
-                              // showed a wave spending 12-17 % of its life in that barrier, waiting for the block's slowest wave with a
-                              // wave slot in hand -- an eighth of the occupancy the register budget buys.  Every writer stores the same
-                              // 1, so sets that overlap (narrow grids: a cell's four rows belong to two waves) need no merging.
-#endif
-// TSDF_BAND_DECL declares the flag set(s) and clears them (`tid` in scope); TSDF_BAND(i) is flag cell i of the set this thread's wave
-// writes (the set's address is worked out at each -- rare -- use: nothing lives in a register across the row loop for it)
-#if TSDF_BAND_PER_WAVE
+// The block's "band seen" flags are collected per WAVE (four private LDS sets) and each wave writes its own out when it is
+// done: no barrier at the block's end (a wave spent 12-17 % of its life in that barrier, waiting for the block's slowest wave
+// with a wave slot in hand).  Every writer stores the same 1, so sets that overlap (narrow grids: a cell's four rows belong
+// to two waves) need no merging, and a wave reads back only what it wrote itself.
+// TSDF_BAND_DECL declares the flag sets and clears them (`tid` in scope); TSDF_BAND(i) is flag cell i of the set this thread's wave
+// writes (the set's address is worked out at each -- rare -- use: nothing lives in a register across the row loop for it);
+// a wave's lanes walk their set from TSDF_BAND_FIRST in steps of TSDF_BAND_STEP.
 #define TSDF_BAND_DECL                                                                                     \
   __shared__ __attribute__((aligned(16))) uint8_t s_band_sets[4][1024];                                    \
   reinterpret_cast<u4 *>(&s_band_sets[0][0])[tid] = (u4){0u, 0u, 0u, 0u} /* 256 threads x 16 B: all four sets; the prologue's barrier follows */
 #define TSDF_BAND(i) s_band_sets[threadIdx.x >> 6][i]
-#define TSDF_BAND_SYNC() ((void)0)
 #define TSDF_BAND_FIRST ((int)(tid & 63u))
 #define TSDF_BAND_STEP 64
-#else
-#define TSDF_BAND_DECL                                                          \
-  __shared__ __attribute__((aligned(16))) uint8_t s_band[1024 + 64];            \
-  reinterpret_cast<uint32_t *>(s_band)[tid] = 0u, s_band[1024 + (tid & 63u)] = 0
-#define TSDF_BAND(i) s_band[i]
-#define TSDF_BAND_SYNC() __syncthreads()
-#define TSDF_BAND_FIRST ((int)tid)
-#define TSDF_BAND_STEP 256
-#endif
-#ifndef TSDF_RECOMPUTE_PX
-#define TSDF_RECOMPUTE_PX 1  // 72 instead of 80 VGPRs: 7 waves per SIMD (A/B on the GPU: 17.3-17.5 against 17.8-17.9 ms)
-#endif
-#ifndef TSDF_WPE_PACKED
-#define TSDF_WPE_PACKED 7  // waves per SIMD the non-counting ALLIN instances ask for: 72 VGPRs, reachable since the x products are redone per
-                           // row (TSDF_RECOMPUTE_PX)
-#endif
-#ifndef TSDF_WPE_PACKED_COLOR
-#define TSDF_WPE_PACKED_COLOR 8  // ... and the timed colour instance (ALLIN, PACKED, colour, certified projection): 64 VGPRs.  Round 4
-                                 // measured 8 waves at 21.4 ms (spills on the row path); after round 5's diet the row body fits
-                                 // (no spill reload on the row path, tools/isa_guard.py) and the eighth wave buys 1.5-2 %: 13.31 / 13.48
-                                 // against 13.63 / 13.65 ms, the configs[4] slab 13.11 against 13.25 (profiles/r05_ab_eight_waves_call19.txt).
-                                 // The colourless instance stays at TSDF_WPE_PACKED: it fits 8 waves as it is (49 VGPRs), and asking
-                                 // for them shrinks its scalar budget (9.51 against 9.07 ms)
-#endif
 // waves per SIMD an instance asks for
 #define TSDF_WPE_OF(ORDER, COLOR, FASTPROJ, COUNT, PACKED, ALLIN) \
   ((ALLIN) && !(COUNT) && (PACKED) && (COLOR) && (FASTPROJ) ? TSDF_WPE_PACKED_COLOR : (ALLIN) && !(COUNT) && ((PACKED) || !(COLOR)) ? TSDF_WPE_PACKED : TSDF_WPE_GENERAL)
-#ifndef TSDF_WPE_GENERAL
-#define TSDF_WPE_GENERAL 7  // ... and every other instance (general, row intervals, counting): 72 VGPRs + two dozen SGPRs spilled into
-                            // VGPR lanes + 30-60 B of scratch, 17.7 against 18.7 ms at 2048^3 + colour (round 4).  Round 3 kept these at 6
-                            // because ONE run of a 7-wave build "gave wrong voxels".  Round 4 rebuilt that configuration (and 8 waves, and
-                            // SGPR spills to scratch instead of lanes), audited its ISA (spill register only ever touched by lane
-                            // accesses; no VALU-writes-SGPR -> VMEM hazard) and ran the bisect script and the integrate / fused test
-                            // modules on it on three GPU boxes: no voxel differs (profiles/r04_wave7_bisect.txt).  Not reproducible;
-                            // tests/test_integrate_gpu.py::test_every_reachable_k_integrate_instance_equals_the_oracle now gates every
-                            // instance of the shipped build
-#endif
-// TSDF_PHASE_TIMER (diagnostic build only, never shipped: tools/build_variant.py phase -DTSDF_PHASE_TIMER=1): a thread trace in
-// software.  This image has no decoder library for rocprofv3 --att (profiles/r06_att_attempt.txt), so the row loop times
-// ITSELF: every wave reads the shader clock (s_memtime) at the phase boundaries of a row and adds the differences to a dozen
-// lane-private accumulators (VGPRs: opaque to the compiler, so they do not raise the scalar register pressure), one atomic add
-// per accumulator and wave at the end into 1024 striped slots of g_phase; the host sums them after each launch and appends a
-// line to $TSDF_HIP_PHASE_FILE.  A mark names the values its phase produced as asm inputs, so the compiler's s_waitcnt for
-// them falls in front of it: the interval that ends there INCLUDES the wait.  Reading the clock costs a scalar-memory round
-// trip per mark (the kernel runs ~1.6x slower): the SHARES of the phases are what this build is for, not its time.
-#ifndef TSDF_PHASE_TIMER
-#define TSDF_PHASE_TIMER 0
-#endif
-#if TSDF_PHASE_TIMER
-#define TSDF_NPHASE 16
-__device__ unsigned long long g_phase[1024 * TSDF_NPHASE];
-static __device__ __forceinline__ uint32_t tsdf_clock_lo() {
-  uint64_t t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return (uint32_t)t;
-}
-#define TSDF_NACC 9  // lane-private accumulators that live across the row loop: phases 0-7 + the count of observed rows (8)
-#define PT_DECL                                                   \
-  uint32_t pt_acc[TSDF_NACC];                                     \
-  _Pragma("unroll") for (int i_ = 0; i_ < TSDF_NACC; ++i_) asm volatile("v_mov_b32 %0, 0" : "=v"(pt_acc[i_])); \
-  const unsigned pt_blk = (blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * gridDim.x * gridDim.y) & 1023u; \
-  uint32_t pt_prev = tsdf_clock_lo();                             \
-  const uint32_t pt_t0 = pt_prev
-#define PT_MARK(k)                           \
-  do {                                       \
-    const uint32_t pt_now = tsdf_clock_lo(); \
-    pt_acc[k] += pt_now - pt_prev;           \
-    pt_prev = pt_now;                        \
-  } while (0)
-/* outside the row loop: straight to the global slot, nothing kept in a register */                    \
-
-#define PT_MARK_OUT(k)                                                                                 \
-  do {                                                                                                 \
-    const uint32_t pt_now = tsdf_clock_lo();                                                           \
-    if ((threadIdx.x & 63u) == 0u) atomicAdd(&g_phase[pt_blk * TSDF_NPHASE + (k)], (unsigned long long)(pt_now - pt_prev)); \
-    pt_prev = pt_now;                                                                                  \
-  } while (0)
-#define PT_COUNT(k) pt_acc[k] += 1u
-#define PT_DEP4(a_, b_, c_, d_) asm volatile("" ::"v"(a_), "v"(b_), "v"(c_), "v"(d_) : "memory")
-#define PT_DEP1(a_) asm volatile("" ::"v"(a_) : "memory")
-#define PT_FLUSH()                                                                                       \
-  do {                                                                                                   \
-    const uint32_t pt_now = tsdf_clock_lo();                                                             \
-    if ((threadIdx.x & 63u) == 0u) {                                                                     \
-      atomicAdd(&g_phase[pt_blk * TSDF_NPHASE + 15], (unsigned long long)(pt_now - pt_t0));              \
-      _Pragma("unroll") for (int i_ = 0; i_ < TSDF_NACC; ++i_)                                           \
-          atomicAdd(&g_phase[pt_blk * TSDF_NPHASE + i_], (unsigned long long)pt_acc[i_]);                \
-    }                                                                                                    \
-  } while (0)
-#else
-#define PT_DECL
-#define PT_MARK(k)
-#define PT_MARK_OUT(k)
-#define PT_COUNT(k)
-#define PT_DEP4(a_, b_, c_, d_)
-#define PT_DEP1(a_)
-#define PT_FLUSH()
-#endif
 // ALLIN (only with FASTPROJ): the host has proved (launch_integrate, `all_inside`: the slab's eight corner voxels, a
 // convex frustum) that EVERY voxel of the launch passes the sensor-range test of hpp:146 and projects inside the image
 // with a pixel to spare, and nx is a multiple of 4: the per-voxel range compares, the image-bounds compares and the
@@ -629,7 +469,6 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
   // brick-level frustum cull (k_cull below): a block none of whose voxels can be observed leaves at once
   static_assert(!(ALLIN && LIVE), "the ALLIN instance knows no row intervals");
   const BlockCoords bc = tsdf_block_coords(a.zfast);
-  PT_DECL;
   bool strad = false;  // LIVE: this block's rows need their intervals (block-uniform)
   if (LIVE) {
     const unsigned flag = live[bc.bx + bc.gdx * (bc.by + bc.gdy * bc.bz)];
@@ -637,31 +476,25 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
     strad = flag == 2u;
   }
   const unsigned tid = threadIdx.x;
-#if TSDF_KTAB
-  __shared__ KEntry s_tab[PACKED ? 256 : 1];  // per count k: decoded weight, Rcp32(k + 1).y, colour rounding offset, next count
-#else
   __shared__ f2 s_rcp[256];  // s_rcp[k] = {Rcp32(k + 1).y, the colour average's rounding offset for that divisor (KEntry::hy)}
-#endif
   // per row of this block (rpb * TY <= 256): the row's part of pcl::transformPoint -- yt[q] = cy * m[q][1] + (cz * m[q][2] + m[q][3])
   // in PCL's SSE order, m[q][1] * cy in the other -- worked out once per block by the thread of that number instead of by every
   // thread in every row (the very same operations: bit-identical), and the z part with it: no per-thread zt registers
   __shared__ f4 s_yt[256];
-  constexpr bool F2 = TSDF_PROJ_F2 && ALLIN && FASTPROJ;  // transform + projection on float pairs (see the row loop)
-  constexpr bool LEAN_K1 = TSDF_LEAN_K && !TSDF_KTAB && TSDF_COLOR_PK == 2 && PACKED && COLOR;  // (see the decode step)
+  // F2: transform + projection on explicit float pairs (v_pk_mul / v_pk_add / v_pk_fma_f32 with the pairs (0,1), (2,3)
+  // throughout: no register shuffles), the x centres re-read from LDS per row (see the row loop)
+  constexpr bool F2 = ALLIN && FASTPROJ;
+  constexpr bool LEAN_K1 = PACKED && COLOR;  // (see the decode step)
   __shared__ f4 s_cx[F2 ? 256 : 1];  // F2: every thread's own four x centres, re-read each row (16 B of LDS instead of four registers)
   __shared__ uint32_t s_iv[LIVE ? 256 : 1];  // LIVE: the row intervals of this block's rows, lo | len << 16 (launch-relative x)
   // "band seen" flags of this block's flag cells (64 x 4 x 1 voxels: <= 64 row groups x TX / 16 cells), collected in
   // LDS by the waves that take the in-band path anyway and written out once when the block is done: the free-space
   // hot path pays nothing for them (a global byte store per in-band row cost 3-5 % of the kernel, measured)
   TSDF_BAND_DECL;
-#if TSDF_KTAB
-  if (PACKED) s_tab[tid] = tsdf_ktab_entry(a, tid);
-#else
   if (PACKED) {
     const KEntry e = tsdf_ktab_entry(a, tid);
     s_rcp[tid] = (f2){e.y, e.hy};
   }
-#endif
   {
     const int yy = (int)bc.by * a.rpb * a.TY + (int)tid;
     {
@@ -698,7 +531,6 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
   __syncthreads();
   // bit r: in its pass r over the block's rows this WAVE touches no flagged cell (wave-uniform: one scalar branch per row)
   const uint64_t quiet = PACKED && a.implied_d ? tsdf_quiet_passes(a, s_bin, tid) : 0ull;
-  PT_MARK_OUT(9);  // block prologue: tables, row transforms, flags, barrier
   const int tx = (int)(tid & (unsigned)(a.TX - 1));
   const int ty = (int)(tid >> a.log2TX);
   const int xq = (int)bc.bx * a.TX + tx;
@@ -725,6 +557,8 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
     const float4 cx4 = *reinterpret_cast<const float4 *>(ctrx + x4);
     const float cxs[4] = {cx4.x, cx4.y, cx4.z, cx4.w};
     // ---- pcl::transformPoint (hpp:145): the x products and the z part, once per thread -------------------
+    // (px_ is not read: the row loop redoes the x products, see there.  The compiler drops it, but taking its loop out of the
+    // source renumbers the constants clang gives the row loop's exits, so it is left to a change that may alter the code object.)
     float px_[4][3], zt[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -734,9 +568,7 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
     }
     const unsigned voff = (unsigned)(ty * (int)a.pitch + x4) * 4u;  // byte offset inside the row group
     const unsigned row_step = (unsigned)a.TY * (unsigned)a.pitch * 4u;
-#if TSDF_EARLY_VOXEL_LOADS
-    bool pred_obs = true;  // TSDF_EARLY_VOXEL_LOADS == 2: this quad was observed in the previous row (the first row asks early)
-#endif
+    bool pred_obs = true;  // this quad was observed in the previous row (the first row asks early): see the early voxel loads
     // [phase: row setup (loop control, row's transform part from LDS)]
     for (int r = 0; r < a.rpb; ++r) {
       const int y = row0 + ty + r * a.TY;
@@ -750,9 +582,9 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
       const unsigned soff = (unsigned)r * row_step;
       const f4 ytv = s_yt[ty + r * a.TY];
       const float yt[3] = {ytv.x, ytv.y, ytv.z};
-#if TSDF_RECOMPUTE_PX
-      // the x products are redone per row (12 multiplies, six packed) instead of living in 12 registers across the
-      // loop: the kernel waits for memory, not for the VALU, and registers are what limits the waves in flight
+      // the x products are redone per row (12 multiplies, six packed) instead of living in 12
+      // registers across the loop: the kernel waits for memory, not for the VALU, and registers are what limits the waves
+      // in flight (72 instead of 80 VGPRs: 7 waves per SIMD)
       float px[4][3];
       if constexpr (!F2) {
         float cxr[4] = {cxs[0], cxs[1], cxs[2], cxs[3]};
@@ -763,9 +595,6 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
 #pragma unroll
           for (int j = 0; j < 4; ++j) px[j][q] = cxr[j] * a.m[4 * q];
       }
-#else
-      const float (&px)[4][3] = px_;
-#endif
       auto transform = [&](int j, int q) -> float {
         if (ORDER == TSDF_XFORM_PCL_SSE) return px[j][q] + yt[q];
         return ((px[j][q] + yt[q]) + zt[q]) + a.m[4 * q + 3];
@@ -779,8 +608,6 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
         asm volatile("" ::: "memory");  // (a compiler barrier, no instruction: the read below is redone each row, so neither
                                         // the centres nor their products live in registers across the loop)
         project_quad_allin<ORDER>(a, a.m, cam, s_cx[tid], ytv, zt, pix, gzs);
-        PT_DEP4(pix[0], pix[1], pix[2], pix[3]);
-        PT_MARK(0);  // loop control + LDS reads + transform + projection + certificate (+ exact fallback)
       } else {
       unsigned amb_mask = 0;
       uint32_t margin[4] = {0u, 0u, 0u, 0u};  // ALLIN: bits of min(fract(ru), fract(rv)) per voxel
@@ -813,41 +640,23 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
         }
       }
       // Voxels whose fp32 projection could not be certified: redo them exactly (rare: a fraction ~4*band of the voxels).
-#if TSDF_AMB_UNROLL
-      if (FASTPROJ && amb_mask) {  // a copy of the fp64 code per voxel of the quad, each under its own exec mask
+      if (FASTPROJ && amb_mask) {  // a copy of the fp64 code per voxel of the quad, each under its own exec mask (an empty one
+                                   // is a skipped branch: one copy in a loop selects its operands through ~90 exec-mask instructions)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           if (amb_mask >> j & 1u) pix[j] = project_exact(a, cam, transform(j, 0), transform(j, 1), transform(j, 2));
       }
-#else
-      // ... one at a time through a single copy of the fp64 code
-      while (FASTPROJ && amb_mask) {
-        const int j = __builtin_ctz(amb_mask);
-        amb_mask &= amb_mask - 1;
-        float g[3];
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-          g[q] = j == 0 ? transform(0, q) : j == 1 ? transform(1, q) : j == 2 ? transform(2, q) : transform(3, q);
-        const int p = project_exact(a, cam, g[0], g[1], g[2]);
-        if (j == 0) pix[0] = p;
-        if (j == 1) pix[1] = p;
-        if (j == 2) pix[2] = p;
-        if (j == 3) pix[3] = p;
       }
-#endif
-      }
-#if TSDF_EARLY_VOXEL_LOADS
       constexpr bool EARLY = PACKED;  // (F32W reads three planes per voxel and is the one key that feels the extra bytes: 22.3 -> 24.6 ms)
-      // the voxel words of the quad are requested TOGETHER with the frame gather instead of after its result: one memory
-      // latency per row instead of two in a row, at the price of reading the planes for quads none of whose voxels turns out
-      // to be observed (behind the surface, no return).  Measured on top of the implied distances (s_bin), same box,
-      // alternating (profiles/r04_ab_implied_distances.txt): 2048^3 + colour 15.48-15.97 -> 15.32-15.41 ms for 58.2 -> 71.1 GB
-      // per launch, without colour 11.60 -> 11.29, the configs[4] slab 14.61 -> 14.58: one to three per cent for a fifth more
-      // traffic, and a frame that sees little of the slab (a wall in front of the camera) would wait a voxel-plane round trip
-      // for every row it has nothing to do in.  OFF.
+      // EARLY: the voxel words of a quad are requested TOGETHER with the frame gather instead of after its result: one memory
+      // latency per row instead of two in a row.  Asking for EVERY quad reads the planes for quads none of whose voxels turns
+      // out to be observed (behind the surface, no return): a fifth more traffic, and a frame that sees little of the slab (a
+      // wall in front of the camera) would wait a voxel-plane round trip for every row it has nothing to do in; hence the
+      // predictor below.
       // (The compiler issues them IN FRONT of the gather, whose wait therefore covers them: vector memory returns in issue
       // order.  Behind it -- the gather's results first, the voxel words still in flight -- LLVM sinks them below the
       // `if (!any) continue` that follows, sched_barrier or not; the branch round the distance load is what keeps them here.)
+      // (PACKED) the distance words are only read where the cell's flag says they cannot be told from the counts
       const bool d_read = !PACKED || !(r < 64 && (quiet >> r & 1ull));
       // (no initial value: where the distance words are not read they are either rebuilt from the counts -- a wave in which a
       // distance can move -- or never looked at; four v_mov per row for a value nobody reads were 2 % of the row's operations)
@@ -855,19 +664,18 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
       asm volatile("" : "=v"(d4));
       u4 w4 = {0u, 0u, 0u, 0u}, c4 = {0u, 0u, 0u, 0u};
       uint32_t k4 = 0u;
-      // TSDF_EARLY_VOXEL_LOADS == 2 (round 5): only the quads PREDICTED to be observed ask early -- the predictor is the quad's
-      // own outcome in the previous row of the block (surfaces are coherent from row to row: the prediction fails where a
-      // surface begins or ends along y), a mispredicted observed quad asks late as before, a mispredicted unobserved one has
-      // read its words for nothing: the one-round-trip row without the fifth more traffic.
+      // Only the quads PREDICTED to be observed ask early -- the predictor is the quad's own outcome in the previous row of
+      // the block (surfaces are coherent from row to row: the prediction fails where a surface begins or ends along y), a
+      // mispredicted observed quad asks late as before, a mispredicted unobserved one has read its words for nothing: the
+      // one-round-trip row for 0.8 % more traffic instead of a fifth.
       // [phase: voxel loads]
-      const bool ask_early = EARLY && (TSDF_EARLY_VOXEL_LOADS != 2 || pred_obs);
+      const bool ask_early = EARLY && pred_obs;
       if (ask_early) {
         if (d_read) d4 = bload128(rsD, voff, soff);
         if (COLOR) c4 = bload128(rsC, voff, soff);
         if (!COLOR) k4 = bload32(rsK, voff >> 2, soff >> 2);
         if (COUNT) rdb += (d_read ? 16u : 0u) + (COLOR ? 16u : 4u);  // plane bytes requested
       }
-#endif
       // [phase: frame gather]
       // ---- gather the frame (L2-resident); pixel -1 is out of the descriptor's range and reads 0 ----------
       float zs[4];
@@ -876,10 +684,7 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
       for (int j = 0; j < 4; ++j) {
         // a valid pixel offset is < npix*4; -1 becomes 0xfffffffc, beyond the descriptor with or without the
         // colour image's scalar offset
-        if (TSDF_EXP_NO_GATHER) {
-          zs[j] = 1e3f + (float)(pix[j] & 1);
-          cs[j] = 0x00406080u + (unsigned)pix[j];
-        } else if (ALLIN) {
+        if (ALLIN) {
           zs[j] = __uint_as_float(tsdf_struct_buffer_load_u32(rsFi, pix[j], 0, 0, TSDF_GATHER_AUX));
           if (COLOR) cs[j] = tsdf_struct_buffer_load_u32(rsFi, pix[j], 0, (int)a.bgra_off, TSDF_GATHER_AUX);
         } else {
@@ -887,9 +692,6 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
           if (COLOR) cs[j] = bload32(rsF, (unsigned)pix[j] << 2, a.bgra_off);
         }
       }
-      PT_MARK(1);  // early voxel loads + frame gather ISSUED
-      PT_DEP4(zs[0], zs[1], zs[2], zs[3]);
-      PT_MARK(2);  // ... and the gathered depths HAVE ARRIVED (the wait also covers the early voxel words: in-order return)
       // [phase: hinge / normalise (hpp:159-198)]
       // ---- hpp:152-198: NaN test, projective SDF, hinge, normalisation ----------------------------------
       // raw / neg through the scale-free ladder: a surviving raw is 0 or, because g.z >= 2^-14 (else `lowz`),
@@ -907,17 +709,14 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
         act[j] = (ALLIN || pix[j] >= 0) && raw[j] >= -a.neg;
         dn[j] = a.pos_over_neg;                                         // hpp:189-192: raw > pos clamps
         any |= act[j];
-        if (!TSDF_LEAN_BAND) any_div |= act[j] && !(raw[j] > a.pos);
       }
-      if (TSDF_LEAN_BAND) {
-        // "some observed voxel lies inside the truncation band" (any_div) decides nothing but which path a wave takes, so the
-        // hot path asks a cheaper question first -- is the least of the four raw values (NaN ignored by v_min) at most pos? --
-        // true for every quad any_div is true for, and otherwise only for a quad with a voxel BEHIND the surface next to
-        // free-space ones (a surface row, where the wave takes that path anyway); the exact test runs only then
-        if (__builtin_fminf(__builtin_fminf(raw[0], raw[1]), __builtin_fminf(raw[2], raw[3])) <= a.pos) {
+      // "some observed voxel lies inside the truncation band" (any_div) decides nothing but which path a wave takes, so the
+      // hot path asks a cheaper question first -- is the least of the four raw values (NaN ignored by v_min) at most pos? --
+      // true for every quad any_div is true for, and otherwise only for a quad with a voxel BEHIND the surface next to
+      // free-space ones (a surface row, where the wave takes that path anyway); the exact test runs only then
+      if (__builtin_fminf(__builtin_fminf(raw[0], raw[1]), __builtin_fminf(raw[2], raw[3])) <= a.pos) {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) any_div |= act[j] && !(raw[j] > a.pos);
-        }
+        for (int j = 0; j < 4; ++j) any_div |= act[j] && !(raw[j] > a.pos);
       }
       // [phase: leave the row if nothing is observed; late voxel loads]
       // The colour gathers are retired HERE, with the depth gathers they were issued behind (they return in order, a few
@@ -927,7 +726,6 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
       // voxel STORES, in every row, whether the path was taken or not (the third memory round trip of a row, found in
       // round 5: profiles/r05_isa_phase_mix.txt)
       if (COLOR) asm volatile("" ::"v"(cs[0]), "v"(cs[1]), "v"(cs[2]), "v"(cs[3]));
-#if TSDF_EARLY_VOXEL_LOADS
       if (EARLY) {  // ... and so are the early voxel words (a quad that turns out unobserved never looks at them)
         if (COLOR)
           asm volatile("" ::"v"(d4), "v"(c4));
@@ -936,18 +734,13 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
       }
       const bool asked_early = ask_early;
       pred_obs = any;
-#endif
-      PT_MARK(3);  // raw distances, observed / in-band tests
       if (!any) continue;
-      PT_COUNT(8);
-#if TSDF_EARLY_VOXEL_LOADS == 2
       if (EARLY && !asked_early) {  // an observed quad the predictor missed: its words are requested now
         if (d_read) d4 = bload128(rsD, voff, soff);
         if (COLOR) c4 = bload128(rsC, voff, soff);
         if (!COLOR) k4 = bload32(rsK, voff >> 2, soff >> 2);
         if (COUNT) rdb += (d_read ? 16u : 0u) + (COLOR ? 16u : 4u);
       }
-#endif
       // [phase: normalise: raw / neg ladder (rows with an in-band voxel)]
       if (any_div) {  // free space (every observed voxel of the wave beyond the hinge) skips all four ladders
 #pragma unroll
@@ -965,21 +758,6 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
       }
       // [phase: voxel loads]
       // ---- read-modify-write -----------------------------------------------------------------------------
-#if TSDF_EXP_NO_VLOAD
-      const uint32_t hb_ = __float_as_uint(a.pos_over_neg);
-      const u4 d4 = {hb_, hb_, hb_, hb_};
-      u4 w4 = {0u, 0u, 0u, 0u}, c4 = {(unsigned)r << 24, (unsigned)r << 24, (unsigned)r << 24, (unsigned)r << 24};
-      uint32_t k4 = 0u;
-      const bool d_read = true;
-#else
-#if !TSDF_EARLY_VOXEL_LOADS
-      // (PACKED) the distance words are only read where the cell's flag says they cannot be told from the counts
-      constexpr bool EARLY = false;
-      const bool d_read = !PACKED || !(r < 64 && (quiet >> r & 1ull));
-      u4 d4 = {0u, 0u, 0u, 0u};
-      u4 w4 = {0u, 0u, 0u, 0u}, c4 = {0u, 0u, 0u, 0u};
-      uint32_t k4 = 0u;
-#endif
       if (!EARLY) {
         if (d_read) d4 = bload128(rsD, voff, soff);
         if (!PACKED) w4 = bload128(rsW, voff, soff);
@@ -987,10 +765,6 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
         if (PACKED && !COLOR) k4 = bload32(rsK, voff >> 2, soff >> 2);
         if (COUNT) rdb += (d_read ? 16u : 0u) + (!PACKED ? 16u : 0u) + (COLOR ? 16u : 0u) + (PACKED && !COLOR ? 4u : 0u);
       }
-#endif
-      PT_MARK(4);  // normalise ladder (in-band rows), late loads issued
-      if (COLOR) PT_DEP4(c4.x, c4.y, c4.z, c4.w); else PT_DEP1(k4);
-      PT_MARK(5);  // the voxel words HAVE ARRIVED (late askers wait here; early askers' words came with the gather)
       // [phase: decode count / weight (PACKED)]
       uint32_t d0u[4] = {d4.x, d4.y, d4.z, d4.w};
       const uint32_t c0[4] = {c4.x, c4.y, c4.z, c4.w};
@@ -999,9 +773,6 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
       uint32_t kw[4];  // PACKED: the count in byte 3 of a word (colour word, or the k8 byte moved there)
       float dv[4], wv[4];
       uint32_t cv[4], k1[4];
-#if TSDF_KTAB
-      float ky[4];
-#endif
       float khy[4] = {0.f, 0.f, 0.f, 0.f};  // PACKED: the colour rounding offset of each voxel's divisor (with Rcp32(k + 1).y from LDS)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -1011,15 +782,11 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
         k1[j] = 0u;
         if (PACKED) {
           kw[j] = COLOR ? c0[j] : (k4 << (24 - 8 * j));
-#if TSDF_KTAB
-          const KEntry e = s_tab[kw[j] >> 24];  // one ds_read_b128
-          w0[j] = e.w, ky[j] = e.y, khy[j] = e.hy, k1[j] = e.k1;
-#else
           // tsdf_decode_w (neither is NaN here).  With an integer max_weight the min is the identity -- and the ALLIN
           // instance is only launched with one, and with kmax == max_weight (launch_integrate) -- but leaving it out lets
-          // LLVM turn the colour sums into integer multiplies and byte shuffles (+70 instructions, measured): TSDF_LEAN_K
-          // hides the value behind an empty asm instead of paying a v_min per voxel for that.
-          if (TSDF_LEAN_K && ALLIN) {
+          // LLVM turn the colour sums into integer multiplies and byte shuffles (+70 instructions, measured): the value
+          // hides behind an empty asm instead of paying a v_min per voxel for that.
+          if (ALLIN) {
             w0[j] = (float)(kw[j] >> 24);
             if (COLOR) asm volatile("" : "+v"(w0[j]));  // (without colour only the rare distance ladder reads it)
           } else {
@@ -1030,7 +797,6 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
           // when kmax == 0).  LEAN_K1: v_cvt_pk_u8_f32 rewrites bytes 0-2 of the word it is handed, so there the old
           // colour bytes may ride along under the clamp (kcap | 0xffffff) and the mask goes away
           k1[j] = LEAN_K1 ? min(kw[j], a.kcap | 0xffffffu) + a.kinc : min(kw[j] & 0xff000000u, a.kcap) + a.kinc;  // == min(k + 1, kmax) << 24 (| old rgb)
-#endif
         }
       }
       // F32W: the fast update is exact if update_is_safe().  PACKED: the divisor k + 1 is an integer in
@@ -1044,18 +810,10 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
 #pragma unroll
         for (int j = 0; j < 4; ++j) safe &= !act[j] || update_is_safe(d0[j], w0[j], dn[j]);
       }
-#if !TSDF_GUARD_ON_RESULT
-      else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          safe &= !act[j] || ((a.wmax_is_int || kw[j] < (a.kmax << 24)) && numerator_ok(d0[j] * w0[j] + dn[j]));
-      }
-#endif
       // PACKED, free space: a wave none of whose observed voxels is inside the truncation band (no `any_div`) and all of
       // whose observed voxels already sit at the hinge value p sees (p*w + p)/(w + 1), which the host has checked to
       // be p for every weight (a.hinge_fixed): d keeps its bits and the four ladders and their guards are skipped.
       bool d_moves = true;
-#if TSDF_SKIP_FIXED_HINGE
       if (PACKED && a.hinge_fixed) {
         bool off_hinge = any_div;
         // (ALLIN: without the `observed` mask -- a quad with an unobserved voxel off the hinge just takes the general
@@ -1066,12 +824,11 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
         } else {  // distances not read (see s_bin): off the hinge value <=> never observed <=> count 0
 #pragma unroll
           for (int j = 0; j < 4; ++j) off_hinge |= (ALLIN || act[j]) && kw[j] < 0x01000000u;
-          // (TSDF_SWAR_K, ALLIN without colour: the same question of the four count bytes at once -- is one of them zero?)
-          if (TSDF_SWAR_K && ALLIN && !COLOR) off_hinge = any_div || ((k4 - 0x01010101u) & ~k4 & 0x80808080u) != 0u;
+          // (ALLIN without colour: the same question of the four count bytes at once -- is one of them zero?)
+          if (ALLIN && !COLOR) off_hinge = any_div || ((k4 - 0x01010101u) & ~k4 & 0x80808080u) != 0u;
         }
         d_moves = __builtin_amdgcn_ballot_w64(off_hinge) != 0ull;  // wave-uniform: one scalar branch
       }
-#endif
       if (PACKED && !d_read && d_moves) {
         // ... and only a wave in which a distance can move needs them at all: never observed = the reset value, else the
         // hinge value
@@ -1089,28 +846,13 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
         for (int j = 0; j < 4; ++j) dv[j] = d0[j], wv[j] = w0[j], cv[j] = c0[j];
         // PACKED without colour: the reciprocal of k + 1 is only wanted where a distance moves (wave-uniform: d_moves is a ballot);
         // in resting free space the count bytes are all there is to update
-        constexpr bool QUAD_COLOR = TSDF_COLOR_F2 && COLOR && PACKED && TSDF_COLOR_PK == 2 && !TSDF_KTAB;  // colour_quad_pk
-        if constexpr (QUAD_COLOR) {
-#pragma unroll
-          for (int j = 0; j < 4; j += 2) {  // voxels (0, 1), then (2, 3)
-            const f2 yh0 = s_rcp[kw[j] >> 24], yh1 = s_rcp[kw[j + 1] >> 24];  // w0 + 1 == k + 1 here (w0 is an integer)
-            rs[j].nb = -(w0[j] + 1.f), rs[j + 1].nb = -(w0[j + 1] + 1.f);
-            rs[j].y = yh0.x, rs[j + 1].y = yh1.x;
-            colour_pair_pk((f2){w0[j], w0[j + 1]}, c0[j], c0[j + 1], cs[j], cs[j + 1], (f2){yh0.x, yh1.x}, (f2){yh0.y, yh1.y}, k1[j], k1[j + 1],
-                           cv[j], cv[j + 1]);
-          }
-        } else
         if (COLOR || !PACKED || d_moves)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {  // colour and weight: every observed voxel
           if (PACKED) {
             rs[j].nb = -(w0[j] + 1.f);
-#if TSDF_KTAB
-            rs[j].y = ky[j];  // w0 + 1 == k + 1 here (w0 is an integer)
-#else
             const f2 yh = s_rcp[kw[j] >> 24];  // w0 + 1 == k + 1 here (w0 is an integer)
             rs[j].y = yh.x, khy[j] = yh.y;
-#endif
           } else {
             rs[j] = rcp32_prepare(w0[j] + 1.f);
           }
@@ -1122,10 +864,9 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
           // a voxel of this quad was observed inside the truncation band: its distance may turn negative, which is what
           // marching cubes looks for (see s_band)
           // (the host only passes `band` when every block's first row is a multiple of 4: local row groups == global ones)
-          if (!TSDF_NO_BAND && any_div) TSDF_BAND(((ty + r * a.TY) >> 2) * max(1, a.TX >> 4) + (tx >> 4)) = 1;
+          if (any_div) TSDF_BAND(((ty + r * a.TY) >> 2) * max(1, a.TX >> 4) + (tx >> 4)) = 1;
 #pragma unroll
           for (int j = 0; j < 4; ++j) dv[j] = div32_fast(d0[j] * w0[j] + dn[j], rs[j]);
-#if TSDF_GUARD_ON_RESULT
           if (PACKED) {
             // the guard, on the RESULT (one v_cmp_class per voxel): a normal quotient is the correctly rounded one
             // (tests/test_div_gpu.py::test_count_divider_*); zero, subnormal, infinite or NaN -- or a weight sitting
@@ -1134,13 +875,12 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
             for (int j = 0; j < 4; ++j)
               safe &= !act[j] || ((ALLIN || a.wmax_is_int || kw[j] < (a.kmax << 24)) && __builtin_amdgcn_classf(dv[j], 0x108));
           }
-#endif
         }
       }
       // [phase: IEEE fallback (rare)]
       if (!safe) {
         d_touched = true;
-        if (!TSDF_NO_BAND && any_div) TSDF_BAND(((ty + r * a.TY) >> 2) * max(1, a.TX >> 4) + (tx >> 4)) = 1;
+        if (any_div) TSDF_BAND(((ty + r * a.TY) >> 2) * max(1, a.TX >> 4) + (tx >> 4)) = 1;
         asm volatile("");  // rare: keep the 16 IEEE divisions out of the hot path's schedule
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -1151,8 +891,6 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
           if (COLOR) cv[j] |= k1[j] & 0xff000000u;  // both flavours return the colour with the new count in byte 3
         }
       }
-      PT_DEP4(dv[0], dv[1], cv[0], cv[1]);
-      PT_MARK(6);  // decode, flags, hinge rest test, colour + distance update
       // [phase: select / change detection / store]
       uint32_t diff_w = 0u, diff_c = 0u, k4n = 0u;
       uint32_t wn_u[4];
@@ -1165,11 +903,10 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
           diff_d |= dn_u[j] ^ d0u[j];
           if (COUNT) chg += dn_u[j] != d0u[j] ? 4u : 0u;
         }
-        if (diff_d && !TSDF_EXP_NO_STORE) bstore128(rsD, voff, soff, (u4){dn_u[0], dn_u[1], dn_u[2], dn_u[3]});
+        if (diff_d) bstore128(rsD, voff, soff, (u4){dn_u[0], dn_u[1], dn_u[2], dn_u[3]});
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if (PACKED && !COLOR && !TSDF_SWAR_K) k4n |= (act[j] ? k1[j] : (kw[j] & 0xff000000u)) >> (24 - 8 * j);
         wn_u[j] = act[j] ? __float_as_uint(wv[j]) : w0u[j];
         cv[j] = act[j] ? cv[j] : c0[j];
         diff_w |= wn_u[j] ^ w0u[j];
@@ -1179,8 +916,8 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
         if (COUNT)  // bytes of voxel words whose VALUE changed: what any layout-preserving kernel has to write
           chg += (!PACKED && wn_u[j] != w0u[j] ? 4u : 0u) + (COLOR && cv[j] != c_before[j] ? 4u : 0u);
       }
-      if (PACKED && !COLOR && TSDF_SWAR_K) {
-        // The four counts of the quad in one word (TSDF_SWAR_K): k' = k + (observed && k < kmax) per byte, == min(k + 1, kmax)
+      if (PACKED && !COLOR) {
+        // The four counts of the quad in one word: k' = k + (observed && k < kmax) per byte, == min(k + 1, kmax)
         // for every count the layout can hold (k <= kmax).  "k < kmax" for all four at once: the even and the odd bytes sit
         // in 16-bit fields with bit 8 set on top; after subtracting kmax from each field that bit survives exactly where
         // k >= kmax (256 + k - kmax stays within the field: no borrow crosses it).  ~13 operations instead of 28 per quad.
@@ -1193,17 +930,12 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
       if (COUNT && PACKED && !COLOR) chg += (unsigned)__popc(((k4n ^ k4) | ((k4n ^ k4) >> 1) | ((k4n ^ k4) >> 2) | ((k4n ^ k4) >> 3) |
                                                             ((k4n ^ k4) >> 4) | ((k4n ^ k4) >> 5) | ((k4n ^ k4) >> 6) | ((k4n ^ k4) >> 7)) & 0x01010101u);
       if (!PACKED && diff_w) bstore128(rsW, voff, soff, (u4){wn_u[0], wn_u[1], wn_u[2], wn_u[3]});
-      if (TSDF_EXP_NO_STORE) {  // keep the results alive without touching memory
-        if ((cv[0] ^ cv[1] ^ cv[2] ^ cv[3]) == 0x12345678u) bstore32(rsD, voff, soff, cv[0] ^ diff_w);
-      } else
       if (COLOR && diff_c) bstore128(rsC, voff, soff, (u4){cv[0], cv[1], cv[2], cv[3]});
       if (PACKED && !COLOR && k4n != k4) bstore32(rsK, voff >> 2, soff >> 2, k4n);
-      PT_MARK(7);  // select, change detection, stores issued
     }
   }
-  PT_MARK_OUT(10);  // what is left of the loop (rows that left early are in 0-3), exit
-  if (!TSDF_NO_BAND && band) {  // the block's flags -> the volume's flag array (every writer stores the same 1: no atomics)
-    TSDF_BAND_SYNC();  // (per-wave sets: none -- a wave reads back what it wrote itself)
+  if (band) {  // the block's flags -> the volume's flag array (every writer stores the same 1: no atomics, and no barrier: a
+               // wave reads back what it wrote itself)
     const int lf = max(0, a.log2TX - 4), fxb = 1 << lf;
     const int yg0 = (a.y_abs0 + row0) >> 2, yg1 = (a.y_abs0 + row0 + max(rows, 1) - 1) >> 2;
     const int xc0 = (a.x_abs0 + (int)bc.bx * a.TX * 4) >> 6;
@@ -1213,8 +945,6 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
       if (TSDF_BAND(i) && yg < a.band_fy && xc < a.band_fx) band[((int64_t)(a.zl0 + zl) * a.band_fy + yg) * a.band_fx + xc] = 1;
     }
   }
-  PT_MARK_OUT(12);  // epilogue: barrier + flag write-out
-  PT_FLUSH();
   if (COUNT) {  // block reduction, then one of 1024 striped counters (summed by the host); slots 1024.. = changed bytes,
                 // slots 2048.. = observed voxels whose distance word was not read
     __shared__ unsigned s_cnt, s_chg, s_imp, s_rdb;
@@ -1263,11 +993,7 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
 // Same arithmetic as k_integrate<ORDER, false, true, COUNT, true, true, false>, operation for operation; the host
 // launches it instead of that instance when, additionally, every row step of a block is whole (ny a multiple of TY),
 // the hinge value rests (hinge_fixed) and max_dist_neg lies in the scale-free divider's window -- else the old instance.
-#ifndef TSDF_WPE_PIPE
-#define TSDF_WPE_PIPE 8  // 63 VGPRs, no scratch.  (LLVM grants 8 waves 80 SGPRs, 7 waves 96+: at 8 the loop's rare blocks carry scalar spills
-                         // in VGPR lanes, at 7 -- 65 VGPRs, seven waves -- hardly any; measured by alternation, 2048^3 without colour:
-                         // 7.61 ms at 8 against 7.81 at 7, 8.98 for k_integrate's own row loop: profiles/r06_ab_pipe_c0_call02.txt)
-#endif
+// (Waves per SIMD: TSDF_WPE_PIPE, at the top of the file.)
 struct PipeRow {      // what stage A hands to stage B
   float gz[4];        // g.z of the quad's four voxels
   uint32_t z[4];      // gathered depths (bits; in flight)
@@ -1361,7 +1087,7 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
         any |= act[j];
       }
       if (__builtin_amdgcn_ballot_w64(any) == 0ull) return;  // nothing of this wave's row is observed
-      bool any_div = false;  // an observed voxel inside the truncation band (k_integrate: TSDF_LEAN_BAND)
+      bool any_div = false;  // an observed voxel inside the truncation band (the least-raw-distance test first: see k_integrate)
       if (__builtin_fminf(__builtin_fminf(raw[0], raw[1]), __builtin_fminf(raw[2], raw[3])) <= a.pos) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) any_div |= act[j] && !(raw[j] > a.pos);
@@ -1380,7 +1106,7 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
       }
       const bool d_moves = __builtin_amdgcn_ballot_w64(any && off_hinge) != 0ull;  // wave-uniform
       // [phase: select / change detection / store]
-      // the four counts in one word (k_integrate: TSDF_SWAR_K): k' = k + (observed && k < kmax) per byte
+      // the four counts in one word (see k4n in k_integrate): k' = k + (observed && k < kmax) per byte
       const uint32_t km2 = a.kmax * 0x00010001u;
       const uint32_t te = ((k4 & 0x00ff00ffu) | 0x01000100u) - km2, to = (((k4 >> 8) & 0x00ff00ffu) | 0x01000100u) - km2;
       const uint32_t lt = ((~te >> 8) & 0x00010001u) | (((~to >> 8) & 0x00010001u) << 8);  // 0x01 in byte j: k_j < kmax
@@ -1414,7 +1140,7 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
           rs.nb = -(w0[j] + 1.f);
           rs.y = s_rcp[kw[j] >> 24].x;
           dv[j] = div32_fast(d0[j] * w0[j] + dn[j], rs);
-          // the guard on the RESULT (k_integrate: TSDF_GUARD_ON_RESULT): a normal quotient is the correctly rounded one
+          // the guard on the RESULT (as in k_integrate): a normal quotient is the correctly rounded one
           safe &= !act[j] || __builtin_amdgcn_classf(dv[j], 0x108);
         }
         // [phase: IEEE fallback (rare)]
@@ -1467,8 +1193,8 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
       consume(r, A);
     }
   }
-  if (band) {  // the block's flags -> the volume's flag array (every writer stores the same 1: no atomics)
-    TSDF_BAND_SYNC();  // (per-wave sets: none -- a wave reads back what it wrote itself)
+  if (band) {  // the block's flags -> the volume's flag array (every writer stores the same 1: no atomics, and no barrier: a
+               // wave reads back what it wrote itself)
     const int lf = max(0, a.log2TX - 4), fxb = 1 << lf;
     const int yg0 = (a.y_abs0 + row0) >> 2, yg1 = (a.y_abs0 + row0 + max(rows, 1) - 1) >> 2;
     const int xc0 = (a.x_abs0 + (int)bc.bx * a.TX * 4) >> 6;
@@ -1513,9 +1239,7 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
 // 12.14): with colour the row moves 58.6 GB per launch, 4.6 TB/s = 82 % of what this box's plain read-modify-write sweep
 // reaches, while the VALU is 80 % busy -- two limiters at once, neither of which the pipeline touches.  OFF by default (knob
 // pipe, bit 1); kept, oracle-gated like every instance (tests/test_integrate_gpu.py), for hardware where the balance differs.
-#ifndef TSDF_WPE_PIPEC
-#define TSDF_WPE_PIPEC 5  // 91 VGPRs, no scratch (six waves: 80 VGPRs + ten spill operations in the row loop, whose waits undo the pipeline)
-#endif
+// (Waves per SIMD: TSDF_WPE_PIPEC, at the top of the file.)
 struct PipeRowC {
   float gz[4];
   uint32_t z[4];   // gathered depths (in flight)
@@ -1645,7 +1369,7 @@ k_integrate_pc(const IntegrateArgs a, float *__restrict__ D, uint32_t *__restric
 #pragma unroll
       for (int j = 0; j < 4; ++j) {  // colour and count: every observed voxel
         float w = (float)(c0[j] >> 24);  // tsdf_decode_w: max_weight is an integer equal to kmax here (ALLIN)
-        asm volatile("" : "+v"(w));      // (keeps LLVM from turning the colour sums into integer multiplies: k_integrate, TSDF_LEAN_K)
+        asm volatile("" : "+v"(w));      // (keeps LLVM from turning the colour sums into integer multiplies: see k_integrate's decode step)
         const uint32_t k1 = min(c0[j], a.kcap | 0xffffffu) + a.kinc;  // min(k + 1, kmax) << 24 | old rgb (v_cvt_pk_u8 rewrites bytes 0-2)
         const f2 yh = s_rcp[c0[j] >> 24];
         Rcp32 rs;
@@ -1740,8 +1464,7 @@ k_integrate_pc(const IntegrateArgs a, float *__restrict__ D, uint32_t *__restric
       consume(r, A, pa, obs_a);
     }
   }
-  if (band) {
-    TSDF_BAND_SYNC();
+  if (band) {  // (no barrier: a wave reads back what it wrote itself)
     const int lf = max(0, a.log2TX - 4), fxb = 1 << lf;
     const int yg0 = (a.y_abs0 + row0) >> 2, yg1 = (a.y_abs0 + row0 + max(rows, 1) - 1) >> 2;
     const int xc0 = (a.x_abs0 + (int)bc.bx * a.TX * 4) >> 6;
@@ -1784,14 +1507,8 @@ struct Frame2 {
   float m[12];        // frame B's cam_from_vol
   unsigned bgra_off;  // ... and the byte offset of its colour image from its depth image
 };
-#ifndef TSDF_K2_PIPE
-#define TSDF_K2_PIPE 0  // 1 = two-row software pipeline (ISSUE(r + 1) before RETIRE(r)): built and measured in round 4 -- 32 more
-                        // registers of row state: at 4 waves 32 VGPRs spill (27.9 ms per frame), at 3 waves none (16.9 ms), against
-                        // 13.3 ms for issue + retire back to back at 5 waves (profiles/r04_ab_k_integrate2.txt): occupancy wins again
-#endif
-#ifndef TSDF_WPE_K2
-#define TSDF_WPE_K2 (TSDF_K2_PIPE ? 4 : 5)
-#endif
+// A row's loads are issued and retired back to back, at TSDF_WPE_K2 waves per SIMD (top of the file): keeping two rows in
+// flight costs 32 more registers of row state, and occupancy wins.
 
 template <int ORDER, bool COLOR, bool COUNT>
 static __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_WPE_K2, TSDF_WPE_MAX)))
@@ -2009,27 +1726,13 @@ k_integrate2(const IntegrateArgs a, const Frame2 fb, float *__restrict__ D, uint
     // rows this thread walks: r = 0 .. nrows - 1 (row0 + ty + r * TY < ny)
     const int left = a.ny - row0 - ty;
     const int nrows = left <= 0 ? 0 : min(a.rpb, (left + a.TY - 1) / a.TY);
-#if TSDF_K2_PIPE
-    RowLoads L0, L1;
-    if (nrows > 0) issue(0, L0);
-    for (int r = 0; r < nrows; r += 2) {
-      if (r + 1 < nrows) issue(r + 1, L1);
-      retire(r, L0);
-      if (r + 1 < nrows) {
-        if (r + 2 < nrows) issue(r + 2, L0);
-        retire(r + 1, L1);
-      }
-    }
-#else
     for (int r = 0; r < nrows; ++r) {
       RowLoads L;
       issue(r, L);
       retire(r, L);
     }
-#endif
   }
-  if (band) {
-    TSDF_BAND_SYNC();  // (per-wave sets: none -- a wave reads back what it wrote itself)
+  if (band) {  // (no barrier: a wave reads back what it wrote itself)
     const int lf = max(0, a.log2TX - 4), fxb = 1 << lf;
     const int yg0 = (a.y_abs0 + row0) >> 2, yg1 = (a.y_abs0 + row0 + max(rows, 1) - 1) >> 2;
     const int xc0 = (a.x_abs0 + (int)bc.bx * a.TX * 4) >> 6;
@@ -3106,29 +2809,6 @@ static void dispatch_fast(tsdf_handle h, const LaunchPlan &pl, const float *d_de
       sse, color, fastproj, count, h->packed, allin, pl.live != nullptr);
 }
 
-#if TSDF_PHASE_TIMER
-// diagnostic build: the phase accumulators of THIS launch, appended to $TSDF_HIP_PHASE_FILE and cleared
-static int dump_phase_timers(tsdf_handle h, bool count, bool allin, bool live) {
-  const char *pf = getenv("TSDF_HIP_PHASE_FILE");
-  if (!pf) return TSDF_HIP_OK;
-  TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
-  static unsigned long long host_ph[1024 * TSDF_NPHASE];
-  TSDF_HIP_TRY(hipMemcpyFromSymbol(host_ph, HIP_SYMBOL(g_phase), sizeof host_ph));
-  unsigned long long sum[TSDF_NPHASE] = {0};
-  for (int i = 0; i < 1024; ++i)
-    for (int k = 0; k < TSDF_NPHASE; ++k) sum[k] += host_ph[i * TSDF_NPHASE + k];
-  memset(host_ph, 0, sizeof host_ph);
-  TSDF_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_phase), host_ph, sizeof host_ph));
-  if (FILE *f = fopen(pf, "a")) {
-    fprintf(f, "{\"color\": %d, \"count\": %d, \"allin\": %d, \"live\": %d, \"packed\": %d, \"blocks\": %d, \"phase\": [",
-            (int)(h->p.integrate_color != 0), (int)count, (int)allin, (int)live, (int)h->packed, h->last_launch[3]);
-    for (int k = 0; k < TSDF_NPHASE; ++k) fprintf(f, "%llu%s", sum[k], k + 1 < TSDF_NPHASE ? ", " : "]}\n");
-    fclose(f);
-  }
-  return TSDF_HIP_OK;
-}
-#endif
-
 // Validation of a launch, in the order the errors have always been reported.
 static int validate_launch(tsdf_handle h, const LaunchPlan &pl, const uint32_t *d_bgra) {
   if (pl.gy > 65535u || pl.gz > 65535u) {
@@ -3191,9 +2871,6 @@ int tsdf_integrate_launch(tsdf_handle h, const float *d_depth, const uint32_t *d
     h->last_launch[3] = (int)std::min<uint64_t>((uint64_t)pl.gx * pl.gy * pl.gz, 0x7fffffffu);
     dispatch_fast(h, pl, d_depth, count, fastproj, allin, pipe, band_arg);
     TSDF_HIP_TRY(hipGetLastError());
-#if TSDF_PHASE_TIMER
-    if (const int e = dump_phase_timers(h, count, allin, live)) return e;
-#endif
   }
   h->count_slots = count ? 4096 : 0;  // slots 1024.. hold the bytes of voxel words whose value changed, 2048.. the observed
                                       // voxels whose distance word was not read, 3072.. the plane bytes requested

@@ -328,11 +328,6 @@ k_mc_classify(const McArgs a, uint64_t *__restrict__ keys, uint64_t capacity,
   // The deferred weight test + the copy-out.  Every lane takes one listed cell:
   // entry = x - 256 blockIdx.x | row << 8 | (z - zs) << 10 | triangles << 15.
   auto flush = [&]() {
-#if defined(MC_PROBE) && MC_PROBE == 4  // probe: the append loop alone -- lists are built and dropped
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    n_buf = 0;
-    return;
-#endif
     // pass 1 (only if a weight can fail): test the 8 corner weights of every listed cell, 64 cells at a time with every
     // lane busy; a cell that fails loses its triangle count (a listed cell always has one), which marks it dropped
     unsigned total = n_buf;
@@ -380,11 +375,7 @@ k_mc_classify(const McArgs a, uint64_t *__restrict__ keys, uint64_t capacity,
         base += (unsigned long long)__popcll(m);
         if (ok) {
           tri_sum += e >> 15;
-#if defined(MC_PROBE) && MC_PROBE == 5  // probe: everything but the key assembly and its store
-          if (slot == ~0ull) {
-#else
           if (slot < capacity) {
-#endif
             const unsigned xr = e & 255u, row = wave * MC_R + ((e >> 8) & 3u), zr = (e >> 10) & 31u;
             keys[slot] = ((xkey_hi | (uint64_t)s_xkey[xr] | s_ykey[row] | s_zkey[zr]) << MC_KEY_SHIFT) | (uint64_t)(e >> 15);
           }
@@ -436,18 +427,10 @@ k_mc_classify(const McArgs a, uint64_t *__restrict__ keys, uint64_t capacity,
     }
     ng = bd = 0u;
     volatile uint32_t *hb = s_halo[z & 1];
-#ifndef MC_PROBE
     const bool quiet = __ballot(mn < 0x3f800000u) == 0ull;
-#elif MC_PROBE < 3  // bandwidth probes (tools/build_variant.py): 1 = every wave takes the quiet path, 2 = and no barrier
-    const bool quiet = __ballot(mn < 0x00000001u) == 0ull;
-#else
-    const bool quiet = __ballot(mn < 0x3f800000u) == 0ull;
-#endif
     if (quiet) {
-#if !defined(MC_PROBE) || MC_PROBE < 2
       hb[wave * 64u + lane] = 0u;
       __syncthreads();
-#endif
       return;
     }
 #pragma unroll
@@ -489,9 +472,6 @@ k_mc_classify(const McArgs a, uint64_t *__restrict__ keys, uint64_t capacity,
     const unsigned V = b0 & (b0 >> 5) & b1 & (b1 >> 5);
     // mixed signs (neither all eight negative nor none) and all eight inside the band
     unsigned cand = ~(A & (A >> 1)) & (O | (O >> 1)) & (V & (V >> 1)) & cell_mask;
-#if defined(MC_PROBE) && MC_PROBE == 3  // probe: mask assembly as usual, but nothing is ever listed
-    cand &= (unsigned)(z < 0);
-#endif
     if (__ballot(cand != 0u)) {
       // appended in two halves (cell rows 0-1, then 2-3): a half adds at most 512 entries, which is the list's size
       for (int half = 0; half < 2; ++half) {

@@ -173,9 +173,9 @@ def test_count_divider_equals_ieee_division(gpu, seed):
 
 
 def test_cvt_pk_u8_rounds_to_nearest_even_and_saturates(gpu):
-    """v_cvt_pk_u8_f32, the one-instruction convert-and-pack the colour update can be built with (TSDF_COLOR_PK, an A/B
-    switch that is off: measured slower than convert + shift-or): it rounds to nearest even, saturates to [0, 255],
-    turns NaN into 0 and leaves the other three bytes alone.  The shipped path truncates with v_cvt_u32_f32."""
+    """v_cvt_pk_u8_f32, the one-instruction convert-and-pack the fast colour update is built with (add_observation_fast):
+    it rounds to nearest even, saturates to [0, 255], turns NaN into 0 and leaves the other three bytes alone.  The
+    update's rounding offset (y / 2 - 1 / 2) relies on that rounding."""
     rng = np.random.RandomState(5)
     x = np.concatenate([np.float32([0.25, 0.5, 0.75, 1.5, 2.5, 3.5, 254.5, 255.4, 255.5, 256.7, 1e9, -0.25, -0.5, -3.0,
                                     np.nan, np.inf, -np.inf, 0.49999997, 1.4999999]),
