@@ -759,6 +759,7 @@ extern "C" int tsdf_hip_reset(tsdf_handle h) {
   TSDF_HIP_TRY(hipMemsetAsync(h->band, 0, (size_t)h->band_fx * h->band_fy * h->nz_alloc, h->stream));
   h->band_exact = true;  // every distance is -1: no voxel inside the band
   h->rest_state = 0;
+  h->frame_staged = 0;  // a staged frame does not outlive the volume it was organised for (as on a multi-GPU set)
   TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
   return TSDF_HIP_OK;
 }

@@ -2537,6 +2537,7 @@ static bool frame_bgra_offset(const tsdf_params &p, const float *d_depth, const 
 static int stage_frame(tsdf_handle h, const float **d_depth, const uint32_t *d_bgra, unsigned *bgra_off) {
   if (frame_bgra_offset(h->p, *d_depth, d_bgra, bgra_off)) return TSDF_HIP_OK;
   const size_t npx = (size_t)h->p.image_width * h->p.image_height;
+  h->frame_staged = 0;  // the repack overwrites what tsdf_hip_organize left there
   if (*d_depth != h->frame_depth)
     TSDF_HIP_TRY(hipMemcpyAsync(h->frame_depth, *d_depth, npx * 4, hipMemcpyDeviceToDevice, h->stream));
   if (d_bgra != h->frame_bgra)
@@ -3196,6 +3197,7 @@ extern "C" int tsdf_hip_integrate(tsdf_handle h, const float *depth, const uint8
     return TSDF_HIP_E_INVALID;
   }
   // through the pinned bounce buffer (tsdf_to_device): the same cost whatever memory the caller hands over
+  h->frame_staged = 0;  // (the upload replaces a frame tsdf_hip_organize staged)
   int rc = tsdf_to_device(h, h->frame_depth, depth, npx * sizeof(float));
   if (rc) return rc;
   if (color && (rc = tsdf_to_device(h, h->frame_bgra, bgra, npx * 4))) return rc;

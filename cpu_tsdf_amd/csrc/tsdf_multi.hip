@@ -481,6 +481,7 @@ static int upload_slot(tsdf_handle h) {
     tsdf_set_error("tsdf_hip_frame_commit without tsdf_hip_frame_begin");
     return TSDF_HIP_E_INVALID;
   }
+  m->frame_staged = 0;  // every slab's staging is overwritten, the first slab's organised frame with it
   for (size_t k = 0; k < m->slab.size(); ++k) {
     tsdf_handle s = m->slab[k];
     TSDF_ON_DEVICE(s->device);
@@ -706,6 +707,8 @@ static int fan_out_device(tsdf_handle h, const float *d_depth, const uint32_t *d
   if (src_slab >= 0) {
     TSDF_ON_DEVICE(m->slab[src_slab]->device);
     TSDF_HIP_TRY(hipEventRecord(m->ev[src_slab], m->slab[src_slab]->stream));
+  } else {
+    m->frame_staged = 0;  // a caller's frame goes into every slab's staging, over the first slab's organised frame
   }
   for (size_t k = 0; k < m->slab.size(); ++k) {
     tsdf_handle s = m->slab[k];
@@ -754,7 +757,7 @@ int tsdf_multi_integrate_staged(tsdf_handle h, const float T[12], uint64_t *n_ob
   if (const int rc_flush = tsdf_multi_flush(h)) return rc_flush;  // (frame pairing: slabs launch what they hold first)
   tsdf_hip_multi *m = h->multi;
   if (!m->frame_staged) {
-    tsdf_set_error("no staged frame: call tsdf_hip_organize first");
+    tsdf_set_error("no organised frame is staged: call tsdf_hip_organize first");
     return TSDF_HIP_E_INVALID;
   }
   tsdf_handle s0 = m->slab[0];

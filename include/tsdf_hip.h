@@ -212,7 +212,15 @@ int tsdf_hip_frame_commit(tsdf_handle h, const float cam_from_vol[12]);
  *   depth_out / bgra_out / n_valid   optional host copies of the frame (NaN = empty pixel) and the number
  *                of filled pixels; with all three NULL the call is asynchronous.
  * The frame stays in the handle; tsdf_hip_integrate_staged integrates it (same as tsdf_hip_integrate_device
- * on it). */
+ * on it), any number of times.  The staged frame is valid until the next call that writes the handle's frame
+ * staging, or until tsdf_hip_reset; after that tsdf_hip_integrate_staged returns TSDF_HIP_E_INVALID ("no organised
+ * frame is staged") until the next tsdf_hip_organize.  The writers: tsdf_hip_integrate; tsdf_hip_integrate_device[2]
+ * on one handle when the colour image does not lie behind its depth image in one allocation (the repack);
+ * tsdf_hip_integrate_device on a multi-GPU set always (the frame is copied into every slab's staging);
+ * tsdf_hip_integrate_async / tsdf_hip_frame_commit on a set without frame pairing.  On one handle, and on a set with
+ * frame pairing, the pipelined calls go through a ring of their own and leave the staged frame valid, as do
+ * tsdf_hip_integrate_device2 on a set and every call that takes no frame (queries, download, upload, raycast, march,
+ * shift, the setters). */
 int tsdf_hip_organize(tsdf_handle h, const float *xyz, size_t xyz_stride, const uint8_t *bgra,
                       size_t bgra_stride, size_t n, float cloud_units, int zero_nans,
                       const double world_to_cam[12], float *depth_out, uint8_t *bgra_out, uint64_t *n_valid);
