@@ -15,7 +15,7 @@ struct tsdf_hip_multi;     // tsdf_multi.hip: the Z-slab handles of a multi-GPU 
 // per-handle state of one feature each, defined in its own translation unit and created by the first call that needs it
 struct tsdf_occ_state;       // tsdf_occupied.hip: the sorted key list of tsdf_hip_occupied, a set's merged list
 struct tsdf_meshpost_state;  // tsdf_meshpost.hip: the working set of tsdf_hip_march_cleanup
-struct tsdf_flatten_state;   // tsdf_flatten.hip: the indexed mesh of tsdf_hip_march_flatten and its working set
+struct tsdf_flatten_state;   // tsdf_meshgrid.h: the indexed mesh of tsdf_hip_march_flatten and its working set
 
 struct tsdf_hip_volume {
   // non-null: this handle is a SET of Z-slab handles on several GPUs (tsdf_hip_create_multi) and owns no voxel plane
@@ -309,6 +309,8 @@ int tsdf_ensure_scratch(tsdf_hip_volume *v, size_t bytes);
 // `src` has been consumed, the device copy being ordered on the handle's stream like any other work.
 int tsdf_to_host(tsdf_hip_volume *v, void *dst, const void *dev_src, size_t bytes);
 int tsdf_to_device(tsdf_hip_volume *v, void *dev_dst, const void *src, size_t bytes);
+// Is `p` host memory the runtime knows as pinned?  (What these two, and the mesh passes' mp_to_host / mp_to_device, copy directly.)
+bool tsdf_is_pinned_host(const void *p);
 void tsdf_pipeline_destroy(tsdf_hip_volume *v);
 // Free v->occ / v->mp / v->fl and null them (free_volume; a handle that never ran the feature has none).  The mesh passes
 // of a set keep their device memory on the first slab's device, so these run before tsdf_multi_free.

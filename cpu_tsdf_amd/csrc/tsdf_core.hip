@@ -332,7 +332,7 @@ static int bounce_wait(tsdf_hip_volume *v, int slot) {
 
 // Is `p` host memory the runtime already knows as pinned (hipHostMalloc / hipHostRegister / tsdf_hip_host_alloc)?
 // Then the DMA engine can write it directly and the bounce buffer -- one host memcpy per transfer -- is skipped.
-static bool is_pinned_host(const void *p) {
+bool tsdf_is_pinned_host(const void *p) {
   hipPointerAttribute_t attr;
   if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
     (void)hipGetLastError();  // an ordinary pageable pointer: not an error
@@ -343,7 +343,7 @@ static bool is_pinned_host(const void *p) {
 
 int tsdf_to_host(tsdf_hip_volume *v, void *dst, const void *dev_src, size_t bytes) {
   if (!bytes) return TSDF_HIP_OK;
-  if (bytes >= (64u << 10) && is_pinned_host(dst)) {
+  if (bytes >= (64u << 10) && tsdf_is_pinned_host(dst)) {
     TSDF_HIP_TRY(hipMemcpyAsync(dst, dev_src, bytes, hipMemcpyDeviceToHost, v->stream));
     TSDF_HIP_TRY(hipStreamSynchronize(v->stream));
     return TSDF_HIP_OK;
@@ -375,7 +375,7 @@ int tsdf_to_host(tsdf_hip_volume *v, void *dst, const void *dev_src, size_t byte
 
 int tsdf_to_device(tsdf_hip_volume *v, void *dev_dst, const void *src, size_t bytes) {
   if (!bytes) return TSDF_HIP_OK;
-  if (bytes >= (64u << 10) && is_pinned_host(src)) {
+  if (bytes >= (64u << 10) && tsdf_is_pinned_host(src)) {
     // (the caller may reuse `src` when the call returns, as with the bounce path: wait for the copy)
     TSDF_HIP_TRY(hipMemcpyAsync(dev_dst, src, bytes, hipMemcpyHostToDevice, v->stream));
     TSDF_HIP_TRY(hipStreamSynchronize(v->stream));

@@ -20,13 +20,13 @@
 //   k_dc_faces     per face: the remapped corners, the degenerate flag, and the sorted triple as two sort keys
 //   rocprim sort   twice, stable, least significant key first (the highest corner, then lowest << b | middle with the
 //                  degenerate flag on top, b = bits of the cluster count): equal triples are contiguous, lowest face first
-//   k_dc_keep      the head of a run of equal triples survives; scan + k_mp_compact keep the order
+//   k_dc_keep      the head of a run of equal triples survives; mp_compact_faces (scan + k_mp_compact) keeps the order
+// The cell key, the face remap, the working set, the handle-less call and the indexed mesh of a handle are shared with the
+// other two mesh passes (tsdf_meshgrid.h / .hip).
 // Cost of k_dc_reduce: a lane's time is its cluster's size, and a wave's that of its largest cluster.  A marched mesh has tens
 // to a few hundred members per cluster (56 at most at a cell of 2 voxels, 175 at 4, on the 32^3 test scene); a cell size that
 // puts ALL vertices into one cell makes ONE lane walk the whole mesh, as slow as the host pass and in one launch.
 // Gather-bound walks and radix sorts: no MFMA, no LDS.
-#include <string.h>
-
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -45,7 +45,7 @@
 #define DC_C_KEPT 4
 static_assert(DC_C_KEPT < MP_IDX_COUNTERS, "the counters of a handle's indexed-mesh passes share one allocation");
 
-static thread_local uint64_t g_dc_stats[4] = {0, 0, 0, 0};  // tsdf_hip_mesh_decimate_stats
+static thread_local MpStats g_dc_stats;  // tsdf_hip_mesh_decimate_stats
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
 static __global__ void __launch_bounds__(256)
@@ -53,20 +53,9 @@ k_dc_key(const float *__restrict__ verts, uint32_t n, double cell, uint64_t *__r
          unsigned long long *__restrict__ counters) {
   const uint32_t v = blockIdx.x * 256u + threadIdx.x;
   if (v >= n) return;
-  const float p[3] = {verts[3ull * v], verts[3ull * v + 1ull], verts[3ull * v + 2ull]};
-  uint64_t key = MP_NO_KEY;
-  if (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])) {
-    key = 0ull;
-    bool out = false;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const double c = floor((double)p[a] / cell);  // PointGrid::c
-      out = out || !(c >= -1048576.0 && c < 1048576.0);
-      key = (key << 21) | (uint64_t)((long long)(out ? 0.0 : c) & 0x1fffff);
-    }
-    if (out) counters[DC_C_RANGE] = 1ull;  // (every writer stores the same 1)
-  }
-  keys[v] = key;
+  bool out = false;
+  keys[v] = mp_cell_key(verts[3ull * v], verts[3ull * v + 1ull], verts[3ull * v + 2ull], cell, out);
+  if (out) counters[DC_C_RANGE] = 1ull;  // (every writer stores the same 1; the mesh is refused, whatever its keys hold)
   idx[v] = v;
 }
 
@@ -85,8 +74,7 @@ k_dc_heads(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ order
     head = dc_head(keys, i);
     first[order[i]] = head ? 1 : 0;  // the sort is stable: a segment's head is its lowest vertex
   }
-  const unsigned long long m = __ballot(head);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[DC_C_CLUSTERS], (unsigned long long)__popcll(m));
+  mp_wave_count(head, &counters[DC_C_CLUSTERS]);
 }
 
 // outidx: the exclusive scan of `first` over the input vertices (rule 2).  One lane per cluster.
@@ -137,23 +125,14 @@ k_dc_faces(const uint32_t *__restrict__ faces, uint32_t n_faces, uint64_t n_vert
   const uint32_t f = blockIdx.x * 256u + threadIdx.x;
   bool good = false;
   if (f < n_faces) {
-    uint64_t a = 3ull * f, bb = a + 1ull, c = a + 2ull;
-    if (faces) a = faces[3ull * f], bb = faces[3ull * f + 1ull], c = faces[3ull * f + 2ull];
-    uint32_t ra = 0u, rb = 0u, rc = 0u;
-    if (a >= n_verts || bb >= n_verts || c >= n_verts) {
-      counters[DC_C_BAD] = 1ull;  // (every writer stores the same 1)
-    } else {
-      ra = remap[a], rb = remap[bb], rc = remap[c];
-      good = ra != rb && rb != rc && rc != ra;
-    }
-    mapped[3ull * f] = ra, mapped[3ull * f + 1ull] = rb, mapped[3ull * f + 2ull] = rc;
-    const uint32_t lo = min(ra, min(rb, rc)), hi = max(ra, max(rb, rc)), mid = (uint32_t)(((uint64_t)ra + rb + rc) - lo - hi);
+    uint32_t r[3];
+    good = mp_face_remap(faces, f, n_verts, remap, mapped, r, &counters[DC_C_BAD]);
+    const uint32_t lo = min(r[0], min(r[1], r[2])), hi = max(r[0], max(r[1], r[2])), mid = (uint32_t)(((uint64_t)r[0] + r[1] + r[2]) - lo - hi);
     key_lm[f] = good ? ((uint64_t)lo << b) | (uint64_t)mid : 1ull << (2u * b);
     key_hi[f] = good ? hi : 0u;
     ord[f] = f;
   }
-  const unsigned long long m = __ballot(good);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[DC_C_NONDEG], (unsigned long long)__popcll(m));
+  mp_wave_count(good, &counters[DC_C_NONDEG]);
 }
 
 // the second key in the order the first sort left
@@ -180,8 +159,7 @@ k_dc_keep(const uint64_t *__restrict__ key_lm, const uint32_t *__restrict__ ord,
     if (!(key >> (2u * b))) k = i == 0u || key_lm[i - 1u] != key || dc_hi(mapped, ord[i - 1u]) != dc_hi(mapped, f);
     keep[f] = k ? 1 : 0;
   }
-  const unsigned long long m = __ballot(k);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[DC_C_KEPT], (unsigned long long)__popcll(m));
+  mp_wave_count(k, &counters[DC_C_KEPT]);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
@@ -196,29 +174,17 @@ struct DcLayout {
 };
 
 static int dc_layout(size_t n, size_t f, hipStream_t s, DcLayout &L) {
-  size_t t[5] = {0, 0, 0, 0, 0};
-  TSDF_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t[0], (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                                         std::max(n, f), 0u, 64u, s));
-  TSDF_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t[1], (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, f, 0u, 32u,
-                                         s));
-  TSDF_HIP_TRY(rocprim::exclusive_scan(nullptr, t[2], MpKeepIt(nullptr, MpKeepCount()), (uint32_t *)nullptr, 0u, std::max(n, f),
-                                       rocprim::plus<uint32_t>(), s));
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += mp_up(bytes);
-    return at;
-  };
+  if (const int rc = mp_tmp_bytes(std::max(n, f), f, 0, std::max(n, f), s, &L.tmp_bytes)) return rc;
+  MpTake take;
   L.remap = take(n * 4), L.mapped = take(f * 12), L.faces = take(f * 12), L.keep = take(f), L.offset = take(f * 4);
-  L.tmp_bytes = *std::max_element(t, t + 5);
   L.tmp = take(L.tmp_bytes);
-  const size_t shared = o;
+  const size_t shared = take.o;
   L.key_a = take(n * 8), L.key_b = take(n * 8), L.idx_a = take(n * 4), L.idx_b = take(n * 4), L.first = take(n), L.outidx = take(n * 4);
-  const size_t end_v = o;
-  o = shared;
+  const size_t end_v = take.o;
+  take.o = shared;
   L.key_lm = take(f * 8), L.lm_a = take(f * 8), L.lm_b = take(f * 8), L.hi_a = take(f * 4), L.hi_b = take(f * 4), L.ord_a = take(f * 4),
   L.ord_b = take(f * 4);
-  L.total = std::max(end_v, o);
+  L.total = std::max(end_v, take.o);
   return TSDF_HIP_OK;
 }
 
@@ -234,10 +200,7 @@ static int dc_core(MpWork &w, hipStream_t s, const float *d_verts, const uint8_t
                    float cell_size, DcLayout &L, uint64_t *n_out, uint64_t *n_kept, const char *who) {
   const uint32_t n = (uint32_t)n_verts, nf = (uint32_t)n_faces;
   int rc = dc_layout(n, nf, s, L);
-  if (rc || (rc = mp_reserve(&w.buf, &w.cap, L.total, s, "mesh decimate"))) return rc;
-  if (!w.counters) TSDF_HIP_TRY(hipMalloc(&w.counters, MP_IDX_COUNTERS * sizeof(unsigned long long)));
-  for (int i = 0; i < 2; ++i)
-    if (!w.ev[i]) TSDF_HIP_TRY(hipEventCreate(&w.ev[i]));
+  if (rc || (rc = mp_reserve(&w.buf, &w.cap, L.total, s, "mesh decimate")) || (rc = mp_work_begin(w, MP_IDX_COUNTERS, 2, s))) return rc;
   char *b = (char *)w.buf;
   uint64_t *key_a = (uint64_t *)(b + L.key_a), *keys = (uint64_t *)(b + L.key_b);
   uint32_t *idx_a = (uint32_t *)(b + L.idx_a), *order = (uint32_t *)(b + L.idx_b), *outidx = (uint32_t *)(b + L.outidx);
@@ -246,7 +209,6 @@ static int dc_core(MpWork &w, hipStream_t s, const float *d_verts, const uint8_t
   uint8_t *first = (uint8_t *)(b + L.first), *keep = (uint8_t *)(b + L.keep);
   const dim3 blk(256), grid_n((n + 255u) / 256u), grid_f((nf + 255u) / 256u);
 
-  TSDF_HIP_TRY(hipMemsetAsync(w.counters, 0, MP_IDX_COUNTERS * sizeof(unsigned long long), s));
   TSDF_HIP_TRY(hipEventRecord(w.ev[0], s));
   hipLaunchKernelGGL(k_dc_key, grid_n, blk, 0, s, d_verts, n, (double)cell_size, key_a, idx_a, w.counters);
   TSDF_HIP_TRY(hipGetLastError());
@@ -298,11 +260,7 @@ static int dc_core(MpWork &w, hipStream_t s, const float *d_verts, const uint8_t
     TSDF_HIP_TRY(rocprim::radix_sort_pairs(b + L.tmp, tmp_bytes, lm_a, lm_b, ord_b, ord_a, (size_t)nf, 0u, bits_lm, s));
     hipLaunchKernelGGL(k_dc_keep, grid_f, blk, 0, s, lm_b, ord_a, mapped, nf, bits, keep, w.counters);
     TSDF_HIP_TRY(hipGetLastError());
-    tmp_bytes = L.tmp_bytes;
-    TSDF_HIP_TRY(rocprim::exclusive_scan(b + L.tmp, tmp_bytes, MpKeepIt(keep, MpKeepCount()), offset, 0u, (size_t)nf, rocprim::plus<uint32_t>(), s));
-    hipLaunchKernelGGL((k_mp_compact<uint32_t, 3>), dim3((unsigned)((3ull * nf + 255ull) / 256ull)), blk, 0, s, mapped, keep, offset, 3ull * nf,
-                       faces_out);
-    TSDF_HIP_TRY(hipGetLastError());
+    if ((rc = mp_compact_faces(s, b + L.tmp, L.tmp_bytes, mapped, keep, offset, nf, faces_out))) return rc;
   }
   TSDF_HIP_TRY(hipEventRecord(w.ev[1], s));
   TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, sizeof counts, hipMemcpyDeviceToHost, s));
@@ -313,7 +271,7 @@ static int dc_core(MpWork &w, hipStream_t s, const float *d_verts, const uint8_t
   }
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, w.ev[0], w.ev[1]);
-  g_dc_stats[0] = n, g_dc_stats[1] = m, g_dc_stats[2] = counts[DC_C_NONDEG] - counts[DC_C_KEPT], g_dc_stats[3] = (uint64_t)(ms * 1000.f);
+  g_dc_stats.set(n, m, counts[DC_C_NONDEG] - counts[DC_C_KEPT], (uint64_t)(ms * 1000.f));
   *n_out = m;
   *n_kept = counts[DC_C_KEPT];
   return TSDF_HIP_OK;
@@ -324,14 +282,8 @@ static int dc_check_args(float cell_size, uint64_t n_verts, uint64_t n_faces, co
     tsdf_set_error(std::string(who) + ": cell_size must be finite and positive");
     return TSDF_HIP_E_INVALID;
   }
-  if (n_verts > (1ull << 31) || n_faces > (1ull << 31)) {
-    tsdf_set_error(std::string(who) + ": vertex and face indices are 32-bit; more than 2^31 vertices or faces are not accepted");
-    return TSDF_HIP_E_INVALID;
-  }
-  return TSDF_HIP_OK;
+  return mp_check_counts(who, n_faces, &n_verts);
 }
-
-static void dc_zero_stats() { g_dc_stats[0] = g_dc_stats[1] = g_dc_stats[2] = g_dc_stats[3] = 0; }
 
 // tsdf_hip_mesh_decimate, and for a set also the faces' keep flags (n_faces bytes; nullable)
 static int dc_mesh(int device, const float *verts, const uint8_t *rgb, uint64_t n_verts, const uint32_t *faces, uint64_t n_faces, float cell_size,
@@ -356,54 +308,29 @@ static int dc_mesh(int device, const float *verts, const uint8_t *rgb, uint64_t 
       tsdf_set_error("tsdf_hip_mesh_decimate: a face names a vertex index >= n_verts");
       return TSDF_HIP_E_INVALID;
     }
-    dc_zero_stats();
+    g_dc_stats.zero();
     return TSDF_HIP_OK;
   }
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-    (void)hipGetLastError();
-    return TSDF_HIP_E_NODEVICE;
-  }
-  if (device >= n_dev) return TSDF_HIP_E_INVALID;
-  TSDF_ON_DEVICE(device);
-  // everything this call allocates goes when it returns: there is no handle to keep it for
-  struct Call {
-    hipStream_t s = nullptr;
-    void *in = nullptr;
-    MpWork work;
-    MpStage stage;
-    ~Call() {
-      if (s) (void)hipStreamSynchronize(s);
-      mp_work_free(work);
-      if (in) (void)hipFree(in);
-      if (s) (void)hipStreamDestroy(s);
-    }
-  } c;
-  TSDF_HIP_TRY(hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking));
+  MpCall c;
   const size_t b_verts = mp_up((size_t)n_verts * 12), b_rgb = rgb ? mp_up((size_t)n_verts * 3) : 0, b_faces = faces ? (size_t)n_faces * 12 : 0;
-  if (hipMalloc(&c.in, b_verts + b_rgb + b_faces) != hipSuccess) {
-    c.in = nullptr;
-    (void)hipGetLastError();
-    tsdf_set_error("tsdf_hip_mesh_decimate: " + std::to_string(b_verts + b_rgb + b_faces) + " bytes of device memory for the mesh are not available");
-    return TSDF_HIP_E_NOMEM;
-  }
+  int rc = c.open(device, b_verts + b_rgb + b_faces, who);
+  if (rc) return rc;
   float *d_verts = (float *)c.in;
   uint8_t *d_rgb = rgb ? (uint8_t *)c.in + b_verts : nullptr;
   uint32_t *d_faces = faces && n_faces ? (uint32_t *)((char *)c.in + b_verts + b_rgb) : nullptr;
-  int rc = mp_to_device(c.stage, d_verts, verts, (size_t)n_verts * 12, c.s);
-  if (!rc && d_rgb) rc = mp_to_device(c.stage, d_rgb, rgb, (size_t)n_verts * 3, c.s);
-  if (!rc && d_faces) rc = mp_to_device(c.stage, d_faces, faces, b_faces, c.s);
-  if (rc) return rc;
+  if ((rc = c.upload(d_verts, verts, (size_t)n_verts * 12)) || (d_rgb && (rc = c.upload(d_rgb, rgb, (size_t)n_verts * 3))) ||
+      (d_faces && (rc = c.upload(d_faces, faces, b_faces))))
+    return rc;
   DcLayout L;
   uint64_t m = 0, kept = 0;
   if ((rc = dc_core(c.work, c.s, d_verts, d_rgb, n_verts, d_faces, n_faces, cell_size, L, &m, &kept, who))) return rc;
   const char *b = (const char *)c.work.buf, *o = (const char *)c.work.cells;
-  if (remap && (rc = mp_to_host(c.stage, remap, b + L.remap, (size_t)n_verts * 4, c.s))) return rc;
-  if (out_verts && (rc = mp_to_host(c.stage, out_verts, o, (size_t)m * 12, c.s))) return rc;
-  if (out_rgb && (rc = mp_to_host(c.stage, out_rgb, o + L.c_rgb, (size_t)m * 3, c.s))) return rc;
-  if (counts && (rc = mp_to_host(c.stage, counts, o + L.c_counts, (size_t)m * 4, c.s))) return rc;
-  if (out_faces && (rc = mp_to_host(c.stage, out_faces, b + L.faces, (size_t)kept * 12, c.s))) return rc;
-  if (keep && n_faces && (rc = mp_to_host(c.stage, keep, b + L.keep, (size_t)n_faces, c.s))) return rc;
+  if (remap && (rc = c.download(remap, b + L.remap, (size_t)n_verts * 4))) return rc;
+  if (out_verts && (rc = c.download(out_verts, o, (size_t)m * 12))) return rc;
+  if (out_rgb && (rc = c.download(out_rgb, o + L.c_rgb, (size_t)m * 3))) return rc;
+  if (counts && (rc = c.download(counts, o + L.c_counts, (size_t)m * 4))) return rc;
+  if (out_faces && (rc = c.download(out_faces, b + L.faces, (size_t)kept * 12))) return rc;
+  if (keep && n_faces && (rc = c.download(keep, b + L.keep, (size_t)n_faces))) return rc;
   if (n_out_verts) *n_out_verts = m;
   if (n_out_faces) *n_out_faces = kept;
   return TSDF_HIP_OK;
@@ -432,14 +359,7 @@ static int dc_multi(tsdf_handle h, tsdf_flatten_state *st, float cell_size) {
   const int rc = dc_mesh(tsdf_multi_first(h)->device, verts, rgb, 3 * n, nullptr, n, cell_size, nullptr, st->h_verts.data(),
                          rgb ? st->h_rgb.data() : nullptr, nullptr, &m, st->h_faces.data(), &kept, keep.data());
   if (rc) return rc;
-  st->h_verts.resize((size_t)m * 3);
-  st->h_rgb.resize(rgb ? (size_t)m * 3 : 0);
-  st->h_faces.resize((size_t)kept * 3);
-  st->h_cell.clear();
-  for (uint64_t f = 0; f < n; ++f)
-    if (keep[f]) st->h_cell.push_back(cell[f]);
-  st->has_rgb = rgb != nullptr;
-  st->n_verts = m, st->n_faces = kept;
+  mp_idx_set_host(st, rgb != nullptr, cell, n, m, kept, keep.data());
   return TSDF_HIP_OK;
 }
 
@@ -448,56 +368,30 @@ extern "C" int tsdf_hip_march_decimate(tsdf_handle h, float cell_size, uint64_t 
   if (!h) return TSDF_HIP_E_INVALID;
   if (n_verts) *n_verts = 0;
   if (n_faces) *n_faces = 0;
-  if (const int rc = dc_check_args(cell_size, 0, 0, who)) return rc;
-  if (!h->mc_valid) {
-    tsdf_set_error("tsdf_hip_march_decimate: the last tsdf_hip_march on this handle did not succeed, or none has run");
-    return TSDF_HIP_E_INVALID;
-  }
-  if (!h->fl) h->fl = new tsdf_flatten_state();
-  tsdf_flatten_state *st = h->fl;
-  st->valid = false;
-  const uint64_t n = h->mc_ntri;
-  if (const int rc = dc_check_args(cell_size, 3 * n, n, who)) return rc;
+  tsdf_flatten_state *st = nullptr;
+  uint64_t n = 0;
+  int rc = dc_check_args(cell_size, 0, 0, who);
+  if (rc || (rc = mp_idx_begin(h, who, &st, &n))) return rc;
   if (!n) {
-    dc_zero_stats();
-    st->n_verts = st->n_faces = 0;
-    st->valid = true;
-    return TSDF_HIP_OK;
-  }
-  if (h->multi) {
-    if (const int rc = dc_multi(h, st, cell_size)) return rc;
+    g_dc_stats.zero();
+  } else if (h->multi) {
+    if ((rc = dc_multi(h, st, cell_size))) return rc;
   } else {
     TSDF_ENTER(h);
     DcLayout L;
     uint64_t m = 0, kept = 0;
     const uint8_t *d_rgb = h->mc_has_rgb ? h->mc_rgb : nullptr;
-    int rc = dc_core(st->work, h->stream, h->mc_verts, d_rgb, 3 * n, nullptr, n, cell_size, L, &m, &kept, who);
-    if (rc) return rc;
-    // the soup stays as it is: the indexed mesh has buffers of its own, laid out as tsdf_hip_march_flatten leaves them
-    st->o_faces = mp_up((size_t)m * 12), st->o_cell = st->o_faces + mp_up((size_t)kept * 12), st->o_rgb = st->o_cell + mp_up((size_t)kept * 8);
-    if ((rc = mp_reserve(&st->out, &st->out_cap, st->o_rgb + mp_up((size_t)m * 3), h->stream, "mesh decimate"))) return rc;
+    if ((rc = dc_core(st->work, h->stream, h->mc_verts, d_rgb, 3 * n, nullptr, n, cell_size, L, &m, &kept, who))) return rc;
+    if ((rc = mp_idx_layout(h, st, m, kept, "mesh decimate"))) return rc;
     const char *b = (const char *)st->work.buf, *c = (const char *)st->work.cells;
     char *o = (char *)st->out;
     TSDF_HIP_TRY(hipMemcpyAsync(o, c, (size_t)m * 12, hipMemcpyDeviceToDevice, h->stream));
     if (d_rgb) TSDF_HIP_TRY(hipMemcpyAsync(o + st->o_rgb, c + L.c_rgb, (size_t)m * 3, hipMemcpyDeviceToDevice, h->stream));
-    if (kept) {
-      TSDF_HIP_TRY(hipMemcpyAsync(o + st->o_faces, b + L.faces, (size_t)kept * 12, hipMemcpyDeviceToDevice, h->stream));
-      hipLaunchKernelGGL((k_mp_compact<uint64_t, 1>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->mc_cell,
-                         (const uint8_t *)(b + L.keep), (const uint32_t *)(b + L.offset), n, (uint64_t *)(o + st->o_cell));
-      TSDF_HIP_TRY(hipGetLastError());
-    }
-    TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
-    st->has_rgb = h->mc_has_rgb;
-    st->n_verts = m, st->n_faces = kept;
+    if ((rc = mp_idx_fill(h, st, m, kept, (const uint32_t *)(b + L.faces), (const uint8_t *)(b + L.keep), (const uint32_t *)(b + L.offset)))) return rc;
   }
-  st->valid = true;
-  if (n_verts) *n_verts = st->n_verts;
-  if (n_faces) *n_faces = st->n_faces;
-  return TSDF_HIP_OK;
+  return mp_idx_end(st, n_verts, n_faces);
 }
 
 extern "C" int tsdf_hip_mesh_decimate_stats(uint64_t out[4]) {
-  if (!out) return TSDF_HIP_E_INVALID;
-  for (int i = 0; i < 4; ++i) out[i] = g_dc_stats[i];
-  return TSDF_HIP_OK;
+  return g_dc_stats.copy_out(out);
 }

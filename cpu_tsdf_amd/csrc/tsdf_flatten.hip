@@ -14,10 +14,10 @@
 // Kernels:
 //   k_fl_key       the host's cell key per finite vertex (a non-finite vertex is in no cell: a seed that merges nothing)
 //   rocprim sort   (key, vertex) pairs, stable; k_fl_gather writes the positions in sorted order and marks run heads, a scan
-//                  numbers the cells, k_mp_cells / k_mp_cellnbr (tsdf_meshgrid.h) build the cell table
+//                  numbers the cells, mp_cells_build (tsdf_meshgrid.hip) makes the cell table
 //   k_fl_round     one round of rule 1 over the list of still undecided vertices, which it compacts for the next round
 //   k_fl_remap     rule 2; rocprim scan: rule 3; k_fl_out: remap and the seed list by output index
-//   k_fl_faces     per face: remapped corners, keep = all three differ; scan + k_mp_compact keep the order
+//   k_fl_faces     per face: remapped corners, keep = all three differ; mp_compact_faces (scan + k_mp_compact) keeps the order
 // The state word of a vertex carries the round that decided it, and a round ignores what the same round decided: every
 // round sees exactly the state the round before left, whatever the order the workgroups run in (so the number of rounds is
 // the depth of the dependency chains, the same in every run), and no kernel waits for another workgroup.
@@ -45,9 +45,10 @@
 #define FL_COUNTERS MP_IDX_COUNTERS
 #define FL_MAX_ROUNDS 0x7fffffffu  // the state word holds round << 1
 
-// (tsdf_flatten_state, the indexed mesh of a handle, is in tsdf_meshgrid.h: tsdf_decimate.hip writes it too)
+// (tsdf_flatten_state, the indexed mesh of a handle, and the mp_idx_* that write it are in tsdf_meshgrid.h / .hip:
+// tsdf_decimate.hip writes it too)
 
-static thread_local uint64_t g_fl_stats[4] = {0, 0, 0, 0};  // tsdf_hip_mesh_flatten_stats
+static thread_local MpStats g_fl_stats;  // tsdf_hip_mesh_flatten_stats
 
 void tsdf_flatten_invalidate(tsdf_hip_volume *v) {
   if (v->fl) v->fl->valid = false;
@@ -70,19 +71,13 @@ k_fl_key(const float *__restrict__ verts, uint32_t n, double cell, uint64_t *__r
   bool fin = false;
   if (v < n) {
     const float x = verts[3ull * v], y = verts[3ull * v + 1ull], z = verts[3ull * v + 2ull];
-    uint64_t key = MP_NO_KEY;
-    if (isfinite(x) && isfinite(y) && isfinite(z)) {
-      // PointGrid::c / key (mesh_post.h:59-62): floor((double)v / cell), 21 bits per axis.  Cells that alias under the masks
-      // share a bucket, as on the host; the distance test rejects what is far.
-      const long long cx = (long long)floor((double)x / cell), cy = (long long)floor((double)y / cell), cz = (long long)floor((double)z / cell);
-      key = ((uint64_t)(cx & 0x1fffff) << 42) | ((uint64_t)(cy & 0x1fffff) << 21) | (uint64_t)(cz & 0x1fffff);
-      fin = true;
-    }
+    bool wraps = false;  // (cells that alias under the key's masks share a bucket, as on the host)
+    const uint64_t key = mp_cell_key(x, y, z, cell, wraps);
+    fin = key != MP_NO_KEY;
     keys[v] = key;
     idx[v] = v;
   }
-  const unsigned long long m = __ballot(fin);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[FL_C_FINITE], (unsigned long long)__popcll(m));
+  mp_wave_count(fin, &counters[FL_C_FINITE]);
 }
 
 // sorted position i -> position of the vertex there, and "first vertex of its cell"
@@ -94,7 +89,7 @@ k_fl_gather(const float *__restrict__ verts, const uint32_t *__restrict__ order,
   const uint64_t key = keys[i];
   const uint64_t v = order[i];
   pos[i] = make_float4(verts[3ull * v], verts[3ull * v + 1ull], verts[3ull * v + 2ull], 0.f);
-  head[i] = key != MP_NO_KEY && (i == 0u || keys[i - 1u] != key) ? 1u : 0u;
+  head[i] = mp_cell_head(keys, i, key);
 }
 
 // State of the vertex at a sorted position: 0 = undecided, else (round that decided it) << 1 | (1 = seed, 0 = merged).
@@ -173,8 +168,7 @@ k_fl_remap(const MpGrid g, uint32_t n, const uint32_t *__restrict__ order, const
     flag[me] = seed ? 1 : 0;
     seed_of[me] = best;
   }
-  const unsigned long long m = __ballot(seed);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[FL_C_SEEDS], (unsigned long long)__popcll(m));
+  mp_wave_count(seed, &counters[FL_C_SEEDS]);
 }
 
 // outidx: the exclusive scan of flag (rule 3)
@@ -194,20 +188,11 @@ k_fl_faces(const uint32_t *__restrict__ faces, uint32_t n_faces, uint64_t n_vert
   const uint32_t f = blockIdx.x * 256u + threadIdx.x;
   bool k = false;
   if (f < n_faces) {
-    uint64_t a = 3ull * f, b = a + 1ull, c = a + 2ull;
-    if (faces) a = faces[3ull * f], b = faces[3ull * f + 1ull], c = faces[3ull * f + 2ull];
-    uint32_t ra = 0u, rb = 0u, rc = 0u;
-    if (a >= n_verts || b >= n_verts || c >= n_verts) {
-      counters[FL_C_BAD] = 1ull;  // (every writer stores the same 1)
-    } else {
-      ra = remap[a], rb = remap[b], rc = remap[c];
-      k = ra != rb && rb != rc && rc != ra;
-    }
-    mapped[3ull * f] = ra, mapped[3ull * f + 1ull] = rb, mapped[3ull * f + 2ull] = rc;
+    uint32_t r[3];
+    k = mp_face_remap(faces, f, n_verts, remap, mapped, r, &counters[FL_C_BAD]);
     keep[f] = k ? 1 : 0;
   }
-  const unsigned long long m = __ballot(k);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[FL_C_KEPT], (unsigned long long)__popcll(m));
+  mp_wave_count(k, &counters[FL_C_KEPT]);
 }
 
 // output vertex o = the seed's position and, on the device-resident path, its colour
@@ -231,24 +216,13 @@ struct FlLayout {  // the arrays inside MpWork::buf
 };
 
 static int fl_layout(size_t n, size_t f, hipStream_t s, FlLayout &L) {
-  size_t t_sort = 0, t_scan = 0, t_scan2 = 0;
-  TSDF_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t_sort, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, n,
-                                         0u, 64u, s));
-  TSDF_HIP_TRY(rocprim::inclusive_scan(nullptr, t_scan, (uint32_t *)nullptr, (uint32_t *)nullptr, n, rocprim::plus<uint32_t>(), s));
-  TSDF_HIP_TRY(rocprim::exclusive_scan(nullptr, t_scan2, MpKeepIt(nullptr, MpKeepCount()), (uint32_t *)nullptr, 0u, std::max(n, f),
-                                       rocprim::plus<uint32_t>(), s));
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += mp_up(bytes);
-    return at;
-  };
+  if (const int rc = mp_tmp_bytes(n, 0, n, std::max(n, f), s, &L.tmp_bytes)) return rc;
+  MpTake take;
   L.key_a = take(n * 8), L.key_b = take(n * 8), L.idx_a = take(n * 4), L.idx_b = take(n * 4), L.pos = take(n * 16);
   L.cellno = take(n * 4), L.flag = take(n), L.remap = take(n * 4), L.seeds = take(n * 4);
   L.mapped = take(f * 12), L.faces = take(f * 12), L.keep = take(f), L.offset = take(f * 4);
-  L.tmp_bytes = std::max(t_sort, std::max(t_scan, t_scan2));
   L.tmp = take(L.tmp_bytes);
-  L.total = o;
+  L.total = take.o;
   return TSDF_HIP_OK;
 }
 
@@ -259,10 +233,7 @@ static int fl_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
                    FlLayout &L, uint64_t *n_out, uint64_t *n_kept, const char *who) {
   const uint32_t n = (uint32_t)n_verts, nf = (uint32_t)n_faces;
   int rc = fl_layout(n, nf, s, L);
-  if (rc || (rc = mp_reserve(&w.buf, &w.cap, L.total, s, "mesh flatten"))) return rc;
-  if (!w.counters) TSDF_HIP_TRY(hipMalloc(&w.counters, FL_COUNTERS * sizeof(unsigned long long)));
-  for (int i = 0; i < 2; ++i)
-    if (!w.ev[i]) TSDF_HIP_TRY(hipEventCreate(&w.ev[i]));
+  if (rc || (rc = mp_reserve(&w.buf, &w.cap, L.total, s, "mesh flatten")) || (rc = mp_work_begin(w, FL_COUNTERS, 2, s))) return rc;
   char *b = (char *)w.buf;
   uint64_t *key_a = (uint64_t *)(b + L.key_a), *key_b = (uint64_t *)(b + L.key_b);
   uint32_t *idx_a = (uint32_t *)(b + L.idx_a), *order = (uint32_t *)(b + L.idx_b), *cellno = (uint32_t *)(b + L.cellno);
@@ -276,7 +247,6 @@ static int fl_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
   uint32_t *seed_of = (uint32_t *)key_b, *outidx = seed_of + n;
   const dim3 blk(256), grid_n((n + 255u) / 256u);
 
-  TSDF_HIP_TRY(hipMemsetAsync(w.counters, 0, FL_COUNTERS * sizeof(unsigned long long), s));
   TSDF_HIP_TRY(hipEventRecord(w.ev[0], s));
   hipLaunchKernelGGL(k_fl_key, grid_n, blk, 0, s, d_verts, n, (double)min_dist, key_a, idx_a, w.counters);
   TSDF_HIP_TRY(hipGetLastError());
@@ -294,21 +264,12 @@ static int fl_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
   const uint32_t n_fin = (uint32_t)counts[FL_C_FINITE];
   MpGrid g{pos, cellno, nullptr, nullptr, n_fin, 0.f};
   if (n_fin) {
-    const size_t o_start = mp_up((size_t)n_cells * 8), o_nbr = o_start + mp_up(((size_t)n_cells + 1) * 4);
-    if ((rc = mp_reserve(&w.cells, &w.cells_cap, o_nbr + (size_t)n_cells * 27 * 4, s, "mesh flatten"))) return rc;
-    uint64_t *cell_key = (uint64_t *)w.cells;
-    uint32_t *cell_start = (uint32_t *)((char *)w.cells + o_start);
-    int32_t *nbr = (int32_t *)((char *)w.cells + o_nbr);
-    hipLaunchKernelGGL(k_mp_cells, grid_n, blk, 0, s, key_b, head, cellno, n, cell_key, cell_start);
-    TSDF_HIP_TRY(hipGetLastError());
-    TSDF_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(cell_start + n_cells), (int)n_fin, 1, s));
-    hipLaunchKernelGGL(k_mp_cellnbr, dim3((unsigned)((27ull * n_cells + 255ull) / 256ull)), blk, 0, s, cell_key, n_cells, nbr);
-    TSDF_HIP_TRY(hipGetLastError());
+    if ((rc = mp_cells_reserve(w, n_cells, s, "mesh flatten")) || (rc = mp_cells_build(w, s, key_b, head, n, n_cells, g))) return rc;
     TSDF_HIP_TRY(hipMemsetAsync(state, 0, (size_t)n * 4, s));
     // mesh_post.h:96,103: the squared distance is compared with min_dist * min_dist AND with min_dist itself
     // (integrate.cpp:124), so with the smaller of the two; its root is <= min_dist, so the 27 cells hold every neighbour
     const float r2 = (float)((double)min_dist * (double)min_dist);
-    g.nbr = nbr, g.cell_start = cell_start, g.r2 = r2 < min_dist ? r2 : min_dist;
+    g.r2 = r2 < min_dist ? r2 : min_dist;
     // rule 1.  The host reads the list's length only once per batch of rounds; the rounds of a batch after the one that
     // emptied the list find nothing to do.
     uint32_t undecided = n_fin, round = 0u, batch = 4u;
@@ -341,11 +302,7 @@ static int fl_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
   if (nf) {
     hipLaunchKernelGGL(k_fl_faces, dim3((nf + 255u) / 256u), blk, 0, s, d_faces, nf, n_verts, remap, mapped, keep, w.counters);
     TSDF_HIP_TRY(hipGetLastError());
-    tmp_bytes = L.tmp_bytes;
-    TSDF_HIP_TRY(rocprim::exclusive_scan(b + L.tmp, tmp_bytes, MpKeepIt(keep, MpKeepCount()), offset, 0u, (size_t)nf, rocprim::plus<uint32_t>(), s));
-    hipLaunchKernelGGL((k_mp_compact<uint32_t, 3>), dim3((unsigned)((3ull * nf + 255ull) / 256ull)), blk, 0, s, mapped, keep, offset, 3ull * nf,
-                       faces_out);
-    TSDF_HIP_TRY(hipGetLastError());
+    if ((rc = mp_compact_faces(s, b + L.tmp, L.tmp_bytes, mapped, keep, offset, nf, faces_out))) return rc;
   }
   TSDF_HIP_TRY(hipEventRecord(w.ev[1], s));
   TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, sizeof counts, hipMemcpyDeviceToHost, s));
@@ -356,7 +313,7 @@ static int fl_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
   }
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, w.ev[0], w.ev[1]);
-  g_fl_stats[0] = n, g_fl_stats[1] = counts[FL_C_SEEDS], g_fl_stats[2] = counts[FL_C_ROUNDS], g_fl_stats[3] = (uint64_t)(ms * 1000.f);
+  g_fl_stats.set(n, counts[FL_C_SEEDS], counts[FL_C_ROUNDS], (uint64_t)(ms * 1000.f));
   *n_out = counts[FL_C_SEEDS];
   *n_kept = counts[FL_C_KEPT];
   return TSDF_HIP_OK;
@@ -367,14 +324,8 @@ static int fl_check_args(float min_dist, uint64_t n_verts, uint64_t n_faces, con
     tsdf_set_error(std::string(who) + ": min_dist must be finite and positive");
     return TSDF_HIP_E_INVALID;
   }
-  if (n_verts > (1ull << 31) || n_faces > (1ull << 31)) {
-    tsdf_set_error(std::string(who) + ": vertex and face indices are 32-bit; more than 2^31 vertices or faces are not accepted");
-    return TSDF_HIP_E_INVALID;
-  }
-  return TSDF_HIP_OK;
+  return mp_check_counts(who, n_faces, &n_verts);
 }
-
-static void fl_zero_stats() { g_fl_stats[0] = g_fl_stats[1] = g_fl_stats[2] = g_fl_stats[3] = 0; }
 
 extern "C" int tsdf_hip_mesh_flatten(int device, const float *verts, uint64_t n_verts, const uint32_t *faces, uint64_t n_faces, float min_dist,
                                      uint32_t *remap, uint32_t *seeds, uint64_t *n_out_verts, uint32_t *out_faces, uint64_t *n_out_faces) {
@@ -395,49 +346,23 @@ extern "C" int tsdf_hip_mesh_flatten(int device, const float *verts, uint64_t n_
       tsdf_set_error("tsdf_hip_mesh_flatten: a face names a vertex index >= n_verts");
       return TSDF_HIP_E_INVALID;
     }
-    fl_zero_stats();
+    g_fl_stats.zero();
     return TSDF_HIP_OK;
   }
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-    (void)hipGetLastError();
-    return TSDF_HIP_E_NODEVICE;
-  }
-  if (device >= n_dev) return TSDF_HIP_E_INVALID;
-  TSDF_ON_DEVICE(device);
-  // everything this call allocates goes when it returns: there is no handle to keep it for
-  struct Call {
-    hipStream_t s = nullptr;
-    void *in = nullptr;
-    MpWork work;
-    MpStage stage;
-    ~Call() {
-      if (s) (void)hipStreamSynchronize(s);
-      mp_work_free(work);
-      if (in) (void)hipFree(in);
-      if (s) (void)hipStreamDestroy(s);
-    }
-  } c;
-  TSDF_HIP_TRY(hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking));
+  MpCall c;
   const size_t b_verts = mp_up((size_t)n_verts * 12), b_faces = faces ? (size_t)n_faces * 12 : 0;
-  if (hipMalloc(&c.in, b_verts + b_faces) != hipSuccess) {
-    c.in = nullptr;
-    (void)hipGetLastError();
-    tsdf_set_error("tsdf_hip_mesh_flatten: " + std::to_string(b_verts + b_faces) + " bytes of device memory for the mesh are not available");
-    return TSDF_HIP_E_NOMEM;
-  }
+  int rc = c.open(device, b_verts + b_faces, "tsdf_hip_mesh_flatten");
+  if (rc) return rc;
   float *d_verts = (float *)c.in;
   uint32_t *d_faces = faces && n_faces ? (uint32_t *)((char *)c.in + b_verts) : nullptr;
-  int rc = mp_to_device(c.stage, d_verts, verts, (size_t)n_verts * 12, c.s);
-  if (!rc && d_faces) rc = mp_to_device(c.stage, d_faces, faces, b_faces, c.s);
-  if (rc) return rc;
+  if ((rc = c.upload(d_verts, verts, (size_t)n_verts * 12)) || (d_faces && (rc = c.upload(d_faces, faces, b_faces)))) return rc;
   FlLayout L;
   uint64_t m = 0, kept = 0;
   if ((rc = fl_core(c.work, c.s, d_verts, n_verts, d_faces, n_faces, min_dist, L, &m, &kept, "tsdf_hip_mesh_flatten"))) return rc;
   const char *b = (const char *)c.work.buf;
-  if (remap && (rc = mp_to_host(c.stage, remap, b + L.remap, (size_t)n_verts * 4, c.s))) return rc;
-  if (seeds && (rc = mp_to_host(c.stage, seeds, b + L.seeds, (size_t)m * 4, c.s))) return rc;
-  if (out_faces && (rc = mp_to_host(c.stage, out_faces, b + L.faces, (size_t)kept * 12, c.s))) return rc;
+  if (remap && (rc = c.download(remap, b + L.remap, (size_t)n_verts * 4))) return rc;
+  if (seeds && (rc = c.download(seeds, b + L.seeds, (size_t)m * 4))) return rc;
+  if (out_faces && (rc = c.download(out_faces, b + L.faces, (size_t)kept * 12))) return rc;
   if (n_out_verts) *n_out_verts = m;
   if (n_out_faces) *n_out_faces = kept;
   return TSDF_HIP_OK;
@@ -457,73 +382,46 @@ static int fl_multi(tsdf_handle h, tsdf_flatten_state *st, float min_dist) {
   const int rc = tsdf_hip_mesh_flatten(tsdf_multi_first(h)->device, verts, 3 * n, nullptr, n, min_dist, remap.data(), seeds.data(), &m,
                                        st->h_faces.data(), &kept);
   if (rc) return rc;
-  st->h_faces.resize((size_t)kept * 3);
-  st->h_verts.resize((size_t)m * 3);
-  st->h_rgb.resize(rgb ? (size_t)m * 3 : 0);
+  std::vector<uint8_t> keep((size_t)n);  // mesh_post.h:107-115, as k_fl_faces decided
+  for (uint64_t f = 0; f < n; ++f) {
+    const uint32_t a = remap[3 * f], b = remap[3 * f + 1], c = remap[3 * f + 2];
+    keep[f] = a != b && b != c && c != a;
+  }
+  mp_idx_set_host(st, rgb != nullptr, cell, n, m, kept, keep.data());
   for (uint64_t o = 0; o < m; ++o) {
     memcpy(&st->h_verts[3 * o], verts + 3ull * seeds[o], 3 * sizeof(float));
     if (rgb) memcpy(&st->h_rgb[3 * o], rgb + 3ull * seeds[o], 3);
   }
-  st->h_cell.clear();
-  for (uint64_t f = 0; f < n; ++f) {
-    const uint32_t a = remap[3 * f], b = remap[3 * f + 1], c = remap[3 * f + 2];
-    if (a != b && b != c && c != a) st->h_cell.push_back(cell[f]);
-  }
-  st->has_rgb = rgb != nullptr;
-  st->n_verts = m, st->n_faces = kept;
   return TSDF_HIP_OK;
 }
 
 extern "C" int tsdf_hip_march_flatten(tsdf_handle h, float min_dist, uint64_t *n_verts, uint64_t *n_faces) {
+  const char *who = "tsdf_hip_march_flatten";
   if (!h) return TSDF_HIP_E_INVALID;
   if (n_verts) *n_verts = 0;
   if (n_faces) *n_faces = 0;
-  if (const int rc = fl_check_args(min_dist, 0, 0, "tsdf_hip_march_flatten")) return rc;
-  if (!h->mc_valid) {
-    tsdf_set_error("tsdf_hip_march_flatten: the last tsdf_hip_march on this handle did not succeed, or none has run");
-    return TSDF_HIP_E_INVALID;
-  }
-  if (!h->fl) h->fl = new tsdf_flatten_state();
-  tsdf_flatten_state *st = h->fl;
-  st->valid = false;
-  const uint64_t n = h->mc_ntri;
-  if (const int rc = fl_check_args(min_dist, 3 * n, n, "tsdf_hip_march_flatten")) return rc;
+  tsdf_flatten_state *st = nullptr;
+  uint64_t n = 0;
+  int rc = fl_check_args(min_dist, 0, 0, who);
+  if (rc || (rc = mp_idx_begin(h, who, &st, &n))) return rc;
   if (!n) {
-    fl_zero_stats();
-    st->n_verts = st->n_faces = 0;
-    st->valid = true;
-    return TSDF_HIP_OK;
-  }
-  if (h->multi) {
-    if (const int rc = fl_multi(h, st, min_dist)) return rc;
+    g_fl_stats.zero();
+  } else if (h->multi) {
+    if ((rc = fl_multi(h, st, min_dist))) return rc;
   } else {
     TSDF_ENTER(h);
     FlLayout L;
     uint64_t m = 0, kept = 0;
-    int rc = fl_core(st->work, h->stream, h->mc_verts, 3 * n, nullptr, n, min_dist, L, &m, &kept, "tsdf_hip_march_flatten");
-    if (rc) return rc;
-    // the soup stays as it is: the indexed mesh gets buffers of its own
-    st->o_faces = mp_up((size_t)m * 12), st->o_cell = st->o_faces + mp_up((size_t)kept * 12), st->o_rgb = st->o_cell + mp_up((size_t)kept * 8);
-    if ((rc = mp_reserve(&st->out, &st->out_cap, st->o_rgb + mp_up((size_t)m * 3), h->stream, "mesh flatten"))) return rc;
-    char *b = (char *)st->work.buf, *o = (char *)st->out;
-    const dim3 blk(256);
-    hipLaunchKernelGGL(k_fl_gather_out, dim3((unsigned)((m + 255) / 256)), blk, 0, h->stream, h->mc_verts, h->mc_has_rgb ? h->mc_rgb : nullptr,
+    if ((rc = fl_core(st->work, h->stream, h->mc_verts, 3 * n, nullptr, n, min_dist, L, &m, &kept, who))) return rc;
+    if ((rc = mp_idx_layout(h, st, m, kept, "mesh flatten"))) return rc;
+    const char *b = (const char *)st->work.buf;
+    char *o = (char *)st->out;
+    hipLaunchKernelGGL(k_fl_gather_out, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, h->mc_verts, h->mc_has_rgb ? h->mc_rgb : nullptr,
                        (const uint32_t *)(b + L.seeds), (uint32_t)m, (float *)o, (uint8_t *)(o + st->o_rgb));
     TSDF_HIP_TRY(hipGetLastError());
-    if (kept) {
-      TSDF_HIP_TRY(hipMemcpyAsync(o + st->o_faces, b + L.faces, (size_t)kept * 12, hipMemcpyDeviceToDevice, h->stream));
-      hipLaunchKernelGGL((k_mp_compact<uint64_t, 1>), dim3((unsigned)((n + 255) / 256)), blk, 0, h->stream, h->mc_cell, (const uint8_t *)(b + L.keep),
-                         (const uint32_t *)(b + L.offset), n, (uint64_t *)(o + st->o_cell));
-      TSDF_HIP_TRY(hipGetLastError());
-    }
-    TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
-    st->has_rgb = h->mc_has_rgb;
-    st->n_verts = m, st->n_faces = kept;
+    if ((rc = mp_idx_fill(h, st, m, kept, (const uint32_t *)(b + L.faces), (const uint8_t *)(b + L.keep), (const uint32_t *)(b + L.offset)))) return rc;
   }
-  st->valid = true;
-  if (n_verts) *n_verts = st->n_verts;
-  if (n_faces) *n_faces = st->n_faces;
-  return TSDF_HIP_OK;
+  return mp_idx_end(st, n_verts, n_faces);
 }
 
 extern "C" int tsdf_hip_march_fetch_indexed(tsdf_handle h, float *verts, uint8_t *rgb, uint32_t *faces, uint64_t *cell) {
@@ -559,7 +457,5 @@ extern "C" int tsdf_hip_march_fetch_indexed(tsdf_handle h, float *verts, uint8_t
 }
 
 extern "C" int tsdf_hip_mesh_flatten_stats(uint64_t out[4]) {
-  if (!out) return TSDF_HIP_E_INVALID;
-  for (int i = 0; i < 4; ++i) out[i] = g_fl_stats[i];
-  return TSDF_HIP_OK;
+  return g_fl_stats.copy_out(out);
 }

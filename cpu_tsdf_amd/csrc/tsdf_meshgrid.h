@@ -1,19 +1,12 @@
-// Internal: what the two mesh passes on the GPU -- tsdf_meshpost.hip (cleanupMesh) and tsdf_flatten.hip (flattenVertices) --
-// share: the uniform grid of cpu_tsdf::mesh_post::PointGrid (csrc/prog/mesh_post.h) as device arrays, and the plumbing
-// around it.  Both passes sort their points (face centroids / vertices) by the host's cell key, and then
-//   k_mp_cells     one entry per occupied cell: key and first sorted position
-//   k_mp_cellnbr   each cell's 27 neighbour cells as indices into that table
-//   mp_for_links   the points strictly within the radius of point i, from those 27 cells: the host's forNeighbours
-//   k_mp_compact   stable compaction of per-face records behind a scan of the keep flags
-//   MpWork / mp_reserve / mp_to_device / mp_to_host   the working set, and caller memory (pinned: direct; pageable: staged)
-//   tsdf_flatten_state   the indexed mesh of a handle, which tsdf_hip_march_flatten and tsdf_hip_march_decimate
-//                  (tsdf_decimate.hip: vertex clustering, on the same cell keys, sort and compaction) both write
-// Everything here is static: each translation unit compiles its own copy.
+// Internal: what the three mesh passes on the GPU -- tsdf_meshpost.hip (cleanupMesh), tsdf_flatten.hip (flattenVertices) and
+// tsdf_decimate.hip (decimateMesh) -- share.  Declared here and defined in tsdf_meshgrid.hip: the cell table (the uniform grid
+// of cpu_tsdf::mesh_post::PointGrid, csrc/prog/mesh_post.h, over points sorted by the host's cell key), the working set of a
+// pass, a handle-less call with its copies of caller memory (pinned: direct; pageable: staged), and the indexed mesh of a
+// handle.  Defined here, because the passes' own kernels inline or instantiate them: mp_cell_key, mp_for_links (the host's
+// forNeighbours), mp_face_remap and k_mp_compact.
 #pragma once
 
-#include <string.h>
-
-#include <algorithm>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -26,37 +19,26 @@
 
 #define MP_NO_KEY (~0ull)  // a point (face centroid, vertex) that is not finite: in no cell (PointGrid skips it), last in the sorted order
 
-// cellno: the inclusive scan of head (cell of position i = cellno[i] - 1)
-static __global__ void __launch_bounds__(256)
-k_mp_cells(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ head, const uint32_t *__restrict__ cellno, uint32_t n,
-           uint64_t *__restrict__ cell_key, uint32_t *__restrict__ cell_start) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n || !head[i]) return;
-  const uint32_t c = cellno[i] - 1u;
-  cell_key[c] = keys[i];
-  cell_start[c] = i;
+// PointGrid::c / key (mesh_post.h:55-62): floor((double)v / cell), 21 bits per axis; MP_NO_KEY for a point that is not finite.
+// Cells that alias under the masks share a bucket, as on the host (the distance test rejects what is far); out_of_range is
+// for the pass that cannot live with that (decimate): a cell lies outside [-2^20, 2^20).
+static __device__ __forceinline__ uint64_t mp_cell_key(float x, float y, float z, double cell, bool &out_of_range) {
+  if (!(isfinite(x) && isfinite(y) && isfinite(z))) return MP_NO_KEY;
+  const double fx = floor((double)x / cell), fy = floor((double)y / cell), fz = floor((double)z / cell);
+  out_of_range = !(fx >= -1048576.0 && fx < 1048576.0) || !(fy >= -1048576.0 && fy < 1048576.0) || !(fz >= -1048576.0 && fz < 1048576.0);
+  const long long cx = (long long)fx, cy = (long long)fy, cz = (long long)fz;
+  return ((uint64_t)(cx & 0x1fffff) << 42) | ((uint64_t)(cy & 0x1fffff) << 21) | (uint64_t)(cz & 0x1fffff);
 }
 
-// the 27 cells PointGrid::forNeighbours visits (mesh_post.h:39-43), as indices into the cell table (-1: empty); slot
-// (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1), so slot 13 is the cell itself
-static __global__ void __launch_bounds__(256)
-k_mp_cellnbr(const uint64_t *__restrict__ cell_key, uint32_t n_cells, int32_t *__restrict__ nbr) {
-  const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (t >= 27ull * n_cells) return;
-  const uint32_t c = (uint32_t)(t / 27ull), s = (uint32_t)(t - 27ull * c);
-  const uint64_t key = cell_key[c];
-  const int dx = (int)(s % 3u) - 1, dy = (int)((s / 3u) % 3u) - 1, dz = (int)(s / 9u) - 1;
-  const uint64_t want = ((((key >> 42) + (uint64_t)(int64_t)dx) & 0x1fffffull) << 42) | ((((key >> 21) + (uint64_t)(int64_t)dy) & 0x1fffffull) << 21) |
-                        ((key + (uint64_t)(int64_t)dz) & 0x1fffffull);
-  uint32_t lo = 0u, hi = n_cells;  // the keys ascend
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (cell_key[mid] < want)
-      lo = mid + 1u;
-    else
-      hi = mid;
-  }
-  nbr[t] = lo < n_cells && cell_key[lo] == want ? (int32_t)lo : -1;
+// is sorted position i the first point of its cell?
+static __device__ __forceinline__ uint32_t mp_cell_head(const uint64_t *__restrict__ keys, uint32_t i, uint64_t key) {
+  return key != MP_NO_KEY && (i == 0u || keys[i - 1u] != key) ? 1u : 0u;
+}
+
+// one atomic per wave: how many of its lanes say yes
+static __device__ __forceinline__ void mp_wave_count(bool yes, unsigned long long *counter) {
+  const unsigned long long m = __ballot(yes);
+  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(counter, (unsigned long long)__popcll(m));
 }
 
 struct MpGrid {
@@ -89,6 +71,25 @@ static __device__ __forceinline__ void mp_for_links(const MpGrid &g, uint32_t i,
   }
 }
 
+// mesh_post.h:107-115: the corners of face f (faces == NULL: the soup's 3 f, 3 f + 1, 3 f + 2) through remap, into r and
+// mapped.  true: all three differ.  A face that names a vertex >= n_verts raises *bad and maps to 0, 0, 0.
+static __device__ __forceinline__ bool mp_face_remap(const uint32_t *__restrict__ faces, uint32_t f, uint64_t n_verts,
+                                                     const uint32_t *__restrict__ remap, uint32_t *__restrict__ mapped, uint32_t r[3],
+                                                     unsigned long long *__restrict__ bad) {
+  uint64_t a = 3ull * f, b = a + 1ull, c = a + 2ull;
+  if (faces) a = faces[3ull * f], b = faces[3ull * f + 1ull], c = faces[3ull * f + 2ull];
+  bool good = false;
+  r[0] = r[1] = r[2] = 0u;
+  if (a >= n_verts || b >= n_verts || c >= n_verts) {
+    *bad = 1ull;  // (every writer stores the same 1)
+  } else {
+    r[0] = remap[a], r[1] = remap[b], r[2] = remap[c];
+    good = r[0] != r[1] && r[1] != r[2] && r[2] != r[0];
+  }
+  mapped[3ull * f] = r[0], mapped[3ull * f + 1ull] = r[1], mapped[3ull * f + 2ull] = r[2];
+  return good;
+}
+
 // stable compaction of per-triangle records of K elements: one thread per input element
 template <typename T, int K>
 static __global__ void __launch_bounds__(256)
@@ -111,99 +112,75 @@ struct MpWork {  // the working set of one pass: a handle's, or a handle-less ca
   void *cells = nullptr;  // per-cell arrays (sized once the number of occupied cells is known)
   size_t cells_cap = 0;
   unsigned long long *counters = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // timed intervals on the stream (cleanup: two; flatten: one, ev[0 .. 1])
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // timed intervals on the stream (cleanup: two; flatten, decimate: one, ev[0 .. 1])
 };
 
-static void mp_work_free(MpWork &w) {
-  if (w.buf) (void)hipFree(w.buf);
-  if (w.cells) (void)hipFree(w.cells);
-  if (w.counters) (void)hipFree(w.counters);
-  for (hipEvent_t e : w.ev)
-    if (e) (void)hipEventDestroy(e);
-  w = MpWork();
-}
-
-static int mp_reserve(void **p, size_t *cap, size_t need, hipStream_t s, const char *who = "mesh cleanup") {
-  if (need <= *cap && *p) return TSDF_HIP_OK;
-  if (*p) {
-    TSDF_HIP_TRY(hipStreamSynchronize(s));
-    TSDF_HIP_TRY(hipFree(*p));
-    *p = nullptr, *cap = 0;
-  }
-  if (hipMalloc(p, need) != hipSuccess) {
-    *p = nullptr;
-    (void)hipGetLastError();
-    tsdf_set_error(std::string(who) + ": " + std::to_string(need) + " bytes of device memory for the working set are not available");
-    return TSDF_HIP_E_NOMEM;
-  }
-  *cap = need;
-  return TSDF_HIP_OK;
-}
+void mp_work_free(MpWork &w);
+int mp_reserve(void **p, size_t *cap, size_t need, hipStream_t s, const char *who);
+// on first use the n_counters counters and the first n_events events; queues the zeroing of the counters
+int mp_work_begin(MpWork &w, int n_counters, int n_events, hipStream_t s);
 
 static inline size_t mp_up(size_t v) { return (v + 255) / 256 * 256; }
 
-// Is `p` host memory the runtime knows as pinned?  (As tsdf_to_host / tsdf_to_device decide: the DMA engine then reads and
-// writes it directly.)
-static bool mp_is_pinned(const void *p) {
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
+struct MpTake {  // arrays one behind the other, each on a multiple of 256 bytes: take(bytes) is the next one's offset
+  size_t o = 0;
+  size_t operator()(size_t bytes) {
+    const size_t at = o;
+    o += mp_up(bytes);
+    return at;
   }
-  return attr.type == hipMemoryTypeHost;
-}
+};
+
+// rocprim's temporary storage, the largest of: radix_sort_pairs of n_sort64 (uint64_t, uint32_t) pairs over 64 bits and of
+// n_sort32 (uint32_t, uint32_t) pairs over 32, an inclusive scan of n_scan uint32_t, an exclusive scan of n_keep keep flags
+int mp_tmp_bytes(size_t n_sort64, size_t n_sort32, size_t n_scan, size_t n_keep, hipStream_t s, size_t *bytes);
+
+// The cell table of n points sorted by key (head: mp_cell_head; g.cellno: the inclusive scan of head, n_cells its last entry;
+// g.n_fin: the points with a key), in two steps: room in MpWork::cells, which may allocate; then, queued on the stream, one
+// entry per occupied cell, the sentinel cell_start[n_cells] = n_fin and each cell's 27 neighbours, which complete g.
+int mp_cells_reserve(MpWork &w, uint32_t n_cells, hipStream_t s, const char *who);
+int mp_cells_build(MpWork &w, hipStream_t s, const uint64_t *keys, const uint32_t *head, uint32_t n, uint32_t n_cells, MpGrid &g);
+
+// offset = the exclusive scan of keep; faces_out = the rows of mapped (3 per face) whose keep flag is set, in order
+int mp_compact_faces(hipStream_t s, void *tmp, size_t tmp_bytes, const uint32_t *mapped, const uint8_t *keep, uint32_t *offset, uint32_t n_faces,
+                     uint32_t *faces_out);
+
+// refuses more than 2^31 faces or vertices (n_verts == NULL: a pass that indexes faces only)
+int mp_check_counts(const char *who, uint64_t n_faces, const uint64_t *n_verts);
+
+struct MpStats {  // the four words of a pass's *_stats entry point; each pass keeps a thread_local one
+  uint64_t v[4] = {0, 0, 0, 0};
+  void zero() { v[0] = v[1] = v[2] = v[3] = 0; }
+  void set(uint64_t a, uint64_t b, uint64_t c, uint64_t d) { v[0] = a, v[1] = b, v[2] = c, v[3] = d; }
+  int copy_out(uint64_t out[4]) const {
+    if (!out) return TSDF_HIP_E_INVALID;
+    for (int i = 0; i < 4; ++i) out[i] = v[i];
+    return TSDF_HIP_OK;
+  }
+};
 
 struct MpStage {  // two pinned slots for pageable caller memory
   char *pinned = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
-  ~MpStage() {
-    if (pinned) (void)hipHostFree(pinned);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  int ready() {
-    if (pinned) return TSDF_HIP_OK;
-    TSDF_HIP_TRY(hipHostMalloc((void **)&pinned, 2 * (size_t)MP_STAGE, hipHostMallocDefault));
-    for (int i = 0; i < 2; ++i) TSDF_HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-    return TSDF_HIP_OK;
-  }
+  ~MpStage();
+  int ready();
 };
 
-static int mp_to_device(MpStage &st, void *dst, const void *src, size_t bytes, hipStream_t s) {
-  if (!bytes) return TSDF_HIP_OK;
-  if (bytes >= (64u << 10) && mp_is_pinned(src)) {
-    TSDF_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-    return TSDF_HIP_OK;
-  }
-  if (const int rc = st.ready()) return rc;
-  for (size_t off = 0, k = 0; off < bytes; off += MP_STAGE, ++k) {
-    const int slot = (int)(k & 1);
-    if (k >= 2) TSDF_HIP_TRY(hipEventSynchronize(st.ev[slot]));  // the copy that last read this slot has finished
-    const size_t len = std::min((size_t)MP_STAGE, bytes - off);
-    memcpy(st.pinned + (size_t)slot * MP_STAGE, (const char *)src + off, len);
-    TSDF_HIP_TRY(hipMemcpyAsync((char *)dst + off, st.pinned + (size_t)slot * MP_STAGE, len, hipMemcpyHostToDevice, s));
-    TSDF_HIP_TRY(hipEventRecord(st.ev[slot], s));
-  }
-  TSDF_HIP_TRY(hipStreamSynchronize(s));  // (the slots are free again for the way back)
-  return TSDF_HIP_OK;
-}
+int mp_to_device(MpStage &st, void *dst, const void *src, size_t bytes, hipStream_t s);
+int mp_to_host(MpStage &st, void *dst, const void *src, size_t bytes, hipStream_t s);
 
-static int mp_to_host(MpStage &st, void *dst, const void *src, size_t bytes, hipStream_t s) {
-  if (!bytes) return TSDF_HIP_OK;
-  if (bytes >= (64u << 10) && mp_is_pinned(dst)) {
-    TSDF_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
-    TSDF_HIP_TRY(hipStreamSynchronize(s));
-    return TSDF_HIP_OK;
-  }
-  if (const int rc = st.ready()) return rc;
-  for (size_t off = 0; off < bytes; off += MP_STAGE) {
-    const size_t len = std::min((size_t)MP_STAGE, bytes - off);
-    TSDF_HIP_TRY(hipMemcpyAsync(st.pinned, (const char *)src + off, len, hipMemcpyDeviceToHost, s));
-    TSDF_HIP_TRY(hipStreamSynchronize(s));
-    memcpy((char *)dst + off, st.pinned, len);
-  }
-  return TSDF_HIP_OK;
-}
+struct MpCall {  // a host-array entry point: everything it allocates goes when it returns (there is no handle to keep it for)
+  std::optional<TsdfDeviceScope> scope;  // (first, so restored last)
+  hipStream_t s = nullptr;
+  void *in = nullptr;  // the caller's arrays on the device
+  MpWork work;
+  MpStage stage;
+  ~MpCall();
+  // after the caller's own argument checks: is there such a device; on it, a stream and in_bytes for the inputs
+  int open(int device, size_t in_bytes, const char *who);
+  int upload(void *dst, const void *src, size_t bytes) { return mp_to_device(stage, dst, src, bytes, s); }
+  int download(void *dst, const void *src, size_t bytes) { return mp_to_host(stage, dst, src, bytes, s); }
+};
 
 #define MP_IDX_COUNTERS 8  // MpWork::counters of the passes that share a handle's tsdf_flatten_state (flatten, decimate)
 
@@ -218,3 +195,17 @@ struct tsdf_flatten_state {  // per handle (tsdf_hip_volume::fl): the indexed me
   std::vector<uint32_t> h_faces;
   std::vector<uint64_t> h_cell;
 };
+
+// tsdf_hip_march_flatten / _decimate after their own argument checks: refuses without a marched soup, or one too large for
+// 32-bit indices; else *st is the handle's state, no longer valid, and *n the soup's triangles (0: only mp_idx_end is left)
+int mp_idx_begin(tsdf_handle h, const char *who, tsdf_flatten_state **st, uint64_t *n);
+// One handle (the soup stays as it is: the indexed mesh has buffers of its own): mp_idx_layout sizes st->out for m vertices
+// and kept faces; the caller queues its vertices to st->out and colours to st->out + st->o_rgb; mp_idx_fill adds the
+// compacted faces and the cell keys of the faces whose keep flag is set, and waits.
+int mp_idx_layout(tsdf_handle h, tsdf_flatten_state *st, uint64_t m, uint64_t kept, const char *who);
+int mp_idx_fill(tsdf_handle h, tsdf_flatten_state *st, uint64_t m, uint64_t kept, const uint32_t *d_faces, const uint8_t *d_keep,
+                const uint32_t *d_offset);
+// A set, once the host-array entry point has filled st->h_*: trims them to m vertices and kept faces, and keeps the cell
+// keys (cell: one per triangle of the soup) of the faces whose keep flag is set.
+void mp_idx_set_host(tsdf_flatten_state *st, bool has_rgb, const uint64_t *cell, uint64_t n, uint64_t m, uint64_t kept, const uint8_t *keep);
+int mp_idx_end(tsdf_flatten_state *st, uint64_t *n_verts, uint64_t *n_faces);

@@ -7,8 +7,9 @@
 // exactly:
 //   k_mp_centroid  centroid ((v0 + v1) + v2) / 3.f and the host's cell key per face; non-finite centroids get the key ~0
 //   rocprim sort   (key, face) pairs; k_mp_gather writes the centroids in sorted order and marks run heads, a scan numbers
-//                  the cells, k_mp_cells / k_mp_cellnbr build the cell table and each cell's 27 neighbour cells (these two,
-//                  mp_for_links and k_mp_compact live in tsdf_meshgrid.h: tsdf_flatten.hip builds the same grid of vertices)
+//                  the cells, mp_cells_build makes the cell table and each cell's 27 neighbour cells (tsdf_meshgrid.hip;
+//                  mp_cell_key, mp_for_links and k_mp_compact are in tsdf_meshgrid.h: tsdf_flatten.hip builds the same
+//                  grid of vertices)
 //   k_mp_degree    links per face, leaving at min_neighbors: a face with that many links is HEAVY -- its group has more than
 //                  min_neighbors faces whatever else it holds.  On a surface nearly every face is heavy after a few tests.
 //   k_mp_link      the LIGHT faces enumerate all their links and join a lock-free union-find (CAS hooking of the larger root
@@ -19,16 +20,12 @@
 // with one lies inside a group that is large enough.  No kernel waits for another workgroup: the only
 // loops over shared state are CAS retries, each of which fails only because another thread's CAS succeeded.
 // Gather-bound pointer chasing and a radix sort: no MFMA.
-#include <string.h>
-
-#include <algorithm>
 #include <cmath>
 #include <string>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
 
 #include "tsdf_meshgrid.h"
 
@@ -44,7 +41,7 @@ struct tsdf_meshpost_state {  // per handle (tsdf_hip_volume::mp); a set has non
   MpWork work;
 };
 
-static thread_local uint64_t g_mp_stats[4] = {0, 0, 0, 0};  // tsdf_hip_mesh_cleanup_stats
+static thread_local MpStats g_mp_stats;  // tsdf_hip_mesh_cleanup_stats
 
 void tsdf_meshpost_release(tsdf_hip_volume *v) {
   if (!v->mp) return;
@@ -76,20 +73,16 @@ k_mp_centroid(const float *__restrict__ verts, uint64_t n_verts, const uint32_t 
   if (f < n) {
     float c[3] = {0.f, 0.f, 0.f};
     uint64_t key = MP_NO_KEY;
-    if (!mp_centroid(verts, n_verts, faces, f, c)) {
+    bool wraps = false;  // (cells that alias under the key's masks share a bucket, as on the host)
+    if (!mp_centroid(verts, n_verts, faces, f, c))
       counters[MP_C_BAD] = 1ull;  // (every writer stores the same 1)
-    } else if (isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2])) {
-      // PointGrid::c / key (mesh_post.h:55-58): floor((double)v / cell), 21 bits per axis
-      const long long cx = (long long)floor((double)c[0] / cell), cy = (long long)floor((double)c[1] / cell),
-                      cz = (long long)floor((double)c[2] / cell);
-      key = ((uint64_t)(cx & 0x1fffff) << 42) | ((uint64_t)(cy & 0x1fffff) << 21) | (uint64_t)(cz & 0x1fffff);
-      fin = true;
-    }
+    else
+      key = mp_cell_key(c[0], c[1], c[2], cell, wraps);
+    fin = key != MP_NO_KEY;
     keys[f] = key;
     idx[f] = f;
   }
-  const unsigned long long m = __ballot(fin);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[MP_C_FINITE], (unsigned long long)__popcll(m));
+  mp_wave_count(fin, &counters[MP_C_FINITE]);
 }
 
 // sorted position i -> centroid of the face there (computed again from the vertices: the same operations give the same
@@ -103,7 +96,7 @@ k_mp_gather(const float *__restrict__ verts, uint64_t n_verts, const uint32_t *_
   float c[3] = {0.f, 0.f, 0.f};
   if (key != MP_NO_KEY) (void)mp_centroid(verts, n_verts, faces, order[i], c);
   cen[i] = make_float4(c[0], c[1], c[2], 0.f);
-  head[i] = key != MP_NO_KEY && (i == 0u || keys[i - 1u] != key) ? 1u : 0u;
+  head[i] = mp_cell_head(keys, i, key);
 }
 
 static __device__ __forceinline__ void mp_add_tests(unsigned tests, unsigned long long *counters) {
@@ -197,8 +190,7 @@ k_mp_keep(uint32_t n, uint32_t n_fin, uint32_t min_nb, const uint32_t *__restric
     }
     keep[order[i]] = k ? 1 : 0;
   }
-  const unsigned long long m = __ballot(k);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&counters[MP_C_KEPT], (unsigned long long)__popcll(m));
+  mp_wave_count(k, &counters[MP_C_KEPT]);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
@@ -207,22 +199,12 @@ struct MpLayout {  // the per-face arrays inside MpWork::buf
 };
 
 static int mp_layout(size_t n, hipStream_t s, MpLayout &L) {
-  size_t t_sort = 0, t_scan = 0, t_scan2 = 0;
-  TSDF_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t_sort, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, n,
-                                         0u, 64u, s));
-  TSDF_HIP_TRY(rocprim::inclusive_scan(nullptr, t_scan, (uint32_t *)nullptr, (uint32_t *)nullptr, n, rocprim::plus<uint32_t>(), s));
-  TSDF_HIP_TRY(rocprim::exclusive_scan(nullptr, t_scan2, MpKeepIt(nullptr, MpKeepCount()), (uint32_t *)nullptr, 0u, n, rocprim::plus<uint32_t>(), s));
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += mp_up(bytes);
-    return at;
-  };
+  if (const int rc = mp_tmp_bytes(n, 0, n, n, s, &L.tmp_bytes)) return rc;
+  MpTake take;
   L.key_a = take(n * 8), L.key_b = take(n * 8), L.idx_a = take(n * 4), L.idx_b = take(n * 4), L.cen = take(n * 16);
   L.cellno = take(n * 4), L.heavy = take(n), L.any_heavy = take(n), L.keep = take(n);
-  L.tmp_bytes = std::max(t_sort, std::max(t_scan, t_scan2));
   L.tmp = take(L.tmp_bytes);
-  L.total = o;
+  L.total = take.o;
   return TSDF_HIP_OK;
 }
 
@@ -232,10 +214,7 @@ static int mp_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
                    int min_neighbors, MpLayout &L, uint64_t *n_kept) {
   const uint32_t n = (uint32_t)n_faces, min_nb = (uint32_t)min_neighbors;
   int rc = mp_layout(n, s, L);
-  if (rc || (rc = mp_reserve(&w.buf, &w.cap, L.total, s))) return rc;
-  if (!w.counters) TSDF_HIP_TRY(hipMalloc(&w.counters, MP_COUNTERS * sizeof(unsigned long long)));
-  for (int i = 0; i < 4; ++i)
-    if (!w.ev[i]) TSDF_HIP_TRY(hipEventCreate(&w.ev[i]));
+  if (rc || (rc = mp_reserve(&w.buf, &w.cap, L.total, s, "mesh cleanup")) || (rc = mp_work_begin(w, MP_COUNTERS, 4, s))) return rc;
   char *b = (char *)w.buf;
   uint64_t *key_a = (uint64_t *)(b + L.key_a), *key_b = (uint64_t *)(b + L.key_b);
   uint32_t *idx_a = (uint32_t *)(b + L.idx_a), *idx_b = (uint32_t *)(b + L.idx_b), *cellno = (uint32_t *)(b + L.cellno);
@@ -245,7 +224,6 @@ static int mp_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
   uint32_t *parent = (uint32_t *)key_a, *members = parent + n, *head = idx_a;
   const dim3 blk(256), grid_n((n + 255u) / 256u);
 
-  TSDF_HIP_TRY(hipMemsetAsync(w.counters, 0, MP_COUNTERS * sizeof(unsigned long long), s));
   TSDF_HIP_TRY(hipEventRecord(w.ev[0], s));
   hipLaunchKernelGGL(k_mp_centroid, grid_n, blk, 0, s, d_verts, n_verts, d_faces, n, (double)face_dist, key_a, idx_a, w.counters);
   TSDF_HIP_TRY(hipGetLastError());
@@ -266,25 +244,15 @@ static int mp_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
     return TSDF_HIP_E_INVALID;
   }
   const uint32_t n_fin = (uint32_t)counts[MP_C_FINITE];
-  if (n_fin) {  // (the cell table is sized before the second timed interval opens: a hipMalloc is not device work)
-    const size_t o_start = mp_up((size_t)n_cells * 8), o_nbr = o_start + mp_up(((size_t)n_cells + 1) * 4);
-    if ((rc = mp_reserve(&w.cells, &w.cells_cap, o_nbr + (size_t)n_cells * 27 * 4, s))) return rc;
-  }
+  // (the cell table is sized before the second timed interval opens: a hipMalloc is not device work)
+  if (n_fin && (rc = mp_cells_reserve(w, n_cells, s, "mesh cleanup"))) return rc;
   TSDF_HIP_TRY(hipEventRecord(w.ev[2], s));
   if (n_fin) {
-    const size_t o_start = mp_up((size_t)n_cells * 8), o_nbr = o_start + mp_up(((size_t)n_cells + 1) * 4);
-    uint64_t *cell_key = (uint64_t *)w.cells;
-    uint32_t *cell_start = (uint32_t *)((char *)w.cells + o_start);
-    int32_t *nbr = (int32_t *)((char *)w.cells + o_nbr);
-    hipLaunchKernelGGL(k_mp_cells, grid_n, blk, 0, s, key_b, head, cellno, n, cell_key, cell_start);
-    TSDF_HIP_TRY(hipGetLastError());
-    TSDF_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(cell_start + n_cells), (int)n_fin, 1, s));
-    hipLaunchKernelGGL(k_mp_cellnbr, dim3((unsigned)((27ull * n_cells + 255ull) / 256ull)), blk, 0, s, cell_key, n_cells, nbr);
-    TSDF_HIP_TRY(hipGetLastError());
+    const float r2 = (float)((double)face_dist * (double)face_dist);  // mesh_post.h:129
+    MpGrid g{cen, cellno, nullptr, nullptr, n_fin, r2};
+    if ((rc = mp_cells_build(w, s, key_b, head, n, n_cells, g))) return rc;
     TSDF_HIP_TRY(hipMemsetAsync(any_heavy, 0, n, s));
     TSDF_HIP_TRY(hipMemsetAsync(members, 0, (size_t)n * 4, s));
-    const float r2 = (float)((double)face_dist * (double)face_dist);  // mesh_post.h:129
-    const MpGrid g{cen, cellno, nbr, cell_start, n_fin, r2};
     const dim3 grid_f((n_fin + 255u) / 256u);
     hipLaunchKernelGGL(k_mp_degree, grid_f, blk, 0, s, g, min_nb, heavy, parent, w.counters);
     TSDF_HIP_TRY(hipGetLastError());
@@ -306,7 +274,7 @@ static int mp_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
   ms += ms2;
   uint64_t tests = 0;
   for (int i = 0; i < MP_TEST_SLOTS; ++i) tests += counts[MP_C_TESTS + i];
-  g_mp_stats[0] = n, g_mp_stats[1] = n - counts[MP_C_KEPT], g_mp_stats[2] = tests, g_mp_stats[3] = (uint64_t)(ms * 1000.f);
+  g_mp_stats.set(n, n - counts[MP_C_KEPT], tests, (uint64_t)(ms * 1000.f));
   *n_kept = counts[MP_C_KEPT];
   return TSDF_HIP_OK;
 }
@@ -316,11 +284,7 @@ static int mp_check_args(float face_dist, int min_neighbors, uint64_t n_faces, c
     tsdf_set_error(std::string(who) + ": face_dist must be finite and positive, min_neighbors >= 0");
     return TSDF_HIP_E_INVALID;
   }
-  if (n_faces > (1ull << 31)) {
-    tsdf_set_error(std::string(who) + ": face indices are 32-bit; more than 2^31 faces are not accepted");
-    return TSDF_HIP_E_INVALID;
-  }
-  return TSDF_HIP_OK;
+  return mp_check_counts(who, n_faces, nullptr);
 }
 
 extern "C" int tsdf_hip_mesh_cleanup(int device, const float *verts, uint64_t n_verts, const uint32_t *faces, uint64_t n_faces, float face_dist,
@@ -329,50 +293,24 @@ extern "C" int tsdf_hip_mesh_cleanup(int device, const float *verts, uint64_t n_
   if (const int rc = mp_check_args(face_dist, min_neighbors, n_faces, "tsdf_hip_mesh_cleanup")) return rc;
   if (device < 0) return TSDF_HIP_E_INVALID;
   if (n_faces == 0) {
-    g_mp_stats[0] = g_mp_stats[1] = g_mp_stats[2] = g_mp_stats[3] = 0;
+    g_mp_stats.zero();
     return TSDF_HIP_OK;
   }
   if (!verts || !keep || n_verts == 0 || (!faces && n_verts / 3 < n_faces)) {
     tsdf_set_error("tsdf_hip_mesh_cleanup: verts and keep must not be NULL, and a triangle soup needs 3 vertices per face");
     return TSDF_HIP_E_INVALID;
   }
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-    (void)hipGetLastError();
-    return TSDF_HIP_E_NODEVICE;
-  }
-  if (device >= n_dev) return TSDF_HIP_E_INVALID;
-  TSDF_ON_DEVICE(device);
-  // everything this call allocates goes when it returns: there is no handle to keep it for
-  struct Call {
-    hipStream_t s = nullptr;
-    void *in = nullptr;
-    MpWork work;
-    MpStage stage;
-    ~Call() {
-      if (s) (void)hipStreamSynchronize(s);
-      mp_work_free(work);
-      if (in) (void)hipFree(in);
-      if (s) (void)hipStreamDestroy(s);
-    }
-  } c;
-  TSDF_HIP_TRY(hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking));
+  MpCall c;
   const size_t b_verts = mp_up((size_t)n_verts * 12), b_faces = faces ? (size_t)n_faces * 12 : 0;
-  if (hipMalloc(&c.in, b_verts + b_faces) != hipSuccess) {
-    c.in = nullptr;
-    (void)hipGetLastError();
-    tsdf_set_error("tsdf_hip_mesh_cleanup: " + std::to_string(b_verts + b_faces) + " bytes of device memory for the mesh are not available");
-    return TSDF_HIP_E_NOMEM;
-  }
+  int rc = c.open(device, b_verts + b_faces, "tsdf_hip_mesh_cleanup");
+  if (rc) return rc;
   float *d_verts = (float *)c.in;
   uint32_t *d_faces = faces ? (uint32_t *)((char *)c.in + b_verts) : nullptr;
-  int rc = mp_to_device(c.stage, d_verts, verts, (size_t)n_verts * 12, c.s);
-  if (!rc && faces) rc = mp_to_device(c.stage, d_faces, faces, b_faces, c.s);
-  if (rc) return rc;
+  if ((rc = c.upload(d_verts, verts, (size_t)n_verts * 12)) || (faces && (rc = c.upload(d_faces, faces, b_faces)))) return rc;
   MpLayout L;
   uint64_t kept = 0;
   if ((rc = mp_core(c.work, c.s, d_verts, n_verts, d_faces, n_faces, face_dist, min_neighbors, L, &kept))) return rc;
-  if ((rc = mp_to_host(c.stage, keep, (char *)c.work.buf + L.keep, (size_t)n_faces, c.s))) return rc;
+  if ((rc = c.download(keep, (char *)c.work.buf + L.keep, (size_t)n_faces))) return rc;
   if (n_kept) *n_kept = kept;
   return TSDF_HIP_OK;
 }
@@ -391,7 +329,7 @@ extern "C" int tsdf_hip_march_cleanup(tsdf_handle h, float face_dist, int min_ne
   const uint64_t n = h->mc_ntri;
   if (const int rc = mp_check_args(face_dist, min_neighbors, n, "tsdf_hip_march_cleanup")) return rc;
   if (!n) {
-    g_mp_stats[0] = g_mp_stats[1] = g_mp_stats[2] = g_mp_stats[3] = 0;
+    g_mp_stats.zero();
     return TSDF_HIP_OK;
   }
   if (!h->mp) h->mp = new tsdf_meshpost_state();
@@ -433,7 +371,5 @@ extern "C" int tsdf_hip_march_cleanup(tsdf_handle h, float face_dist, int min_ne
 }
 
 extern "C" int tsdf_hip_mesh_cleanup_stats(uint64_t out[4]) {
-  if (!out) return TSDF_HIP_E_INVALID;
-  for (int i = 0; i < 4; ++i) out[i] = g_mp_stats[i];
-  return TSDF_HIP_OK;
+  return g_mp_stats.copy_out(out);
 }
