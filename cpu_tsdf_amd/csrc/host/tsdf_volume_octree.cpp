@@ -589,6 +589,23 @@ bool TSDFVolumeOctree::shiftVolume(int sx, int sy, int sz, Eigen::Vector3d *move
   return true;
 }
 
+// ---- mergeVolume (not in the reference): tsdf_hip_merge -----------------------------------------------------------------------
+bool TSDFVolumeOctree::mergeVolume(const TSDFVolumeOctree &src, const Eigen::Affine3d *dst_from_src, float min_weight, uint64_t *merged) {
+  if (!ready("mergeVolume") || !src.ready("mergeVolume (src)")) return false;
+  const Eigen::Affine3d m = dst_from_src ? *dst_from_src : global_transform_.inverse() * src.global_transform_;
+  double T[12];
+  pose12(m.inverse(), T);  // the C ABI takes src_from_dst
+  uint64_t n = 0;
+  const int rc = tsdf_hip_merge(h_, src.h_, T, min_weight, merged ? &n : nullptr);
+  if (rc) {
+    report("mergeVolume", rc);
+    return false;
+  }
+  if (merged) *merged = n;
+  is_empty_ = is_empty_ && src.is_empty_;
+  return true;
+}
+
 // ---- save / load: the reference's .vol format (src/lib/tsdf_volume_octree.cpp:222-275) -----------------------
 // The format and the block streaming live behind the C ABI (tsdf_hip_save / tsdf_hip_load); this class adds
 // what only it knows: max cell size, the empty flag, the weighting flags and the global transform.

@@ -3,6 +3,8 @@
 // runs marching cubes on the GPU with the class defaults (min weight 2.5, no colour) and writes a binary PLY.
 // An extension: `tsdf2mesh foo.vol foo.ply --decimate <cell size in metres>` decimates the mesh by vertex clustering before
 // it is written (cpu_tsdf::mesh_post::decimateMeshAuto); without the option the output is what it was.
+// Another: `tsdf2mesh foo.vol foo.ply --merge bar.vol [--merge baz.vol ...]` loads every further volume and merges it into the
+// first by the global transforms the files carry (TSDFVolumeOctree::mergeVolume), in the order given, before meshing.
 #include <cpu_tsdf/marching_cubes_tsdf_octree.h>
 #include <cpu_tsdf/tsdf_interface.h>
 #include <cpu_tsdf/tsdf_volume_octree.h>
@@ -13,19 +15,23 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "mesh_post.h"
 
 int main(int argc, char **argv) {
   if (argc < 3) {
-    PCL_INFO("Renders a mesh from a TSDF volume saved with TSDFVolumeOctree::save.\nUsage: %s foo.vol foo.ply [--decimate <cell size in metres>]\n",
+    PCL_INFO("Renders a mesh from a TSDF volume saved with TSDFVolumeOctree::save.\nUsage: %s foo.vol foo.ply [--merge other.vol]... [--decimate <cell size in metres>]\n",
              argv[0]);
     return 1;
   }
   bool decimate_on = false;
   float decimate = 0.f;
+  std::vector<std::string> merge;
   for (int i = 3; i < argc; ++i) {
-    if (!strcmp(argv[i], "--decimate") && i + 1 < argc) {
+    if (!strcmp(argv[i], "--merge") && i + 1 < argc) {
+      merge.push_back(argv[++i]);
+    } else if (!strcmp(argv[i], "--decimate") && i + 1 < argc) {
       decimate_on = true;
       decimate = (float)atof(argv[++i]);
     } else {
@@ -36,6 +42,16 @@ int main(int argc, char **argv) {
   cpu_tsdf::TSDFVolumeOctree::Ptr tsdf(new cpu_tsdf::TSDFVolumeOctree);
   tsdf->load(argv[1]);
   if (!tsdf->handle()) return 1;
+  for (const std::string &name : merge) {
+    cpu_tsdf::TSDFVolumeOctree other;
+    other.load(name);
+    uint64_t merged = 0;  // (asking for the count makes the call wait: `other` is freed at the end of this block)
+    if (!other.handle() || !tsdf->mergeVolume(other, nullptr, 0.f, &merged)) {
+      PCL_ERROR("--merge %s failed\n", name.c_str());
+      return 1;
+    }
+    PCL_INFO("merged %llu voxels of %s\n", (unsigned long long)merged, name.c_str());
+  }
   cpu_tsdf::MarchingCubesTSDFOctree mc;
   mc.setInputTSDF(tsdf);
   mc.setColorByConfidence(false);

@@ -124,6 +124,13 @@ struct tsdf_hip_volume {
   hipEvent_t shift_ev[2] = {nullptr, nullptr};  // tsdf_hip_shift_stats: around the work of the last tsdf_hip_shift (tsdf_shift.hip)
   bool shift_timed = false;                     // ... both have been recorded
   uint64_t shift_stats[3] = {0, 0, 0};          // voxels that kept a value, voxels reset, 1 if the band flags were carried over
+  hipEvent_t merge_ev[3] = {nullptr, nullptr, nullptr};  // tsdf_hip_merge (tsdf_merge.hip) with this handle as dst: around the kernel; [2] hands
+                                                         // the order of the two streams over (recorded on src's, then on dst's)
+  bool merge_timed = false;                     // ... [0] and [1] have been recorded (a merge with an empty launch box records nothing)
+  unsigned long long *merge_count = nullptr;    // device: voxels the last merge's kernel merged (a counter of its own: an asynchronous
+                                                // merge leaves it for tsdf_hip_merge_stats, whatever runs in between)
+  uint64_t merge_stats[3] = {0, 0, 0};          // voxels in the launch box, voxels merged (once read back), 1 if live band flags were dropped
+  bool merge_count_pending = false;             // merge_stats[1] is still on the device
   void *scratch = nullptr;
   size_t scratch_bytes = 0;
   tsdf_occ_state *occ = nullptr;

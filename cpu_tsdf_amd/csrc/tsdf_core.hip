@@ -439,6 +439,9 @@ static void free_volume(tsdf_hip_volume *v) {
     if (v->align_ev[i]) (void)hipEventDestroy(v->align_ev[i]);
   for (int i = 0; i < 2; ++i)
     if (v->shift_ev[i]) (void)hipEventDestroy(v->shift_ev[i]);
+  for (int i = 0; i < 3; ++i)
+    if (v->merge_ev[i]) (void)hipEventDestroy(v->merge_ev[i]);
+  if (v->merge_count) (void)hipFree(v->merge_count);
   if (v->scratch) (void)hipFree(v->scratch);
   delete v;
 }

@@ -1,6 +1,7 @@
-// The gather kernels' view of a volume and the per-point arithmetic of getFxn / getGradient / getHessian, shared by
-// tsdf_query.hip (k_raycast, k_sample) and tsdf_align.hip (k_align_system): ONE statement of the reference's operation
-// order, so that what tests/test_query_gpu.py pins to the oracle is what every caller computes.
+// The gather kernels' view of a volume, Octree::getContainingVoxel and the per-point arithmetic of getFxn / getGradient /
+// getHessian, shared by tsdf_query.hip (k_raycast, k_lookup_rgb, k_sample), tsdf_align.hip (k_align_system) and
+// tsdf_merge.hip (k_merge): ONE statement of the reference's operation order, so that what tests/test_query_gpu.py pins to
+// the oracle is what every caller computes.
 // Compiled with -ffp-contract=off; float/double operation order follows the reference line by line.
 #pragma once
 
@@ -59,6 +60,42 @@ static __device__ __forceinline__ int voxel_index(const GridView &g, int a, floa
   const int res = a == 0 ? g.nx : a == 1 ? g.ny : g.nz;
   const double off = (double)g.size[a] / 2.0;
   return cvtt(floor(((double)x + off) / (double)g.size[a] * (double)res));
+}
+
+// One axis of OctreeNode::getContainingVoxel's descent (octree.cpp:112-121): child bit = (x - ctr) > 0.
+static __device__ __forceinline__ int descend_axis(float x, float size, int L) {
+  float c = 0.f, s = size;
+  int i = 0;
+  for (int l = 0; l < L; ++l) {
+    const bool b = (x - c) > 0.f;
+    const float off = s / 4;
+    c = b ? c + off : c - off;
+    s = s / 2;
+    i = i * 2 + (b ? 1 : 0);
+  }
+  return i;
+}
+
+static __device__ __forceinline__ int axis_index(const GridView &g, int a, float x) {
+  if (g.lv[a] >= 0) return descend_axis(x, g.nsize[a], g.lv[a]);
+  const int res = a == 0 ? g.nx : a == 1 ? g.ny : g.nz;
+  int i = cvtt(floor(((double)x + (double)g.size[a] / 2.0) / (double)g.size[a] * (double)res));
+  return i < 0 ? 0 : (i >= res ? res - 1 : i);
+}
+
+// Octree::getContainingVoxel (octree.cpp:628-643) on a fully refined tree; false == NULL.
+// `local` reports whether the voxel's plane is held by this handle (always true for a whole grid).
+static __device__ __forceinline__ bool containing(const GridView &g, float x, float y, float z, int64_t &vi,
+                                                  bool &local, int &k) {
+  local = true;
+  k = -1;
+  if (isnan(z) || fabsf(x) > g.half[0] || fabsf(y) > g.half[1] || fabsf(z) > g.half[2]) return false;
+  const int i = axis_index(g, 0, x), j = axis_index(g, 1, y);
+  k = axis_index(g, 2, z);
+  const int kl = k - g.z_first;
+  local = kl >= 0 && kl < g.nz_alloc;
+  vi = ((int64_t)(local ? kl : 0) * g.ny + j) * g.pitch + i;
+  return true;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -606,6 +606,42 @@ class TSDFVolumeOctree:
         capi.check(capi.load().tsdf_hip_shift_stats(self._need(), out), "shift_stats")
         return tuple(int(v) for v in out)
 
+    def mergeVolume(self, src, dst_from_src=None, min_weight=0.0, count=False):
+        """Not in the reference: resample volume ``src`` at this volume's voxel centres and add the samples as weighted
+        observations, on the GPU (tsdf_hip_merge; the rule and every refusal are in include/tsdf_hip.h).  ``dst_from_src``
+        (4 x 4 or 3 x 4) takes src volume coordinates to this volume's; None = the two global transforms,
+        getGlobalTransform()^-1 * src.getGlobalTransform().  A voxel is merged iff getFxn(src, q) succeeds at its centre q,
+        the eight neighbour voxels there all have w > min_weight, and src has a voxel containing q, whose weight and colour
+        the observation carries.  Returns True, or the number of merged voxels when ``count`` is set (the call then waits).
+        src is unchanged; this volume's band flags are dropped as by upload().  One device, whole-grid volumes, "RGB"
+        colour, no depth / variance weighting, src cubic; a PACKED volume takes a PACKED src with the same weight limit."""
+        h, hs = self._need(), src._need()
+        if dst_from_src is None:
+            m = np.linalg.inv(self._global_transform) @ src._global_transform
+        else:
+            m = np.asarray(dst_from_src, dtype=np.float64)
+            if m.shape not in ((4, 4), (3, 4)):
+                raise ValueError(f"mergeVolume: a transform is a 4 x 4 (or 3 x 4) matrix, got shape {m.shape}")
+            m = np.vstack([m[:3, :4], [0.0, 0.0, 0.0, 1.0]])
+        with np.errstate(all="ignore"):
+            try:
+                inv = np.linalg.inv(m)
+            except np.linalg.LinAlgError:
+                raise ValueError("mergeVolume: dst_from_src cannot be inverted") from None
+        T = np.ascontiguousarray(inv[:3, :4]).reshape(12)
+        n = C.c_uint64(0)
+        capi.check(capi.load().tsdf_hip_merge(h, hs, T.ctypes.data_as(C.POINTER(C.c_double)), float(min_weight),
+                                              C.byref(n) if count else None), "merge")
+        self._is_empty = self._is_empty and src._is_empty
+        return int(n.value) if count else True
+
+    def mergeStats(self):
+        """Report-only, of the last mergeVolume into this volume: (voxels in the launch box, voxels merged, 1 if live band
+        flags had to be dropped, device microseconds).  Waits for the merge to finish."""
+        out = (C.c_uint64 * 4)()
+        capi.check(capi.load().tsdf_hip_merge_stats(self._need(), out), "merge_stats")
+        return tuple(int(v) for v in out)
+
     def occupiedTiming(self):
         """Report-only: device milliseconds (scan, sort, gather) of the last getOccupiedVoxelIndices."""
         ms = (C.c_float * 3)()

@@ -167,6 +167,17 @@ class TSDFVolumeOctree : public TSDFInterface {
   // pose handed to integrateCloud / renderView / alignCloud afterwards is Translation(-moved) * trans_old.
   // false (and a PCL_ERROR) before reset(), or when the call fails (a setZSlab volume with sz != 0).
   bool shiftVolume(int sx, int sy, int sz, Eigen::Vector3d *moved = nullptr);
+  // Not in the reference: resample `src` at this volume's voxel centres under a rigid transform and add the samples as
+  // weighted observations, on the GPU (tsdf_hip_merge: the rule and every refusal are in include/tsdf_hip.h) -- joining
+  // submaps, changing the resolution, re-centring by a fraction of a voxel or a rotation.  dst_from_src takes src volume
+  // coordinates to this volume's; nullptr = getGlobalTransform().inverse() * src.getGlobalTransform().  A voxel is merged
+  // iff getFxn(src, q) succeeds at its centre q, the eight neighbour voxels there all have weight > min_weight, and src has
+  // a voxel containing q, whose weight and colour the observation carries (RGBNode::addObservation).  *merged (optional)
+  // receives the number of merged voxels; the call then waits for the kernel.  src is unchanged.  One device, whole-grid
+  // volumes, "RGB" colour, no depth / variance weighting, src cubic; a PACKED volume takes a PACKED src with the same
+  // weight limit.  false (and a PCL_ERROR) before reset() of either volume and on any refusal, which changes nothing.
+  bool mergeVolume(const TSDFVolumeOctree &src, const Eigen::Affine3d *dst_from_src = nullptr, float min_weight = 0.f,
+                   uint64_t *merged = nullptr);
 
   const float UNOBSERVED_VOXEL;
 

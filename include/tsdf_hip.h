@@ -662,6 +662,55 @@ int tsdf_hip_occupied_timing(tsdf_handle h, float ms[3]);
 int tsdf_hip_shift(tsdf_handle h, const int32_t shift[3]);
 int tsdf_hip_shift_stats(tsdf_handle h, uint64_t out[4]);
 
+/* mergeVolume -- NOT IN THE REFERENCE (its volumes can only be fused frame by frame).  Resamples volume `src` at the voxel
+ * centres of volume `dst` under a rigid transform and adds the samples to dst as weighted observations, on the device: what
+ * joining submaps, changing a volume's resolution, and re-centring one by a fraction of a voxel or a rotation all come to.
+ *   src_from_dst  the first three rows, row-major, of the transform that takes dst volume coordinates to src volume
+ *                 coordinates (the caller's Eigen computes it, as for cam_from_vol); cast to float as the reference casts poses.
+ *   min_weight    the gate's threshold, >= 0.
+ *   n_merged      nullable; the number of dst voxels that received an observation.  The call is asynchronous on dst's stream
+ *                 unless it is given.
+ * RULE, per voxel (x, y, z) of dst:
+ *   c   = (ctr_x[x], ctr_y[y], ctr_z[z]): dst's own centre tables (tsdf_hip_centers; what integrateCloud projects).
+ *   q_r = ((M[r][0] * c.x + M[r][1] * c.y) + M[r][2] * c.z) + M[r][3] in fp32, M = (float)src_from_dst: tsdf_hip_align_system's order.
+ *   ok, val = getFxn(q) on src, bit for bit what tsdf_hip_sample(src, q) returns.
+ *   GATE: the voxel is merged iff ok, all eight neighbour voxels of q in src have weight > min_weight (strictly; any layout),
+ *   val is not NaN, and src has a voxel that CONTAINS q -- the one tsdf_hip_lookup_rgb finds (Octree::getContainingVoxel),
+ *   always one of the eight.  w_s and the colour c_s are that voxel's (not a blend of the eight: only so does merging two
+ *   volumes fused from disjoint frames on one grid give the weights, and to rounding the distances, of fusing all frames).
+ *   UPDATE = RGBNode::addObservation(val, w_s, max_weight of dst, c_s) (src/lib/octree.cpp:153-163, 329-337): colour first,
+ *   per channel (uint8)((w * c + w_s * c_s) / (w + w_s)) with the old w, and only if BOTH volumes store colour (else dst's
+ *   colour stays); then d = (d * w + val * w_s) / (w + w_s) in fp32 in that order with IEEE division; then w += w_s, clamped
+ *   to dst's max_weight.  w_s > min_weight >= 0 keeps 0 / 0 out.  M_ / nsample_ are not touched.  A voxel that is not merged is
+ *   neither read nor written.
+ *   Consequences of getFxn's neighbour rule (getNeighbors wants the voxel of q and the next one up along every axis): a dst
+ *   voxel whose q lies in the last half voxel of src along an axis, or whose upper neighbours are unobserved, is not merged --
+ *   under the identity on equal grids that is the top plane, row and column, and every voxel next to an unobserved one on its
+ *   upper side.  Where q hits a src voxel centre exactly, the seven upper neighbours enter val with interpolation weight 0
+ *   (val is that voxel's d, up to the rounding of c^3 * d / c^3: exact for a dyadic voxel size) but still have to pass the gate.
+ * CONVENTIONS: dst may be any grid (non-cubic, any resolution); only a box of dst voxels that encloses src's bounding box
+ * (transformed in fp64, padded by two voxels) is visited, and a src that does not reach dst returns OK with 0 merged, touching
+ * nothing.  Both handles first launch a frame held back by frame pairing.  The kernel runs on dst's stream after everything
+ * queued on src's stream so far, and work queued on src's stream afterwards waits for it.  src is unchanged in every respect
+ * (tsdf_hip_destroy(src) waits on src's stream, and with it for a merge that is still reading it).
+ * Afterwards dst's "band seen" flags no longer describe its planes, exactly as after tsdf_hip_upload: tsdf_hip_march,
+ * tsdf_hip_occupied and the PACKED integrate launches read everything until the next tsdf_hip_reset.  A list made by
+ * tsdf_hip_occupied stays valid, as after an upload (its values are gathered at the fetch).
+ * TSDF_HIP_E_INVALID: a NULL handle or matrix, dst == src, a matrix entry that is not finite, min_weight negative or NaN.
+ * TSDF_HIP_E_UNSUPPORTED, with the reason in tsdf_hip_last_error:
+ *   - either handle is a multi-GPU set or owns only part of its grid (z_begin / z_end);
+ *   - the handles are on different devices;
+ *   - src's res[0..2] or size[0..2] are not all equal (getFxn's weights assume cubic voxels);
+ *   - max_dist_pos or max_dist_neg differ (d is stored divided by max_dist_neg);
+ *   - either volume uses TSDF_COLOR_RGB_NORMALIZED or TSDF_COLOR_LAB, or weights by depth or by variance;
+ *   - dst is PACKED and src is not PACKED with the same max_weight (only then does every merged weight have a count).
+ * Nothing on the device is touched before all of these checks have passed.
+ * tsdf_hip_merge_stats: report-only, of the last tsdf_hip_merge with the handle as dst: out[0] = voxels in the launch box,
+ * out[1] = voxels merged, out[2] = 1 if dst's band flags were live and had to be dropped, out[3] = device microseconds of the
+ * kernel (HIP events on dst's stream; the call waits for the second event, i.e. for the merge to finish). */
+int tsdf_hip_merge(tsdf_handle dst, tsdf_handle src, const double src_from_dst[12], float min_weight, uint64_t *n_merged);
+int tsdf_hip_merge_stats(tsdf_handle dst, uint64_t out[4]);
+
 /* Block transfer of raw voxels (parity tests, save/load, halo exchange).  Coordinates are global
  * grid indices; the block must lie inside the handle's slab + halo.  Any pointer may be NULL.
  * rgb is 3 bytes per voxel (r,g,b).  *_device variants take device pointers (rgb then 4 bytes). */
