@@ -606,6 +606,45 @@ bool TSDFVolumeOctree::mergeVolume(const TSDFVolumeOctree &src, const Eigen::Aff
   return true;
 }
 
+// ---- computeDistanceField / getDistanceField / getDistance (not in the reference): tsdf_hip_esdf ----------------------------
+bool TSDFVolumeOctree::computeDistanceField(int r_max_voxels, float min_weight, uint64_t *sites) {
+  if (!ready("computeDistanceField")) return false;
+  uint64_t n = 0;
+  const int rc = tsdf_hip_esdf(h_, nullptr, r_max_voxels, min_weight, &n);
+  if (rc) {
+    report("computeDistanceField", rc);
+    return false;
+  }
+  if (sites) *sites = n;
+  return true;
+}
+bool TSDFVolumeOctree::getDistanceField(std::vector<float> &dist, std::vector<uint32_t> *d2) const {
+  if (!ready("getDistanceField")) return false;
+  uint64_t st[4];
+  int rc = tsdf_hip_esdf_stats(h_, st);
+  if (!rc) {
+    dist.resize((size_t)st[0]);  // (0 before the first computeDistanceField: the fetch then refuses)
+    if (d2) d2->resize((size_t)st[0]);
+    rc = tsdf_hip_esdf_fetch(h_, d2 ? d2->data() : nullptr, dist.data());
+  }
+  if (rc) report("getDistanceField", rc);
+  return rc == 0;
+}
+bool TSDFVolumeOctree::getDistance(const pcl::PointXYZ &pt, float &dist) const {
+  if (!ready("getDistance")) return false;
+  const float xyz[3] = {pt.x, pt.y, pt.z};
+  float v = 0.f;
+  uint8_t found = 0;
+  const int rc = tsdf_hip_esdf_sample(h_, xyz, 1, &v, &found);
+  if (rc) {
+    report("getDistance", rc);
+    return false;
+  }
+  if (!found) return false;
+  dist = v;
+  return true;
+}
+
 // ---- save / load: the reference's .vol format (src/lib/tsdf_volume_octree.cpp:222-275) -----------------------
 // The format and the block streaming live behind the C ABI (tsdf_hip_save / tsdf_hip_load); this class adds
 // what only it knows: max cell size, the empty flag, the weighting flags and the global transform.

@@ -5,6 +5,9 @@
 // it is written (cpu_tsdf::mesh_post::decimateMeshAuto); without the option the output is what it was.
 // Another: `tsdf2mesh foo.vol foo.ply --merge bar.vol [--merge baz.vol ...]` loads every further volume and merges it into the
 // first by the global transforms the files carry (TSDFVolumeOctree::mergeVolume), in the order given, before meshing.
+// And: `tsdf2mesh foo.vol foo.ply --esdf foo.npy [--esdf-radius N]` also writes the Euclidean distance field of the whole grid
+// (TSDFVolumeOctree::computeDistanceField, after any --merge; truncated at N voxels if given) as a NumPy .npy file: float32
+// metres, shape (nz, ny, nx).
 #include <cpu_tsdf/marching_cubes_tsdf_octree.h>
 #include <cpu_tsdf/tsdf_interface.h>
 #include <cpu_tsdf/tsdf_volume_octree.h>
@@ -18,19 +21,26 @@
 #include <vector>
 
 #include "mesh_post.h"
+#include "npy_write.h"
 
 int main(int argc, char **argv) {
   if (argc < 3) {
-    PCL_INFO("Renders a mesh from a TSDF volume saved with TSDFVolumeOctree::save.\nUsage: %s foo.vol foo.ply [--merge other.vol]... [--decimate <cell size in metres>]\n",
+    PCL_INFO("Renders a mesh from a TSDF volume saved with TSDFVolumeOctree::save.\nUsage: %s foo.vol foo.ply [--merge other.vol]... [--decimate <cell size in metres>] [--esdf field.npy [--esdf-radius <voxels>]]\n",
              argv[0]);
     return 1;
   }
   bool decimate_on = false;
   float decimate = 0.f;
   std::vector<std::string> merge;
+  std::string esdf;
+  int esdf_radius = 0;
   for (int i = 3; i < argc; ++i) {
     if (!strcmp(argv[i], "--merge") && i + 1 < argc) {
       merge.push_back(argv[++i]);
+    } else if (!strcmp(argv[i], "--esdf") && i + 1 < argc) {
+      esdf = argv[++i];
+    } else if (!strcmp(argv[i], "--esdf-radius") && i + 1 < argc) {
+      esdf_radius = atoi(argv[++i]);
     } else if (!strcmp(argv[i], "--decimate") && i + 1 < argc) {
       decimate_on = true;
       decimate = (float)atof(argv[++i]);
@@ -51,6 +61,18 @@ int main(int argc, char **argv) {
       return 1;
     }
     PCL_INFO("merged %llu voxels of %s\n", (unsigned long long)merged, name.c_str());
+  }
+  if (!esdf.empty()) {
+    std::vector<float> dist;
+    uint64_t sites = 0;
+    int rx, ry, rz;
+    tsdf->getResolution(rx, ry, rz);
+    if (!tsdf->computeDistanceField(esdf_radius, 0.f, &sites) || !tsdf->getDistanceField(dist) ||
+        !npy_write_f32(esdf.c_str(), dist.data(), (size_t)rz, (size_t)ry, (size_t)rx)) {
+      PCL_ERROR("--esdf %s failed\n", esdf.c_str());
+      return 1;
+    }
+    PCL_INFO("distance field: %llu sites, written to %s\n", (unsigned long long)sites, esdf.c_str());
   }
   cpu_tsdf::MarchingCubesTSDFOctree mc;
   mc.setInputTSDF(tsdf);

@@ -16,6 +16,7 @@ struct tsdf_hip_multi;     // tsdf_multi.hip: the Z-slab handles of a multi-GPU 
 struct tsdf_occ_state;       // tsdf_occupied.hip: the sorted key list of tsdf_hip_occupied, a set's merged list
 struct tsdf_meshpost_state;  // tsdf_meshpost.hip: the working set of tsdf_hip_march_cleanup
 struct tsdf_flatten_state;   // tsdf_meshgrid.h: the indexed mesh of tsdf_hip_march_flatten and its working set
+struct tsdf_esdf_state;      // tsdf_esdf.hip: the distance field of tsdf_hip_esdf (d2, the sign plane) and its scratch
 
 struct tsdf_hip_volume {
   // non-null: this handle is a SET of Z-slab handles on several GPUs (tsdf_hip_create_multi) and owns no voxel plane
@@ -136,6 +137,7 @@ struct tsdf_hip_volume {
   tsdf_occ_state *occ = nullptr;
   tsdf_meshpost_state *mp = nullptr;
   tsdf_flatten_state *fl = nullptr;
+  tsdf_esdf_state *esdf = nullptr;
 };
 
 // Multi-GPU forwarding targets (tsdf_multi.hip); `h` is a handle with h->multi != nullptr.
@@ -309,6 +311,9 @@ static inline float tsdf_node_size(const tsdf_params &p, int axis) {
   const bool cubic_pow2 = r > 0 && (r & (r - 1)) == 0 && p.res[1] == r && p.res[2] == r;
   return cubic_pow2 ? p.size[0] : p.size[axis];
 }
+// The fp32 voxel edge getFxn scales its weights by (sample_point's `c` in tsdf_gridview.h: size[0] / res[0], one IEEE
+// division), and the unit of tsdf_hip_esdf's distances.
+static inline float tsdf_voxel_edge(const tsdf_params &p) { return p.size[0] / p.res[0]; }
 int tsdf_ensure_scratch(tsdf_hip_volume *v, size_t bytes);
 // Copies between DEVICE memory and the CALLER's host memory, through the handle's pinned bounce buffer in chunks
 // (two slots, the host memcpy of one chunk overlapping the DMA of the next).  tsdf_to_host returns with the
@@ -329,6 +334,12 @@ void tsdf_flatten_release(tsdf_hip_volume *v);
 void tsdf_flatten_invalidate(tsdf_hip_volume *v);
 // A list made by tsdf_hip_occupied names voxels by index: after tsdf_hip_shift the fetches refuse until the next scan.
 void tsdf_occupied_invalidate(tsdf_hip_volume *v);
+// The distance field of tsdf_hip_esdf (tsdf_esdf.hip): freed with the handle (free_volume); dropped, memory included, by
+// tsdf_hip_reset once the stream has been synchronised; after tsdf_hip_shift its indices name other voxels, and the fetches
+// and the sample refuse until the next tsdf_hip_esdf.
+void tsdf_esdf_release(tsdf_hip_volume *v);
+void tsdf_esdf_drop(tsdf_hip_volume *v);
+void tsdf_esdf_invalidate(tsdf_hip_volume *v);
 // The pieces of tsdf_hip_shift (tsdf_shift.hip) a multi-GPU set puts together per slab (tsdf_multi.hip), all asynchronous on
 // the handle's stream: every voxel array of the allocated planes [dz0, dz1) <- the voxels at (+sx, +sy, +sz), the reset state
 // where that lies outside the allocated planes; the band flags of all allocated planes likewise (only while band_exact);

@@ -403,6 +403,7 @@ static void free_volume(tsdf_hip_volume *v) {
   tsdf_occupied_release(v);
   tsdf_meshpost_release(v);
   tsdf_flatten_release(v);
+  tsdf_esdf_release(v);
   if (v->multi) tsdf_multi_free(v);
   TsdfDeviceScope scope(v->device);
   tsdf_pipeline_destroy(v);
@@ -764,6 +765,7 @@ extern "C" int tsdf_hip_reset(tsdf_handle h) {
   h->rest_state = 0;
   h->frame_staged = 0;  // a staged frame does not outlive the volume it was organised for (as on a multi-GPU set)
   TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
+  tsdf_esdf_drop(h);  // a distance field describes the volume that has just been erased
   return TSDF_HIP_OK;
 }
 

@@ -231,6 +231,7 @@ extern "C" int tsdf_hip_shift(tsdf_handle h, const int32_t shift[3]) {
   if (!rc) rc = tsdf_shift_band(h, s[0], s[1], s[2]);
   if (!rc) rc = tsdf_shift_mark(h, 1);
   tsdf_occupied_invalidate(h);  // its list names the voxels by their old indices
+  tsdf_esdf_invalidate(h);      // and so does the box of a distance field
   if (rc) {
     h->band_exact = false;
     return rc;

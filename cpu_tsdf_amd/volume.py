@@ -642,6 +642,48 @@ class TSDFVolumeOctree:
         capi.check(capi.load().tsdf_hip_merge_stats(self._need(), out), "merge_stats")
         return tuple(int(v) for v in out)
 
+    def computeDistanceField(self, r_max=0, min_weight=0.0, box=None):
+        """Not in the reference: the exact Euclidean distance transform of the volume's zero crossing, on the GPU
+        (tsdf_hip_esdf; the rule and every refusal are in include/tsdf_hip.h).  A voxel of ``box`` = (x0, y0, z0, nx, ny, nz)
+        (None: the whole grid) is a site iff it is observed (w > min_weight, d not NaN) and a 6-neighbour inside the grid is
+        observed with the other sign of d; every voxel of the box then gets the squared distance, in voxels, to the nearest
+        site of the box -- exact integers, FAR (0xFFFFFFFF) above ``r_max``^2 when r_max > 0.  Returns the number of sites.
+        The field stays on the volume, describing it as it was at this call, until reset(), close() or the next
+        computeDistanceField; after shiftVolume it has to be computed again.  One device, a whole-grid volume with cubic
+        voxels on a cubic grid."""
+        b = (C.c_int32 * 6)(*[int(v) for v in box]) if box is not None else None
+        n = C.c_uint64(0)
+        capi.check(capi.load().tsdf_hip_esdf(self._need(), b, int(r_max), float(min_weight), C.byref(n)), "esdf")
+        self._esdf_shape = tuple(int(v) for v in (box[5], box[4], box[3])) if box is not None else tuple(int(v) for v in self._p.res)[::-1]
+        return int(n.value)
+
+    def getDistanceField(self):
+        """(d2, dist) of the last computeDistanceField, each of shape (nz, ny, nx) of its box: d2 uint32 squared voxel
+        distances (FAR = 0xFFFFFFFF), dist float32 metres = sgn * voxel * sqrt(d2), negative where the voxel was observed with
+        d < 0, +-inf where FAR."""
+        shape = getattr(self, "_esdf_shape", (0, 0, 0))
+        d2, dist = np.empty(shape, np.uint32), np.empty(shape, np.float32)
+        capi.check(capi.load().tsdf_hip_esdf_fetch(self._need(), d2.ctypes.data_as(C.POINTER(C.c_uint32)), capi.as_f32p(dist)), "esdf_fetch")
+        return d2, dist
+
+    def getDistance(self, points):
+        """(dist, found) for an (n, 3) array of points in volume coordinates: the distance-field value of the voxel that
+        contains each point (no interpolation).  found is False, and dist NaN, where no voxel contains the point or that
+        voxel lies outside the field's box."""
+        pts = capi.f32c(points).reshape(-1, 3)
+        n = len(pts)
+        dist, found = np.empty(n, np.float32), np.empty(n, np.uint8)
+        if n:
+            capi.check(capi.load().tsdf_hip_esdf_sample(self._need(), capi.as_f32p(pts), n, capi.as_f32p(dist), capi.as_u8p(found)), "esdf_sample")
+        return dist, found.astype(bool)
+
+    def distanceFieldStats(self):
+        """Report-only, of the last computeDistanceField: (voxels of the box, sites, bytes of device memory the field and
+        its scratch hold, device microseconds of the three passes)."""
+        out = (C.c_uint64 * 4)()
+        capi.check(capi.load().tsdf_hip_esdf_stats(self._need(), out), "esdf_stats")
+        return tuple(int(v) for v in out)
+
     def occupiedTiming(self):
         """Report-only: device milliseconds (scan, sort, gather) of the last getOccupiedVoxelIndices."""
         ms = (C.c_float * 3)()

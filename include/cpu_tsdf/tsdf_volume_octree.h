@@ -178,6 +178,20 @@ class TSDFVolumeOctree : public TSDFInterface {
   // weight limit.  false (and a PCL_ERROR) before reset() of either volume and on any refusal, which changes nothing.
   bool mergeVolume(const TSDFVolumeOctree &src, const Eigen::Affine3d *dst_from_src = nullptr, float min_weight = 0.f,
                    uint64_t *merged = nullptr);
+  // Not in the reference: the exact Euclidean distance transform of the volume's zero crossing, on the GPU (tsdf_hip_esdf:
+  // the rule and every refusal are in include/tsdf_hip.h) -- what a planner or a collision checker asks of the map.  A voxel
+  // is a site iff it is observed (weight > min_weight, d not NaN) and a 6-neighbour is observed with the other sign of d;
+  // every voxel gets the squared distance in voxels to the nearest site, exactly, or FAR above r_max_voxels^2 when
+  // r_max_voxels > 0.  *sites (optional) receives the number of sites.  The field stays on the volume, describing it as it
+  // was at this call, until reset(), the destructor or the next computeDistanceField; after shiftVolume it has to be
+  // computed again.  getDistanceField returns it for the whole grid, [z][y][x]: dist in metres (sgn * voxel * sqrt(d2),
+  // negative where the voxel was observed with d < 0, +-inf where FAR) and, optionally, d2 itself.  getDistance returns the
+  // value of the voxel that CONTAINS pt (Octree::getContainingVoxel, no interpolation); false where there is none.
+  // One device, a whole-grid volume with cubic voxels on a cubic grid.  All three return false (with a PCL_ERROR) before
+  // reset() and on any refusal; the getters also before the first computeDistanceField.
+  bool computeDistanceField(int r_max_voxels = 0, float min_weight = 0.f, uint64_t *sites = nullptr);
+  bool getDistanceField(std::vector<float> &dist, std::vector<uint32_t> *d2 = nullptr) const;
+  bool getDistance(const pcl::PointXYZ &pt, float &dist) const;
 
   const float UNOBSERVED_VOXEL;
 

@@ -711,6 +711,54 @@ int tsdf_hip_shift_stats(tsdf_handle h, uint64_t out[4]);
 int tsdf_hip_merge(tsdf_handle dst, tsdf_handle src, const double src_from_dst[12], float min_weight, uint64_t *n_merged);
 int tsdf_hip_merge_stats(tsdf_handle dst, uint64_t out[4]);
 
+/* computeDistanceField -- NOT IN THE REFERENCE (its volumes only know the truncated distance d, which says nothing outside
+ * the band of +- one truncation distance).  The exact Euclidean distance transform of the volume's zero crossing, computed
+ * on the device, kept on the handle and readable as a whole field, into device buffers and by batched point queries.
+ *   box         x0, y0, z0, nx, ny, nz (voxel indices) inside the grid; NULL = the whole grid.
+ *   r_max       >= 0, in voxels.  0 = unlimited; otherwise every d2 above r_max^2 becomes TSDF_HIP_ESDF_FAR.
+ *   min_weight  >= 0: a voxel counts as observed iff its weight is above it (strictly).
+ *   n_sites     nullable; the number of sites in the box.
+ * RULE.  d_v and w_v are the floats tsdf_hip_download returns for voxel v (PACKED layout: w = min(k, max_weight)).
+ *   valid(v) := w_v > min_weight and d_v is not NaN.      neg(v) := valid(v) and d_v < 0  (-0.0 is not negative).
+ *   SITE: a voxel v inside the box is a site iff valid(v) and some 6-neighbour u inside the GRID has valid(u) and
+ *   neg(u) != neg(v).  u may lie outside the box; it may not lie outside the grid (a voxel on the grid border has no
+ *   neighbour beyond it).  Both voxels of a crossing edge are therefore sites.  The "band seen" flags are not consulted.
+ *   d2, for EVERY voxel v of the box: the minimum over the sites s in the box of |v - s|^2 in voxel units, an exact uint32.
+ *   With r_max > 0 any value above r_max^2 becomes TSDF_HIP_ESDF_FAR; with r_max == 0 a voxel is FAR only if the box holds
+ *   no site.
+ *   dist(v) = sgn * voxel * sqrtf((float)d2): sgn = -1 iff neg(v), else +1 (unobserved voxels are positive: a caller that
+ *   must tell "unknown" apart reads w); FAR gives sgn * INFINITY; voxel is the fp32 voxel edge size[0] / res[0] that getFxn
+ *   scales by on this handle (tsdf_voxel_edge in the library's tsdf_common.h, sample_point's `c`); sqrtf is the correctly
+ *   rounded one and the product one fp32 multiplication, so the field is bit for bit
+ *   np.sqrt(d2.astype(np.float32)) * np.float32(voxel), negated where neg(v).
+ * LIFETIME, as tsdf_hip_occupied's list: the field describes the volume AT THE TIME OF THE CALL -- the sign as well, which
+ * is recorded then -- and stays valid, and STALE BY DESIGN, across later integrates, marches, uploads and downloads.  It is
+ * dropped by tsdf_hip_reset, tsdf_hip_destroy and the next tsdf_hip_esdf on the handle that is not refused.
+ * After tsdf_hip_shift the fetches and the sample return E_INVALID until the field has been computed again: the indices
+ * moved.  The same before the first tsdf_hip_esdf.  Like every entry point that reads the planes, the call first launches
+ * a frame held back by frame pairing.  The volume's planes and "band seen" flags are neither written nor invalidated, and
+ * the results tsdf_hip_march and tsdf_hip_occupied keep on the handle survive the call.  The call waits for its kernels.
+ *   tsdf_hip_esdf_fetch         d2 and dist of the box to the host, [z][y][x] of the box; either may be NULL.
+ *   tsdf_hip_esdf_fetch_device  the same into DEVICE buffers of the caller, asynchronous on the handle's stream.
+ *   tsdf_hip_esdf_sample        per point (n x 3 floats, volume coordinates) the value of the voxel that CONTAINS it -- the
+ *                               voxel tsdf_hip_lookup_rgb finds (Octree::getContainingVoxel); no interpolation.  found = 1
+ *                               iff that voxel exists and lies in the box; otherwise found = 0 and dist = NaN.
+ *   tsdf_hip_esdf_stats         report-only, of the last tsdf_hip_esdf: out[0] = voxels of the box, out[1] = sites, out[2] =
+ *                               bytes of device memory the field and its scratch hold (d2: 4 per voxel; the sign plane: one
+ *                               bit per voxel; the envelopes of the y / z passes: up to 8 per voxel, at most 1 GiB), out[3]
+ *                               = device microseconds of the three passes (HIP events).
+ * TSDF_HIP_E_INVALID: a NULL handle; a box outside the grid or with a non-positive extent; r_max < 0; min_weight negative
+ * or NaN.  TSDF_HIP_E_UNSUPPORTED, with the reason in tsdf_hip_last_error: a multi-GPU set; a handle that owns only part
+ * of its grid (distances cross slab borders); res[0..2] or size[0..2] not all equal; a box of more than 16384 voxels along
+ * an axis.  TSDF_HIP_E_NOMEM, with the bytes needed in tsdf_hip_last_error, if the field and its scratch do not fit -- a
+ * smaller box then works.  Every refusal but the last comes before the device is touched. */
+#define TSDF_HIP_ESDF_FAR 0xFFFFFFFFu
+int tsdf_hip_esdf(tsdf_handle h, const int32_t box[6], int32_t r_max, float min_weight, uint64_t *n_sites);
+int tsdf_hip_esdf_fetch(tsdf_handle h, uint32_t *d2, float *dist);
+int tsdf_hip_esdf_fetch_device(tsdf_handle h, uint32_t *d_d2, float *d_dist);
+int tsdf_hip_esdf_sample(tsdf_handle h, const float *xyz, size_t n, float *dist, uint8_t *found);
+int tsdf_hip_esdf_stats(tsdf_handle h, uint64_t out[4]);
+
 /* Block transfer of raw voxels (parity tests, save/load, halo exchange).  Coordinates are global
  * grid indices; the block must lie inside the handle's slab + halo.  Any pointer may be NULL.
  * rgb is 3 bytes per voxel (r,g,b).  *_device variants take device pointers (rgb then 4 bytes). */
