@@ -53,6 +53,14 @@ typedef int i4_rsrc __attribute__((ext_vector_type(4)));
 __device__ unsigned tsdf_struct_buffer_load_u32(i4_rsrc rsrc, int vindex, int voffset, int soffset, int aux)
     __asm("llvm.amdgcn.struct.buffer.load.i32");
 
+// ... and its 64-bit form (`buffer_load_dwordx2 ... idxen`): one 8-byte record per index
+typedef unsigned u2 __attribute__((ext_vector_type(2)));
+__device__ u2 tsdf_struct_buffer_load_u32x2(i4_rsrc rsrc, int vindex, int voffset, int soffset, int aux)
+    __asm("llvm.amdgcn.struct.buffer.load.v2i32");
+static __device__ __forceinline__ u2 bload64(rsrc_t r, unsigned voff, unsigned soff) {
+  return __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, 0);
+}
+
 static __device__ __forceinline__ i4_rsrc make_rsrc_2d(const void *p, unsigned row_bytes, unsigned rows) {
   const unsigned long long a = (unsigned long long)p;
   i4_rsrc r;

@@ -60,6 +60,9 @@ struct tsdf_hip_volume {
   std::vector<float> h_ctr[3];
   float *frame_depth = nullptr;  // staging for the host-pointer entry points
   uint32_t *frame_bgra = nullptr;  // = frame_depth + W*H (same allocation)
+  // integrate_color: the frame of the launch in flight as 8-byte pixel records {depth bits, bgra}, written by k_frame_pairs on
+  // the handle's stream right before the colour fast kernel that gathers from it ([1]: frame B of k_integrate2)
+  uint2 *frame_pairs[2] = {nullptr, nullptr};
   // pinned two-slot bounce buffer every host<->device transfer of caller memory goes through (tsdf_to_host /
   // tsdf_to_device in tsdf_core.hip)
   char *bounce = nullptr;
@@ -371,6 +374,7 @@ struct TsdfTuning {
   int implied_d;       // PACKED integrate launches do not read distance words the "band seen" flags and the counts determine (1)
   int pipe;            // ALLIN PACKED launches run the software-pipelined row loop: bit 0 without colour (k_integrate_p: on), bit 1 with (k_integrate_pc: measured no faster than k_integrate's own loop, off); 1
   int lab_chunk;       // LAB volumes: voxels per host round trip of the exact LAB2RGB colours (tsdf_lab_exact_colors; tests lower it)
+  int frame_pairs;     // colour fast kernels gather the frame as 8-byte pixel records {depth, bgra} (k_frame_pairs: one pass over the frame per call) instead of from the two planes: 1 on (default), 0 = the planar gathers (A/B in one build, parity tests)
 };
 const TsdfTuning &tsdf_tuning();
 // Edge of the voxel blocks save / load stream through host memory: TSDF_HIP_VOL_CHUNK, read at EVERY call (an I/O path: a

@@ -58,7 +58,7 @@ static TsdfTuning &tuning_storage() {
                          env_int("TSDF_HIP_CULL", 1), std::max(1, env_int("TSDF_HIP_VOL_CHUNK", 256)),
                          env_int("TSDF_HIP_PLAIN_KERNEL", 0), env_int("TSDF_HIP_ALLOC_TRIES", 3), env_int("TSDF_HIP_ALLIN", 1),
                          env_int("TSDF_HIP_REFCULL_PLAIN", 0), env_int("TSDF_HIP_LIVE_LOG2TX", 5), env_int("TSDF_HIP_ZFAST", 1), env_int("TSDF_HIP_FUSE2", 1), env_int("TSDF_HIP_IMPLIED_D", 1),
-                         env_int("TSDF_HIP_PIPE", 1), std::max(1, env_int("TSDF_HIP_LAB_CHUNK", 16 << 20))};
+                         env_int("TSDF_HIP_PIPE", 1), std::max(1, env_int("TSDF_HIP_LAB_CHUNK", 16 << 20)), env_int("TSDF_HIP_FRAME_PAIRS", 1)};
   return t;
 }
 
@@ -110,6 +110,8 @@ extern "C" int tsdf_hip_set_tuning(const char *name, int value) {
     t.zfast = value;
   else if (n == "lab_chunk")
     t.lab_chunk = std::max(1, value);
+  else if (n == "frame_pairs")
+    t.frame_pairs = value;
   else
     return TSDF_HIP_E_INVALID;
   return TSDF_HIP_OK;
@@ -420,6 +422,8 @@ static void free_volume(tsdf_hip_volume *v) {
   for (int a = 0; a < 3; ++a)
     if (v->ctr[a]) (void)hipFree(v->ctr[a]);
   if (v->frame_depth) (void)hipFree(v->frame_depth);
+  for (int i = 0; i < 2; ++i)
+    if (v->frame_pairs[i]) (void)hipFree(v->frame_pairs[i]);
   if (v->bounce) (void)hipHostFree(v->bounce);
   for (int i = 0; i < 2; ++i)
     if (v->bounce_ev[i]) (void)hipEventDestroy(v->bounce_ev[i]);
@@ -720,6 +724,9 @@ extern "C" int tsdf_hip_create(const tsdf_params *p, tsdf_handle *out) {
   // one allocation [depth | bgra]: the integrate kernel addresses the frame through ONE buffer descriptor
   TRY_OR_BAIL(hipMalloc(&v->frame_depth, 2 * npx * sizeof(float)));
   v->frame_bgra = reinterpret_cast<uint32_t *>(v->frame_depth + npx);
+  // the frame as pixel records for the colour fast kernels (k_frame_pairs); the second one is k_integrate2's frame B
+  if (p->integrate_color)
+    for (int i = 0; i < 2; ++i) TRY_OR_BAIL(hipMalloc(&v->frame_pairs[i], 8 * npx));
   {
     const double cam[4] = {p->fx, p->fy, p->cx, p->cy};  // read by the rare exact-projection path only
     TRY_OR_BAIL(hipMalloc(&v->cam64, sizeof cam));

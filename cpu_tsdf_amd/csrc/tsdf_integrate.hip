@@ -459,7 +459,10 @@ static __device__ __forceinline__ KEntry tsdf_ktab_entry(const IntegrateArgs &a,
 // (Never with ALLIN.  A slab wholly in view that the reference's cull cuts takes this instance for all its blocks: the
 // alternative -- an ALLIN pass over the blocks flagged 1 plus an interval pass over those flagged 2 -- was built and
 // measured slower, profiles/r04_refcull_dual_launch_measured_and_removed.txt.)
-template <int ORDER, bool COLOR, bool FASTPROJ, bool COUNT, bool PACKED, bool ALLIN = false, bool LIVE = false>
+// PAIRS (only with COLOR): `depth` is the frame as 8-byte records {depth bits, bgra} per pixel (k_frame_pairs below), and a
+// voxel's depth and colour come with ONE 8-byte gather instead of two 4-byte ones from the [depth | bgra] planes: the same bits
+// from half the vector-memory instructions, address computations and tag look-ups, and from one cache line.
+template <int ORDER, bool COLOR, bool FASTPROJ, bool COUNT, bool PACKED, bool ALLIN = false, bool LIVE = false, bool PAIRS = false>
 static __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_WPE_OF(ORDER, COLOR, FASTPROJ, COUNT, PACKED, ALLIN) < TSDF_WPE_MAX ? TSDF_WPE_OF(ORDER, COLOR, FASTPROJ, COUNT, PACKED, ALLIN) : TSDF_WPE_MAX, TSDF_WPE_MAX)))
 k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt, uint32_t *__restrict__ RGB,
             uint8_t *__restrict__ K8, const float *__restrict__ depth, const double *__restrict__ cam,
@@ -468,6 +471,7 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
             const uint32_t *__restrict__ row_iv) {
   // brick-level frustum cull (k_cull below): a block none of whose voxels can be observed leaves at once
   static_assert(!(ALLIN && LIVE), "the ALLIN instance knows no row intervals");
+  static_assert(!PAIRS || COLOR, "pixel records carry the colour: the colourless frame is the depth plane itself");
   const BlockCoords bc = tsdf_block_coords(a.zfast);
   bool strad = false;  // LIVE: this block's rows need their intervals (block-uniform)
   if (LIVE) {
@@ -547,10 +551,10 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
   const rsrc_t rsC = make_rsrc(COLOR ? RGB + e0 : (uint32_t *)D, COLOR ? span * 4u : 0u);
   const rsrc_t rsK = make_rsrc(PACKED && !COLOR ? K8 + e0 : (uint8_t *)D, PACKED && !COLOR ? span : 0u);
   const unsigned npix = (unsigned)a.W * (unsigned)a.H;
-  const rsrc_t rsF = make_rsrc(depth, COLOR ? a.bgra_off + npix * 4u : npix * 4u);  // [depth ... bgra]
-  // ALLIN: every pixel index is valid, so the gather can address the frame by INDEX (stride 4, `idxen`): no shift per
-  // pixel, and no range check is wanted (NUM_RECORDS at its maximum, whichever unit the hardware counts it in)
-  const i4_rsrc rsFi = make_rsrc_2d(depth, 4u, 0xffffffffu);
+  const rsrc_t rsF = make_rsrc(depth, PAIRS ? npix * 8u : COLOR ? a.bgra_off + npix * 4u : npix * 4u);  // [depth ... bgra], or the records
+  // ALLIN: every pixel index is valid, so the gather can address the frame by INDEX (stride 4, or 8 for records; `idxen`):
+  // no shift per pixel, and no range check is wanted (NUM_RECORDS at its maximum, whichever unit the hardware counts it in)
+  const i4_rsrc rsFi = make_rsrc_2d(depth, PAIRS ? 8u : 4u, 0xffffffffu);
   if (xq < a.qpr) {
     const int x4 = xq * 4;
     const float cz = ctrz[a.z_global0 + zl];
@@ -683,8 +687,11 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         // a valid pixel offset is < npix*4; -1 becomes 0xfffffffc, beyond the descriptor with or without the
-        // colour image's scalar offset
-        if (ALLIN) {
+        // colour image's scalar offset (records: < npix*8, and 0xfffffff8)
+        if (PAIRS) {
+          const u2 zc = ALLIN ? tsdf_struct_buffer_load_u32x2(rsFi, pix[j], 0, 0, TSDF_GATHER_AUX) : bload64(rsF, (unsigned)pix[j] << 3, 0u);
+          zs[j] = __uint_as_float(zc.x), cs[j] = zc.y;
+        } else if (ALLIN) {
           zs[j] = __uint_as_float(tsdf_struct_buffer_load_u32(rsFi, pix[j], 0, 0, TSDF_GATHER_AUX));
           if (COLOR) cs[j] = tsdf_struct_buffer_load_u32(rsFi, pix[j], 0, (int)a.bgra_off, TSDF_GATHER_AUX);
         } else {
@@ -1248,7 +1255,7 @@ struct PipeRowC {
   u4 d4;           // its distance words (in flight)
 };
 
-template <int ORDER, bool COUNT>
+template <int ORDER, bool COUNT, bool PAIRS>
 static __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_WPE_PIPEC < TSDF_WPE_MAX ? TSDF_WPE_PIPEC : TSDF_WPE_MAX, TSDF_WPE_MAX)))
 k_integrate_pc(const IntegrateArgs a, float *__restrict__ D, uint32_t *__restrict__ RGB, const float *__restrict__ depth,
                const double *__restrict__ cam, const float *__restrict__ ctrx, const float *__restrict__ ctry,
@@ -1288,7 +1295,7 @@ k_integrate_pc(const IntegrateArgs a, float *__restrict__ D, uint32_t *__restric
   const unsigned span = (unsigned)rows * (unsigned)a.pitch;
   const rsrc_t rsD = make_rsrc(D + e0, span * 4u);
   const rsrc_t rsC = make_rsrc(RGB + e0, span * 4u);
-  const i4_rsrc rsFi = make_rsrc_2d(depth, 4u, 0xffffffffu);
+  const i4_rsrc rsFi = make_rsrc_2d(depth, PAIRS ? 8u : 4u, 0xffffffffu);  // PAIRS: pixel records (see k_integrate)
   const uint32_t pbits = __float_as_uint(a.pos_over_neg);
   if (xq < a.qpr) {
     const int x4 = xq * 4;
@@ -1315,8 +1322,13 @@ k_integrate_pc(const IntegrateArgs a, float *__restrict__ D, uint32_t *__restric
       // [phase: frame gather]
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        R.z[j] = tsdf_struct_buffer_load_u32(rsFi, pix[j], 0, 0, TSDF_GATHER_AUX);
-        R.cs[j] = tsdf_struct_buffer_load_u32(rsFi, pix[j], 0, (int)a.bgra_off, TSDF_GATHER_AUX);
+        if (PAIRS) {  // (stage A then issues SIX loads, statically as before)
+          const u2 zc = tsdf_struct_buffer_load_u32x2(rsFi, pix[j], 0, 0, TSDF_GATHER_AUX);
+          R.z[j] = zc.x, R.cs[j] = zc.y;
+        } else {
+          R.z[j] = tsdf_struct_buffer_load_u32(rsFi, pix[j], 0, 0, TSDF_GATHER_AUX);
+          R.cs[j] = tsdf_struct_buffer_load_u32(rsFi, pix[j], 0, (int)a.bgra_off, TSDF_GATHER_AUX);
+        }
       }
       if (COUNT) rdb += pred ? (d_read ? 32u : 16u) : 0u;
     };
@@ -1510,7 +1522,7 @@ struct Frame2 {
 // A row's loads are issued and retired back to back, at TSDF_WPE_K2 waves per SIMD (top of the file): keeping two rows in
 // flight costs 32 more registers of row state, and occupancy wins.
 
-template <int ORDER, bool COLOR, bool COUNT>
+template <int ORDER, bool COLOR, bool COUNT, bool PAIRS>
 static __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_WPE_K2, TSDF_WPE_MAX)))
 k_integrate2(const IntegrateArgs a, const Frame2 fb, float *__restrict__ D, uint32_t *__restrict__ RGB, uint8_t *__restrict__ K8,
              const float *__restrict__ depthA, const float *__restrict__ depthB, const double *__restrict__ cam,
@@ -1553,7 +1565,9 @@ k_integrate2(const IntegrateArgs a, const Frame2 fb, float *__restrict__ D, uint
   const rsrc_t rsD = make_rsrc(D + e0, span * 4u);
   const rsrc_t rsC = make_rsrc(COLOR ? RGB + e0 : (uint32_t *)D, COLOR ? span * 4u : 0u);
   const rsrc_t rsK = make_rsrc(!COLOR ? K8 + e0 : (uint8_t *)D, !COLOR ? span : 0u);
-  const i4_rsrc rsFA = make_rsrc_2d(depthA, 4u, 0xffffffffu), rsFB = make_rsrc_2d(depthB, 4u, 0xffffffffu);
+  static_assert(!PAIRS || COLOR, "pixel records carry the colour");
+  const unsigned fstride = PAIRS ? 8u : 4u;  // PAIRS: both frames as pixel records (see k_integrate)
+  const i4_rsrc rsFA = make_rsrc_2d(depthA, fstride, 0xffffffffu), rsFB = make_rsrc_2d(depthB, fstride, 0xffffffffu);
   const uint32_t hinge_bits = __float_as_uint(a.pos_over_neg);
   if (xq < a.qpr) {
     const int x4 = xq * 4;
@@ -1582,13 +1596,23 @@ k_integrate2(const IntegrateArgs a, const Frame2 fb, float *__restrict__ D, uint
       project_quad_allin<ORDER>(a, fb.m, cam, s_cx[tid], s_ytB[ty + r * a.TY], ztB, pixB, L.gzB);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        L.zsA[j] = __uint_as_float(tsdf_struct_buffer_load_u32(rsFA, pixA[j], 0, 0, TSDF_GATHER_AUX));
-        L.csA[j] = COLOR ? tsdf_struct_buffer_load_u32(rsFA, pixA[j], 0, (int)a.bgra_off, TSDF_GATHER_AUX) : 0u;
+        if (PAIRS) {
+          const u2 zc = tsdf_struct_buffer_load_u32x2(rsFA, pixA[j], 0, 0, TSDF_GATHER_AUX);
+          L.zsA[j] = __uint_as_float(zc.x), L.csA[j] = zc.y;
+        } else {
+          L.zsA[j] = __uint_as_float(tsdf_struct_buffer_load_u32(rsFA, pixA[j], 0, 0, TSDF_GATHER_AUX));
+          L.csA[j] = COLOR ? tsdf_struct_buffer_load_u32(rsFA, pixA[j], 0, (int)a.bgra_off, TSDF_GATHER_AUX) : 0u;
+        }
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        L.zsB[j] = __uint_as_float(tsdf_struct_buffer_load_u32(rsFB, pixB[j], 0, 0, TSDF_GATHER_AUX));
-        L.csB[j] = COLOR ? tsdf_struct_buffer_load_u32(rsFB, pixB[j], 0, (int)fb.bgra_off, TSDF_GATHER_AUX) : 0u;
+        if (PAIRS) {
+          const u2 zc = tsdf_struct_buffer_load_u32x2(rsFB, pixB[j], 0, 0, TSDF_GATHER_AUX);
+          L.zsB[j] = __uint_as_float(zc.x), L.csB[j] = zc.y;
+        } else {
+          L.zsB[j] = __uint_as_float(tsdf_struct_buffer_load_u32(rsFB, pixB[j], 0, 0, TSDF_GATHER_AUX));
+          L.csB[j] = COLOR ? tsdf_struct_buffer_load_u32(rsFB, pixB[j], 0, (int)fb.bgra_off, TSDF_GATHER_AUX) : 0u;
+        }
       }
       L.d4 = bload128(rsD, voff, soff);
       L.c4 = (u4){0u, 0u, 0u, 0u};
@@ -2519,9 +2543,10 @@ static bool slab_all_inside(const tsdf_hip_volume *h, const float T[12]) {
   return all_inside;
 }
 
-// The fast kernels read the frame through ONE buffer descriptor based at the depth image, with the colour image at a
-// 32-bit byte offset from it.  True, and *off (0 without colour), when the caller's buffers already lie so: the colour
-// image behind the depth image, within 2 GB.
+// The PLANAR frame (colourless launches; colour launches with knob frame_pairs = 0): the fast kernels read it through ONE
+// buffer descriptor based at the depth image, with the colour image at a 32-bit byte offset from it.  True, and *off (0
+// without colour), when the caller's buffers already lie so: the colour image behind the depth image, within 2 GB.
+// (Colour launches otherwise gather pixel records: k_frame_pairs below.)
 static bool frame_bgra_offset(const tsdf_params &p, const float *d_depth, const uint32_t *d_bgra, unsigned *off) {
   *off = 0;
   if (!p.integrate_color) return true;
@@ -2530,6 +2555,12 @@ static bool frame_bgra_offset(const tsdf_params &p, const float *d_depth, const 
   if (!(cb >= zd + npx * 4 && (size_t)(cb - zd) + npx * 4 < (1ull << 31))) return false;
   *off = (unsigned)(cb - zd);
   return true;
+}
+
+// ... the question alone: do the caller's two images already form a planar frame?
+static bool frame_is_planar(const tsdf_params &p, const float *d_depth, const uint32_t *d_bgra) {
+  unsigned off;
+  return frame_bgra_offset(p, d_depth, d_bgra, &off);
 }
 
 // Frame staging: caller buffers laid out otherwise are copied into the handle's [depth | bgra] allocation first (two
@@ -2546,6 +2577,37 @@ static int stage_frame(tsdf_handle h, const float **d_depth, const uint32_t *d_b
   *bgra_off = (unsigned)(npx * 4);
   return TSDF_HIP_OK;
 }
+
+// The frame as 8-byte pixel records {depth bits, bgra} for the colour fast kernels (PAIRS): one pass over the frame per call
+// (2.4 MB read, 2.4 MB written at 640x480) against a kernel that gathers each pixel thousands of times.  BITS are copied --
+// integer loads, so NaN payloads and the alpha byte arrive untouched -- two pixels per thread, one 16-byte store.
+static __global__ void __launch_bounds__(256)
+k_frame_pairs(const uint32_t *__restrict__ depth, const uint32_t *__restrict__ bgra, uint2 *__restrict__ out, unsigned npix) {
+  const unsigned i = (blockIdx.x * 256u + threadIdx.x) * 2u;
+  if (i + 1u < npix) {
+    // (the callers' images are only known to be 4-byte aligned: word loads; out is the handle's own allocation, i is even)
+    const uint4 v = {depth[i], bgra[i], depth[i + 1u], bgra[i + 1u]};
+    *reinterpret_cast<uint4 *>(out + i) = v;
+  } else if (i < npix) {
+    out[i] = make_uint2(depth[i], bgra[i]);
+  }
+}
+
+static int launch_frame_pairs(tsdf_handle h, const float *d_depth, const uint32_t *d_bgra, uint2 *out) {
+  const unsigned npix = (unsigned)h->p.image_width * (unsigned)h->p.image_height;
+  if (!out || !d_depth || !d_bgra) {  // (an error, never a quiet return to the planar frame)
+    tsdf_set_error("colour launch without its pixel-record buffer or frame");
+    return TSDF_HIP_E_INVALID;
+  }
+  hipLaunchKernelGGL(k_frame_pairs, dim3((npix + 511u) / 512u), dim3(256), 0, h->stream, reinterpret_cast<const uint32_t *>(d_depth),
+                     d_bgra, out, npix);
+  TSDF_HIP_TRY(hipGetLastError());
+  return TSDF_HIP_OK;
+}
+
+// The colour fast kernels read pixel records unless the knob says otherwise: tsdf_hip_create allocates both record buffers
+// for every handle with integrate_color (or fails), so there is no third case in which a launch could fall back quietly
+static bool frame_pairs_apply(tsdf_handle h) { return tsdf_tuning().frame_pairs && h->p.integrate_color; }
 
 // planes fastest when the frame outgrows an XCD's L2 (knob zfast: -1 auto, 0 / 1 force)
 static int zfast_for(const tsdf_params &p, unsigned gx) {
@@ -2783,31 +2845,33 @@ static int plan_live(tsdf_handle h, const float T[12], bool all_inside, bool rc_
 
 // Dispatch: the instance of k_integrate (or, `pipe`, of the pipelined kernels) for this launch.
 static void dispatch_fast(tsdf_handle h, const LaunchPlan &pl, const float *d_depth, bool count, bool fastproj, bool allin,
-                          bool pipe, uint8_t *band_arg) {
+                          bool pipe, bool pairs, uint8_t *band_arg) {
   const IntegrateArgs &a = pl.a;
   const dim3 grid(a.zfast ? pl.gz : pl.gx, pl.gy, a.zfast ? pl.gx : pl.gz), block(256);
   const bool sse = h->p.xform_order == TSDF_XFORM_PCL_SSE, color = h->p.integrate_color != 0;
+  pairs = pairs && color;  // (`pairs`: d_depth holds pixel records)
   if (pipe) {
     with_consts(
-        [&](auto SSE, auto COUNT) {
+        [&](auto SSE, auto COUNT, auto PAIRS) {
           if (color)
-            hipLaunchKernelGGL((k_integrate_pc<xform_order_of(SSE), COUNT>), grid, block, 0, h->stream, a, pl.D, pl.RGB, d_depth,
+            hipLaunchKernelGGL((k_integrate_pc<xform_order_of(SSE), COUNT, PAIRS>), grid, block, 0, h->stream, a, pl.D, pl.RGB, d_depth,
                                h->cam64, pl.ctrx, pl.ctry, h->ctr[2], h->counter, band_arg);
-          else
+          else if constexpr (!PAIRS)
             hipLaunchKernelGGL((k_integrate_p<xform_order_of(SSE), COUNT>), grid, block, 0, h->stream, a, pl.D, pl.K8, d_depth,
                                h->cam64, pl.ctrx, pl.ctry, h->ctr[2], h->counter, band_arg);
         },
-        sse, count);
+        sse, count, pairs);
     return;
   }
   with_consts(
-      [&](auto SSE, auto COLOR, auto FASTPROJ, auto COUNT, auto PACKED, auto ALLIN, auto LIVE) {
-        if constexpr (!(ALLIN && (!FASTPROJ || LIVE)))  // (never built: ALLIN without the fast projection, ALLIN with LIVE)
-          hipLaunchKernelGGL((k_integrate<xform_order_of(SSE), COLOR, FASTPROJ, COUNT, PACKED, ALLIN, LIVE>), grid, block, 0,
+      [&](auto SSE, auto COLOR, auto FASTPROJ, auto COUNT, auto PACKED, auto ALLIN, auto LIVE, auto PAIRS) {
+        // (never built: ALLIN without the fast projection, ALLIN with LIVE, pixel records without colour)
+        if constexpr (!(ALLIN && (!FASTPROJ || LIVE)) && !(PAIRS && !COLOR))
+          hipLaunchKernelGGL((k_integrate<xform_order_of(SSE), COLOR, FASTPROJ, COUNT, PACKED, ALLIN, LIVE, PAIRS>), grid, block, 0,
                              h->stream, a, pl.D, pl.Wt, pl.RGB, pl.K8, d_depth, h->cam64, pl.ctrx, pl.ctry, h->ctr[2], h->counter,
                              pl.live, band_arg, h->row_iv);
       },
-      sse, color, fastproj, count, h->packed, allin, pl.live != nullptr);
+      sse, color, fastproj, count, h->packed, allin, pl.live != nullptr, pairs);
 }
 
 // Validation of a launch, in the order the errors have always been reported.
@@ -2851,7 +2915,16 @@ int tsdf_integrate_launch(tsdf_handle h, const float *d_depth, const uint32_t *d
     h->band_exact = false;  // the plain kernels keep no "band seen" flags: marching cubes reads everything
     return launch_plain_family(h, a, pl.gz, plain_mode, d_depth, d_bgra, T, count);
   }
-  if (const int e = stage_frame(h, &d_depth, d_bgra, &a.bgra_off)) return e;
+  // Colour: the fast kernels gather pixel records built from the caller's two images wherever they lie (k_frame_pairs, queued
+  // right in front of the kernel below) -- no repack into [depth | bgra]; a staged frame ends where the repack would have
+  // ended it.  Without colour, or with the knob off: the planar frame.
+  const bool pairs = frame_pairs_apply(h);
+  if (pairs) {
+    if (!frame_is_planar(h->p, d_depth, d_bgra)) h->frame_staged = 0;
+    a.bgra_off = 0;  // (the record instances do not read it)
+  } else if (const int e = stage_frame(h, &d_depth, d_bgra, &a.bgra_off)) {
+    return e;
+  }
   const LaunchKind kind = launch_kind(h, T, a, rc, rc_rows);
   if (kind.live)
     if (const int e = plan_live(h, T, kind.all_inside, rc_rows, pl)) return e;
@@ -2870,7 +2943,11 @@ int tsdf_integrate_launch(tsdf_handle h, const float *d_depth, const uint32_t *d
     h->last_launch[1] = fastproj;
     h->last_launch[2] = live ? (rc_rows ? 2 : 1) : 0;
     h->last_launch[3] = (int)std::min<uint64_t>((uint64_t)pl.gx * pl.gy * pl.gz, 0x7fffffffu);
-    dispatch_fast(h, pl, d_depth, count, fastproj, allin, pipe, band_arg);
+    if (pairs) {
+      if (const int e = launch_frame_pairs(h, d_depth, d_bgra, h->frame_pairs[0])) return e;
+      d_depth = reinterpret_cast<const float *>(h->frame_pairs[0]);
+    }
+    dispatch_fast(h, pl, d_depth, count, fastproj, allin, pipe, pairs, band_arg);
     TSDF_HIP_TRY(hipGetLastError());
   }
   h->count_slots = count ? 4096 : 0;  // slots 1024.. hold the bytes of voxel words whose value changed, 2048.. the observed
@@ -2950,11 +3027,14 @@ int tsdf_integrate_launch2(tsdf_handle h, const float *dA, const uint32_t *cA, c
   // both poses pass fusable_pose (fast projection; the slab all inside with its margins; a reference cull that keeps the
   // whole slab, so no row intervals) on a PACKED handle whose grid and weights admit ALLIN under cull = 1 -- which is
   // launch_kind's allin && !live.  (The predicate also asks for h->packed, which `ok` requires anyway.)
+  // Colour: both frames as pixel records (k_frame_pairs; the callers' images may lie anywhere), else as [depth | bgra] in place
+  const bool pairs = frame_pairs_apply(h);
+  a.bgra_off = fb.bgra_off = 0;  // (set below for a planar pair; the record instances do not read them)
   const bool pipe_wins = !color && tsdf_tuning().fuse2 == 1 && pipelined_rows_apply(h, a, color, true, true, false);
   const bool ok = tsdf_tuning().fuse2 && !pipe_wins && tsdf_tuning().cull == 1 && tsdf_tuning().allin && h->packed && !h->cn[0] && !h->weight_by_depth &&
                   !h->weight_by_variance && !tsdf_tuning().plain_kernel && (h->nx & 3) == 0 && a.wmax_is_int && (float)h->kmax == p.max_weight &&
-                  pl.gy <= 65535u && pl.gz <= 65535u && pl.gz > 0 && frame_bgra_offset(p, dA, cA, &a.bgra_off) &&
-                  frame_bgra_offset(p, dB, cB, &fb.bgra_off) && fusable_pose(h, hh, TA, planesA) && fusable_pose(h, hh, TB, planesB);
+                  pl.gy <= 65535u && pl.gz <= 65535u && pl.gz > 0 &&
+                  (pairs || (frame_bgra_offset(p, dA, cA, &a.bgra_off) && frame_bgra_offset(p, dB, cB, &fb.bgra_off))) && fusable_pose(h, hh, TA, planesA) && fusable_pose(h, hh, TB, planesB);
   if (fused) *fused = ok;
   if (!ok) {  // two launches, each with its own planes; with `count` the first one's counters are read before the second runs
     int rc = tsdf_hip_set_reference_cull(h, planesA);
@@ -2983,12 +3063,20 @@ int tsdf_integrate_launch2(tsdf_handle h, const float *dA, const uint32_t *cA, c
   h->last_launch[3] = (int)std::min<uint64_t>((uint64_t)pl.gx * pl.gy * pl.gz, 0x7fffffffu);
   a.zfast = zfast_for(p, pl.gx);
   const dim3 grid(a.zfast ? pl.gz : pl.gx, pl.gy, a.zfast ? pl.gx : pl.gz), block(256);
+  if (pairs) {
+    // (a staged frame ends where the two launches' repack would have ended it: include/tsdf_hip.h, tsdf_hip_organize)
+    if (!frame_is_planar(p, dA, cA) || !frame_is_planar(p, dB, cB)) h->frame_staged = 0;
+    if (const int e = launch_frame_pairs(h, dA, cA, h->frame_pairs[0])) return e;
+    if (const int e = launch_frame_pairs(h, dB, cB, h->frame_pairs[1])) return e;
+    dA = reinterpret_cast<const float *>(h->frame_pairs[0]), dB = reinterpret_cast<const float *>(h->frame_pairs[1]);
+  }
   with_consts(
-      [&](auto SSE, auto COLOR, auto COUNT) {
-        hipLaunchKernelGGL((k_integrate2<xform_order_of(SSE), COLOR, COUNT>), grid, block, 0, h->stream, a, fb, h->d, h->rgb, h->k8,
-                           dA, dB, h->cam64, h->ctr[0], h->ctr[1], h->ctr[2], h->counter, band_arg);
+      [&](auto SSE, auto COLOR, auto COUNT, auto PAIRS) {
+        if constexpr (!(PAIRS && !COLOR))
+          hipLaunchKernelGGL((k_integrate2<xform_order_of(SSE), COLOR, COUNT, PAIRS>), grid, block, 0, h->stream, a, fb, h->d, h->rgb, h->k8,
+                             dA, dB, h->cam64, h->ctr[0], h->ctr[1], h->ctr[2], h->counter, band_arg);
       },
-      p.xform_order == TSDF_XFORM_PCL_SSE, color, count);
+      p.xform_order == TSDF_XFORM_PCL_SSE, color, count, pairs);
   TSDF_HIP_TRY(hipGetLastError());
   h->count_slots = count ? 3072 : 0;
   h->count_ran = true;
@@ -3765,9 +3853,63 @@ static __global__ void k_selftest_struct_oob(const float *img, int W, int H, uns
   out[i] = tsdf_struct_buffer_load_u32(r, uv[2 * i + 1], uv[2 * i] * 4, (int)soff, 0);
 }
 
+// ... and its RECORD form (planes == 2, plane == -1): k_frame_pairs on [depth | bgra], then the colour kernels' raw 8-byte gather
+// (byte offset pix << 3 on a descriptor of 8 * W * H bytes; pixel -1 for a (u, v) outside the image) at each (u, v).
+static __global__ void k_selftest_record_gather(const uint2 *rec, int W, int H, const int *uv, unsigned *out, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int u = uv[2 * i], v = uv[2 * i + 1];
+  const int pix = (unsigned)u < (unsigned)W && (unsigned)v < (unsigned)H ? v * W + u : -1;
+  const rsrc_t rs = make_rsrc(rec, (unsigned)W * (unsigned)H * 8u);
+  const u2 zc = bload64(rs, (unsigned)pix << 3, 0u);
+  out[2 * i] = zc.x, out[2 * i + 1] = zc.y;
+}
+
+static int selftest_record_gather(const float *img, int W, int H, const int32_t *uv, uint32_t *out, int n) {
+  const size_t npx = (size_t)W * H;
+  if (npx > (size_t)1 << 24) return TSDF_HIP_E_INVALID;
+  struct DeviceBuffers {  // freed on every way out, the early returns of TSDF_HIP_TRY included
+    void *p[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~DeviceBuffers() {
+      for (void *q : p)
+        if (q) (void)hipFree(q);
+    }
+  } buf;
+  TSDF_HIP_TRY(hipMalloc(&buf.p[0], npx * 8));
+  TSDF_HIP_TRY(hipMalloc(&buf.p[1], (npx + 2) * 8));  // two guard records behind the last one
+  TSDF_HIP_TRY(hipMalloc(&buf.p[2], (size_t)n * 8));
+  TSDF_HIP_TRY(hipMalloc(&buf.p[3], (size_t)n * 8));
+  uint32_t *d_img = static_cast<uint32_t *>(buf.p[0]);
+  uint2 *d_rec = static_cast<uint2 *>(buf.p[1]);
+  int *d_uv = static_cast<int *>(buf.p[2]);
+  unsigned *d_out = static_cast<unsigned *>(buf.p[3]);
+  TSDF_HIP_TRY(hipMemcpy(d_img, img, npx * 8, hipMemcpyHostToDevice));
+  TSDF_HIP_TRY(hipMemcpy(d_uv, uv, (size_t)n * 8, hipMemcpyHostToDevice));
+  TSDF_HIP_TRY(hipMemset(d_rec, 0xa5, (npx + 2) * 8));
+  hipLaunchKernelGGL(k_frame_pairs, dim3((unsigned)((npx + 511) / 512)), dim3(256), 0, 0, d_img, d_img + npx, d_rec, (unsigned)npx);
+  hipLaunchKernelGGL(k_selftest_record_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_rec, W, H, d_uv, d_out, n);
+  TSDF_HIP_TRY(hipGetLastError());
+  TSDF_HIP_TRY(hipMemcpy(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost));
+  uint32_t guard[4] = {0, 0, 0, 0};
+  TSDF_HIP_TRY(hipMemcpy(guard, d_rec + npx, sizeof guard, hipMemcpyDeviceToHost));
+  std::vector<uint32_t> after(2 * npx);
+  TSDF_HIP_TRY(hipMemcpy(after.data(), d_img, npx * 8, hipMemcpyDeviceToHost));
+  if (guard[0] != 0xa5a5a5a5u || guard[1] != 0xa5a5a5a5u || guard[2] != 0xa5a5a5a5u || guard[3] != 0xa5a5a5a5u) {
+    tsdf_set_error("k_frame_pairs wrote behind the last record");
+    return TSDF_HIP_E_HIP;
+  }
+  if (memcmp(after.data(), img, npx * 8) != 0) {
+    tsdf_set_error("k_frame_pairs changed the images it read");
+    return TSDF_HIP_E_HIP;
+  }
+  return TSDF_HIP_OK;
+}
+
 extern "C" int tsdf_hip_selftest_struct_oob(const float *img, int W, int H, int planes, int plane, const int32_t *uv, uint32_t *out,
                                             int n) {
-  if (!img || !uv || !out || n <= 0 || W <= 0 || H <= 0 || planes < 1 || plane < 0 || plane >= planes) return TSDF_HIP_E_INVALID;
+  const bool records = planes == 2 && plane == -1;  // the record form (include/tsdf_hip_test.h)
+  if (!img || !uv || !out || n <= 0 || W <= 0 || H <= 0 || planes < 1 || (!records && (plane < 0 || plane >= planes))) return TSDF_HIP_E_INVALID;
+  if (records) return selftest_record_gather(img, W, H, uv, out, n);
   float *d_img = nullptr;
   int *d_uv = nullptr;
   unsigned *d_out = nullptr;

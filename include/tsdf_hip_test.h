@@ -42,7 +42,12 @@ int tsdf_hip_selftest_project(tsdf_handle h, const float *g, size_t n, int32_t *
 
 /* Test hook: structured buffer loads (row index v, byte offset 4 u, descriptor of H rows of W floats, image `plane` of
  * `planes` back-to-back images selected by the scalar offset) at n (u, v) pairs, inside and outside the image: the
- * integrate kernel's frame gather relies on what the hardware returns out of range. */
+ * integrate kernel's frame gather relies on what the hardware returns out of range.
+ * RECORD form, planes == 2 and plane == -1: img = [depth | bgra] (any bits); the colour kernels' record pass (k_frame_pairs)
+ * lays it out as W * H 8-byte pixel records {depth bits, bgra}, and each (u, v) is gathered from them the way the kernels do
+ * (one 8-byte load at byte offset pix << 3, pix = v * W + u inside the image, -1 outside): out takes 2 n words,
+ * out[2 i] = depth bits, out[2 i + 1] = bgra, both 0 outside.  The call fails (TSDF_HIP_E_HIP, with a message) if the pass
+ * wrote behind the last record or changed a bit of the two images it read. */
 int tsdf_hip_selftest_struct_oob(const float *img, int W, int H, int planes, int plane, const int32_t *uv, uint32_t *out, int n);
 
 /* Test hook: the voxel Octree::getContainingVoxel (src/lib/octree.cpp:112-133,628-643) returns for n points,
@@ -77,7 +82,7 @@ int tsdf_hip_selftest_read_sweep(tsdf_handle h, int stride_bytes, uint64_t *span
 int tsdf_hip_selftest_occupancy_mc(int out[2]);
 
 /* Test / A-B hook: set a launch-shape knob ("rows_per_block", "blocks_per_cu", "fast_projection",
- * "mc_flush_at", "mc_skip", "cull", "vol_chunk", "plain_kernel", "alloc_tries", "allin", "refcull_plain", "live_log2tx", "fuse2", "lab_chunk" -- the
+ * "mc_flush_at", "mc_skip", "cull", "vol_chunk", "plain_kernel", "alloc_tries", "allin", "refcull_plain", "live_log2tx", "fuse2", "lab_chunk", "frame_pairs" -- the
  * TSDF_HIP_* environment variables, which the product library reads once) at run time.  No knob changes results. */
 int tsdf_hip_set_tuning(const char *name, int value);
 

@@ -102,8 +102,8 @@ def main():
     }
     # k_integrate2 (two frames per sweep: the bench line's extras.fused2 leg), when the profiled command ran it: its own
     # counters instead of an algorithmic estimate
-    def timed2(summary):  # the non-counting instance of k_integrate2 (last template argument false): the leg's timed launches + its one probe launch
-        return next((k for k in summary if k.startswith("k_integrate2<") and k.rstrip(">").endswith("false")), None)
+    def timed2(summary):  # the non-counting instance of k_integrate2 (<ORDER, COLOR, COUNT = false, PAIRS>): the leg's timed launches + its one probe launch
+        return next((k for k in summary if k.startswith("k_integrate2<") and k.rstrip(">").split("<")[1].split(",")[2] == "false"), None)
     if timed2(fetch) and timed2(write) and timed2(trace):
         k2 = timed2(fetch)
         rd2 = fetch[k2]["FETCH_SIZE"] * 1024 * round(cal_r)
