@@ -10,7 +10,7 @@
 
 #include "tsdf_hip.h"
 
-struct tsdf_hip_pipeline;  // tsdf_integrate.hip: pinned staging ring of tsdf_hip_integrate_async
+struct tsdf_hip_pipeline;  // tsdf_pipeline.hip: pinned staging ring of tsdf_hip_integrate_async
 struct tsdf_hip_multi;     // tsdf_multi.hip: the Z-slab handles of a multi-GPU volume
 // per-handle state of one feature each, defined in its own translation unit and created by the first call that needs it
 struct tsdf_occ_state;       // tsdf_occupied.hip: the sorted key list of tsdf_hip_occupied, a set's merged list
@@ -179,6 +179,8 @@ void tsdf_multi_mesh(tsdf_handle h, const float **verts, const uint8_t **rgb, co
 // frame pairing on a set (round 6): the slabs pair the frames of their own rings; tsdf_multi_flush lets them launch what they hold
 int tsdf_multi_flush(tsdf_handle h);
 int tsdf_multi_set_frame_pairing(tsdf_handle h, int on);
+int tsdf_multi_frame_begin(tsdf_handle h, float **depth, uint8_t **bgra);
+int tsdf_multi_frame_commit(tsdf_handle h, const float T[12]);
 int tsdf_multi_shift(tsdf_handle h, const int32_t shift[3]);
 int tsdf_multi_integrate_device2(tsdf_handle h, const float *da, const uint32_t *ca, const float TA[12], const float *planes_a, const float *db,
                                  const uint32_t *cb, const float TB[12], const float *planes_b, uint64_t *n_observed, int32_t *fused);
@@ -196,6 +198,13 @@ int tsdf_integrate_collect(tsdf_handle h, uint64_t *n_observed);
 int tsdf_integrate_launch2(tsdf_handle h, const float *dA, const uint32_t *cA, const float TA[12], const float *planesA,
                            const float *dB, const uint32_t *cB, const float TB[12], const float *planesB, bool count, bool *fused);
 int tsdf_integrate_collect2(tsdf_handle h, uint64_t n_observed[2]);
+int tsdf_integrate_frame(tsdf_handle h, const float *d_depth, const uint32_t *d_bgra, const float T[12], uint64_t *n_observed);  // launch (+ collect)
+// A slab of a set takes frames through its own staging ring (tsdf_pipeline.hip; called by tsdf_multi.hip, which brings `copy`).
+int tsdf_pipeline_commit_from(tsdf_handle s, const void *src, int src_dev, const float T[12], bool pairing, hipEvent_t uploaded,
+                              int (*copy)(void *ctx, void *dst, int dst_dev, const void *src, int src_dev, size_t bytes, hipStream_t st), void *ctx);
+int tsdf_pipeline_pair_from(tsdf_handle s, const void *src_a, const void *src_b, int src_dev, const float TA[12], const float *planes_a,
+                            const float TB[12], const float *planes_b, bool count, bool *fused,
+                            int (*copy)(void *ctx, void *dst, int dst_dev, const void *src, int src_dev, size_t bytes, hipStream_t st), void *ctx);
 
 // Compact ray lists of the one-process multi-GPU renderView (tsdf_query.hip; all asynchronous on the slab's stream).
 #define TSDF_MAX_SLABS 64

@@ -143,7 +143,7 @@ static __device__ __forceinline__ int project_fast(const IntegrateArgs &a, float
   const float rv = __builtin_fmaf(gy * a.fyf, y, a.cyf);
   const int u = (int)ru, v = (int)rv;  // v_cvt_i32_f32: truncates, saturates, NaN -> 0
   // ALLIN: the host has proved that every voxel of the launch projects at least a pixel inside the image border and
-  // has 1e-3 <= g.z (launch_integrate, `all_inside`), so R~ is finite and positive, a certified (u, v) needs no bounds
+  // has 1e-3 <= g.z (launch_kind, `all_inside`), so R~ is finite and positive, a certified (u, v) needs no bounds
   // test, and the certificate is handed back as ONE number -- min(fract(ru), fract(rv)), to be compared against
   // max(hb_u, hb_v): slightly stricter than the two separate tests -- so that the caller can certify a whole quad
   // with one compare.  The fractions lie in [0, 1): their bit patterns order like the values, and integer minima
@@ -165,7 +165,7 @@ static __device__ __forceinline__ int project_fast(const IntegrateArgs &a, float
 // the same operands (v_pk_mul / v_pk_add / v_pk_fma_f32 round each half like the scalar instruction), so g, R~ and the
 // certificate are bit for bit those of the scalar form; written on pairs so that the compiler keeps ONE pairing from the
 // centres to the pixel index (the scalar form cost eight register shuffles per row).  cxv = the quad's x centres, ytv = the
-// row's part of the transform (k_integrate's s_yt), zt = the plane's part (used by the left-to-right order only).
+// row's part of the transform (an s_yt entry: tsdf_row_part), zt = the plane's part (used by the left-to-right order only).
 template <int ORDER>
 static __device__ __forceinline__ void project_quad_allin(const IntegrateArgs &a, const float (&m)[12], const double *__restrict__ cam,
                                                           const f4 cxv, const f4 ytv, const float (&zt)[3], int (&pix)[4],
@@ -381,20 +381,50 @@ static __device__ __forceinline__ BlockCoords tsdf_block_coords(int zfast) {
 // K8 (no colour); w = min(k, max_weight), k' = min(k + 1, kmax); a thread then moves 8 (5) bytes per voxel
 // each way instead of 12 (8), and 1/(k+1) comes from a 256-entry LDS table of refined reciprocals.
 // COUNT = accumulate the observed-voxel counter.
+
+// The rows of a block and where they lie in a plane array (wave-uniform): the kernels base their buffer descriptors on it.
+// (voff and row_step stay two lines inside each kernel's `xq < qpr` branch: worked out here, in front of it, they change the timed code.)
+struct BlockRows {
+  int row0, rows;  // the block's first row, counted from the launch's, and how many rows it has (the last block of a column: fewer)
+  int64_t e0;      // element index of the block's first row in a plane array
+  unsigned span;   // elements of this block's row group: what a buffer descriptor based at e0 may reach
+};
+static __device__ __forceinline__ BlockRows tsdf_block_rows(const IntegrateArgs &a, const BlockCoords &bc) {
+  BlockRows b;
+  b.row0 = (int)bc.by * a.rpb * a.TY;
+  b.rows = min(a.rpb * a.TY, a.ny - b.row0);
+  b.e0 = ((int64_t)(a.zl0 + (int)bc.bz) * a.plane_rows + b.row0) * a.pitch;
+  b.span = (unsigned)b.rows * (unsigned)a.pitch;
+  return b;
+}
+
+// The "band seen" flag cells (64 x 4 x 1 voxels) that the rows of a block lie in, numbered row group major --
+// the order of the block's own s_band and s_bin.  Used before the row loop (tsdf_flags_before) and behind it (tsdf_flags_write_out).
+struct BandCells {
+  int lf, fxb;   // cells per row group of four rows: TX / 16 = 1 << lf, a power of two
+  int yg0, xc0;  // the block's first cell in the plane's [band_fy][band_fx] array
+  int n_fl;      // cells that hold voxels of the block
+};
+static __device__ __forceinline__ BandCells tsdf_band_cells(const IntegrateArgs &a, const BlockCoords &bc, const BlockRows &br) {
+  // [phase: select / change detection / store]  (tools/isa_phase_mix.py books the flag write-out behind the row loop under the row's stores)
+  BandCells c;
+  c.lf = max(0, a.log2TX - 4), c.fxb = 1 << c.lf;
+  c.yg0 = (a.y_abs0 + br.row0) >> 2;
+  const int yg1 = (a.y_abs0 + br.row0 + max(br.rows, 1) - 1) >> 2;
+  c.xc0 = (a.x_abs0 + (int)bc.bx * a.TX * 4) >> 6;
+  c.n_fl = (yg1 - c.yg0 + 1) << c.lf;
+  return c;
+}
+// [phase: (prologue / other)]  (the helpers from here on run in front of the row loop)
 // Implied distances (see k_integrate's s_bin): the "band seen" flags of a block's cells as they stood BEFORE the launch, in
 // the order of the block's own s_band (row group major, TX / 16 cells per row group); cells without voxels read 0.
 static __device__ __forceinline__ void tsdf_flags_before(const IntegrateArgs &a, const BlockCoords &bc, const uint8_t *band,
                                                          uint8_t *s_bin, unsigned tid) {
-  const int row0 = (int)bc.by * a.rpb * a.TY;
-  const int rows = min(a.rpb * a.TY, a.ny - row0);
-  const int lf = max(0, a.log2TX - 4), fxb = 1 << lf;  // cells per row group of the block: TX / 16, a power of two
-  const int yg0 = (a.y_abs0 + row0) >> 2, yg1 = (a.y_abs0 + row0 + max(rows, 1) - 1) >> 2;
-  const int xc0 = (a.x_abs0 + (int)bc.bx * a.TX * 4) >> 6;
-  const int n_fl = (yg1 - yg0 + 1) << lf;
-  const int n_all = ((a.rpb * a.TY + 3) >> 2) << lf;  // every cell tsdf_quiet_passes may look at (<= 1024)
+  const BandCells c = tsdf_band_cells(a, bc, tsdf_block_rows(a, bc));
+  const int n_all = ((a.rpb * a.TY + 3) >> 2) << c.lf;  // every cell tsdf_quiet_passes may look at (<= 1024)
   for (int i = (int)tid; i < n_all; i += 256) {
-    const int yg = yg0 + (i >> lf), xc = xc0 + (i & (fxb - 1));
-    s_bin[i] = i < n_fl && yg < a.band_fy && xc < a.band_fx ? band[((int64_t)(a.zl0 + (int)bc.bz) * a.band_fy + yg) * a.band_fx + xc] : (uint8_t)0;
+    const int yg = c.yg0 + (i >> c.lf), xc = c.xc0 + (i & (c.fxb - 1));
+    s_bin[i] = i < c.n_fl && yg < a.band_fy && xc < a.band_fx ? band[((int64_t)(a.zl0 + (int)bc.bz) * a.band_fy + yg) * a.band_fx + xc] : (uint8_t)0;
   }
 }
 // ... and from them, per wave: bit r = none of the cells the wave's 64 quads lie in during pass r (rows ty + r * TY) had its
@@ -443,10 +473,110 @@ static __device__ __forceinline__ KEntry tsdf_ktab_entry(const IntegrateArgs &a,
 #define TSDF_BAND(i) s_band_sets[threadIdx.x >> 6][i]
 #define TSDF_BAND_FIRST ((int)(tid & 63u))
 #define TSDF_BAND_STEP 64
+// the flag cell of this thread's quad in pass r over the block's rows (`ty`, `tx` in scope)
+// (the host only passes `band` when every block's first row is a multiple of 4: local row groups == global ones)
+#define TSDF_BAND_CELL(r) (((ty + (r) * a.TY) >> 2) * max(1, a.TX >> 4) + (tx >> 4))
+// ... and a wave's own flags -> the volume's flag array, when the wave is done with its rows (every writer stores the same 1:
+// no atomics, and no barrier: a wave reads back what it wrote itself).  `sets` = the kernel's s_band_sets.
+static __device__ __forceinline__ void tsdf_flags_write_out(const IntegrateArgs &a, const BlockCoords &bc, const BlockRows &br,
+                                                            const uint8_t (*sets)[1024], uint8_t *band, unsigned tid) {
+  // [phase: select / change detection / store]
+  const BandCells c = tsdf_band_cells(a, bc, br);
+  for (int i = TSDF_BAND_FIRST; i < c.n_fl; i += TSDF_BAND_STEP) {
+    const int yg = c.yg0 + (i >> c.lf), xc = c.xc0 + (i & (c.fxb - 1));
+    if (sets[threadIdx.x >> 6][i] && yg < a.band_fy && xc < a.band_fx) band[((int64_t)(a.zl0 + (int)bc.bz) * a.band_fy + yg) * a.band_fx + xc] = 1;
+  }
+}
+// [phase: (prologue / other)]
+
+// Block prologue: the pieces the four kernels share.  The block's LDS tables hold one entry per thread (the prologue's barrier follows):
+//   s_rcp[k] = tsdf_rcp_entry(k): {Rcp32(k + 1).y, the colour average's rounding offset for that divisor (KEntry::hy)}
+//   s_yt[i]  = tsdf_row_part of row i of this block (rpb * TY <= 256), worked out once per block by the thread of that number instead
+//              of by every thread in every row, and the z part with it: no per-thread zt registers in PCL's SSE order
+//   s_cx[t]  = thread t's own four x centres, re-read each row: 16 B of LDS instead of four registers (tsdf_park_centres)
+// (The loop that fills an s_yt entry stands in each kernel, over tsdf_row_part: inside a helper it is unrolled before the kernel's own
+// code is simplified, and the timed instances come out with other registers and spills -- k_integrate_p 400 instructions longer.)
+static __device__ __forceinline__ f2 tsdf_rcp_entry(const IntegrateArgs &a, unsigned k) {
+  const KEntry e = tsdf_ktab_entry(a, k);
+  return (f2){e.y, e.hy};
+}
+// Component q of the row's part of pcl::transformPoint, for the row with centre cy in the plane with centre cz: cy * m[q][1] +
+// (cz * m[q][2] + m[q][3]) in PCL's SSE order, m[q][1] * cy in the other (there the plane's part is tsdf_plane_part, per thread) --
+// the very operations a thread would do in every row: bit-identical.
+template <int ORDER>
+static __device__ __forceinline__ float tsdf_row_part(const float (&m)[12], int q, float cy, float cz) {
+  return ORDER == TSDF_XFORM_PCL_SSE ? cy * m[4 * q + 1] + (cz * m[4 * q + 2] + m[4 * q + 3]) : m[4 * q + 1] * cy;
+}
+template <int ORDER>
+static __device__ __forceinline__ void tsdf_plane_part(const float (&m)[12], float cz, float (&zt)[3]) {
+#pragma unroll
+  for (int q = 0; q < 3; ++q) zt[q] = ORDER == TSDF_XFORM_PCL_SSE ? cz * m[4 * q + 2] + m[4 * q + 3] : m[4 * q + 2] * cz;
+}
+// each thread parks the x centres of ITS quad (where this is used nx is a multiple of 4: every quad is whole)
+static __device__ __forceinline__ void tsdf_park_centres(const IntegrateArgs &a, const BlockCoords &bc, const float *ctrx, f4 *s_cx, unsigned tid) {
+  const int xq_ = (int)bc.bx * a.TX + (int)(tid & (unsigned)(a.TX - 1));
+  if (xq_ < a.qpr) s_cx[tid] = *reinterpret_cast<const f4 *>(ctrx + xq_ * 4);
+}
+// PACKED without colour: the four counts of a quad in one word, k' = k + (observed && k < kmax) per byte, == min(k + 1, kmax)
+// for every count the layout can hold (k <= kmax).  "k < kmax" for all four at once: the even and the odd bytes sit
+// in 16-bit fields with bit 8 set on top; after subtracting kmax from each field that bit survives exactly where
+// k >= kmax (256 + k - kmax stays within the field: no borrow crosses it).  ~13 operations instead of 28 per quad.
+static __device__ __forceinline__ uint32_t tsdf_bump_counts4(uint32_t k4, const bool (&act)[4], unsigned kmax) {
+  // [phase: select / change detection / store]
+  const uint32_t km2 = kmax * 0x00010001u;
+  const uint32_t te = ((k4 & 0x00ff00ffu) | 0x01000100u) - km2, to = (((k4 >> 8) & 0x00ff00ffu) | 0x01000100u) - km2;
+  const uint32_t lt = ((~te >> 8) & 0x00010001u) | (((~to >> 8) & 0x00010001u) << 8);  // 0x01 in byte j: k_j < kmax
+  const uint32_t actb = (act[0] ? 0x00000001u : 0u) | (act[1] ? 0x00000100u : 0u) | (act[2] ? 0x00010000u : 0u) | (act[3] ? 0x01000000u : 0u);
+  return k4 + (lt & actb);
+}
+// COUNT: how many of the four bytes of x are not zero (x = old ^ new count bytes: the bytes of the K8 plane whose value changed)
+static __device__ __forceinline__ unsigned tsdf_nonzero_bytes(uint32_t x) {
+  return (unsigned)__popc((x | (x >> 1) | (x >> 2) | (x >> 3) | (x >> 4) | (x >> 5) | (x >> 6) | (x >> 7)) & 0x01010101u);
+}
+
+// The counting instances' counters: per quantity a stripe of slots in the handle's counter array, a block adding to the slot of its
+// number; the host sums each stripe.
+enum {  // one frame: k_integrate, k_integrate_p, k_integrate_pc -> tsdf_integrate_collect
+  TSDF_CNT_STRIPE = 1024,
+  TSDF_CNT_OBSERVED = 0,    // voxels brought to addObservation (all k_integrate_plain counts: TSDF_CNT_STRIPE slots)
+  TSDF_CNT_CHANGED = 1024,  // bytes of voxel words whose VALUE changed: what any layout-preserving kernel has to write
+  TSDF_CNT_IMPLIED = 2048,  // observed voxels whose distance word was not read
+  TSDF_CNT_READ = 3072,     // bytes of the voxel planes the launch requested, observed voxel or not
+  TSDF_CNT_SLOTS = 4096
+};
+enum {  // a pair of frames: k_integrate2 -> tsdf_integrate_collect2
+  TSDF_CNT2_STRIPE = 512,
+  TSDF_CNT2_A = 0,           // voxels frame A brought to addObservation
+  TSDF_CNT2_B = 512,         // ... and frame B (what two separate launches report)
+  TSDF_CNT2_EITHER = 1024,   // ... and at least one of the two
+  TSDF_CNT2_CHANGED = 1536,  // as TSDF_CNT_CHANGED, over the pair
+  TSDF_CNT2_IMPLIED = 2048,  // stays 0: k_integrate2 reads every distance word
+  TSDF_CNT2_READ = 2560,
+  TSDF_CNT2_SLOTS = 3072
+};
+static __device__ __forceinline__ unsigned tsdf_block_number(const BlockCoords &bc) { return bc.bx + bc.by * bc.gdx + bc.bz * bc.gdx * bc.gdy; }
+// COUNT, one frame: block reduction of the threads' four sums in the kernel's own LDS words s[0..3], then one add per stripe.
+static __device__ __forceinline__ void tsdf_count_out(const BlockCoords &bc, unsigned *s, unsigned long long *n_obs,
+                                                      unsigned tid, unsigned cnt, unsigned chg, unsigned imp, unsigned rdb) {
+  if (tid == 0) s[0] = s[1] = s[2] = s[3] = 0;
+  __syncthreads();
+  if (cnt) atomicAdd(&s[0], cnt);
+  if (chg) atomicAdd(&s[1], chg);
+  if (imp) atomicAdd(&s[2], imp);
+  if (rdb) atomicAdd(&s[3], rdb);
+  __syncthreads();
+  if (tid == 0 && (s[0] || s[3])) {
+    const unsigned b = tsdf_block_number(bc) & (TSDF_CNT_STRIPE - 1u);
+    if (s[0]) atomicAdd(n_obs + TSDF_CNT_OBSERVED + b, (unsigned long long)s[0]);
+    if (s[1]) atomicAdd(n_obs + TSDF_CNT_CHANGED + b, (unsigned long long)s[1]);
+    if (s[2]) atomicAdd(n_obs + TSDF_CNT_IMPLIED + b, (unsigned long long)s[2]);
+    if (s[3]) atomicAdd(n_obs + TSDF_CNT_READ + b, (unsigned long long)s[3]);
+  }
+}
 // waves per SIMD an instance asks for
 #define TSDF_WPE_OF(ORDER, COLOR, FASTPROJ, COUNT, PACKED, ALLIN) \
   ((ALLIN) && !(COUNT) && (PACKED) && (COLOR) && (FASTPROJ) ? TSDF_WPE_PACKED_COLOR : (ALLIN) && !(COUNT) && ((PACKED) || !(COLOR)) ? TSDF_WPE_PACKED : TSDF_WPE_GENERAL)
-// ALLIN (only with FASTPROJ): the host has proved (launch_integrate, `all_inside`: the slab's eight corner voxels, a
+// ALLIN (only with FASTPROJ): the host has proved (launch_kind, `all_inside`: the slab's eight corner voxels, a
 // convex frustum) that EVERY voxel of the launch passes the sensor-range test of hpp:146 and projects inside the image
 // with a pixel to spare, and nx is a multiple of 4: the per-voxel range compares, the image-bounds compares and the
 // "nothing in range" exits go away -- the turntable / object-in-front-of-the-camera case the headline is quoted on.
@@ -480,41 +610,29 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
     strad = flag == 2u;
   }
   const unsigned tid = threadIdx.x;
-  __shared__ f2 s_rcp[256];  // s_rcp[k] = {Rcp32(k + 1).y, the colour average's rounding offset for that divisor (KEntry::hy)}
-  // per row of this block (rpb * TY <= 256): the row's part of pcl::transformPoint -- yt[q] = cy * m[q][1] + (cz * m[q][2] + m[q][3])
-  // in PCL's SSE order, m[q][1] * cy in the other -- worked out once per block by the thread of that number instead of by every
-  // thread in every row (the very same operations: bit-identical), and the z part with it: no per-thread zt registers
+  __shared__ f2 s_rcp[256];  // (the three tables: see tsdf_rcp_entry)
   __shared__ f4 s_yt[256];
   // F2: transform + projection on explicit float pairs (v_pk_mul / v_pk_add / v_pk_fma_f32 with the pairs (0,1), (2,3)
   // throughout: no register shuffles), the x centres re-read from LDS per row (see the row loop)
   constexpr bool F2 = ALLIN && FASTPROJ;
   constexpr bool LEAN_K1 = PACKED && COLOR;  // (see the decode step)
-  __shared__ f4 s_cx[F2 ? 256 : 1];  // F2: every thread's own four x centres, re-read each row (16 B of LDS instead of four registers)
+  __shared__ f4 s_cx[F2 ? 256 : 1];
   __shared__ uint32_t s_iv[LIVE ? 256 : 1];  // LIVE: the row intervals of this block's rows, lo | len << 16 (launch-relative x)
   // "band seen" flags of this block's flag cells (64 x 4 x 1 voxels: <= 64 row groups x TX / 16 cells), collected in
   // LDS by the waves that take the in-band path anyway and written out once when the block is done: the free-space
   // hot path pays nothing for them (a global byte store per in-band row cost 3-5 % of the kernel, measured)
   TSDF_BAND_DECL;
-  if (PACKED) {
-    const KEntry e = tsdf_ktab_entry(a, tid);
-    s_rcp[tid] = (f2){e.y, e.hy};
-  }
+  if (PACKED) s_rcp[tid] = tsdf_rcp_entry(a, tid);
   {
     const int yy = (int)bc.by * a.rpb * a.TY + (int)tid;
-    {
-      const float cy_ = ctry[yy < a.ny ? yy : a.ny - 1], cz_ = ctrz[a.z_global0 + (int)bc.bz];
-      f4 t = {0.f, 0.f, 0.f, 0.f};
+    const float cy_ = ctry[yy < a.ny ? yy : a.ny - 1], cz_ = ctrz[a.z_global0 + (int)bc.bz];
+    f4 t = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int q = 0; q < 3; ++q)
-        t[q] = ORDER == TSDF_XFORM_PCL_SSE ? cy_ * a.m[4 * q + 1] + (cz_ * a.m[4 * q + 2] + a.m[4 * q + 3]) : a.m[4 * q + 1] * cy_;
-      s_yt[tid] = t;
-    }
-    if (F2) {  // each thread parks the x centres of ITS quad (ALLIN: nx is a multiple of 4, every quad is whole)
-      const int xq_ = (int)bc.bx * a.TX + (int)(tid & (unsigned)(a.TX - 1));
-      if (xq_ < a.qpr) s_cx[tid] = *reinterpret_cast<const f4 *>(ctrx + xq_ * 4);
-    }
+    for (int q = 0; q < 3; ++q) t[q] = tsdf_row_part<ORDER>(a.m, q, cy_, cz_);
+    s_yt[tid] = t;
     if (LIVE && strad) s_iv[tid] = yy < a.ny ? row_iv[(int64_t)bc.bz * a.ny + yy] : 0u;  // [launch plane][launch row]
   }
+  if (F2) tsdf_park_centres(a, bc, ctrx, s_cx, tid);  // (never with LIVE)
   // IMPLIED DISTANCES (PACKED, a.implied_d).  The flags as they stood BEFORE this launch, same cells and same order as
   // s_band.  While the flags describe the planes (tsdf_hip_volume::band_exact) and every launch since the reset used the
   // same hinge value p = pos / neg with (p*w + p)/(w + 1) == p (a.hinge_fixed; the host keeps that record,
@@ -541,15 +659,11 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
   const int zl = (int)bc.bz;
   const Rcp32 rneg = rcp32_prepare(a.neg);
   unsigned cnt = 0, chg = 0, imp = 0, rdb = 0;
-  // wave-uniform bases
-  const int row0 = (int)bc.by * a.rpb * a.TY;
-  const int rows = min(a.rpb * a.TY, a.ny - row0);
-  const int64_t e0 = ((int64_t)(a.zl0 + zl) * a.plane_rows + row0) * a.pitch;
-  const unsigned span = (unsigned)rows * (unsigned)a.pitch;  // elements of this block's row group
-  const rsrc_t rsD = make_rsrc(D + e0, span * 4u);
-  const rsrc_t rsW = make_rsrc(PACKED ? D : Wt + e0, PACKED ? 0u : span * 4u);
-  const rsrc_t rsC = make_rsrc(COLOR ? RGB + e0 : (uint32_t *)D, COLOR ? span * 4u : 0u);
-  const rsrc_t rsK = make_rsrc(PACKED && !COLOR ? K8 + e0 : (uint8_t *)D, PACKED && !COLOR ? span : 0u);
+  const BlockRows br = tsdf_block_rows(a, bc);
+  const rsrc_t rsD = make_rsrc(D + br.e0, br.span * 4u);
+  const rsrc_t rsW = make_rsrc(PACKED ? D : Wt + br.e0, PACKED ? 0u : br.span * 4u);
+  const rsrc_t rsC = make_rsrc(COLOR ? RGB + br.e0 : (uint32_t *)D, COLOR ? br.span * 4u : 0u);
+  const rsrc_t rsK = make_rsrc(PACKED && !COLOR ? K8 + br.e0 : (uint8_t *)D, PACKED && !COLOR ? br.span : 0u);
   const unsigned npix = (unsigned)a.W * (unsigned)a.H;
   const rsrc_t rsF = make_rsrc(depth, PAIRS ? npix * 8u : COLOR ? a.bgra_off + npix * 4u : npix * 4u);  // [depth ... bgra], or the records
   // ALLIN: every pixel index is valid, so the gather can address the frame by INDEX (stride 4, or 8 for records; `idxen`):
@@ -575,7 +689,7 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
     bool pred_obs = true;  // this quad was observed in the previous row (the first row asks early): see the early voxel loads
     // [phase: row setup (loop control, row's transform part from LDS)]
     for (int r = 0; r < a.rpb; ++r) {
-      const int y = row0 + ty + r * a.TY;
+      const int y = br.row0 + ty + r * a.TY;
       if (y >= a.ny) break;
       unsigned iv_lo = 0u, iv_len = 0u;
       if (LIVE && strad) {  // the row's interval: a quad that misses it has nothing to do (a wave all of whose quads miss skips the row)
@@ -790,7 +904,7 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
         if (PACKED) {
           kw[j] = COLOR ? c0[j] : (k4 << (24 - 8 * j));
           // tsdf_decode_w (neither is NaN here).  With an integer max_weight the min is the identity -- and the ALLIN
-          // instance is only launched with one, and with kmax == max_weight (launch_integrate) -- but leaving it out lets
+          // instance is only launched with one, and with kmax == max_weight (launch_kind) -- but leaving it out lets
           // LLVM turn the colour sums into integer multiplies and byte shuffles (+70 instructions, measured): the value
           // hides behind an empty asm instead of paying a v_min per voxel for that.
           if (ALLIN) {
@@ -870,8 +984,7 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
           d_touched = true;
           // a voxel of this quad was observed inside the truncation band: its distance may turn negative, which is what
           // marching cubes looks for (see s_band)
-          // (the host only passes `band` when every block's first row is a multiple of 4: local row groups == global ones)
-          if (any_div) TSDF_BAND(((ty + r * a.TY) >> 2) * max(1, a.TX >> 4) + (tx >> 4)) = 1;
+          if (any_div) TSDF_BAND(TSDF_BAND_CELL(r)) = 1;
 #pragma unroll
           for (int j = 0; j < 4; ++j) dv[j] = div32_fast(d0[j] * w0[j] + dn[j], rs[j]);
           if (PACKED) {
@@ -887,7 +1000,7 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
       // [phase: IEEE fallback (rare)]
       if (!safe) {
         d_touched = true;
-        if (any_div) TSDF_BAND(((ty + r * a.TY) >> 2) * max(1, a.TX >> 4) + (tx >> 4)) = 1;
+        if (any_div) TSDF_BAND(TSDF_BAND_CELL(r)) = 1;
         asm volatile("");  // rare: keep the 16 IEEE divisions out of the hot path's schedule
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -923,52 +1036,17 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
         if (COUNT)  // bytes of voxel words whose VALUE changed: what any layout-preserving kernel has to write
           chg += (!PACKED && wn_u[j] != w0u[j] ? 4u : 0u) + (COLOR && cv[j] != c_before[j] ? 4u : 0u);
       }
-      if (PACKED && !COLOR) {
-        // The four counts of the quad in one word: k' = k + (observed && k < kmax) per byte, == min(k + 1, kmax)
-        // for every count the layout can hold (k <= kmax).  "k < kmax" for all four at once: the even and the odd bytes sit
-        // in 16-bit fields with bit 8 set on top; after subtracting kmax from each field that bit survives exactly where
-        // k >= kmax (256 + k - kmax stays within the field: no borrow crosses it).  ~13 operations instead of 28 per quad.
-        const uint32_t km2 = a.kmax * 0x00010001u;
-        const uint32_t te = ((k4 & 0x00ff00ffu) | 0x01000100u) - km2, to = (((k4 >> 8) & 0x00ff00ffu) | 0x01000100u) - km2;
-        const uint32_t lt = ((~te >> 8) & 0x00010001u) | (((~to >> 8) & 0x00010001u) << 8);  // 0x01 in byte j: k_j < kmax
-        const uint32_t actb = (act[0] ? 0x00000001u : 0u) | (act[1] ? 0x00000100u : 0u) | (act[2] ? 0x00010000u : 0u) | (act[3] ? 0x01000000u : 0u);
-        k4n = k4 + (lt & actb);
-      }
-      if (COUNT && PACKED && !COLOR) chg += (unsigned)__popc(((k4n ^ k4) | ((k4n ^ k4) >> 1) | ((k4n ^ k4) >> 2) | ((k4n ^ k4) >> 3) |
-                                                            ((k4n ^ k4) >> 4) | ((k4n ^ k4) >> 5) | ((k4n ^ k4) >> 6) | ((k4n ^ k4) >> 7)) & 0x01010101u);
+      if (PACKED && !COLOR) k4n = tsdf_bump_counts4(k4, act, a.kmax);
+      if (COUNT && PACKED && !COLOR) chg += tsdf_nonzero_bytes(k4n ^ k4);
       if (!PACKED && diff_w) bstore128(rsW, voff, soff, (u4){wn_u[0], wn_u[1], wn_u[2], wn_u[3]});
       if (COLOR && diff_c) bstore128(rsC, voff, soff, (u4){cv[0], cv[1], cv[2], cv[3]});
       if (PACKED && !COLOR && k4n != k4) bstore32(rsK, voff >> 2, soff >> 2, k4n);
     }
   }
-  if (band) {  // the block's flags -> the volume's flag array (every writer stores the same 1: no atomics, and no barrier: a
-               // wave reads back what it wrote itself)
-    const int lf = max(0, a.log2TX - 4), fxb = 1 << lf;
-    const int yg0 = (a.y_abs0 + row0) >> 2, yg1 = (a.y_abs0 + row0 + max(rows, 1) - 1) >> 2;
-    const int xc0 = (a.x_abs0 + (int)bc.bx * a.TX * 4) >> 6;
-    const int n_fl = (yg1 - yg0 + 1) << lf;
-    for (int i = TSDF_BAND_FIRST; i < n_fl; i += TSDF_BAND_STEP) {
-      const int yg = yg0 + (i >> lf), xc = xc0 + (i & (fxb - 1));
-      if (TSDF_BAND(i) && yg < a.band_fy && xc < a.band_fx) band[((int64_t)(a.zl0 + zl) * a.band_fy + yg) * a.band_fx + xc] = 1;
-    }
-  }
-  if (COUNT) {  // block reduction, then one of 1024 striped counters (summed by the host); slots 1024.. = changed bytes,
-                // slots 2048.. = observed voxels whose distance word was not read
-    __shared__ unsigned s_cnt, s_chg, s_imp, s_rdb;
-    if (tid == 0) s_cnt = s_chg = s_imp = s_rdb = 0;
-    __syncthreads();
-    if (cnt) atomicAdd(&s_cnt, cnt);
-    if (chg) atomicAdd(&s_chg, chg);
-    if (imp) atomicAdd(&s_imp, imp);
-    if (rdb) atomicAdd(&s_rdb, rdb);
-    __syncthreads();
-    if (tid == 0 && (s_cnt || s_rdb)) {  // (slots 3072..: bytes of the voxel planes the launch requested, observed voxel or not)
-      const unsigned b = bc.bx + bc.by * bc.gdx + bc.bz * bc.gdx * bc.gdy;
-      if (s_cnt) atomicAdd(n_obs + (b & 1023u), (unsigned long long)s_cnt);
-      if (s_chg) atomicAdd(n_obs + 1024u + (b & 1023u), (unsigned long long)s_chg);
-      if (s_imp) atomicAdd(n_obs + 2048u + (b & 1023u), (unsigned long long)s_imp);
-      if (s_rdb) atomicAdd(n_obs + 3072u + (b & 1023u), (unsigned long long)s_rdb);
-    }
+  if (band) tsdf_flags_write_out(a, bc, br, s_band_sets, band, tid);
+  if (COUNT) {
+    __shared__ unsigned s_count[4];
+    tsdf_count_out(bc, s_count, n_obs, tid, cnt, chg, imp, rdb);
   }
 }
 
@@ -1015,24 +1093,21 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
               const float *__restrict__ ctrz, unsigned long long *__restrict__ n_obs, uint8_t *__restrict__ band) {
   const BlockCoords bc = tsdf_block_coords(a.zfast);
   const unsigned tid = threadIdx.x;
-  __shared__ f2 s_rcp[256];  // s_rcp[k] = {Rcp32(k + 1).y, unused here}
-  __shared__ f4 s_yt[256];   // the rows' part of pcl::transformPoint (see k_integrate)
-  __shared__ f4 s_cx[256];   // every thread's own four x centres
+  __shared__ f2 s_rcp[256];  // (the three tables: see tsdf_rcp_entry; the colour offset in s_rcp is not used here)
+  __shared__ f4 s_yt[256];
+  __shared__ f4 s_cx[256];
   __shared__ uint8_t s_bin[1024];
   TSDF_BAND_DECL;
+  s_rcp[tid] = tsdf_rcp_entry(a, tid);
   {
-    const KEntry e = tsdf_ktab_entry(a, tid);
-    s_rcp[tid] = (f2){e.y, e.hy};
     const int yy = (int)bc.by * a.rpb * a.TY + (int)tid;
     const float cy_ = ctry[yy < a.ny ? yy : a.ny - 1], cz_ = ctrz[a.z_global0 + (int)bc.bz];
     f4 t = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
-      t[q] = ORDER == TSDF_XFORM_PCL_SSE ? cy_ * a.m[4 * q + 1] + (cz_ * a.m[4 * q + 2] + a.m[4 * q + 3]) : a.m[4 * q + 1] * cy_;
+    for (int q = 0; q < 3; ++q) t[q] = tsdf_row_part<ORDER>(a.m, q, cy_, cz_);
     s_yt[tid] = t;
-    const int xq_ = (int)bc.bx * a.TX + (int)(tid & (unsigned)(a.TX - 1));
-    if (xq_ < a.qpr) s_cx[tid] = *reinterpret_cast<const f4 *>(ctrx + xq_ * 4);
   }
+  tsdf_park_centres(a, bc, ctrx, s_cx, tid);
   if (a.implied_d) tsdf_flags_before(a, bc, band, s_bin, tid);
   __syncthreads();
   const uint64_t quiet = a.implied_d ? tsdf_quiet_passes(a, s_bin, tid) : 0ull;
@@ -1042,21 +1117,15 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
   const int zl = (int)bc.bz;
   const Rcp32 rneg = rcp32_prepare(a.neg);
   unsigned cnt = 0, chg = 0, imp = 0, rdb = 0;
-  const int row0 = (int)bc.by * a.rpb * a.TY;
-  const int rows = min(a.rpb * a.TY, a.ny - row0);  // a multiple of TY (the host checked)
-  const int64_t e0 = ((int64_t)(a.zl0 + zl) * a.plane_rows + row0) * a.pitch;
-  const unsigned span = (unsigned)rows * (unsigned)a.pitch;
-  const rsrc_t rsD = make_rsrc(D + e0, span * 4u);
-  const rsrc_t rsK = make_rsrc(K8 + e0, span);
+  const BlockRows br = tsdf_block_rows(a, bc);  // (rows: a multiple of TY, the host checked)
+  const rsrc_t rsD = make_rsrc(D + br.e0, br.span * 4u);
+  const rsrc_t rsK = make_rsrc(K8 + br.e0, br.span);
   const i4_rsrc rsFi = make_rsrc_2d(depth, 4u, 0xffffffffu);
   const uint32_t pbits = __float_as_uint(a.pos_over_neg);
   if (xq < a.qpr) {
-    const int x4 = xq * 4;
-    const float cz = ctrz[a.z_global0 + zl];
     float zt[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) zt[q] = ORDER == TSDF_XFORM_PCL_SSE ? cz * a.m[4 * q + 2] + a.m[4 * q + 3] : a.m[4 * q + 2] * cz;
-    const unsigned voff = (unsigned)(ty * (int)a.pitch + x4) * 4u;
+    tsdf_plane_part<ORDER>(a.m, ctrz[a.z_global0 + zl], zt);
+    const unsigned voff = (unsigned)(ty * (int)a.pitch + xq * 4) * 4u;
     const unsigned row_step = (unsigned)a.TY * (unsigned)a.pitch * 4u;
 
     // ---- stage A: transform + certified projection (project_quad_allin), then every load of the row ----------------
@@ -1084,6 +1153,8 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
       const unsigned soff = (unsigned)r * row_step;
       const bool d_read = !(r < 64 && (quiet >> r & 1ull));
       // [phase: hinge / normalise (hpp:159-198)]
+      // (These opening tests -- raw / act / any, the ballot exit, any_div -- stand in this kernel, in k_integrate_pc and, any_div, in
+      // k_integrate: as shared functions, with or without their loops, by reference or by value, they change a timed instance's code.)
       float raw[4];
       bool act[4];
       bool any = false;
@@ -1113,12 +1184,7 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
       }
       const bool d_moves = __builtin_amdgcn_ballot_w64(any && off_hinge) != 0ull;  // wave-uniform
       // [phase: select / change detection / store]
-      // the four counts in one word (see k4n in k_integrate): k' = k + (observed && k < kmax) per byte
-      const uint32_t km2 = a.kmax * 0x00010001u;
-      const uint32_t te = ((k4 & 0x00ff00ffu) | 0x01000100u) - km2, to = (((k4 >> 8) & 0x00ff00ffu) | 0x01000100u) - km2;
-      const uint32_t lt = ((~te >> 8) & 0x00010001u) | (((~to >> 8) & 0x00010001u) << 8);  // 0x01 in byte j: k_j < kmax
-      const uint32_t actb = (act[0] ? 0x00000001u : 0u) | (act[1] ? 0x00000100u : 0u) | (act[2] ? 0x00010000u : 0u) | (act[3] ? 0x01000000u : 0u);
-      const uint32_t k4n = k4 + (lt & actb);
+      const uint32_t k4n = tsdf_bump_counts4(k4, act, a.kmax);
       if (d_moves) {  // (a tenth of the observed wave-rows: surfaces, first observations)
         // [phase: normalise: raw / neg ladder (rows with an in-band voxel)]
         float dn[4];
@@ -1139,7 +1205,7 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
           d0[j] = __uint_as_float(d0u[j]);
         }
         // [phase: d update (octree.cpp:152-163)]
-        if (any_div) TSDF_BAND(((ty + r * a.TY) >> 2) * max(1, a.TX >> 4) + (tx >> 4)) = 1;
+        if (any_div) TSDF_BAND(TSDF_BAND_CELL(r)) = 1;
         bool safe = true;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -1176,14 +1242,13 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
           cnt += act[j] ? 1u : 0u;
           imp += act[j] && !d_read ? 1u : 0u;
         }
-        const uint32_t x = k4n ^ k4;
-        chg += (unsigned)__popc((x | (x >> 1) | (x >> 2) | (x >> 3) | (x >> 4) | (x >> 5) | (x >> 6) | (x >> 7)) & 0x01010101u);
+        chg += tsdf_nonzero_bytes(k4n ^ k4);
       }
       if (k4n != k4) bstore32(rsK, voff >> 2, soff >> 2, k4n);
     };
 
     PipeRow A, B;
-    const int nr = rows / a.TY;  // (the grid's last block may be shorter: the host checked that ny is a multiple of TY)
+    const int nr = br.rows / a.TY;  // (the grid's last block may be shorter: the host checked that ny is a multiple of TY)
     issue(0, A);
     int r = 0;
     for (; r + 2 < nr; r += 2) {  // steady state: every trip issues two rows and consumes two
@@ -1200,33 +1265,10 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
       consume(r, A);
     }
   }
-  if (band) {  // the block's flags -> the volume's flag array (every writer stores the same 1: no atomics, and no barrier: a
-               // wave reads back what it wrote itself)
-    const int lf = max(0, a.log2TX - 4), fxb = 1 << lf;
-    const int yg0 = (a.y_abs0 + row0) >> 2, yg1 = (a.y_abs0 + row0 + max(rows, 1) - 1) >> 2;
-    const int xc0 = (a.x_abs0 + (int)bc.bx * a.TX * 4) >> 6;
-    const int n_fl = (yg1 - yg0 + 1) << lf;
-    for (int i = TSDF_BAND_FIRST; i < n_fl; i += TSDF_BAND_STEP) {
-      const int yg = yg0 + (i >> lf), xc = xc0 + (i & (fxb - 1));
-      if (TSDF_BAND(i) && yg < a.band_fy && xc < a.band_fx) band[((int64_t)(a.zl0 + zl) * a.band_fy + yg) * a.band_fx + xc] = 1;
-    }
-  }
-  if (COUNT) {  // the same four striped counters as k_integrate
-    __shared__ unsigned s_cnt, s_chg, s_imp, s_rdb;
-    if (tid == 0) s_cnt = s_chg = s_imp = s_rdb = 0;
-    __syncthreads();
-    if (cnt) atomicAdd(&s_cnt, cnt);
-    if (chg) atomicAdd(&s_chg, chg);
-    if (imp) atomicAdd(&s_imp, imp);
-    if (rdb) atomicAdd(&s_rdb, rdb);
-    __syncthreads();
-    if (tid == 0 && (s_cnt || s_rdb)) {
-      const unsigned b = bc.bx + bc.by * bc.gdx + bc.bz * bc.gdx * bc.gdy;
-      if (s_cnt) atomicAdd(n_obs + (b & 1023u), (unsigned long long)s_cnt);
-      if (s_chg) atomicAdd(n_obs + 1024u + (b & 1023u), (unsigned long long)s_chg);
-      if (s_imp) atomicAdd(n_obs + 2048u + (b & 1023u), (unsigned long long)s_imp);
-      if (s_rdb) atomicAdd(n_obs + 3072u + (b & 1023u), (unsigned long long)s_rdb);
-    }
+  if (band) tsdf_flags_write_out(a, bc, br, s_band_sets, band, tid);
+  if (COUNT) {
+    __shared__ unsigned s_count[4];
+    tsdf_count_out(bc, s_count, n_obs, tid, cnt, chg, imp, rdb);
   }
 }
 
@@ -1262,24 +1304,21 @@ k_integrate_pc(const IntegrateArgs a, float *__restrict__ D, uint32_t *__restric
                const float *__restrict__ ctrz, unsigned long long *__restrict__ n_obs, uint8_t *__restrict__ band) {
   const BlockCoords bc = tsdf_block_coords(a.zfast);
   const unsigned tid = threadIdx.x;
-  __shared__ f2 s_rcp[256];  // s_rcp[k] = {Rcp32(k + 1).y, the colour average's rounding offset for that divisor}
+  __shared__ f2 s_rcp[256];  // (the three tables: see tsdf_rcp_entry)
   __shared__ f4 s_yt[256];
   __shared__ f4 s_cx[256];
   __shared__ uint8_t s_bin[1024];
   TSDF_BAND_DECL;
+  s_rcp[tid] = tsdf_rcp_entry(a, tid);
   {
-    const KEntry e = tsdf_ktab_entry(a, tid);
-    s_rcp[tid] = (f2){e.y, e.hy};
     const int yy = (int)bc.by * a.rpb * a.TY + (int)tid;
     const float cy_ = ctry[yy < a.ny ? yy : a.ny - 1], cz_ = ctrz[a.z_global0 + (int)bc.bz];
     f4 t = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int q = 0; q < 3; ++q)
-      t[q] = ORDER == TSDF_XFORM_PCL_SSE ? cy_ * a.m[4 * q + 1] + (cz_ * a.m[4 * q + 2] + a.m[4 * q + 3]) : a.m[4 * q + 1] * cy_;
+    for (int q = 0; q < 3; ++q) t[q] = tsdf_row_part<ORDER>(a.m, q, cy_, cz_);
     s_yt[tid] = t;
-    const int xq_ = (int)bc.bx * a.TX + (int)(tid & (unsigned)(a.TX - 1));
-    if (xq_ < a.qpr) s_cx[tid] = *reinterpret_cast<const f4 *>(ctrx + xq_ * 4);
   }
+  tsdf_park_centres(a, bc, ctrx, s_cx, tid);
   if (a.implied_d) tsdf_flags_before(a, bc, band, s_bin, tid);
   __syncthreads();
   const uint64_t quiet = a.implied_d ? tsdf_quiet_passes(a, s_bin, tid) : 0ull;
@@ -1289,21 +1328,15 @@ k_integrate_pc(const IntegrateArgs a, float *__restrict__ D, uint32_t *__restric
   const int zl = (int)bc.bz;
   const Rcp32 rneg = rcp32_prepare(a.neg);
   unsigned cnt = 0, chg = 0, imp = 0, rdb = 0;
-  const int row0 = (int)bc.by * a.rpb * a.TY;
-  const int rows = min(a.rpb * a.TY, a.ny - row0);  // a multiple of TY (the host checked)
-  const int64_t e0 = ((int64_t)(a.zl0 + zl) * a.plane_rows + row0) * a.pitch;
-  const unsigned span = (unsigned)rows * (unsigned)a.pitch;
-  const rsrc_t rsD = make_rsrc(D + e0, span * 4u);
-  const rsrc_t rsC = make_rsrc(RGB + e0, span * 4u);
+  const BlockRows br = tsdf_block_rows(a, bc);  // (rows: a multiple of TY, the host checked)
+  const rsrc_t rsD = make_rsrc(D + br.e0, br.span * 4u);
+  const rsrc_t rsC = make_rsrc(RGB + br.e0, br.span * 4u);
   const i4_rsrc rsFi = make_rsrc_2d(depth, PAIRS ? 8u : 4u, 0xffffffffu);  // PAIRS: pixel records (see k_integrate)
   const uint32_t pbits = __float_as_uint(a.pos_over_neg);
   if (xq < a.qpr) {
-    const int x4 = xq * 4;
-    const float cz = ctrz[a.z_global0 + zl];
     float zt[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) zt[q] = ORDER == TSDF_XFORM_PCL_SSE ? cz * a.m[4 * q + 2] + a.m[4 * q + 3] : a.m[4 * q + 2] * cz;
-    const unsigned voff = (unsigned)(ty * (int)a.pitch + x4) * 4u;
+    tsdf_plane_part<ORDER>(a.m, ctrz[a.z_global0 + zl], zt);
+    const unsigned voff = (unsigned)(ty * (int)a.pitch + xq * 4) * 4u;
     const unsigned row_step = (unsigned)a.TY * (unsigned)a.pitch * 4u;
     bool obs_a = true, obs_b = true;  // this quad's outcome in the last even / odd row whose stage B has run (the predictor)
 
@@ -1338,6 +1371,7 @@ k_integrate_pc(const IntegrateArgs a, float *__restrict__ D, uint32_t *__restric
       const unsigned soff = (unsigned)r * row_step;
       const bool d_read = !(r < 64 && (quiet >> r & 1ull));
       // [phase: hinge / normalise (hpp:159-198)]
+      // (the opening tests as in k_integrate_p, spelled out in both: see there)
       float raw[4];
       bool act[4];
       bool any = false;
@@ -1403,7 +1437,7 @@ k_integrate_pc(const IntegrateArgs a, float *__restrict__ D, uint32_t *__restric
           w0[j] = (float)(c0[j] >> 24);
         }
         if (any_div) {
-          TSDF_BAND(((ty + r * a.TY) >> 2) * max(1, a.TX >> 4) + (tx >> 4)) = 1;
+          TSDF_BAND(TSDF_BAND_CELL(r)) = 1;
 #pragma unroll
           for (int j = 0; j < 4; ++j) dn[j] = raw[j] > a.pos ? a.pos_over_neg : div32_fast(raw[j], rneg);  // hpp:198
         }
@@ -1453,7 +1487,7 @@ k_integrate_pc(const IntegrateArgs a, float *__restrict__ D, uint32_t *__restric
     };
 
     PipeRowC A, B;
-    const int nr = rows / a.TY;  // (the grid's last block may be shorter: the host checked that ny is a multiple of TY)
+    const int nr = br.rows / a.TY;  // (the grid's last block may be shorter: the host checked that ny is a multiple of TY)
     issue(0, A, true);
     int r = 0;
     for (; r + 2 < nr; r += 2) {  // steady state: every trip issues two rows and consumes two
@@ -1476,32 +1510,16 @@ k_integrate_pc(const IntegrateArgs a, float *__restrict__ D, uint32_t *__restric
       consume(r, A, pa, obs_a);
     }
   }
-  if (band) {  // (no barrier: a wave reads back what it wrote itself)
-    const int lf = max(0, a.log2TX - 4), fxb = 1 << lf;
-    const int yg0 = (a.y_abs0 + row0) >> 2, yg1 = (a.y_abs0 + row0 + max(rows, 1) - 1) >> 2;
-    const int xc0 = (a.x_abs0 + (int)bc.bx * a.TX * 4) >> 6;
-    const int n_fl = (yg1 - yg0 + 1) << lf;
-    for (int i = TSDF_BAND_FIRST; i < n_fl; i += TSDF_BAND_STEP) {
-      const int yg = yg0 + (i >> lf), xc = xc0 + (i & (fxb - 1));
+  if (band) {  // tsdf_flags_write_out's loop, spelled out: through the helper this kernel comes out with 91 VGPRs and ~40 more instructions
+    const BandCells c = tsdf_band_cells(a, bc, br);
+    for (int i = TSDF_BAND_FIRST; i < c.n_fl; i += TSDF_BAND_STEP) {
+      const int yg = c.yg0 + (i >> c.lf), xc = c.xc0 + (i & (c.fxb - 1));
       if (TSDF_BAND(i) && yg < a.band_fy && xc < a.band_fx) band[((int64_t)(a.zl0 + zl) * a.band_fy + yg) * a.band_fx + xc] = 1;
     }
   }
   if (COUNT) {
-    __shared__ unsigned s_cnt, s_chg, s_imp, s_rdb;
-    if (tid == 0) s_cnt = s_chg = s_imp = s_rdb = 0;
-    __syncthreads();
-    if (cnt) atomicAdd(&s_cnt, cnt);
-    if (chg) atomicAdd(&s_chg, chg);
-    if (imp) atomicAdd(&s_imp, imp);
-    if (rdb) atomicAdd(&s_rdb, rdb);
-    __syncthreads();
-    if (tid == 0 && (s_cnt || s_rdb)) {
-      const unsigned b = bc.bx + bc.by * bc.gdx + bc.bz * bc.gdx * bc.gdy;
-      if (s_cnt) atomicAdd(n_obs + (b & 1023u), (unsigned long long)s_cnt);
-      if (s_chg) atomicAdd(n_obs + 1024u + (b & 1023u), (unsigned long long)s_chg);
-      if (s_imp) atomicAdd(n_obs + 2048u + (b & 1023u), (unsigned long long)s_imp);
-      if (s_rdb) atomicAdd(n_obs + 3072u + (b & 1023u), (unsigned long long)s_rdb);
-    }
+    __shared__ unsigned s_count[4];
+    tsdf_count_out(bc, s_count, n_obs, tid, cnt, chg, imp, rdb);
   }
 }
 
@@ -1531,22 +1549,18 @@ k_integrate2(const IntegrateArgs a, const Frame2 fb, float *__restrict__ D, uint
   const unsigned tid = threadIdx.x;
   const BlockCoords bc = tsdf_block_coords(a.zfast);
   __shared__ KEntry s_tab[256];        // per count k: decoded weight, Rcp32(k + 1).y, colour rounding offset, next count (k_integrate)
-  __shared__ f4 s_ytA[256], s_ytB[256];  // per row of the block: the row's part of each frame's transform (k_integrate's s_yt)
+  __shared__ f4 s_ytA[256], s_ytB[256];  // per row of the block: the row's part of each frame's transform (tsdf_row_part)
   __shared__ f4 s_cx[256];             // every thread's own four x centres, re-read each row
   TSDF_BAND_DECL;
   s_tab[tid] = tsdf_ktab_entry(a, tid);
-  {
+  {  // (whole KEntry rows in LDS, and two frames' row parts)
     const int yy = (int)bc.by * a.rpb * a.TY + (int)tid;
     const float cy_ = ctry[yy < a.ny ? yy : a.ny - 1], cz_ = ctrz[a.z_global0 + (int)bc.bz];
     f4 tA = {0.f, 0.f, 0.f, 0.f}, tB = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      tA[q] = ORDER == TSDF_XFORM_PCL_SSE ? cy_ * a.m[4 * q + 1] + (cz_ * a.m[4 * q + 2] + a.m[4 * q + 3]) : a.m[4 * q + 1] * cy_;
-      tB[q] = ORDER == TSDF_XFORM_PCL_SSE ? cy_ * fb.m[4 * q + 1] + (cz_ * fb.m[4 * q + 2] + fb.m[4 * q + 3]) : fb.m[4 * q + 1] * cy_;
-    }
+    for (int q = 0; q < 3; ++q) tA[q] = tsdf_row_part<ORDER>(a.m, q, cy_, cz_), tB[q] = tsdf_row_part<ORDER>(fb.m, q, cy_, cz_);
     s_ytA[tid] = tA, s_ytB[tid] = tB;
-    const int xq_ = (int)bc.bx * a.TX + (int)(tid & (unsigned)(a.TX - 1));
-    if (xq_ < a.qpr) s_cx[tid] = *reinterpret_cast<const f4 *>(ctrx + xq_ * 4);  // (nx is a multiple of 4: every quad is whole)
+    tsdf_park_centres(a, bc, ctrx, s_cx, tid);
   }
   // (No implied distances here -- k_integrate's s_bin: built into this kernel in round 4, they cost it 0.5 ms per frame of
   // scalar work and nineteen spilled scalar registers for bytes an issue-bound kernel gains nothing from, DESIGN 3.1b;
@@ -1558,24 +1572,20 @@ k_integrate2(const IntegrateArgs a, const Frame2 fb, float *__restrict__ D, uint
   const int zl = (int)bc.bz;
   const Rcp32 rneg = rcp32_prepare(a.neg);
   unsigned cnt = 0, chg = 0, cntA = 0, cntB = 0, rdb = 0;
-  const int row0 = (int)bc.by * a.rpb * a.TY;
-  const int rows = min(a.rpb * a.TY, a.ny - row0);
-  const int64_t e0 = ((int64_t)(a.zl0 + zl) * a.plane_rows + row0) * a.pitch;
-  const unsigned span = (unsigned)rows * (unsigned)a.pitch;
-  const rsrc_t rsD = make_rsrc(D + e0, span * 4u);
-  const rsrc_t rsC = make_rsrc(COLOR ? RGB + e0 : (uint32_t *)D, COLOR ? span * 4u : 0u);
-  const rsrc_t rsK = make_rsrc(!COLOR ? K8 + e0 : (uint8_t *)D, !COLOR ? span : 0u);
+  const BlockRows br = tsdf_block_rows(a, bc);
+  const rsrc_t rsD = make_rsrc(D + br.e0, br.span * 4u);
+  const rsrc_t rsC = make_rsrc(COLOR ? RGB + br.e0 : (uint32_t *)D, COLOR ? br.span * 4u : 0u);
+  const rsrc_t rsK = make_rsrc(!COLOR ? K8 + br.e0 : (uint8_t *)D, !COLOR ? br.span : 0u);
   static_assert(!PAIRS || COLOR, "pixel records carry the colour");
   const unsigned fstride = PAIRS ? 8u : 4u;  // PAIRS: both frames as pixel records (see k_integrate)
   const i4_rsrc rsFA = make_rsrc_2d(depthA, fstride, 0xffffffffu), rsFB = make_rsrc_2d(depthB, fstride, 0xffffffffu);
   const uint32_t hinge_bits = __float_as_uint(a.pos_over_neg);
   if (xq < a.qpr) {
-    const int x4 = xq * 4;
     const float cz = ctrz[a.z_global0 + zl];
     float ztA[3], ztB[3];  // the plane's part of the transform: only the left-to-right order still needs it per thread
 #pragma unroll
     for (int q = 0; q < 3; ++q) ztA[q] = a.m[4 * q + 2] * cz, ztB[q] = fb.m[4 * q + 2] * cz;
-    const unsigned voff = (unsigned)(ty * (int)a.pitch + x4) * 4u;
+    const unsigned voff = (unsigned)(ty * (int)a.pitch + xq * 4) * 4u;
     const unsigned row_step = (unsigned)a.TY * (unsigned)a.pitch * 4u;
     // A row's work in two stages: ISSUE(r) = project both frames and request everything the row needs at once -- the two
     // frames' depth / colour gathers and the quad's voxel words (read whether or not a voxel turns out to be observed: in
@@ -1703,7 +1713,7 @@ k_integrate2(const IntegrateArgs a, const Frame2 fb, float *__restrict__ D, uint
           }
           if (d_moves) {
             d_touched = true;
-            if (any_div) TSDF_BAND(((ty + r * a.TY) >> 2) * max(1, a.TX >> 4) + (tx >> 4)) = 1;
+            if (any_div) TSDF_BAND(TSDF_BAND_CELL(r)) = 1;
 #pragma unroll
             for (int j = 0; j < 4; ++j) dv[j] = div32_fast(d0[j] * w0[j] + dn[j], rs[j]);
 #pragma unroll
@@ -1741,14 +1751,13 @@ k_integrate2(const IntegrateArgs a, const Frame2 fb, float *__restrict__ D, uint
         if (COUNT) cntA += (obsA >> j & 1u), cntB += (obsB >> j & 1u);
         if (COUNT) chg += (du[j] != d0u[j] ? 4u : 0u) + (COLOR && kw[j] != c0[j] ? 4u : 0u);
       }
-      if (COUNT && !COLOR) chg += (unsigned)__popc(((k4n ^ k4) | ((k4n ^ k4) >> 1) | ((k4n ^ k4) >> 2) | ((k4n ^ k4) >> 3) |
-                                                   ((k4n ^ k4) >> 4) | ((k4n ^ k4) >> 5) | ((k4n ^ k4) >> 6) | ((k4n ^ k4) >> 7)) & 0x01010101u);
+      if (COUNT && !COLOR) chg += tsdf_nonzero_bytes(k4n ^ k4);
       if (diff_d) bstore128(rsD, voff, soff, (u4){du[0], du[1], du[2], du[3]});
       if (COLOR && diff_c) bstore128(rsC, voff, soff, (u4){kw[0], kw[1], kw[2], kw[3]});
       if (!COLOR && k4n != k4) bstore32(rsK, voff >> 2, soff >> 2, k4n);
     };
     // rows this thread walks: r = 0 .. nrows - 1 (row0 + ty + r * TY < ny)
-    const int left = a.ny - row0 - ty;
+    const int left = a.ny - br.row0 - ty;
     const int nrows = left <= 0 ? 0 : min(a.rpb, (left + a.TY - 1) / a.TY);
     for (int r = 0; r < nrows; ++r) {
       RowLoads L;
@@ -1756,16 +1765,7 @@ k_integrate2(const IntegrateArgs a, const Frame2 fb, float *__restrict__ D, uint
       retire(r, L);
     }
   }
-  if (band) {  // (no barrier: a wave reads back what it wrote itself)
-    const int lf = max(0, a.log2TX - 4), fxb = 1 << lf;
-    const int yg0 = (a.y_abs0 + row0) >> 2, yg1 = (a.y_abs0 + row0 + max(rows, 1) - 1) >> 2;
-    const int xc0 = (a.x_abs0 + (int)bc.bx * a.TX * 4) >> 6;
-    const int n_fl = (yg1 - yg0 + 1) << lf;
-    for (int i = TSDF_BAND_FIRST; i < n_fl; i += TSDF_BAND_STEP) {
-      const int yg = yg0 + (i >> lf), xc = xc0 + (i & (fxb - 1));
-      if (TSDF_BAND(i) && yg < a.band_fy && xc < a.band_fx) band[((int64_t)(a.zl0 + zl) * a.band_fy + yg) * a.band_fx + xc] = 1;
-    }
-  }
+  if (band) tsdf_flags_write_out(a, bc, br, s_band_sets, band, tid);
   if (COUNT) {
     __shared__ unsigned s_cnt, s_chg, s_cntA, s_cntB, s_rdb;
     if (tid == 0) s_cnt = s_chg = s_cntA = s_cntB = s_rdb = 0;
@@ -1776,14 +1776,13 @@ k_integrate2(const IntegrateArgs a, const Frame2 fb, float *__restrict__ D, uint
     if (cntB) atomicAdd(&s_cntB, cntB);
     if (rdb) atomicAdd(&s_rdb, rdb);
     __syncthreads();
-    if (tid == 0 && s_rdb) atomicAdd(n_obs + 2560u + ((bc.bx + bc.by * bc.gdx + bc.bz * bc.gdx * bc.gdy) & 511u), (unsigned long long)s_rdb);
-    if (tid == 0 && s_cnt) {  // 512 striped slots each: frame A, frame B, either, changed bytes, (slots 2048.. stay 0: voxels
-                              // whose distance word was not read -- none in this kernel), plane bytes requested (tsdf_integrate_collect2)
-      const unsigned b = (bc.bx + bc.by * bc.gdx + bc.bz * bc.gdx * bc.gdy) & 511u;
-      if (s_cntA) atomicAdd(n_obs + b, (unsigned long long)s_cntA);
-      if (s_cntB) atomicAdd(n_obs + 512u + b, (unsigned long long)s_cntB);
-      atomicAdd(n_obs + 1024u + b, (unsigned long long)s_cnt);
-      if (s_chg) atomicAdd(n_obs + 1536u + b, (unsigned long long)s_chg);
+    if (tid == 0 && s_rdb) atomicAdd(n_obs + TSDF_CNT2_READ + (tsdf_block_number(bc) & (TSDF_CNT2_STRIPE - 1u)), (unsigned long long)s_rdb);
+    if (tid == 0 && s_cnt) {
+      const unsigned b = tsdf_block_number(bc) & (TSDF_CNT2_STRIPE - 1u);
+      if (s_cntA) atomicAdd(n_obs + TSDF_CNT2_A + b, (unsigned long long)s_cntA);
+      if (s_cntB) atomicAdd(n_obs + TSDF_CNT2_B + b, (unsigned long long)s_cntB);
+      atomicAdd(n_obs + TSDF_CNT2_EITHER + b, (unsigned long long)s_cnt);
+      if (s_chg) atomicAdd(n_obs + TSDF_CNT2_CHANGED + b, (unsigned long long)s_chg);
     }
   }
 }
@@ -2127,7 +2126,7 @@ static __device__ __forceinline__ void plain_count(bool observed, unsigned long 
   if (!n_obs) return;
   const unsigned long long m = __ballot(observed);
   if ((threadIdx.x & 63u) == 0u && m)
-    atomicAdd(n_obs + ((blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * gridDim.x * gridDim.y) & 1023u),
+    atomicAdd(n_obs + TSDF_CNT_OBSERVED + ((blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * gridDim.x * gridDim.y) & (TSDF_CNT_STRIPE - 1u)),
               (unsigned long long)__popcll(m));
 }
 
@@ -2641,7 +2640,7 @@ static int launch_plain_family(tsdf_handle h, const IntegrateArgs &a, unsigned g
     tsdf_set_error("weight_by_depth needs the F32W layout and TSDF_COLOR_RGB");
     return TSDF_HIP_E_UNSUPPORTED;
   }
-  if (count) TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, 1024 * sizeof(unsigned long long), h->stream));
+  if (count) TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, TSDF_CNT_STRIPE * sizeof(unsigned long long), h->stream));
   const bool pose_ok = pose_is_finite(T);
   if (pose_ok) {
     const dim3 grid((unsigned)((h->pitch + 255) / 256), (unsigned)h->ny, gz), block(256);
@@ -2680,7 +2679,7 @@ static int launch_plain_family(tsdf_handle h, const IntegrateArgs &a, unsigned g
     }
     TSDF_HIP_TRY(hipGetLastError());
   }
-  h->count_slots = count ? 1024 : 0;
+  h->count_slots = count ? TSDF_CNT_STRIPE : 0;
   h->count_ran = pose_ok;
   return TSDF_HIP_OK;
 }
@@ -2928,7 +2927,7 @@ int tsdf_integrate_launch(tsdf_handle h, const float *d_depth, const uint32_t *d
   const LaunchKind kind = launch_kind(h, T, a, rc, rc_rows);
   if (kind.live)
     if (const int e = plan_live(h, T, kind.all_inside, rc_rows, pl)) return e;
-  if (count) TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, 4096 * sizeof(unsigned long long), h->stream));
+  if (count) TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, TSDF_CNT_SLOTS * sizeof(unsigned long long), h->stream));
   const bool pose_ok = pose_is_finite(T);
   const bool fastproj = fast_projection_ok(hh, h->p.integrate_color != 0);
   h->last_launch[0] = h->last_launch[1] = h->last_launch[2] = h->last_launch[3] = 0;
@@ -2950,8 +2949,7 @@ int tsdf_integrate_launch(tsdf_handle h, const float *d_depth, const uint32_t *d
     dispatch_fast(h, pl, d_depth, count, fastproj, allin, pipe, pairs, band_arg);
     TSDF_HIP_TRY(hipGetLastError());
   }
-  h->count_slots = count ? 4096 : 0;  // slots 1024.. hold the bytes of voxel words whose value changed, 2048.. the observed
-                                      // voxels whose distance word was not read, 3072.. the plane bytes requested
+  h->count_slots = count ? TSDF_CNT_SLOTS : 0;
   h->count_ran = pose_ok && !pl.nothing_observable;
   return TSDF_HIP_OK;
 }
@@ -2964,15 +2962,15 @@ int tsdf_integrate_collect(tsdf_handle h, uint64_t *n_observed) {
     tsdf_set_error("tsdf_integrate_collect without a counting launch");
     return TSDF_HIP_E_INVALID;
   }
-  unsigned long long c[4096];
-  const int slots = h->count_slots;
+  unsigned long long c[TSDF_CNT_SLOTS];
+  const int slots = h->count_slots;  // (k_integrate_plain fills the first stripe only)
   TSDF_HIP_TRY(hipMemcpyAsync(c, h->counter, (size_t)slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
   TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
   unsigned long long sum = 0, changed = 0, implied = 0, read_bytes = 0;
-  for (int i = 0; i < 1024; ++i) sum += c[i];
-  for (int i = 1024; i < slots && i < 2048; ++i) changed += c[i];
-  for (int i = 2048; i < slots && i < 3072; ++i) implied += c[i];
-  for (int i = 3072; i < slots; ++i) read_bytes += c[i];
+  for (int i = TSDF_CNT_OBSERVED; i < TSDF_CNT_CHANGED; ++i) sum += c[i];
+  for (int i = TSDF_CNT_CHANGED; i < slots && i < TSDF_CNT_IMPLIED; ++i) changed += c[i];
+  for (int i = TSDF_CNT_IMPLIED; i < slots && i < TSDF_CNT_READ; ++i) implied += c[i];
+  for (int i = TSDF_CNT_READ; i < slots; ++i) read_bytes += c[i];
   h->last_observed = h->count_ran ? sum : 0;
   h->last_changed_bytes = h->count_ran ? changed : 0;
   h->last_implied = h->count_ran ? implied : 0;
@@ -2982,8 +2980,7 @@ int tsdf_integrate_collect(tsdf_handle h, uint64_t *n_observed) {
   return TSDF_HIP_OK;
 }
 
-static int launch_integrate(tsdf_handle h, const float *d_depth, const uint32_t *d_bgra, const float T[12],
-                            uint64_t *n_observed) {
+int tsdf_integrate_frame(tsdf_handle h, const float *d_depth, const uint32_t *d_bgra, const float T[12], uint64_t *n_observed) {
   const int rc = tsdf_integrate_launch(h, d_depth, d_bgra, T, n_observed != nullptr);
   if (rc || !n_observed) return rc;
   return tsdf_integrate_collect(h, n_observed);
@@ -3054,7 +3051,7 @@ int tsdf_integrate_launch2(tsdf_handle h, const float *dA, const uint32_t *cA, c
   for (int i = 0; i < 24; ++i) h->cull_planes[i] = planesB ? planesB[i] : 0.f;
   h->count_slots = 0;
   h->count_ran = false;
-  if (count) TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, 3072 * sizeof(unsigned long long), h->stream));
+  if (count) TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, TSDF_CNT2_SLOTS * sizeof(unsigned long long), h->stream));
   uint8_t *band_arg = band_flags_for(h, a);
   (void)implied_distances(h, a, band_arg != nullptr);  // the record every flag-keeping launch keeps (rest_state); k_integrate2
   a.implied_d = 0;                                      // itself reads every distance word (see the kernel)
@@ -3078,7 +3075,7 @@ int tsdf_integrate_launch2(tsdf_handle h, const float *dA, const uint32_t *cA, c
       },
       p.xform_order == TSDF_XFORM_PCL_SSE, color, count, pairs);
   TSDF_HIP_TRY(hipGetLastError());
-  h->count_slots = count ? 3072 : 0;
+  h->count_slots = count ? TSDF_CNT2_SLOTS : 0;
   h->count_ran = true;
   h->pair_fused = true;
   return TSDF_HIP_OK;
@@ -3103,16 +3100,16 @@ int tsdf_integrate_collect2(tsdf_handle h, uint64_t n_observed[2]) {
     tsdf_set_error("tsdf_integrate_collect2 without a counting launch");
     return TSDF_HIP_E_INVALID;
   }
-  unsigned long long c[3072];
+  unsigned long long c[TSDF_CNT2_SLOTS];
   TSDF_HIP_TRY(hipMemcpyAsync(c, h->counter, sizeof c, hipMemcpyDeviceToHost, h->stream));
   TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
-  unsigned long long sum[6] = {0, 0, 0, 0, 0, 0};  // A, B, union, changed bytes, distance words not read, plane bytes requested: 512 striped slots each
-  for (int i = 0; i < 3072; ++i) sum[i >> 9] += c[i];
-  n_observed[0] = sum[0], n_observed[1] = sum[1];
-  h->last_observed = sum[2];
-  h->last_changed_bytes = sum[3];
-  h->last_implied = sum[4];
-  h->last_read_bytes = sum[5];
+  unsigned long long sum[TSDF_CNT2_SLOTS / TSDF_CNT2_STRIPE] = {};  // one per stripe
+  for (int i = 0; i < TSDF_CNT2_SLOTS; ++i) sum[i / TSDF_CNT2_STRIPE] += c[i];
+  n_observed[0] = sum[TSDF_CNT2_A / TSDF_CNT2_STRIPE], n_observed[1] = sum[TSDF_CNT2_B / TSDF_CNT2_STRIPE];
+  h->last_observed = sum[TSDF_CNT2_EITHER / TSDF_CNT2_STRIPE];
+  h->last_changed_bytes = sum[TSDF_CNT2_CHANGED / TSDF_CNT2_STRIPE];
+  h->last_implied = sum[TSDF_CNT2_IMPLIED / TSDF_CNT2_STRIPE];
+  h->last_read_bytes = sum[TSDF_CNT2_READ / TSDF_CNT2_STRIPE];
   h->count_slots = 0;
   return TSDF_HIP_OK;
 }
@@ -3270,7 +3267,7 @@ extern "C" int tsdf_hip_integrate_device(tsdf_handle h, const float *d_depth, co
   if (!h || !d_depth || !cam_from_vol) return TSDF_HIP_E_INVALID;
   if (h->multi) return tsdf_multi_integrate_device(h, d_depth, d_bgra, cam_from_vol, n_observed);
   TSDF_ENTER(h);
-  return launch_integrate(h, d_depth, d_bgra, cam_from_vol, n_observed);
+  return tsdf_integrate_frame(h, d_depth, d_bgra, cam_from_vol, n_observed);
 }
 
 extern "C" int tsdf_hip_integrate(tsdf_handle h, const float *depth, const uint8_t *bgra,
@@ -3289,257 +3286,10 @@ extern "C" int tsdf_hip_integrate(tsdf_handle h, const float *depth, const uint8
   int rc = tsdf_to_device(h, h->frame_depth, depth, npx * sizeof(float));
   if (rc) return rc;
   if (color && (rc = tsdf_to_device(h, h->frame_bgra, bgra, npx * 4))) return rc;
-  rc = launch_integrate(h, h->frame_depth, color ? h->frame_bgra : nullptr, cam_from_vol, n_observed);
+  rc = tsdf_integrate_frame(h, h->frame_depth, color ? h->frame_bgra : nullptr, cam_from_vol, n_observed);
   if (rc) return rc;
   TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
   return TSDF_HIP_OK;
-}
-
-// Pipelined host entry point: the caller's frame is copied into one of two pinned staging slots and the call
-// returns; the host-to-device copy runs on a private copy stream while the previous frame's kernel is still
-// busy, and the kernel of this frame waits for the copy through an event.  A stream of host frames then runs
-// at the kernel's rate instead of kernel + upload + synchronise.  Results are identical to tsdf_hip_integrate;
-// every other entry point is ordered after it on the handle's stream; errors of the asynchronous part surface
-// at the next synchronising call (tsdf_hip_synchronize, download, march, ...).
-struct tsdf_hip_pipeline {
-  static const int SLOTS = 4;  // two frames may wait for their shared sweep while the next two are being staged
-  hipStream_t copy_stream = nullptr;
-  float *pinned[SLOTS] = {nullptr, nullptr, nullptr, nullptr};   // host, [depth | bgra]
-  float *device[SLOTS] = {nullptr, nullptr, nullptr, nullptr};   // device, [depth | bgra]
-  hipEvent_t copied[SLOTS] = {nullptr, nullptr, nullptr, nullptr}, consumed[SLOTS] = {nullptr, nullptr, nullptr, nullptr};
-  unsigned long long frames = 0;
-  // frame pairing (tsdf_hip_set_frame_pairing): a committed frame whose kernel launch waits for a partner
-  bool pairing = false;
-  int pend_slot = 0;
-  float pend_T[12];
-  bool pend_has_planes = false;
-  float pend_planes[24];
-};
-
-void tsdf_pipeline_destroy(tsdf_hip_volume *v) {
-  tsdf_hip_pipeline *p = v->pipe;
-  if (!p) return;
-  for (int i = 0; i < tsdf_hip_pipeline::SLOTS; ++i) {
-    if (p->consumed[i]) (void)hipEventSynchronize(p->consumed[i]);
-    if (p->pinned[i]) (void)hipHostFree(p->pinned[i]);
-    if (p->device[i]) (void)hipFree(p->device[i]);
-    if (p->copied[i]) (void)hipEventDestroy(p->copied[i]);
-    if (p->consumed[i]) (void)hipEventDestroy(p->consumed[i]);
-  }
-  if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
-  delete p;
-  v->pipe = nullptr;
-  v->pair_pending = false;
-}
-
-// The ring itself: tsdf_hip_frame_begin hands out the next pinned slot (waiting until the kernel that last read it
-// has finished), tsdf_hip_frame_commit uploads it on the private copy stream and queues the integrate launch behind
-// the upload.  A caller that can write its frame straight into the slot (the C++ integrateCloud template stripping a
-// PCL cloud) saves the intermediate copy; tsdf_hip_integrate_async is begin + memcpy + commit.
-static int pipeline_ready(tsdf_handle h) {
-  if (h->pipe) return TSDF_HIP_OK;
-  const size_t npx = (size_t)h->p.image_width * h->p.image_height;
-  tsdf_hip_pipeline *p = new tsdf_hip_pipeline;
-  // the ring is attached to the handle only once every allocation has succeeded: a half-built one would hand NULL
-  // slot pointers to the next tsdf_hip_frame_begin
-  auto build = [&]() -> int {
-    TSDF_HIP_TRY(hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking));
-    for (int i = 0; i < tsdf_hip_pipeline::SLOTS; ++i) {
-      TSDF_HIP_TRY(hipHostMalloc((void **)&p->pinned[i], npx * 8, hipHostMallocPortable));
-      TSDF_HIP_TRY(hipMalloc((void **)&p->device[i], npx * 8));
-      TSDF_HIP_TRY(hipEventCreateWithFlags(&p->copied[i], hipEventDisableTiming));
-      TSDF_HIP_TRY(hipEventCreateWithFlags(&p->consumed[i], hipEventDisableTiming));
-    }
-    return TSDF_HIP_OK;
-  };
-  const int rc = build();
-  h->pipe = p;
-  if (rc) tsdf_pipeline_destroy(h);  // frees what was built and detaches it
-  return rc;
-}
-
-int tsdf_multi_frame_begin(tsdf_handle h, float **depth, uint8_t **bgra);
-int tsdf_multi_frame_commit(tsdf_handle h, const float T[12]);
-
-// Frame pairing launches the frame it has been holding back on its own: with that frame's pose and cull planes, the
-// handle's current planes put back afterwards.  Called by every entry point that reads or writes the volume (TSDF_ENTER).
-int tsdf_pipeline_flush(tsdf_hip_volume *h) {
-  tsdf_hip_pipeline *p = h->pipe;
-  if (!h->pair_pending || !p) {
-    h->pair_pending = false;
-    return TSDF_HIP_OK;
-  }
-  h->pair_pending = false;
-  const bool color = h->p.integrate_color != 0;
-  const size_t npx = (size_t)h->p.image_width * h->p.image_height;
-  const bool cur_has = h->ref_cull;
-  float cur[24];
-  for (int i = 0; i < 24; ++i) cur[i] = h->cull_planes[i];
-  h->ref_cull = p->pend_has_planes;
-  for (int i = 0; i < 24; ++i) h->cull_planes[i] = p->pend_has_planes ? p->pend_planes[i] : 0.f;
-  const int s = p->pend_slot;
-  const int rc = tsdf_integrate_launch(h, p->device[s], color ? reinterpret_cast<const uint32_t *>(p->device[s] + npx) : nullptr, p->pend_T, false);
-  h->ref_cull = cur_has;
-  for (int i = 0; i < 24; ++i) h->cull_planes[i] = cur[i];
-  if (rc) return rc;
-  TSDF_HIP_TRY(hipEventRecord(p->consumed[s], h->stream));
-  return TSDF_HIP_OK;
-}
-
-extern "C" int tsdf_hip_set_frame_pairing(tsdf_handle h, int on) {
-  if (!h) return TSDF_HIP_E_INVALID;
-  if (h->multi) return tsdf_multi_set_frame_pairing(h, on);
-  TSDF_ENTER(h);  // (switching it off launches what was waiting)
-  const int rc = pipeline_ready(h);
-  if (rc) return rc;
-  h->pipe->pairing = on != 0;
-  return TSDF_HIP_OK;
-}
-
-extern "C" int tsdf_hip_frame_begin(tsdf_handle h, float **depth, uint8_t **bgra) {
-  if (!h || !depth) return TSDF_HIP_E_INVALID;
-  if (h->multi) return tsdf_multi_frame_begin(h, depth, bgra);
-  TSDF_ON_DEVICE(h->device);
-  const int rc = pipeline_ready(h);
-  if (rc) return rc;
-  tsdf_hip_pipeline *p = h->pipe;
-  const size_t npx = (size_t)h->p.image_width * h->p.image_height;
-  const int slot = (int)(p->frames % tsdf_hip_pipeline::SLOTS);
-  // the slot was last used SLOTS frames ago: its kernel must be done before the staging buffers are reused
-  if (p->frames >= (unsigned)tsdf_hip_pipeline::SLOTS) TSDF_HIP_TRY(hipEventSynchronize(p->consumed[slot]));
-  *depth = p->pinned[slot];
-  if (bgra) *bgra = h->p.integrate_color ? reinterpret_cast<uint8_t *>(p->pinned[slot] + npx) : nullptr;
-  return TSDF_HIP_OK;
-}
-
-// The ring's second half, once frame `slot` is on its way into p->device[slot] and the handle's stream waits for it: launch
-// it, or -- frame pairing -- hold it back for a partner / launch it together with the frame that was waiting.
-static int pipeline_commit_uploaded(tsdf_handle h, int slot, const float cam_from_vol[12]) {
-  tsdf_hip_pipeline *p = h->pipe;
-  const bool color = h->p.integrate_color != 0;
-  const size_t npx = (size_t)h->p.image_width * h->p.image_height;
-  auto bgra_of = [&](int s) { return color ? reinterpret_cast<const uint32_t *>(p->device[s] + npx) : nullptr; };
-  if (h->pair_pending) {  // the partner has arrived: one sweep for both where the poses allow it, two launches otherwise
-    h->pair_pending = false;
-    const int sa = p->pend_slot;
-    const int rc = tsdf_integrate_launch2(h, p->device[sa], bgra_of(sa), p->pend_T, p->pend_has_planes ? p->pend_planes : nullptr,
-                                          p->device[slot], bgra_of(slot), cam_from_vol, h->ref_cull ? h->cull_planes : nullptr, false, nullptr);
-    // Whatever the launch did, both ring slots are handed back in order (their `consumed` events recorded, the frame
-    // counter advanced): a failure must not leave a slot whose upload or launch state the next frame_begin cannot know
-    // (ADVICE r04).  A failed launch integrated NEITHER frame or only the first: the error text says a frame was lost.
-    (void)hipEventRecord(p->consumed[sa], h->stream);
-    (void)hipEventRecord(p->consumed[slot], h->stream);
-    if (rc) {
-      p->frames++;
-      const std::string why = tsdf_hip_last_error();
-      tsdf_set_error("paired commit failed -- the frame held back for pairing and this one are LOST (not integrated): " + why);
-      return rc;
-    }
-  } else if (p->pairing) {  // uploaded, but its kernel waits for the next frame (or for any other call on the volume)
-    p->pend_slot = slot;
-    for (int i = 0; i < 12; ++i) p->pend_T[i] = cam_from_vol[i];
-    p->pend_has_planes = h->ref_cull;
-    for (int i = 0; i < 24; ++i) p->pend_planes[i] = h->cull_planes[i];
-    h->pair_pending = true;
-  } else {
-    const int rc = launch_integrate(h, p->device[slot], bgra_of(slot), cam_from_vol, nullptr);
-    if (rc) return rc;
-    TSDF_HIP_TRY(hipEventRecord(p->consumed[slot], h->stream));
-  }
-  p->frames++;
-  return TSDF_HIP_OK;
-}
-
-extern "C" int tsdf_hip_frame_commit(tsdf_handle h, const float cam_from_vol[12]) {
-  if (!h || !cam_from_vol) return TSDF_HIP_E_INVALID;
-  if (h->multi) return tsdf_multi_frame_commit(h, cam_from_vol);
-  if (!h->pipe) {
-    tsdf_set_error("tsdf_hip_frame_commit without tsdf_hip_frame_begin");
-    return TSDF_HIP_E_INVALID;
-  }
-  TSDF_ON_DEVICE(h->device);
-  tsdf_hip_pipeline *p = h->pipe;
-  const bool color = h->p.integrate_color != 0;
-  const size_t npx = (size_t)h->p.image_width * h->p.image_height, bytes = npx * 4 * (color ? 2 : 1);
-  const int slot = (int)(p->frames % tsdf_hip_pipeline::SLOTS);
-  TSDF_HIP_TRY(hipMemcpyAsync(p->device[slot], p->pinned[slot], bytes, hipMemcpyHostToDevice, p->copy_stream));
-  TSDF_HIP_TRY(hipEventRecord(p->copied[slot], p->copy_stream));
-  TSDF_HIP_TRY(hipStreamWaitEvent(h->stream, p->copied[slot], 0));
-  return pipeline_commit_uploaded(h, slot, cam_from_vol);
-}
-
-// A SLAB of a multi-GPU set takes a frame through its own ring (tsdf_multi.hip, frame pairing on a set): the frame already
-// sits in `src` -- the set's pinned host slot (src_dev < 0: one upload over this GPU's own PCIe link) or a device buffer on
-// GPU src_dev (a peer copy, or the pinned relay where the driver refuses peer access: `copy`) -- and goes into the slab's next
-// ring slot on the slab's copy stream; then exactly what tsdf_hip_frame_commit does.  *uploaded, when given, is recorded on
-// the copy stream behind the copy (the set waits for it before it reuses its pinned slot).
-int tsdf_pipeline_commit_from(tsdf_handle s, const void *src, int src_dev, const float T[12], bool pairing, hipEvent_t uploaded,
-                              int (*copy)(void *ctx, void *dst, int dst_dev, const void *src, int src_dev, size_t bytes, hipStream_t st), void *ctx) {
-  TSDF_ON_DEVICE(s->device);
-  int rc = pipeline_ready(s);
-  if (rc) return rc;
-  tsdf_hip_pipeline *p = s->pipe;
-  if (p->pairing != pairing) {
-    if (s->pair_pending && (rc = tsdf_pipeline_flush(s))) return rc;
-    p->pairing = pairing;
-  }
-  const bool color = s->p.integrate_color != 0;
-  const size_t npx = (size_t)s->p.image_width * s->p.image_height, bytes = npx * 4 * (color ? 2 : 1);
-  const int slot = (int)(p->frames % tsdf_hip_pipeline::SLOTS);
-  if (p->frames >= (unsigned)tsdf_hip_pipeline::SLOTS) TSDF_HIP_TRY(hipEventSynchronize(p->consumed[slot]));
-  if (src_dev < 0) {
-    TSDF_HIP_TRY(hipMemcpyAsync(p->device[slot], src, bytes, hipMemcpyHostToDevice, p->copy_stream));
-  } else if ((rc = copy(ctx, p->device[slot], s->device, src, src_dev, bytes, p->copy_stream))) {
-    return rc;
-  }
-  TSDF_HIP_TRY(hipEventRecord(p->copied[slot], p->copy_stream));
-  if (uploaded) TSDF_HIP_TRY(hipEventRecord(uploaded, p->copy_stream));
-  TSDF_HIP_TRY(hipStreamWaitEvent(s->stream, p->copied[slot], 0));
-  return pipeline_commit_uploaded(s, slot, T);
-}
-
-// ... and two device frames at once (tsdf_hip_integrate_device2 on a set): both into ring slots, one tsdf_integrate_launch2.
-int tsdf_pipeline_pair_from(tsdf_handle s, const void *src_a, const void *src_b, int src_dev, const float TA[12], const float *planes_a,
-                            const float TB[12], const float *planes_b, bool count, bool *fused,
-                            int (*copy)(void *ctx, void *dst, int dst_dev, const void *src, int src_dev, size_t bytes, hipStream_t st), void *ctx) {
-  TSDF_ENTER(s);  // (a frame this slab was holding back goes first)
-  int rc = pipeline_ready(s);
-  if (rc) return rc;
-  tsdf_hip_pipeline *p = s->pipe;
-  const bool color = s->p.integrate_color != 0;
-  const size_t npx = (size_t)s->p.image_width * s->p.image_height, bytes = npx * 4 * (color ? 2 : 1);
-  int slot[2];
-  const void *src[2] = {src_a, src_b};
-  for (int k = 0; k < 2; ++k) {
-    slot[k] = (int)((p->frames + k) % tsdf_hip_pipeline::SLOTS);
-    if (p->frames + k >= (unsigned)tsdf_hip_pipeline::SLOTS) TSDF_HIP_TRY(hipEventSynchronize(p->consumed[slot[k]]));
-    if ((rc = copy(ctx, p->device[slot[k]], s->device, src[k], src_dev, bytes, p->copy_stream))) return rc;
-    TSDF_HIP_TRY(hipEventRecord(p->copied[slot[k]], p->copy_stream));
-    TSDF_HIP_TRY(hipStreamWaitEvent(s->stream, p->copied[slot[k]], 0));
-  }
-  auto bgra_of = [&](int q) { return color ? reinterpret_cast<const uint32_t *>(p->device[q] + npx) : nullptr; };
-  rc = tsdf_integrate_launch2(s, p->device[slot[0]], bgra_of(slot[0]), TA, planes_a, p->device[slot[1]], bgra_of(slot[1]), TB, planes_b, count, fused);
-  (void)hipEventRecord(p->consumed[slot[0]], s->stream);
-  (void)hipEventRecord(p->consumed[slot[1]], s->stream);
-  p->frames += 2;
-  return rc;
-}
-
-extern "C" int tsdf_hip_integrate_async(tsdf_handle h, const float *depth, const uint8_t *bgra,
-                                        const float cam_from_vol[12]) {
-  if (!h || !depth || !cam_from_vol) return TSDF_HIP_E_INVALID;
-  if (h->p.integrate_color && !bgra) {
-    tsdf_set_error("integrate_color is set but no colour image was given");
-    return TSDF_HIP_E_INVALID;
-  }
-  float *sd = nullptr;
-  uint8_t *sc = nullptr;
-  const int rc = tsdf_hip_frame_begin(h, &sd, &sc);
-  if (rc) return rc;
-  const size_t npx = (size_t)h->p.image_width * h->p.image_height;
-  memcpy(sd, depth, npx * 4);
-  if (sc) memcpy(sc, bgra, npx * 4);
-  return tsdf_hip_frame_commit(h, cam_from_vol);
 }
 
 #ifdef TSDF_HIP_TEST_HOOKS  // everything below: libtsdf_hip_test.so only (include/tsdf_hip_test.h)
@@ -3660,7 +3410,7 @@ static bool selftest_centers(const tsdf_params &p, std::vector<float> ctr[3], in
   return true;
 }
 
-// Test hook, host only (no device needed): the index box launch_integrate would restrict a frame's launch to.
+// Test hook, host only (no device needed): the index box tsdf_integrate_launch would restrict a frame's launch to.
 // rc 0 and box = {lo x,y,z, hi x,y,z} (inclusive); *state = 0 box valid, 1 nothing observable, 2 no claim.
 extern "C" int tsdf_hip_selftest_index_box(const tsdf_params *p, const float cam_from_vol[12], int32_t box[6], int32_t *state) {
   if (!p || !cam_from_vol || !box || !state) return TSDF_HIP_E_INVALID;

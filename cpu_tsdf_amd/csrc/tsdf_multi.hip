@@ -300,16 +300,11 @@ int tsdf_multi_reset(tsdf_handle h) {
 }
 
 // ---- frame pairing on a set (round 6) -------------------------------------------------------------
-// Every slab has the ring of a single handle (tsdf_hip_pipeline, tsdf_integrate.hip) and pairs the frames that pass through
+// Every slab has the ring of a single handle (tsdf_hip_pipeline, tsdf_pipeline.hip) and pairs the frames that pass through
 // it by itself: a committed frame is copied into the slab's next ring slot at once -- from the set's pinned slot over the
 // slab's own PCIe link, or from a device buffer over xGMI -- and its kernel waits for the partner; with both at hand the slab
 // runs k_integrate2 where BOTH poses see all of THAT slab (two launches in order otherwise: slabs decide independently).
 // tsdf_multi_flush: every entry point of the set that reads or writes voxels first lets the slabs launch what they hold.
-int tsdf_pipeline_commit_from(tsdf_handle s, const void *src, int src_dev, const float T[12], bool pairing, hipEvent_t uploaded,
-                              int (*copy)(void *ctx, void *dst, int dst_dev, const void *src, int src_dev, size_t bytes, hipStream_t st), void *ctx);
-int tsdf_pipeline_pair_from(tsdf_handle s, const void *src_a, const void *src_b, int src_dev, const float TA[12], const float *planes_a,
-                            const float TB[12], const float *planes_b, bool count, bool *fused,
-                            int (*copy)(void *ctx, void *dst, int dst_dev, const void *src, int src_dev, size_t bytes, hipStream_t st), void *ctx);
 static int tsdf_multi_copy(tsdf_hip_multi *m, void *dst, int dst_dev, const void *src, int src_dev, size_t bytes, hipStream_t stream, bool cross_slab);
 static int copy_thunk(void *ctx, void *dst, int dst_dev, const void *src, int src_dev, size_t bytes, hipStream_t st) {
   return tsdf_multi_copy(static_cast<tsdf_hip_multi *>(ctx), dst, dst_dev, src, src_dev, bytes, st, true);
