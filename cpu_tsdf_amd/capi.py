@@ -143,6 +143,9 @@ SIGNATURES = {
                                          _u64p]),
     "tsdf_hip_march_decimate": (C.c_int, [C.c_void_p, C.c_float, _u64p, _u64p]),
     "tsdf_hip_mesh_decimate_stats": (C.c_int, [_u64p]),
+    "tsdf_hip_mesh_smooth": (C.c_int, [C.c_int, _f32p, C.c_uint64, _u32p, C.c_uint64, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, _u8p, _u32p]),
+    "tsdf_hip_march_smooth": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, _u64p]),
+    "tsdf_hip_mesh_smooth_stats": (C.c_int, [_u64p]),
     "tsdf_hip_occupied": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), _u64p]),
     "tsdf_hip_occupied_fetch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), _f32p, _f32p, _u8p]),
     "tsdf_hip_occupied_fetch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -2,7 +2,8 @@
 // Mirrors performReconstruction of the reference (src/lib/marching_cubes_tsdf_octree.cpp:108-143): build
 // the vertex cloud (3 vertices per triangle, no sharing), move it by the volume's global transform,
 // pack it into the PolygonMesh blob, polygons = {3i, 3i+1, 3i+2}.  With setFlatten (an extension) the vertex cloud and the
-// polygons are the indexed mesh of tsdf_hip_march_flatten instead, with setDecimate that of tsdf_hip_march_decimate.
+// polygons are the indexed mesh of tsdf_hip_march_flatten instead, with setDecimate that of tsdf_hip_march_decimate; setSmooth
+// moves that mesh's vertices (tsdf_hip_march_smooth) before they are fetched.
 #include <cpu_tsdf/marching_cubes_tsdf_octree.h>
 #include <pcl/common/transforms.h>
 #include <pcl/console/print.h>
@@ -86,10 +87,37 @@ void MarchingCubesTSDFOctree::clearDecimate() {
   g_decimate.erase(this);
 }
 
+// setSmooth's arguments per object, kept likewise
+struct SmoothArgs {
+  int iterations;
+  float lambda, mu;
+  bool keep_boundary;
+};
+static std::map<const MarchingCubesTSDFOctree *, SmoothArgs> g_smooth;
+
+void MarchingCubesTSDFOctree::setSmooth(int iterations, float lambda, float mu, bool keep_boundary) {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  g_smooth[this] = SmoothArgs{iterations, lambda, mu, keep_boundary};
+}
+
+void MarchingCubesTSDFOctree::clearSmooth() {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  g_smooth.erase(this);
+}
+
 MarchingCubesTSDFOctree::~MarchingCubesTSDFOctree() {
   clearCleanup();
   clearFlatten();
   clearDecimate();
+  clearSmooth();
+}
+
+static bool smooth_of(const MarchingCubesTSDFOctree *mc, SmoothArgs &out) {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  const auto it = g_smooth.find(mc);
+  if (it == g_smooth.end()) return false;
+  out = it->second;
+  return true;
 }
 
 static bool decimate_of(const MarchingCubesTSDFOctree *mc, float &out) {
@@ -119,9 +147,11 @@ static bool cleanup_of(const MarchingCubesTSDFOctree *mc, CleanupArgs &out) {
 // cleanup: NULL, or the arguments of setCleanup -- tsdf_hip_march_cleanup between the march and the fetch.  flatten: NULL,
 // or setFlatten's min_dist -- tsdf_hip_march_flatten after that, and the INDEXED mesh is fetched: `indexed` is set and
 // `faces` holds its polygons (otherwise the soup: polygon i = {3i, 3i + 1, 3i + 2}).  decimate: NULL, or setDecimate's
-// cell_size -- tsdf_hip_march_decimate in flatten's place (with both set, flatten is skipped), fetched the same way.
+// cell_size -- tsdf_hip_march_decimate in flatten's place (with both set, flatten is skipped), fetched the same way.  smooth:
+// NULL, or the arguments of setSmooth -- tsdf_hip_march_smooth last, on the indexed mesh; with neither flatten nor decimate,
+// flatten runs first at its default min_dist.
 static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mode, const CleanupArgs *cleanup, const float *flatten, const float *decimate,
-                      std::vector<float> &verts, std::vector<unsigned char> &rgb, std::vector<uint32_t> &faces, bool &indexed) {
+                      const SmoothArgs *smooth, std::vector<float> &verts, std::vector<unsigned char> &rgb, std::vector<uint32_t> &faces, bool &indexed) {
   verts.clear();
   rgb.clear();
   faces.clear();
@@ -134,10 +164,12 @@ static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mo
   uint64_t n_tri = 0;
   int rc = tsdf_hip_march(vol->handle(), w_min, mode, &n_tri);
   if (rc == 0 && cleanup) rc = tsdf_hip_march_cleanup(vol->handle(), cleanup->face_dist, cleanup->min_neighbors, &n_tri);
-  if (rc == 0 && (flatten || decimate)) {
+  if (rc == 0 && (flatten || decimate || smooth)) {
     uint64_t n_verts = 0, n_faces = 0;
     rc = decimate ? tsdf_hip_march_decimate(vol->handle(), *decimate, &n_verts, &n_faces)
-                  : tsdf_hip_march_flatten(vol->handle(), *flatten, &n_verts, &n_faces);
+                  : tsdf_hip_march_flatten(vol->handle(), flatten ? *flatten : 0.0001f, &n_verts, &n_faces);
+    if (rc == 0 && smooth)
+      rc = tsdf_hip_march_smooth(vol->handle(), smooth->lambda, smooth->mu, smooth->iterations, smooth->keep_boundary ? 1 : 0, nullptr);
     if (rc == 0) {
       indexed = true;
       verts.resize((size_t)n_verts * 3);
@@ -181,9 +213,10 @@ void MarchingCubesTSDFOctree::performReconstruction(pcl::PolygonMesh &output) {
   std::vector<uint32_t> faces;
   bool indexed = false;
   CleanupArgs cleanup;
+  SmoothArgs smooth;
   float flatten = 0.f, decimate = 0.f;
   run_march(tsdf_volume_, w_min_, mode, cleanup_of(this, cleanup) ? &cleanup : nullptr, flatten_of(this, flatten) ? &flatten : nullptr,
-            decimate_of(this, decimate) ? &decimate : nullptr, verts, rgb, faces, indexed);
+            decimate_of(this, decimate) ? &decimate : nullptr, smooth_of(this, smooth) ? &smooth : nullptr, verts, rgb, faces, indexed);
   const size_t n = verts.size() / 3;
   const Eigen::Affine3d g = tsdf_volume_ ? tsdf_volume_->getGlobalTransform() : Eigen::Affine3d::Identity();
   if (mode) {
@@ -226,9 +259,10 @@ void MarchingCubesTSDFOctree::performReconstruction(pcl::PointCloud<pcl::PointXY
   std::vector<uint32_t> faces;
   bool indexed = false;
   CleanupArgs cleanup;
+  SmoothArgs smooth;
   float flatten = 0.f, decimate = 0.f;
   run_march(tsdf_volume_, w_min_, 0, cleanup_of(this, cleanup) ? &cleanup : nullptr, flatten_of(this, flatten) ? &flatten : nullptr,
-            decimate_of(this, decimate) ? &decimate : nullptr, verts, rgb, faces, indexed);
+            decimate_of(this, decimate) ? &decimate : nullptr, smooth_of(this, smooth) ? &smooth : nullptr, verts, rgb, faces, indexed);
   const size_t n = verts.size() / 3;
   points.points.resize(n);
   points.width = (uint32_t)n;

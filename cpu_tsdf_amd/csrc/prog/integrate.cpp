@@ -13,7 +13,9 @@
 //   frame pose = poses[0]^-1 * poses[i]                                                            :650
 //   --organized: the cloud must already have the image size                                        :585-592
 //   mesh: min weight, colour by RGB when --color, --flatten, --cleanup, PLY ascii/binary           :685-716
-//   --decimate <cell size in metres> (an extension): vertex clustering, applied last
+//   --decimate <cell size in metres> (an extension): vertex clustering, after --flatten and --cleanup
+//   --smooth <iterations> [--smooth-lambda L] [--smooth-mu M] (an extension): Taubin's lambda | mu smoothing, applied last; a
+//     mesh that neither --flatten nor --decimate has indexed is flattened first
 // Not reproduced: --visualize (PCLVisualizer) and the reference's PCL_INFO chatter.  --cloud-only works but
 // its VoxelGrid thinning needs real PCL.
 #include <cpu_tsdf/marching_cubes_tsdf_octree.h>
@@ -49,8 +51,9 @@ struct Settings {
        zero_nans = false, save_ascii = false, save_tsdf = false, cloud_only = false, color = false;
   float cloud_units = 1.f, pose_units = 1.f, max_sensor_dist = 3.0f, min_sensor_dist = 0.f, min_weight = 0.f,
         trunc_pos = 0.03f, trunc_neg = 0.03f, volume_size = 12.f, cell_size = 0.006f, max_cell_size = 0.5f,
-        decimate = 0.f;
-  bool decimate_on = false;
+        decimate = 0.f, smooth_lambda = 0.5f, smooth_mu = -0.53f;
+  bool decimate_on = false, smooth_on = false;
+  int smooth = 0;
   int width = 640, height = 480, num_random_splits = 1;
   float fx = 525.f, fy = 525.f, cx = 319.5f, cy = 239.5f;
   bool limit_frames = false;
@@ -84,7 +87,10 @@ int parseCommandLine(int argc, char **argv, Settings &s) {
       "trunc-dist-pos", bpo::value<float>(), "Positive truncation distance")(
       "trunc-dist-neg", bpo::value<float>(), "Negative truncation distance")("min-weight", bpo::value<float>(), "Minimum weight to render")(
       "cloud-only", "Save aggregate cloud rather than actually running TSDF")(
-      "decimate", bpo::value<float>(), "Decimate the mesh by vertex clustering: cell size in metres (applied last)");
+      "decimate", bpo::value<float>(), "Decimate the mesh by vertex clustering: cell size in metres (after flatten and cleanup)")(
+      "smooth", bpo::value<int>(), "Smooth the mesh (Taubin): iterations (applied last)")(
+      "smooth-lambda", bpo::value<float>(), "Smoothing factor of the first step of an iteration (default 0.5)")(
+      "smooth-mu", bpo::value<float>(), "Factor of the second step, <= 0; 0 = plain Laplacian smoothing (default -0.53)");
   bpo::variables_map vm;
   bpo::store(bpo::parse_command_line(argc, argv, d, bpo::command_line_style::unix_style ^ bpo::command_line_style::allow_short), vm);
   bool bad = false;
@@ -115,6 +121,10 @@ int parseCommandLine(int argc, char **argv, Settings &s) {
   s.color = vm.count("color");
   s.decimate_on = vm.count("decimate");
   take(vm, "decimate", s.decimate);
+  s.smooth_on = vm.count("smooth");
+  take(vm, "smooth", s.smooth);
+  take(vm, "smooth-lambda", s.smooth_lambda);
+  take(vm, "smooth-mu", s.smooth_mu);
   take(vm, "cloud-units", s.cloud_units);
   take(vm, "pose-units", s.pose_units);
   take(vm, "num-random-splits", s.num_random_splits);
@@ -328,6 +338,13 @@ int main(int argc, char **argv) {
     std::string why;
     if (const int rc = cpu_tsdf::mesh_post::decimateMeshAuto(mesh, s.decimate, &why)) {
       PCL_ERROR("--decimate: %s: %s\n", tsdf_hip_error_string(rc), why.c_str());
+      return 1;
+    }
+  }
+  if (s.smooth_on) {  // an extension, last: on the GPU (tsdf_hip_mesh_smooth); TSDF_HIP_HOST_MESH_POST=1 keeps the host pass
+    std::string why;
+    if (const int rc = cpu_tsdf::mesh_post::smoothProgramMesh(mesh, !s.flatten && !s.decimate_on, s.smooth, s.smooth_lambda, s.smooth_mu, &why)) {
+      PCL_ERROR("--smooth: %s: %s\n", tsdf_hip_error_string(rc), why.c_str());
       return 1;
     }
   }

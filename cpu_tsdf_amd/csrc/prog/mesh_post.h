@@ -18,6 +18,9 @@
 //     the mean of its members; faces are re-indexed, degenerate and duplicate faces dropped.  decimateArrays below states the
 //     rules; decimateMeshGpu gets the same arrays from the GPU (tsdf_hip_mesh_decimate); the host pass stays: it defines the
 //     result.
+//   smoothMesh: Taubin's lambda | mu smoothing of an indexed mesh over the neighbours its faces define -- only the vertices
+//     move.  smoothArrays below states the rules; smoothMeshGpu gets the same vertices from the GPU (tsdf_hip_mesh_smooth);
+//     the host pass stays: it defines the result.
 #pragma once
 
 #include <pcl/PolygonMesh.h>
@@ -502,6 +505,188 @@ inline int decimateMeshAuto(pcl::PolygonMesh &mesh, float cell_size, std::string
   const int rc = decimateMeshGpu(mesh, cell_size);
   if (rc && error) *error = tsdf_hip_last_error();
   return rc;
+}
+
+// ---- smoothMesh: Taubin's lambda | mu -------------------------------------------------------------------------------------------
+struct Smoothed {
+  std::vector<float> verts;           // n x 3
+  std::vector<std::uint8_t> fixed;    // n: rule 3's bits
+  std::vector<std::uint32_t> degree;  // n
+  std::uint64_t edges = 0;            // unique undirected edges
+};
+
+// The definition (umbrella operator, uniform weights, Jacobi steps), as one sequential pass.
+//   1. N(i) is the set of j != i such that some face has both i and j among its corners, ordered by ascending index;
+//      deg(i) = |N(i)|.  A degenerate face (a, a, b) still contributes a-b; duplicate faces contribute once.
+//   2. The multiplicity of the undirected edge {a, b}, a != b, is the number of corner pairs (0,1), (1,2), (2,0) of all faces
+//      that name it; a BOUNDARY edge has multiplicity exactly 1.
+//   3. fixed[i], decided once from the input positions, is the OR of 1 (a component of i or of some j in N(i) is not finite),
+//      2 (deg(i) == 0) and 4 (keep_boundary != 0 and i is an endpoint of a boundary edge).  A fixed vertex keeps its three
+//      words bit for bit through every step.
+//   4. One step with factor f, the float widened to double, every vertex reading the positions of the step before: per
+//      component s = +0.0; for j in N(i) ascending s += (double)x_j; m = s / (double)deg(i); p = (double)x_i;
+//      x'_i = (float)(p + f * (m - p)).  Each operation is rounded once (the programs are built with -ffp-contract=off), and the
+//      order of the adds is part of the definition: the GPU pass performs exactly these.
+//   5. One iteration is a step with lambda and then, iff mu != 0, a step with mu.  iterations == 0 returns the input.
+// xyz n x 3, faces nf x 3 (required: a soup shares no vertices).  0, or TSDF_HIP_E_INVALID with the reason in *error and `out`
+// untouched.
+inline int smoothArrays(const float *xyz, size_t n, const std::uint32_t *faces, size_t nf, float lambda, float mu, int iterations, int keep_boundary,
+                        Smoothed &out, std::string *error = nullptr) {
+  const auto refuse = [&](const std::string &why) {
+    if (error) *error = why;
+    return (int)TSDF_HIP_E_INVALID;
+  };
+  if (!std::isfinite(lambda) || !(lambda > 0.f && lambda <= 1.f)) return refuse("smoothMesh: lambda must be finite and in (0, 1]");
+  if (!std::isfinite(mu) || !(mu >= -1.f && mu <= 0.f)) return refuse("smoothMesh: mu must be finite and in [-1, 0]");
+  if (iterations < 0 || iterations > 1000) return refuse("smoothMesh: iterations must be in [0, 1000]");
+  if (n > ((size_t)1 << 31) || nf > ((size_t)1 << 31)) return refuse("smoothMesh: more than 2^31 vertices or faces");
+  if (!faces && (n || nf)) return refuse("smoothMesh: a triangle soup shares no vertices, so it has no neighbours to smooth with: flatten or decimate first");
+  if (n && !xyz) return refuse("smoothMesh: verts must not be NULL");
+  for (size_t e = 0; e < 3 * nf; ++e)
+    if (faces[e] >= n) return refuse("smoothMesh: a face names a vertex index >= n_verts");
+  // rules 1 and 2: every corner pair in both directions; after sorting, a run of equal (a, b) is as long as the multiplicity
+  std::vector<std::uint64_t> key;
+  key.reserve(6 * nf);
+  for (size_t f = 0; f < nf; ++f)
+    for (int k = 0; k < 3; ++k) {
+      const std::uint64_t a = faces[3 * f + k], b = faces[3 * f + (k + 1) % 3];
+      if (a == b) continue;
+      key.push_back(a << 32 | b);
+      key.push_back(b << 32 | a);
+    }
+  std::sort(key.begin(), key.end());
+  std::vector<std::uint32_t> row(n + 1, 0), col;
+  std::vector<char> boundary(n, 0);
+  for (size_t i = 0; i < key.size();) {
+    size_t j = i + 1;
+    while (j < key.size() && key[j] == key[i]) ++j;
+    const std::uint32_t a = (std::uint32_t)(key[i] >> 32);
+    if (j - i == 1) boundary[a] = 1;
+    ++row[a + 1];
+    col.push_back((std::uint32_t)key[i]);
+    i = j;
+  }
+  for (size_t i = 0; i < n; ++i) row[i + 1] += row[i];
+  const auto finite = [&](size_t i) { return std::isfinite(xyz[3 * i]) && std::isfinite(xyz[3 * i + 1]) && std::isfinite(xyz[3 * i + 2]); };
+  Smoothed r;
+  r.edges = col.size() / 2;
+  r.fixed.resize(n);
+  r.degree.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    bool fin = finite(i);
+    for (std::uint32_t e = row[i]; e < row[i + 1] && fin; ++e) fin = finite(col[e]);
+    r.degree[i] = row[i + 1] - row[i];
+    r.fixed[i] = (std::uint8_t)((fin ? 0 : 1) | (r.degree[i] == 0 ? 2 : 0) | (keep_boundary && boundary[i] ? 4 : 0));
+  }
+  r.verts.assign(xyz, xyz + 3 * n);
+  std::vector<float> next(3 * n);
+  for (int it = 0; it < iterations; ++it)
+    for (int half = 0; half < (mu != 0.f ? 2 : 1); ++half) {
+      const double f = (double)(half ? mu : lambda);
+      for (size_t i = 0; i < n; ++i) {
+        if (r.fixed[i]) {
+          std::memcpy(&next[3 * i], &r.verts[3 * i], 3 * sizeof(float));
+          continue;
+        }
+        for (int c = 0; c < 3; ++c) {
+          double s = 0.0;
+          for (std::uint32_t e = row[i]; e < row[i + 1]; ++e) s += (double)r.verts[3 * (size_t)col[e] + c];
+          const double m = s / (double)r.degree[i], p = (double)r.verts[3 * i + c];
+          next[3 * i + c] = (float)(p + f * (m - p));
+        }
+      }
+      r.verts.swap(next);
+    }
+  out = std::move(r);
+  return 0;
+}
+
+// the offsets of the x, y, z fields (FLOAT32) in the cloud blob; false: the cloud has no such fields
+inline bool positionOffsets(const pcl::PolygonMesh &mesh, std::uint32_t off[3]) {
+  int found = 0;
+  for (const auto &f : mesh.cloud.fields)
+    for (int k = 0; k < 3; ++k)
+      if (f.name == std::string(1, "xyz"[k]) && f.datatype == pcl::PCLPointField::FLOAT32) off[k] = f.offset, found |= 1 << k;
+  return found == 7;
+}
+
+// both smooth passes on a PolygonMesh: the positions out of the blob, pass(xyz, faces, out), and the x, y, z fields of the blob
+// rewritten -- every other field (rgb) survives.  A polygon that is not a triangle refuses the mesh.
+template <typename Pass>
+inline int smoothBlob(pcl::PolygonMesh &mesh, std::string *error, Pass pass) {
+  std::vector<std::uint32_t> faces;
+  std::uint32_t off[3];
+  const size_t n = (size_t)mesh.cloud.width * mesh.cloud.height, step = mesh.cloud.point_step;
+  if (!triangleIndices(mesh, faces) || (n && !positionOffsets(mesh, off))) {
+    if (error) *error = "smoothMesh: a polygon is not a triangle, or the cloud has no float x, y, z fields";
+    return (int)TSDF_HIP_E_INVALID;
+  }
+  std::vector<float> xyz(3 * n), out;
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < 3; ++k) std::memcpy(&xyz[3 * i + k], mesh.cloud.data.data() + i * step + off[k], 4);
+  const int rc = pass(xyz, faces, out);
+  if (rc) return rc;
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < 3; ++k) std::memcpy(mesh.cloud.data.data() + i * step + off[k], &out[3 * i + k], 4);
+  return 0;
+}
+
+// The host pass on a PolygonMesh.  0, or TSDF_HIP_E_INVALID (the reason in *error) with the mesh untouched.
+inline int smoothMesh(pcl::PolygonMesh &mesh, int iterations, float lambda = 0.5f, float mu = -0.53f, bool keep_boundary = true,
+                      std::string *error = nullptr) {
+  return smoothBlob(mesh, error, [&](const std::vector<float> &xyz, const std::vector<std::uint32_t> &faces, std::vector<float> &out) {
+    Smoothed s;
+    // (an empty vector's data() may be NULL: an empty mesh is not a soup)
+    static const std::uint32_t none[3] = {0, 0, 0};
+    const int rc = smoothArrays(xyz.data(), xyz.size() / 3, faces.empty() ? none : faces.data(), faces.size() / 3, lambda, mu, iterations,
+                                keep_boundary ? 1 : 0, s, error);
+    out.swap(s.verts);
+    return rc;
+  });
+}
+
+// The same result from the GPU (tsdf_hip_mesh_smooth, which reproduces the pass above bit for bit).  0, or the library's
+// error code (its text in tsdf_hip_last_error, or in *error for what this function refuses itself) with the mesh untouched.
+inline int smoothMeshGpu(pcl::PolygonMesh &mesh, int iterations, float lambda = 0.5f, float mu = -0.53f, bool keep_boundary = true, int device = 0,
+                         std::string *error = nullptr) {
+  bool own = false;  // the refusal is smoothBlob's own, not the library's
+  std::string why;
+  const int rc = smoothBlob(mesh, &why, [&](const std::vector<float> &xyz, const std::vector<std::uint32_t> &faces, std::vector<float> &out) {
+    own = true;
+    static const std::uint32_t none[3] = {0, 0, 0};
+    out.resize(xyz.size());
+    return tsdf_hip_mesh_smooth(device, xyz.data(), xyz.size() / 3, faces.empty() ? none : faces.data(), faces.size() / 3, lambda, mu, iterations,
+                                keep_boundary ? 1 : 0, out.data(), nullptr, nullptr);
+  });
+  if (rc && error) *error = own ? std::string(tsdf_hip_last_error()) : why;
+  return rc;
+}
+
+// Vertices up to which --smooth keeps the host pass: the largest prefix at which tools/time_smooth.py measured the GPU-backed
+// pass (upload, device pass, download) slower than smoothMesh (profiles/smooth_timing.json,
+// "gpu_backed_pass_loses_up_to_vertices": 10000 at 512^3 and 10 iterations -- 5.9 ms against 4.8 ms; the next prefix, 30000,
+// wins with 6.5 ms against 15.9 ms).
+constexpr size_t kSmoothHostBelowVertices = 10000;
+
+// --smooth of the programs: the GPU pass from the crossover up, the host pass below it, or always with
+// TSDF_HIP_HOST_MESH_POST=1 (A/B runs, tools/time_smooth.py).  The result does not depend on the choice.
+inline int smoothMeshAuto(pcl::PolygonMesh &mesh, int iterations, float lambda = 0.5f, float mu = -0.53f, bool keep_boundary = true,
+                          std::string *error = nullptr) {
+  const char *host = std::getenv("TSDF_HIP_HOST_MESH_POST");
+  if ((host && host[0] == '1') || (size_t)mesh.cloud.width * mesh.cloud.height <= kSmoothHostBelowVertices)
+    return smoothMesh(mesh, iterations, lambda, mu, keep_boundary, error);
+  return smoothMeshGpu(mesh, iterations, lambda, mu, keep_boundary, 0, error);
+}
+
+// --smooth of the programs, applied last.  still_soup: neither --flatten nor --decimate has run, so no two faces share a vertex
+// yet: flattenVerticesAuto at its default distance comes first.  0, or the error code with its text in *error.
+inline int smoothProgramMesh(pcl::PolygonMesh &mesh, bool still_soup, int iterations, float lambda, float mu, std::string *error) {
+  if (still_soup)
+    if (const int rc = flattenVerticesAuto(mesh)) {
+      if (error) *error = tsdf_hip_last_error();
+      return rc;
+    }
+  return smoothMeshAuto(mesh, iterations, lambda, mu, true, error);
 }
 
 }  // namespace mesh_post

@@ -3,6 +3,8 @@
 // runs marching cubes on the GPU with the class defaults (min weight 2.5, no colour) and writes a binary PLY.
 // An extension: `tsdf2mesh foo.vol foo.ply --decimate <cell size in metres>` decimates the mesh by vertex clustering before
 // it is written (cpu_tsdf::mesh_post::decimateMeshAuto); without the option the output is what it was.
+// Likewise `--smooth <iterations> [--smooth-lambda L] [--smooth-mu M]`: Taubin's lambda | mu smoothing (defaults 0.5 and -0.53),
+// applied last; a mesh that no --decimate has indexed is flattened first (cpu_tsdf::mesh_post::smoothProgramMesh).
 // Another: `tsdf2mesh foo.vol foo.ply --merge bar.vol [--merge baz.vol ...]` loads every further volume and merges it into the
 // first by the global transforms the files carry (TSDFVolumeOctree::mergeVolume), in the order given, before meshing.
 // And: `tsdf2mesh foo.vol foo.ply --esdf foo.npy [--esdf-radius N]` also writes the Euclidean distance field of the whole grid
@@ -25,12 +27,15 @@
 
 int main(int argc, char **argv) {
   if (argc < 3) {
-    PCL_INFO("Renders a mesh from a TSDF volume saved with TSDFVolumeOctree::save.\nUsage: %s foo.vol foo.ply [--merge other.vol]... [--decimate <cell size in metres>] [--esdf field.npy [--esdf-radius <voxels>]]\n",
+    PCL_INFO("Renders a mesh from a TSDF volume saved with TSDFVolumeOctree::save.\nUsage: %s foo.vol foo.ply [--merge other.vol]... [--decimate <cell size in metres>] [--smooth <iterations> [--smooth-lambda L] [--smooth-mu M]] [--esdf field.npy [--esdf-radius <voxels>]]\n",
              argv[0]);
     return 1;
   }
   bool decimate_on = false;
   float decimate = 0.f;
+  bool smooth_on = false;
+  int smooth = 0;
+  float smooth_lambda = 0.5f, smooth_mu = -0.53f;
   std::vector<std::string> merge;
   std::string esdf;
   int esdf_radius = 0;
@@ -44,6 +49,13 @@ int main(int argc, char **argv) {
     } else if (!strcmp(argv[i], "--decimate") && i + 1 < argc) {
       decimate_on = true;
       decimate = (float)atof(argv[++i]);
+    } else if (!strcmp(argv[i], "--smooth") && i + 1 < argc) {
+      smooth_on = true;
+      smooth = atoi(argv[++i]);
+    } else if (!strcmp(argv[i], "--smooth-lambda") && i + 1 < argc) {
+      smooth_lambda = (float)atof(argv[++i]);
+    } else if (!strcmp(argv[i], "--smooth-mu") && i + 1 < argc) {
+      smooth_mu = (float)atof(argv[++i]);
     } else {
       PCL_ERROR("unknown option %s\n", argv[i]);
       return 1;
@@ -84,6 +96,13 @@ int main(int argc, char **argv) {
     std::string why;
     if (const int rc = cpu_tsdf::mesh_post::decimateMeshAuto(mesh, decimate, &why)) {
       PCL_ERROR("--decimate: %s: %s\n", tsdf_hip_error_string(rc), why.c_str());
+      return 1;
+    }
+  }
+  if (smooth_on) {
+    std::string why;
+    if (const int rc = cpu_tsdf::mesh_post::smoothProgramMesh(mesh, !decimate_on, smooth, smooth_lambda, smooth_mu, &why)) {
+      PCL_ERROR("--smooth: %s: %s\n", tsdf_hip_error_string(rc), why.c_str());
       return 1;
     }
   }

@@ -2,7 +2,8 @@
 // tsdf_decimate.hip (decimateMesh) -- share.  Declared here and defined in tsdf_meshgrid.hip: the cell table (the uniform grid
 // of cpu_tsdf::mesh_post::PointGrid, csrc/prog/mesh_post.h, over points sorted by the host's cell key), the working set of a
 // pass, a handle-less call with its copies of caller memory (pinned: direct; pageable: staged), and the indexed mesh of a
-// handle.  Defined here, because the passes' own kernels inline or instantiate them: mp_cell_key, mp_for_links (the host's
+// handle.  tsdf_smooth.hip (smoothMesh), which moves the vertices of that indexed mesh, uses the working set, the call and
+// the staging too.  Defined here, because the passes' own kernels inline or instantiate them: mp_cell_key, mp_for_links (the host's
 // forNeighbours), mp_face_remap and k_mp_compact.
 #pragma once
 

@@ -807,6 +807,7 @@ class MarchingCubesTSDFOctree:
         self._cleanup = None
         self._flatten = None
         self._decimate = None
+        self._smooth = None
 
     def setCleanup(self, face_dist=0.02, min_neighbors=5):
         """Extension (no reference counterpart on the class): reconstruct() drops the faces in connected groups of at most
@@ -852,6 +853,20 @@ class MarchingCubesTSDFOctree:
     def clearDecimate(self):
         self._decimate = None
 
+    def setSmooth(self, iterations, lam=0.5, mu=-0.53, keep_boundary=True):
+        """Extension (no reference counterpart): reconstruct() smooths the INDEXED mesh last -- Taubin's lambda | mu:
+        `iterations` times a step with `lam` and, iff mu != 0, a step with `mu`; keep_boundary fixes the endpoints of boundary
+        edges (tsdf_hip_march_smooth; include/tsdf_hip.h states the rules).  It acts in the VOLUME frame, before the global
+        transform, and moves the vertices only.  With neither setFlatten nor setDecimate, flatten runs first at its default
+        min_dist: a soup has no shared vertices to smooth over."""
+        iterations, lam, mu = int(iterations), float(lam), float(mu)
+        if not (np.isfinite(lam) and 0 < lam <= 1) or not (np.isfinite(mu) and -1 <= mu <= 0) or not 0 <= iterations <= 1000:
+            raise ValueError("setSmooth: lam must be in (0, 1], mu in [-1, 0], iterations in [0, 1000]")
+        self._smooth = (iterations, lam, mu, bool(keep_boundary))
+
+    def clearSmooth(self):
+        self._smooth = None
+
     def setInputTSDF(self, volume):
         self._vol = volume
 
@@ -867,7 +882,8 @@ class MarchingCubesTSDFOctree:
     def reconstruct(self, want_cells=False):
         """marching_cubes_tsdf_octree.cpp:108-143.  Returns dict(vertices (3n,3) float32 after the global
         transform, polygons (n,3) int32 = [3i,3i+1,3i+2], rgb (3n,3) uint8 or None, cells).  With setFlatten: the indexed
-        mesh -- vertices (m,3), polygons (k,3) int32 into them, rgb (m,3) or None, cells (k,); with setDecimate likewise."""
+        mesh -- vertices (m,3), polygons (k,3) int32 into them, rgb (m,3) or None, cells (k,); with setDecimate and with
+        setSmooth likewise."""
         vol = self._vol
         vol._cubic_for_queries("MarchingCubesTSDFOctree.reconstruct")
         h = vol._need()
@@ -877,7 +893,7 @@ class MarchingCubesTSDFOctree:
         capi.check(lib.tsdf_hip_march(h, self._w_min, mode, C.byref(n)), "march")
         if self._cleanup is not None:
             capi.check(lib.tsdf_hip_march_cleanup(h, self._cleanup[0], self._cleanup[1], C.byref(n)), "march_cleanup")
-        if self._decimate is not None or self._flatten is not None:
+        if self._decimate is not None or self._flatten is not None or self._smooth is not None:
             return self._fetch_indexed(vol, h, mode, want_cells)
         nt = int(n.value)
         verts = np.empty((nt * 3, 3), dtype=np.float32)
@@ -900,7 +916,10 @@ class MarchingCubesTSDFOctree:
         if self._decimate is not None:
             capi.check(lib.tsdf_hip_march_decimate(h, self._decimate, C.byref(m), C.byref(k)), "march_decimate")
         else:
-            capi.check(lib.tsdf_hip_march_flatten(h, self._flatten, C.byref(m), C.byref(k)), "march_flatten")
+            capi.check(lib.tsdf_hip_march_flatten(h, 0.0001 if self._flatten is None else self._flatten, C.byref(m), C.byref(k)), "march_flatten")
+        if self._smooth is not None:
+            it, lam, mu, keep = self._smooth
+            capi.check(lib.tsdf_hip_march_smooth(h, lam, mu, it, 1 if keep else 0, None), "march_smooth")
         m, k = int(m.value), int(k.value)
         verts = np.empty((m, 3), dtype=np.float32)
         rgb = np.empty((m, 3), dtype=np.uint8) if mode else None
@@ -994,6 +1013,27 @@ def decimate_mesh(vertices, polygons=None, colors=None, cell_size=None, device=0
     m, k = int(m.value), int(k.value)
     return {"vertices": out_verts[:m].copy(), "polygons": out_faces[:k].astype(np.int32), "rgb": out_rgb[:m].copy() if out_rgb is not None else None,
             "remap": remap, "counts": counts[:m].copy()}
+
+
+def smooth_mesh(vertices, polygons, lam=0.5, mu=-0.53, iterations=10, keep_boundary=True, device=0):
+    """Taubin's lambda | mu smoothing of an indexed mesh on the GPU (tsdf_hip_mesh_smooth; include/tsdf_hip.h states the
+    rules): `iterations` times a step with `lam` and, iff mu != 0, a step with `mu`, over the neighbours the faces define.
+    vertices (n, 3) float32; polygons (k, 3) vertex indices -- required: a triangle soup shares no vertices, flatten or
+    decimate it first.  Returns dict(vertices (n, 3) float32, fixed (n,) uint8: 1 = not finite or next to such a vertex, 2 = in
+    no face, 4 = on a boundary edge with keep_boundary, degree (n,) uint32: neighbours of each vertex)."""
+    if polygons is None:
+        raise ValueError("smooth_mesh: polygons are required (a triangle soup shares no vertices: flatten or decimate first)")
+    verts = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    faces = np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
+    out = np.zeros_like(verts)
+    fixed = np.zeros(len(verts), dtype=np.uint8)
+    degree = np.zeros(len(verts), dtype=np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    capi.check(
+        capi.load().tsdf_hip_mesh_smooth(int(device), capi.as_f32p(verts), len(verts), faces.ctypes.data_as(u32p), len(faces), float(lam), float(mu),
+                                         int(iterations), 1 if keep_boundary else 0, capi.as_f32p(out), capi.as_u8p(fixed),
+                                         degree.ctypes.data_as(u32p)), "mesh_smooth")
+    return {"vertices": out, "fixed": fixed, "degree": degree}
 
 
 def reference_cull_planes(p, trans):

@@ -19,7 +19,7 @@ class MarchingCubesTSDFOctree : public pcl::MarchingCubes<pcl::PointXYZ> {
  public:
   MarchingCubesTSDFOctree()
       : pcl::MarchingCubes<pcl::PointXYZ>(), color_by_confidence_(false), color_by_rgb_(false), w_min_(2.5f) {}
-  ~MarchingCubesTSDFOctree() override;  // forgets the object's setCleanup / setFlatten / setDecimate (see there)
+  ~MarchingCubesTSDFOctree() override;  // forgets the object's setCleanup / setFlatten / setDecimate / setSmooth (see there)
 
   // Mirrors the reference (:44-83): remembers the volume and dresses the base class the same way -- grid resolution,
   // the 8-corner "input cloud", no grid extension, iso level 0, bounding box and size_voxel_.
@@ -52,6 +52,13 @@ class MarchingCubesTSDFOctree : public pcl::MarchingCubes<pcl::PointXYZ> {
   // would.  The argument lives in the shell library next to setFlatten's: the class keeps its size.
   void setDecimate(float cell_size);
   void clearDecimate();
+  // Extension likewise: reconstruct smooths the INDEXED mesh LAST -- Taubin's lambda | mu, `iterations` times a step with
+  // lambda and, iff mu != 0, a step with mu; keep_boundary fixes the endpoints of boundary edges (tsdf_hip_march_smooth;
+  // include/tsdf_hip.h states the rules) -- in the VOLUME frame, before the global transform.  Only the vertices move.  With
+  // neither setFlatten nor setDecimate, flatten runs first at its default min_dist: a soup has no shared vertices to smooth
+  // over.  The arguments live in the shell library next to setDecimate's: the class keeps its size.
+  void setSmooth(int iterations, float lambda = 0.5f, float mu = -0.53f, bool keep_boundary = true);
+  void clearSmooth();
 
   using pcl::MarchingCubes<pcl::PointXYZ>::reconstruct;  // reconstruct(PolygonMesh&), reconstruct(points, polygons)
 

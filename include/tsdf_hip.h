@@ -589,6 +589,52 @@ int tsdf_hip_march_decimate(tsdf_handle h, float cell_size, uint64_t *n_verts, u
  * inside, the transfers of the host-array entry point do not). */
 int tsdf_hip_mesh_decimate_stats(uint64_t out[4]);
 
+/* smoothMesh -- Taubin's lambda | mu smoothing of an INDEXED mesh (umbrella operator, uniform weights, Jacobi steps); an
+ * extension with no counterpart in the reference.  The vertices move, nothing else changes.  The result is defined by the
+ * sequential host pass cpu_tsdf::mesh_post::smoothArrays (csrc/prog/mesh_post.h) and equals it bit for bit:
+ *   1. N(i), the neighbours of vertex i, are the j != i such that some face has both i and j among its corners, in ascending
+ *      index; deg(i) = |N(i)|.  A degenerate face (a, a, b) still contributes a-b; duplicate faces contribute once.
+ *   2. the multiplicity of the undirected edge {a, b}, a != b, is the number of corner pairs (0,1), (1,2), (2,0) of all faces
+ *      that name it.  A BOUNDARY edge has multiplicity exactly 1 (a face given twice: 2, three faces on one edge: 3 -- neither
+ *      is boundary).
+ *   3. fixed[i], decided once from the input positions, is the OR of 1: a component of vertex i or of one of its neighbours
+ *      is not finite; 2: deg(i) == 0; 4: keep_boundary != 0 and i is an endpoint of a boundary edge.  A vertex with
+ *      fixed[i] != 0 keeps its three words bit for bit through every step (NaN payloads and -0.0 survive).
+ *   4. one step with factor f (the float widened to double): every vertex reads the positions of the step before.  Per
+ *      component of a vertex that is not fixed: a double sum starting at +0.0 takes (double)x_j one add at a time over N(i)
+ *      in ascending index, m = s / (double)deg(i), p = (double)x_i, x'_i = (float)(p + f * (m - p)) -- the subtraction, the
+ *      product, the sum and the cast each rounded once, no FMA.
+ *   5. one iteration is a step with lambda and then, iff mu != 0, a step with mu.  iterations == 0 returns the input.
+ *   verts, faces   HOST arrays (pinned memory is used directly, pageable memory is staged): n_verts x 3 floats, n_faces x 3
+ *                  vertex indices.  faces is required: a triangle soup shares no vertices -- flatten or decimate first.
+ *   out_verts      n_verts x 3 floats; may be `verts` itself.
+ *   fixed, degree  n_verts entries each: rule 3's bits and deg(i); each nullable.
+ * E_INVALID: lambda not finite or outside (0, 1], mu not finite or outside [-1, 0], iterations outside [0, 1000], more than
+ * 2^31 vertices or faces (and more than 715827882 faces: the 6 directed edge entries per face are indexed with 32 bits), NULL
+ * verts, out_verts or faces, device < 0, a face naming a vertex >= n_verts (nothing is written then).  All of these but the
+ * last are checked before any device call.  n_verts == 0 (with no face) is OK and touches no device.  E_NOMEM, with the bytes
+ * in tsdf_hip_last_error, when the mesh or the working set (41 n_verts + 102 n_faces bytes and the sort's temporary storage)
+ * does not fit.  (Positions that overflow to infinity in a later step are not fixed: what follows from them is NaN, whose
+ * sign and payload are the arithmetic unit's.)
+ * Cost: one radix sort of the 6 n_faces directed edge keys builds the neighbour table, once.  Then 1 or 2 kernel launches per
+ * iteration, all queued without a host read in between, in which ONE lane walks each vertex's neighbour list so that the
+ * adds keep the host's order.  A marched mesh has degree 4-8; a vertex with thousands of neighbours makes one lane walk
+ * them all, twice per iteration. */
+int tsdf_hip_mesh_smooth(int device, const float *verts, uint64_t n_verts, const uint32_t *faces, uint64_t n_faces,
+                         float lambda, float mu, int iterations, int keep_boundary, float *out_verts /* may be verts */,
+                         uint8_t *fixed /* nullable */, uint32_t *degree /* nullable */);
+/* The same, in place, on the handle's INDEXED mesh: the one the last tsdf_hip_march_flatten or tsdf_hip_march_decimate made.
+ * tsdf_hip_march_fetch_indexed then returns the moved vertices; rgb, faces and cell are unchanged, and the soup STAYS.  A
+ * second call smooths further.  *n_fixed (nullable): the vertices rule 3 fixed.  E_INVALID while there is no valid indexed
+ * mesh (the rules are those documented for flatten: a later tsdf_hip_march or tsdf_hip_march_cleanup invalidates it), and
+ * for the arguments as above.  On a multi-GPU handle the host-held merged mesh goes through tsdf_hip_mesh_smooth on the
+ * first slab's device; the result equals one handle holding the whole grid. */
+int tsdf_hip_march_smooth(tsdf_handle h, float lambda, float mu, int iterations, int keep_boundary, uint64_t *n_fixed /* nullable */);
+/* Report-only, of the last smooth (either entry point) on the calling thread: out[0] = vertices, out[1] = unique undirected
+ * edges, out[2] = fixed vertices, out[3] = device microseconds from the first kernel to the last (HIP events on the stream;
+ * no host read falls inside, nor do the transfers of the host-array entry point). */
+int tsdf_hip_mesh_smooth_stats(uint64_t out[4]);
+
 /* getOccupiedVoxelIndices -- src/lib/tsdf_volume_octree.cpp:590-609 (+ OctreeNode::getLeaves, src/lib/octree.cpp:99-109):
  * the voxels with w > 0 && fabsf(d) < 1, d and w being the floats tsdf_hip_download returns (PACKED layout:
  * w = min(k, max_weight); a NaN distance is not listed), in the reference's leaf order: ascending key
