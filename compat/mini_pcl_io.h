@@ -229,6 +229,8 @@ namespace detail {
 struct MeshLayout {
   int x = -1, y = -1, z = -1, rgb = -1;
   bool alpha = false;
+  int normal[3] = {-1, -1, -1};  // FLOAT32 fields normal_x, normal_y, normal_z (mesh_post::meshNormals appends them)
+  bool normals() const { return normal[0] >= 0 && normal[1] >= 0 && normal[2] >= 0; }
 };
 inline MeshLayout mesh_layout(const PolygonMesh &m) {
   MeshLayout l;
@@ -240,6 +242,8 @@ inline MeshLayout mesh_layout(const PolygonMesh &m) {
       l.rgb = (int)fd.offset;
       l.alpha = fd.name == "rgba";
     }
+    for (int k = 0; k < 3; ++k)
+      if (fd.name == std::string("normal_") + "xyz"[k] && fd.datatype == PCLPointField::FLOAT32) l.normal[k] = (int)fd.offset;
   }
   return l;
 }
@@ -254,6 +258,7 @@ inline int save_ply(const std::string &file, const PolygonMesh &mesh, bool binar
     f << "property uchar red\nproperty uchar green\nproperty uchar blue\n";
     if (l.alpha) f << "property uchar alpha\n";
   }
+  if (l.normals()) f << "property float nx\nproperty float ny\nproperty float nz\n";
   f << "element face " << mesh.polygons.size() << "\nproperty list uchar int vertex_indices\nend_header\n";
   if (!binary) f << std::setprecision((int)precision);
   for (size_t i = 0; i < nv; ++i) {
@@ -264,18 +269,23 @@ inline int save_ply(const std::string &file, const PolygonMesh &mesh, bool binar
     if (l.z >= 0) std::memcpy(&xyz[2], p + l.z, 4);
     unsigned char c[4] = {0, 0, 0, 0};  // memory order b, g, r, a
     if (l.rgb >= 0) std::memcpy(c, p + l.rgb, 4);
+    float nrm[3] = {0, 0, 0};
+    if (l.normals())
+      for (int k = 0; k < 3; ++k) std::memcpy(&nrm[k], p + l.normal[k], 4);
     if (binary) {
       f.write((const char *)xyz, 12);
       if (l.rgb >= 0) {
         const unsigned char rgb[4] = {c[2], c[1], c[0], c[3]};
         f.write((const char *)rgb, l.alpha ? 4 : 3);
       }
+      if (l.normals()) f.write((const char *)nrm, 12);
     } else {
       f << xyz[0] << " " << xyz[1] << " " << xyz[2];
       if (l.rgb >= 0) {
         f << " " << (int)c[2] << " " << (int)c[1] << " " << (int)c[0];
         if (l.alpha) f << " " << (int)c[3];
       }
+      if (l.normals()) f << " " << nrm[0] << " " << nrm[1] << " " << nrm[2];
       f << "\n";
     }
   }

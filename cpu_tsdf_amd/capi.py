@@ -146,6 +146,10 @@ SIGNATURES = {
     "tsdf_hip_mesh_smooth": (C.c_int, [C.c_int, _f32p, C.c_uint64, _u32p, C.c_uint64, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, _u8p, _u32p]),
     "tsdf_hip_march_smooth": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, _u64p]),
     "tsdf_hip_mesh_smooth_stats": (C.c_int, [_u64p]),
+    "tsdf_hip_mesh_normals": (C.c_int, [C.c_int, _f32p, C.c_uint64, _u32p, C.c_uint64, _f32p, _u8p]),
+    "tsdf_hip_march_normals": (C.c_int, [C.c_void_p, _u64p, _u64p]),
+    "tsdf_hip_march_fetch_normals": (C.c_int, [C.c_void_p, _f32p]),
+    "tsdf_hip_mesh_normals_stats": (C.c_int, [_u64p]),
     "tsdf_hip_occupied": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), _u64p]),
     "tsdf_hip_occupied_fetch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), _f32p, _f32p, _u8p]),
     "tsdf_hip_occupied_fetch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -9,8 +9,11 @@
 #include <pcl/console/print.h>
 #include <pcl/conversions.h>
 
+#include <cstring>
 #include <map>
 #include <mutex>
+#include <set>
+#include <string>
 #include <vector>
 
 namespace cpu_tsdf {
@@ -105,11 +108,28 @@ void MarchingCubesTSDFOctree::clearSmooth() {
   g_smooth.erase(this);
 }
 
+// setNormals' argument per object, kept likewise: the objects that asked for normals
+static std::set<const MarchingCubesTSDFOctree *> g_normals;
+
+void MarchingCubesTSDFOctree::setNormals(bool on) {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  if (on)
+    g_normals.insert(this);
+  else
+    g_normals.erase(this);
+}
+
+static bool normals_of(const MarchingCubesTSDFOctree *mc) {
+  std::lock_guard<std::mutex> lock(g_cleanup_mutex);
+  return g_normals.count(mc) != 0;
+}
+
 MarchingCubesTSDFOctree::~MarchingCubesTSDFOctree() {
   clearCleanup();
   clearFlatten();
   clearDecimate();
   clearSmooth();
+  setNormals(false);
 }
 
 static bool smooth_of(const MarchingCubesTSDFOctree *mc, SmoothArgs &out) {
@@ -149,13 +169,15 @@ static bool cleanup_of(const MarchingCubesTSDFOctree *mc, CleanupArgs &out) {
 // `faces` holds its polygons (otherwise the soup: polygon i = {3i, 3i + 1, 3i + 2}).  decimate: NULL, or setDecimate's
 // cell_size -- tsdf_hip_march_decimate in flatten's place (with both set, flatten is skipped), fetched the same way.  smooth:
 // NULL, or the arguments of setSmooth -- tsdf_hip_march_smooth last, on the indexed mesh; with neither flatten nor decimate,
-// flatten runs first at its default min_dist.
+// flatten runs first at its default min_dist.  normals: NULL, or where setNormals' normals go -- tsdf_hip_march_normals last of
+// all, on the mesh that is fetched (the indexed one, or the soup), one row per vertex.
 static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mode, const CleanupArgs *cleanup, const float *flatten, const float *decimate,
-                      const SmoothArgs *smooth, std::vector<float> &verts, std::vector<unsigned char> &rgb, std::vector<uint32_t> &faces, bool &indexed) {
+                      const SmoothArgs *smooth, std::vector<float> *normals, std::vector<float> &verts, std::vector<unsigned char> &rgb, std::vector<uint32_t> &faces, bool &indexed) {
   verts.clear();
   rgb.clear();
   faces.clear();
   indexed = false;
+  if (normals) normals->clear();
   if (!vol || !vol->handle()) {
     PCL_ERROR("[cpu_tsdf::MarchingCubesTSDFOctree::reconstruct] no TSDF volume set (or reset() not called)\n");
     return false;
@@ -182,6 +204,17 @@ static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mo
     if (mode) rgb.resize((size_t)n_tri * 9);
     rc = tsdf_hip_march_fetch(vol->handle(), verts.data(), mode ? rgb.data() : nullptr, nullptr);
   }
+  if (rc == 0 && normals) {
+    uint64_t n_verts = 0;
+    rc = tsdf_hip_march_normals(vol->handle(), &n_verts, nullptr);
+    if (rc == 0 && n_verts * 3 != verts.size()) {
+      PCL_ERROR("[cpu_tsdf::MarchingCubesTSDFOctree::reconstruct] the normals describe %llu vertices, the mesh has %llu\n",
+                (unsigned long long)n_verts, (unsigned long long)(verts.size() / 3));
+      rc = TSDF_HIP_E_INVALID;
+    }
+    normals->resize(verts.size());
+    if (rc == 0 && n_verts) rc = tsdf_hip_march_fetch_normals(vol->handle(), normals->data());
+  }
   if (rc) {
     PCL_ERROR("[cpu_tsdf::MarchingCubesTSDFOctree::reconstruct] %s: %s\n", tsdf_hip_error_string(rc),
               tsdf_hip_last_error());
@@ -189,6 +222,7 @@ static bool run_march(const TSDFVolumeOctree::ConstPtr &vol, float w_min, int mo
     rgb.clear();
     faces.clear();
     indexed = false;
+    if (normals) normals->clear();
     return false;
   }
   return true;
@@ -204,6 +238,38 @@ static void fill_polygons(size_t n_vertices, bool indexed, const std::vector<uin
   }
 }
 
+// setNormals: three FLOAT32 fields normal_x, normal_y, normal_z appended to the blob, after the fields it has.  The normals are
+// those of the mesh in the VOLUME frame (tsdf_hip_march_normals) word for word while the global transform's linear part is the
+// identity; otherwise they are turned by it like the vertices (a rotation: the global transform is rigid).
+static void append_normals(const std::vector<float> &normals, const Eigen::Affine3d &g, pcl::PCLPointCloud2 &cloud) {
+  const size_t n = normals.size() / 3, step = cloud.point_step, wide = step + 12;
+  const Eigen::Matrix4d m = g.matrix();
+  bool identity = true;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) identity = identity && m(r, c) == (r == c ? 1.0 : 0.0);
+  std::vector<std::uint8_t> data(n * wide);
+  for (size_t i = 0; i < n; ++i) {
+    std::memcpy(data.data() + i * wide, cloud.data.data() + i * step, step);
+    float v[3] = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
+    if (!identity) {
+      const double x = v[0], y = v[1], z = v[2];
+      for (int r = 0; r < 3; ++r) v[r] = static_cast<float>(x * m(r, 0) + (y * m(r, 1) + z * m(r, 2)));
+    }
+    std::memcpy(data.data() + i * wide + step, v, 12);
+  }
+  cloud.data.swap(data);
+  for (int k = 0; k < 3; ++k) {
+    pcl::PCLPointField f;
+    f.name = std::string("normal_") + "xyz"[k];
+    f.offset = (uint32_t)(step + 4 * k);
+    f.datatype = pcl::PCLPointField::FLOAT32;
+    f.count = 1;
+    cloud.fields.push_back(f);
+  }
+  cloud.point_step = (uint32_t)wide;
+  cloud.row_step = (uint32_t)(wide * cloud.width);
+}
+
 void MarchingCubesTSDFOctree::performReconstruction(pcl::PolygonMesh &output) {
   output.polygons.clear();
   // color_by_confidence_ wins over color_by_rgb_ (marching_cubes_tsdf_octree.cpp:215-231)
@@ -215,8 +281,11 @@ void MarchingCubesTSDFOctree::performReconstruction(pcl::PolygonMesh &output) {
   CleanupArgs cleanup;
   SmoothArgs smooth;
   float flatten = 0.f, decimate = 0.f;
-  run_march(tsdf_volume_, w_min_, mode, cleanup_of(this, cleanup) ? &cleanup : nullptr, flatten_of(this, flatten) ? &flatten : nullptr,
-            decimate_of(this, decimate) ? &decimate : nullptr, smooth_of(this, smooth) ? &smooth : nullptr, verts, rgb, faces, indexed);
+  std::vector<float> normals;
+  const bool want_normals = normals_of(this);
+  const bool ok = run_march(tsdf_volume_, w_min_, mode, cleanup_of(this, cleanup) ? &cleanup : nullptr, flatten_of(this, flatten) ? &flatten : nullptr,
+                            decimate_of(this, decimate) ? &decimate : nullptr, smooth_of(this, smooth) ? &smooth : nullptr,
+                            want_normals ? &normals : nullptr, verts, rgb, faces, indexed);
   const size_t n = verts.size() / 3;
   const Eigen::Affine3d g = tsdf_volume_ ? tsdf_volume_->getGlobalTransform() : Eigen::Affine3d::Identity();
   if (mode) {
@@ -250,6 +319,7 @@ void MarchingCubesTSDFOctree::performReconstruction(pcl::PolygonMesh &output) {
     pcl::toPCLPointCloud2(cloud, output.cloud);
   }
   fill_polygons(n, indexed, faces, output.polygons);
+  if (want_normals && ok) append_normals(normals, g, output.cloud);
 }
 
 void MarchingCubesTSDFOctree::performReconstruction(pcl::PointCloud<pcl::PointXYZ> &points,
@@ -262,7 +332,7 @@ void MarchingCubesTSDFOctree::performReconstruction(pcl::PointCloud<pcl::PointXY
   SmoothArgs smooth;
   float flatten = 0.f, decimate = 0.f;
   run_march(tsdf_volume_, w_min_, 0, cleanup_of(this, cleanup) ? &cleanup : nullptr, flatten_of(this, flatten) ? &flatten : nullptr,
-            decimate_of(this, decimate) ? &decimate : nullptr, smooth_of(this, smooth) ? &smooth : nullptr, verts, rgb, faces, indexed);
+            decimate_of(this, decimate) ? &decimate : nullptr, smooth_of(this, smooth) ? &smooth : nullptr, nullptr, verts, rgb, faces, indexed);
   const size_t n = verts.size() / 3;
   points.points.resize(n);
   points.width = (uint32_t)n;

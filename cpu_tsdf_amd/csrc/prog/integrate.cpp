@@ -16,6 +16,8 @@
 //   --decimate <cell size in metres> (an extension): vertex clustering, after --flatten and --cleanup
 //   --smooth <iterations> [--smooth-lambda L] [--smooth-mu M] (an extension): Taubin's lambda | mu smoothing, applied last; a
 //     mesh that neither --flatten nor --decimate has indexed is flattened first
+//   --normals (an extension): area-weighted vertex normals of the final mesh, computed from it after --smooth -- on a soup as
+//     well -- and written as the PLY properties nx, ny, nz
 // Not reproduced: --visualize (PCLVisualizer) and the reference's PCL_INFO chatter.  --cloud-only works but
 // its VoxelGrid thinning needs real PCL.
 #include <cpu_tsdf/marching_cubes_tsdf_octree.h>
@@ -52,7 +54,7 @@ struct Settings {
   float cloud_units = 1.f, pose_units = 1.f, max_sensor_dist = 3.0f, min_sensor_dist = 0.f, min_weight = 0.f,
         trunc_pos = 0.03f, trunc_neg = 0.03f, volume_size = 12.f, cell_size = 0.006f, max_cell_size = 0.5f,
         decimate = 0.f, smooth_lambda = 0.5f, smooth_mu = -0.53f;
-  bool decimate_on = false, smooth_on = false;
+  bool decimate_on = false, smooth_on = false, normals_on = false;
   int smooth = 0;
   int width = 640, height = 480, num_random_splits = 1;
   float fx = 525.f, fy = 525.f, cx = 319.5f, cy = 239.5f;
@@ -90,7 +92,8 @@ int parseCommandLine(int argc, char **argv, Settings &s) {
       "decimate", bpo::value<float>(), "Decimate the mesh by vertex clustering: cell size in metres (after flatten and cleanup)")(
       "smooth", bpo::value<int>(), "Smooth the mesh (Taubin): iterations (applied last)")(
       "smooth-lambda", bpo::value<float>(), "Smoothing factor of the first step of an iteration (default 0.5)")(
-      "smooth-mu", bpo::value<float>(), "Factor of the second step, <= 0; 0 = plain Laplacian smoothing (default -0.53)");
+      "smooth-mu", bpo::value<float>(), "Factor of the second step, <= 0; 0 = plain Laplacian smoothing (default -0.53)")(
+      "normals", "Write area-weighted vertex normals (nx ny nz) of the final mesh (applied last, after smooth)");
   bpo::variables_map vm;
   bpo::store(bpo::parse_command_line(argc, argv, d, bpo::command_line_style::unix_style ^ bpo::command_line_style::allow_short), vm);
   bool bad = false;
@@ -121,6 +124,7 @@ int parseCommandLine(int argc, char **argv, Settings &s) {
   s.color = vm.count("color");
   s.decimate_on = vm.count("decimate");
   take(vm, "decimate", s.decimate);
+  s.normals_on = vm.count("normals");
   s.smooth_on = vm.count("smooth");
   take(vm, "smooth", s.smooth);
   take(vm, "smooth-lambda", s.smooth_lambda);
@@ -345,6 +349,13 @@ int main(int argc, char **argv) {
     std::string why;
     if (const int rc = cpu_tsdf::mesh_post::smoothProgramMesh(mesh, !s.flatten && !s.decimate_on, s.smooth, s.smooth_lambda, s.smooth_mu, &why)) {
       PCL_ERROR("--smooth: %s: %s\n", tsdf_hip_error_string(rc), why.c_str());
+      return 1;
+    }
+  }
+  if (s.normals_on) {  // an extension, last of all: on the GPU (tsdf_hip_mesh_normals); TSDF_HIP_HOST_MESH_POST=1 keeps the host pass
+    std::string why;
+    if (const int rc = cpu_tsdf::mesh_post::meshNormalsAuto(mesh, &why)) {
+      PCL_ERROR("--normals: %s: %s\n", tsdf_hip_error_string(rc), why.c_str());
       return 1;
     }
   }

@@ -21,6 +21,9 @@
 //   smoothMesh: Taubin's lambda | mu smoothing of an indexed mesh over the neighbours its faces define -- only the vertices
 //     move.  smoothArrays below states the rules; smoothMeshGpu gets the same vertices from the GPU (tsdf_hip_mesh_smooth);
 //     the host pass stays: it defines the result.
+//   meshNormals: area-weighted vertex normals of the final mesh, appended to the cloud as normal_x, normal_y, normal_z.
+//     normalArrays below states the rules; meshNormalsGpu gets the same normals from the GPU (tsdf_hip_mesh_normals); the host
+//     pass stays: it defines the result.
 #pragma once
 
 #include <pcl/PolygonMesh.h>
@@ -687,6 +690,181 @@ inline int smoothProgramMesh(pcl::PolygonMesh &mesh, bool still_soup, int iterat
       return rc;
     }
   return smoothMeshAuto(mesh, iterations, lambda, mu, true, error);
+}
+
+// ---- meshNormals: area-weighted vertex normals ---------------------------------------------------------------------------------
+struct Normals {
+  std::vector<float> normals;       // n x 3
+  std::vector<std::uint8_t> flags;  // n: rule 4's bits
+  std::uint64_t skipped = 0;        // faces with a coordinate that is not finite
+  std::uint64_t zero = 0;           // vertices whose normal is zero
+};
+
+// The definition, as one sequential pass over the faces in index order and one over the vertices.
+//   1. The face vector of f = (a, b, c): e1 = (double)p_b - (double)p_a, e2 = (double)p_c - (double)p_a componentwise,
+//      g_f = (e1y * e2z - e1z * e2y, e1z * e2x - e1x * e2z, e1x * e2y - e1y * e2x); every difference, product and subtraction is
+//      rounded once (the programs are built with -ffp-contract=off: a contracted fma(e1y, e2z, -(e1z * e2y)) would make the
+//      zero vector of a face with two corners at one position nonzero).  |g_f| is twice the area.  A face with a coordinate
+//      that is not finite at any corner is skipped: it adds nothing and is counted.
+//   2. Per component s_i = +0.0; over the faces that name i in ascending face index, s_i += g_f once per corner that names i.
+//      The order of the adds is part of the definition: the GPU pass performs exactly these.
+//   3. l2 = (sx * sx + sy * sy) + sz * sz, l = sqrt(l2); l2 == 0: three +0.0f; else ((float)(sx / l), (float)(sy / l),
+//      (float)(sz / l)), by division.
+//   4. flags[i] = 1 (no face names i) | 2 (rule 3 wrote zero) | 4 (a face that names i was skipped).
+//   5. Orientation: the normal points to the side from which a -> b -> c appear counter-clockwise, along
+//      (p_b - p_a) x (p_c - p_a); on a marched mesh that is out of the surface, into observed free space.
+// xyz n x 3, faces nf x 3 or NULL for a soup (n a multiple of 3, face f = vertices 3f, 3f + 1, 3f + 2, nf = n / 3 or 0).  0, or
+// TSDF_HIP_E_INVALID with the reason in *error and `out` untouched.
+inline int normalArrays(const float *xyz, size_t n, const std::uint32_t *faces, size_t nf, Normals &out, std::string *error = nullptr) {
+  const auto refuse = [&](const std::string &why) {
+    if (error) *error = why;
+    return (int)TSDF_HIP_E_INVALID;
+  };
+  if (n > ((size_t)1 << 31) || nf > (size_t)1431655765) return refuse("meshNormals: more than 2^31 vertices or 1431655765 faces");
+  if (n && !xyz) return refuse("meshNormals: verts must not be NULL");
+  if (!faces && (n % 3 || (nf && nf != n / 3)))
+    return refuse("meshNormals: a triangle soup has 3 vertices per face: n_verts must be a multiple of 3 and n_faces 0 or n_verts / 3");
+  if (faces)
+    for (size_t e = 0; e < 3 * nf; ++e)
+      if (faces[e] >= n) return refuse("meshNormals: a face names a vertex index >= n_verts");
+  Normals r;
+  r.normals.assign(3 * n, 0.f);
+  r.flags.assign(n, 0);
+  std::vector<double> s(3 * n, 0.0);
+  std::vector<char> named(n, 0);
+  for (size_t f = 0; f < nf; ++f) {
+    size_t v[3];
+    for (int k = 0; k < 3; ++k) v[k] = faces ? faces[3 * f + k] : 3 * f + k;
+    const float *a = xyz + 3 * v[0], *b = xyz + 3 * v[1], *c = xyz + 3 * v[2];
+    bool fin = true;
+    for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(a[k]) && std::isfinite(b[k]) && std::isfinite(c[k]);
+    double g[3] = {0.0, 0.0, 0.0};
+    if (fin) {
+      const double e1x = (double)b[0] - (double)a[0], e1y = (double)b[1] - (double)a[1], e1z = (double)b[2] - (double)a[2];
+      const double e2x = (double)c[0] - (double)a[0], e2y = (double)c[1] - (double)a[1], e2z = (double)c[2] - (double)a[2];
+      g[0] = e1y * e2z - e1z * e2y;
+      g[1] = e1z * e2x - e1x * e2z;
+      g[2] = e1x * e2y - e1y * e2x;
+    } else {
+      ++r.skipped;
+    }
+    for (int k = 0; k < 3; ++k) {
+      named[v[k]] = 1;
+      if (!fin) {
+        r.flags[v[k]] |= 4;
+        continue;
+      }
+      for (int j = 0; j < 3; ++j) s[3 * v[k] + j] += g[j];
+    }
+  }
+  for (size_t i = 0; i < n; ++i) {
+    const double sx = s[3 * i], sy = s[3 * i + 1], sz = s[3 * i + 2];
+    const double l2 = (sx * sx + sy * sy) + sz * sz;
+    if (!named[i]) r.flags[i] |= 1;
+    if (l2 == 0.0) {
+      r.flags[i] |= 2;
+      ++r.zero;
+      continue;
+    }
+    const double l = std::sqrt(l2);
+    r.normals[3 * i] = (float)(sx / l), r.normals[3 * i + 1] = (float)(sy / l), r.normals[3 * i + 2] = (float)(sz / l);
+  }
+  out = std::move(r);
+  return 0;
+}
+
+// the offsets of the FLOAT32 fields normal_x, normal_y, normal_z in the cloud blob; false: the cloud does not have all three
+inline bool normalOffsets(const pcl::PolygonMesh &mesh, std::uint32_t off[3]) {
+  int found = 0;
+  for (const auto &f : mesh.cloud.fields)
+    for (int k = 0; k < 3; ++k)
+      if (f.name == std::string("normal_") + "xyz"[k] && f.datatype == pcl::PCLPointField::FLOAT32) off[k] = f.offset, found |= 1 << k;
+  return found == 7;
+}
+
+// both normal passes on a PolygonMesh: the positions out of the blob, pass(xyz, faces or NULL for a soup, n_faces, out), and
+// three FLOAT32 fields normal_x, normal_y, normal_z APPENDED to the blob after the fields it has (rewritten if they are
+// there already); every other field and the polygons stay.  A mesh whose polygon f is (3f, 3f + 1, 3f + 2) throughout is
+// handed over as a soup: the result is the same and the GPU pass needs no sort.  A polygon that is not a triangle refuses
+// the mesh.
+template <typename Pass>
+inline int normalsBlob(pcl::PolygonMesh &mesh, std::string *error, Pass pass) {
+  std::vector<std::uint32_t> faces;
+  std::uint32_t off[3];
+  const size_t n = (size_t)mesh.cloud.width * mesh.cloud.height, step = mesh.cloud.point_step;
+  if (!triangleIndices(mesh, faces) || (n && !positionOffsets(mesh, off))) {
+    if (error) *error = "meshNormals: a polygon is not a triangle, or the cloud has no float x, y, z fields";
+    return (int)TSDF_HIP_E_INVALID;
+  }
+  const size_t nf = faces.size() / 3;
+  bool soup = nf && n == 3 * nf;
+  for (size_t e = 0; e < faces.size() && soup; ++e) soup = faces[e] == e;
+  std::vector<float> xyz(3 * n), out;
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < 3; ++k) std::memcpy(&xyz[3 * i + k], mesh.cloud.data.data() + i * step + off[k], 4);
+  static const std::uint32_t none[3] = {0, 0, 0};  // (an empty vector's data() may be NULL: a mesh without faces is no soup)
+  const int rc = pass(xyz, soup ? nullptr : (nf ? faces.data() : none), nf, out);
+  if (rc) return rc;
+  std::uint32_t at[3];
+  if (!normalOffsets(mesh, at)) {
+    const size_t wide = step + 12;
+    std::vector<std::uint8_t> data(n * wide);
+    for (size_t i = 0; i < n; ++i) std::memcpy(data.data() + i * wide, mesh.cloud.data.data() + i * step, step);
+    mesh.cloud.data.swap(data);
+    for (int k = 0; k < 3; ++k) {
+      pcl::PCLPointField f;
+      f.name = std::string("normal_") + "xyz"[k];
+      f.offset = at[k] = (std::uint32_t)(step + 4 * k);
+      f.datatype = pcl::PCLPointField::FLOAT32;
+      f.count = 1;
+      mesh.cloud.fields.push_back(f);
+    }
+    mesh.cloud.point_step = (std::uint32_t)wide;
+    mesh.cloud.row_step = (std::uint32_t)(wide * mesh.cloud.width);
+  }
+  const size_t now = mesh.cloud.point_step;
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < 3; ++k) std::memcpy(mesh.cloud.data.data() + i * now + at[k], &out[3 * i + k], 4);
+  return 0;
+}
+
+// The host pass on a PolygonMesh.  0, or TSDF_HIP_E_INVALID (the reason in *error) with the mesh untouched.
+inline int meshNormals(pcl::PolygonMesh &mesh, std::string *error = nullptr) {
+  return normalsBlob(mesh, error, [&](const std::vector<float> &xyz, const std::uint32_t *faces, size_t nf, std::vector<float> &out) {
+    Normals r;
+    const int rc = normalArrays(xyz.data(), xyz.size() / 3, faces, nf, r, error);
+    out.swap(r.normals);
+    return rc;
+  });
+}
+
+// The same result from the GPU (tsdf_hip_mesh_normals, which reproduces the pass above word for word).  0, or the library's
+// error code (its text in tsdf_hip_last_error, or in *error for what this function refuses itself) with the mesh untouched.
+inline int meshNormalsGpu(pcl::PolygonMesh &mesh, int device = 0, std::string *error = nullptr) {
+  bool own = false;  // the refusal is normalsBlob's own, not the library's
+  std::string why;
+  const int rc = normalsBlob(mesh, &why, [&](const std::vector<float> &xyz, const std::uint32_t *faces, size_t nf, std::vector<float> &out) {
+    own = true;
+    out.resize(xyz.size());
+    return tsdf_hip_mesh_normals(device, xyz.data(), xyz.size() / 3, faces, nf, out.data(), nullptr);
+  });
+  if (rc && error) *error = own ? std::string(tsdf_hip_last_error()) : why;
+  return rc;
+}
+
+// Vertices up to which --normals keeps the host pass: the largest prefix at which tools/time_normals.py measured the
+// GPU-backed pass (upload, device pass, download) slower than meshNormals (profiles/normals_timing.json,
+// "gpu_backed_pass_loses_up_to_vertices": 300000 at 512^3 -- 11.4 ms against 7.8 ms; the full mesh, 946378 vertices, wins with
+// 22.4 ms against 35.5 ms).  The host pass is one cheap loop: the device pass itself takes 0.5 ms there, and
+// the transfers and allocations around it decide.
+constexpr size_t kNormalsHostBelowVertices = 300000;
+
+// --normals of the programs: the GPU pass from the crossover up, the host pass below it, or always with
+// TSDF_HIP_HOST_MESH_POST=1 (A/B runs, tools/time_normals.py).  The result does not depend on the choice.
+inline int meshNormalsAuto(pcl::PolygonMesh &mesh, std::string *error = nullptr) {
+  const char *host = std::getenv("TSDF_HIP_HOST_MESH_POST");
+  if ((host && host[0] == '1') || (size_t)mesh.cloud.width * mesh.cloud.height <= kNormalsHostBelowVertices) return meshNormals(mesh, error);
+  return meshNormalsGpu(mesh, 0, error);
 }
 
 }  // namespace mesh_post

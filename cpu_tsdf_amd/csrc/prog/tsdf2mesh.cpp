@@ -5,6 +5,8 @@
 // it is written (cpu_tsdf::mesh_post::decimateMeshAuto); without the option the output is what it was.
 // Likewise `--smooth <iterations> [--smooth-lambda L] [--smooth-mu M]`: Taubin's lambda | mu smoothing (defaults 0.5 and -0.53),
 // applied last; a mesh that no --decimate has indexed is flattened first (cpu_tsdf::mesh_post::smoothProgramMesh).
+// And `--normals`: area-weighted vertex normals of the mesh that is written, computed from it last of all -- on the soup as well
+// (flat normals need no flatten) -- and written as the PLY properties nx, ny, nz (cpu_tsdf::mesh_post::meshNormalsAuto).
 // Another: `tsdf2mesh foo.vol foo.ply --merge bar.vol [--merge baz.vol ...]` loads every further volume and merges it into the
 // first by the global transforms the files carry (TSDFVolumeOctree::mergeVolume), in the order given, before meshing.
 // And: `tsdf2mesh foo.vol foo.ply --esdf foo.npy [--esdf-radius N]` also writes the Euclidean distance field of the whole grid
@@ -27,7 +29,7 @@
 
 int main(int argc, char **argv) {
   if (argc < 3) {
-    PCL_INFO("Renders a mesh from a TSDF volume saved with TSDFVolumeOctree::save.\nUsage: %s foo.vol foo.ply [--merge other.vol]... [--decimate <cell size in metres>] [--smooth <iterations> [--smooth-lambda L] [--smooth-mu M]] [--esdf field.npy [--esdf-radius <voxels>]]\n",
+    PCL_INFO("Renders a mesh from a TSDF volume saved with TSDFVolumeOctree::save.\nUsage: %s foo.vol foo.ply [--merge other.vol]... [--decimate <cell size in metres>] [--smooth <iterations> [--smooth-lambda L] [--smooth-mu M]] [--normals] [--esdf field.npy [--esdf-radius <voxels>]]\n",
              argv[0]);
     return 1;
   }
@@ -36,6 +38,7 @@ int main(int argc, char **argv) {
   bool smooth_on = false;
   int smooth = 0;
   float smooth_lambda = 0.5f, smooth_mu = -0.53f;
+  bool normals_on = false;
   std::vector<std::string> merge;
   std::string esdf;
   int esdf_radius = 0;
@@ -56,6 +59,8 @@ int main(int argc, char **argv) {
       smooth_lambda = (float)atof(argv[++i]);
     } else if (!strcmp(argv[i], "--smooth-mu") && i + 1 < argc) {
       smooth_mu = (float)atof(argv[++i]);
+    } else if (!strcmp(argv[i], "--normals")) {
+      normals_on = true;
     } else {
       PCL_ERROR("unknown option %s\n", argv[i]);
       return 1;
@@ -103,6 +108,13 @@ int main(int argc, char **argv) {
     std::string why;
     if (const int rc = cpu_tsdf::mesh_post::smoothProgramMesh(mesh, !decimate_on, smooth, smooth_lambda, smooth_mu, &why)) {
       PCL_ERROR("--smooth: %s: %s\n", tsdf_hip_error_string(rc), why.c_str());
+      return 1;
+    }
+  }
+  if (normals_on) {
+    std::string why;
+    if (const int rc = cpu_tsdf::mesh_post::meshNormalsAuto(mesh, &why)) {
+      PCL_ERROR("--normals: %s: %s\n", tsdf_hip_error_string(rc), why.c_str());
       return 1;
     }
   }

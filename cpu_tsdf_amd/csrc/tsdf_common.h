@@ -344,6 +344,9 @@ void tsdf_flatten_release(tsdf_hip_volume *v);
 // The indexed mesh tsdf_hip_march_flatten left on a handle describes the soup it was made from: a later tsdf_hip_march or
 // tsdf_hip_march_cleanup makes tsdf_hip_march_fetch_indexed refuse until flatten has run again.
 void tsdf_flatten_invalidate(tsdf_hip_volume *v);
+// The normals of tsdf_hip_march_normals (tsdf_normals.hip) live in v->fl: tsdf_flatten_invalidate drops them too, and so does
+// tsdf_hip_reset, through this.
+void tsdf_normals_invalidate(tsdf_hip_volume *v);
 // A list made by tsdf_hip_occupied names voxels by index: after tsdf_hip_shift the fetches refuse until the next scan.
 void tsdf_occupied_invalidate(tsdf_hip_volume *v);
 // The distance field of tsdf_hip_esdf (tsdf_esdf.hip): freed with the handle (free_volume); dropped, memory included, by

@@ -748,6 +748,7 @@ extern "C" int tsdf_hip_create(const tsdf_params *p, tsdf_handle *out) {
 // (octree.h:177-180).
 extern "C" int tsdf_hip_reset(tsdf_handle h) {
   if (!h) return TSDF_HIP_E_INVALID;
+  tsdf_normals_invalidate(h);
   if (h->multi) return tsdf_multi_reset(h);
   TSDF_ENTER(h);
   const int64_t n = h->pitch * h->ny * h->nz_alloc;

@@ -51,7 +51,7 @@
 static thread_local MpStats g_fl_stats;  // tsdf_hip_mesh_flatten_stats
 
 void tsdf_flatten_invalidate(tsdf_hip_volume *v) {
-  if (v->fl) v->fl->valid = false;
+  if (v->fl) v->fl->valid = v->fl->nm_valid = false;  // (normals describe the mesh they were made from: tsdf_normals.hip)
 }
 
 void tsdf_flatten_release(tsdf_hip_volume *v) {
@@ -59,6 +59,7 @@ void tsdf_flatten_release(tsdf_hip_volume *v) {
   TsdfDeviceScope scope(v->device);  // (a set keeps its indexed mesh on the host: work and out are empty)
   mp_work_free(v->fl->work);
   if (v->fl->out) (void)hipFree(v->fl->out);
+  if (v->fl->nm_out) (void)hipFree(v->fl->nm_out);
   delete v->fl;
   v->fl = nullptr;
 }

@@ -2,8 +2,8 @@
 // tsdf_decimate.hip (decimateMesh) -- share.  Declared here and defined in tsdf_meshgrid.hip: the cell table (the uniform grid
 // of cpu_tsdf::mesh_post::PointGrid, csrc/prog/mesh_post.h, over points sorted by the host's cell key), the working set of a
 // pass, a handle-less call with its copies of caller memory (pinned: direct; pageable: staged), and the indexed mesh of a
-// handle.  tsdf_smooth.hip (smoothMesh), which moves the vertices of that indexed mesh, uses the working set, the call and
-// the staging too.  Defined here, because the passes' own kernels inline or instantiate them: mp_cell_key, mp_for_links (the host's
+// handle.  tsdf_smooth.hip (smoothMesh), which moves the vertices of that indexed mesh, and tsdf_normals.hip (meshNormals),
+// which reads it or the soup, use the working set, the call and the staging too, and mp_lower_bound.  Defined here, because the passes' own kernels inline or instantiate them: mp_cell_key, mp_for_links (the host's
 // forNeighbours), mp_face_remap and k_mp_compact.
 #pragma once
 
@@ -40,6 +40,20 @@ static __device__ __forceinline__ uint32_t mp_cell_head(const uint64_t *__restri
 static __device__ __forceinline__ void mp_wave_count(bool yes, unsigned long long *counter) {
   const unsigned long long m = __ballot(yes);
   if ((threadIdx.x & 63u) == 0u && m) atomicAdd(counter, (unsigned long long)__popcll(m));
+}
+
+// the first position of the ascending keys[0 .. n_keys) whose key is >= want (n_keys: none is): the row offsets of an inverted
+// index whose keys carry the row in their high word
+static __device__ __forceinline__ uint32_t mp_lower_bound(const uint64_t *__restrict__ keys, uint32_t n_keys, uint64_t want) {
+  uint32_t lo = 0u, hi = n_keys;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (keys[mid] < want)
+      lo = mid + 1u;
+    else
+      hi = mid;
+  }
+  return lo;
 }
 
 struct MpGrid {
@@ -195,6 +209,13 @@ struct tsdf_flatten_state {  // per handle (tsdf_hip_volume::fl): the indexed me
   std::vector<uint8_t> h_rgb;
   std::vector<uint32_t> h_faces;
   std::vector<uint64_t> h_cell;
+  // tsdf_hip_march_normals (tsdf_normals.hip): the normals of the indexed mesh while it is valid, else of the soup, in a buffer
+  // of their own; every later march, cleanup, flatten, decimate, smooth or reset drops them (nm_valid)
+  bool nm_valid = false;
+  uint64_t nm_n = 0;       // vertices they describe
+  void *nm_out = nullptr;  // one handle: normals, flags (device)
+  size_t nm_cap = 0;
+  std::vector<float> h_normals;  // a multi-GPU set: on the host
 };
 
 // tsdf_hip_march_flatten / _decimate after their own argument checks: refuses without a marched soup, or one too large for

@@ -224,7 +224,7 @@ int mp_idx_begin(tsdf_handle h, const char *who, tsdf_flatten_state **st_out, ui
   }
   if (!h->fl) h->fl = new tsdf_flatten_state();
   tsdf_flatten_state *st = *st_out = h->fl;
-  st->valid = false;
+  st->valid = st->nm_valid = false;
   const uint64_t n = *n_out = h->mc_ntri, n_verts = 3 * n;
   if (const int rc = mp_check_counts(who, n, &n_verts)) return rc;
   if (!n) st->n_verts = st->n_faces = 0;

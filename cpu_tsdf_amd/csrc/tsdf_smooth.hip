@@ -95,15 +95,7 @@ k_sm_rows(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ offset
           const unsigned long long *__restrict__ counters, uint32_t *__restrict__ row) {
   const uint32_t v = blockIdx.x * 256u + threadIdx.x;
   if (v > n) return;
-  const uint64_t want = (uint64_t)v << 32;
-  uint32_t lo = 0u, hi = n_keys;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < want)
-      lo = mid + 1u;
-    else
-      hi = mid;
-  }
+  const uint32_t lo = mp_lower_bound(keys, n_keys, (uint64_t)v << 32);
   row[v] = lo < n_keys ? offset[lo] : (uint32_t)counters[SM_C_DIRECTED];
 }
 
@@ -315,6 +307,7 @@ extern "C" int tsdf_hip_march_smooth(tsdf_handle h, float lambda, float mu, int 
                                (float *)o, L, &fixed, who))
       return rc;
   }
+  st->nm_valid = false;  // (normals of the vertices before they moved: tsdf_normals.hip)
   if (n_fixed) *n_fixed = fixed;
   return TSDF_HIP_OK;
 }

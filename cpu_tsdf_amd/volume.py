@@ -808,6 +808,7 @@ class MarchingCubesTSDFOctree:
         self._flatten = None
         self._decimate = None
         self._smooth = None
+        self._normals = False
 
     def setCleanup(self, face_dist=0.02, min_neighbors=5):
         """Extension (no reference counterpart on the class): reconstruct() drops the faces in connected groups of at most
@@ -867,6 +868,14 @@ class MarchingCubesTSDFOctree:
     def clearSmooth(self):
         self._smooth = None
 
+    def setNormals(self, on=True):
+        """Extension (no reference counterpart): reconstruct() computes area-weighted vertex normals LAST of all -- after
+        cleanup, flatten / decimate and smooth -- from the mesh it returns, the soup included (tsdf_hip_march_normals;
+        include/tsdf_hip.h states the rule and the orientation: out of the surface, into observed free space), and adds
+        "normals" (float32, one row per returned vertex) to its dict.  They are computed in the VOLUME frame and turned by the
+        global transform's rotation."""
+        self._normals = bool(on)
+
     def setInputTSDF(self, volume):
         self._vol = volume
 
@@ -883,7 +892,7 @@ class MarchingCubesTSDFOctree:
         """marching_cubes_tsdf_octree.cpp:108-143.  Returns dict(vertices (3n,3) float32 after the global
         transform, polygons (n,3) int32 = [3i,3i+1,3i+2], rgb (3n,3) uint8 or None, cells).  With setFlatten: the indexed
         mesh -- vertices (m,3), polygons (k,3) int32 into them, rgb (m,3) or None, cells (k,); with setDecimate and with
-        setSmooth likewise."""
+        setSmooth likewise.  With setNormals: also normals, float32, one row per returned vertex."""
         vol = self._vol
         vol._cubic_for_queries("MarchingCubesTSDFOctree.reconstruct")
         h = vol._need()
@@ -908,7 +917,10 @@ class MarchingCubesTSDFOctree:
         if not np.array_equal(g, np.eye(4)):
             verts = transform_points_f64(verts, g)
         polys = np.arange(nt * 3, dtype=np.int32).reshape(nt, 3)
-        return {"vertices": verts, "polygons": polys, "rgb": rgb, "cells": cells}
+        out = {"vertices": verts, "polygons": polys, "rgb": rgb, "cells": cells}
+        if self._normals:
+            out["normals"] = self._fetch_normals(h, nt * 3, g)
+        return out
 
     def _fetch_indexed(self, vol, h, mode, want_cells):
         lib = capi.load()
@@ -934,7 +946,25 @@ class MarchingCubesTSDFOctree:
         g = vol.getGlobalTransform()
         if not np.array_equal(g, np.eye(4)):
             verts = transform_points_f64(verts, g)
-        return {"vertices": verts, "polygons": faces.astype(np.int32), "rgb": rgb, "cells": cells}
+        out = {"vertices": verts, "polygons": faces.astype(np.int32), "rgb": rgb, "cells": cells}
+        if self._normals:
+            out["normals"] = self._fetch_normals(h, m, g)
+        return out
+
+    @staticmethod
+    def _fetch_normals(h, n_expected, g):
+        lib = capi.load()
+        n = C.c_uint64(0)
+        capi.check(lib.tsdf_hip_march_normals(h, C.byref(n), None), "march_normals")
+        if int(n.value) != n_expected:
+            raise RuntimeError(f"march_normals describes {int(n.value)} vertices, the mesh has {n_expected}")
+        normals = np.zeros((n_expected, 3), dtype=np.float32)
+        if n_expected:
+            capi.check(lib.tsdf_hip_march_fetch_normals(h, capi.as_f32p(normals)), "march_fetch_normals")
+        if not np.array_equal(g[:3, :3], np.eye(3)):  # turned like the vertices, in the C++ class' order of operations
+            r, n64 = np.asarray(g, np.float64)[:3, :3], normals.astype(np.float64)
+            normals = (n64[:, 0:1] * r[:, 0] + (n64[:, 1:2] * r[:, 1] + n64[:, 2:3] * r[:, 2])).astype(np.float32)
+        return normals
 
 
 def cleanup_mesh(vertices, polygons=None, face_dist=0.02, min_neighbors=5, device=0):
@@ -1034,6 +1064,27 @@ def smooth_mesh(vertices, polygons, lam=0.5, mu=-0.53, iterations=10, keep_bound
                                          int(iterations), 1 if keep_boundary else 0, capi.as_f32p(out), capi.as_u8p(fixed),
                                          degree.ctypes.data_as(u32p)), "mesh_smooth")
     return {"vertices": out, "fixed": fixed, "degree": degree}
+
+
+def mesh_normals(vertices, polygons=None, device=0):
+    """Area-weighted vertex normals of a triangle mesh on the GPU (tsdf_hip_mesh_normals; include/tsdf_hip.h states the rule):
+    the fp64 sum of the face vectors (p_b - p_a) x (p_c - p_a) of the faces that name a vertex, in ascending face index,
+    normalised -- pointing to the side from which a face's corners appear counter-clockwise.  vertices (n, 3) float32;
+    polygons (k, 3) vertex indices, or None for a triangle soup (face f = vertices 3f, 3f+1, 3f+2).  Returns dict(normals
+    (n, 3) float32, flags (n,) uint8: 1 = in no face, 2 = the normal is zero, 4 = a face of the vertex has a coordinate that
+    is not finite and was skipped)."""
+    verts = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    faces = None if polygons is None else np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
+    if faces is None and len(verts) % 3:
+        raise ValueError("mesh_normals: a triangle soup needs 3 vertices per face")
+    n_faces = len(verts) // 3 if faces is None else len(faces)
+    normals = np.zeros((len(verts), 3), dtype=np.float32)
+    flags = np.zeros(len(verts), dtype=np.uint8)
+    # (an array without elements may have no address: an indexed mesh without faces is not a soup)
+    fp = None if faces is None else (faces if len(faces) else np.zeros((1, 3), np.uint32)).ctypes.data_as(C.POINTER(C.c_uint32))
+    capi.check(capi.load().tsdf_hip_mesh_normals(int(device), capi.as_f32p(verts), len(verts), fp, n_faces, capi.as_f32p(normals), capi.as_u8p(flags)),
+               "mesh_normals")
+    return {"normals": normals, "flags": flags}
 
 
 def reference_cull_planes(p, trans):

@@ -19,7 +19,7 @@ class MarchingCubesTSDFOctree : public pcl::MarchingCubes<pcl::PointXYZ> {
  public:
   MarchingCubesTSDFOctree()
       : pcl::MarchingCubes<pcl::PointXYZ>(), color_by_confidence_(false), color_by_rgb_(false), w_min_(2.5f) {}
-  ~MarchingCubesTSDFOctree() override;  // forgets the object's setCleanup / setFlatten / setDecimate / setSmooth (see there)
+  ~MarchingCubesTSDFOctree() override;  // forgets the object's setCleanup / setFlatten / setDecimate / setSmooth / setNormals (see there)
 
   // Mirrors the reference (:44-83): remembers the volume and dresses the base class the same way -- grid resolution,
   // the 8-corner "input cloud", no grid extension, iso level 0, bounding box and size_voxel_.
@@ -59,6 +59,13 @@ class MarchingCubesTSDFOctree : public pcl::MarchingCubes<pcl::PointXYZ> {
   // over.  The arguments live in the shell library next to setDecimate's: the class keeps its size.
   void setSmooth(int iterations, float lambda = 0.5f, float mu = -0.53f, bool keep_boundary = true);
   void clearSmooth();
+  // Extension likewise: reconstruct(PolygonMesh&) computes area-weighted vertex normals LAST of all -- after cleanup,
+  // flatten / decimate and smooth -- from the mesh it returns (tsdf_hip_march_normals; include/tsdf_hip.h states the rule and
+  // the orientation: out of the surface, into observed free space), and appends three FLOAT32 fields normal_x, normal_y,
+  // normal_z to the cloud blob.  It works on the soup as well (flat normals).  The normals are computed in the VOLUME frame
+  // and turned by the global transform's rotation.  reconstruct(points, polygons) has no place for them.  The argument lives
+  // in the shell library next to setSmooth's: the class keeps its size.
+  void setNormals(bool on = true);
 
   using pcl::MarchingCubes<pcl::PointXYZ>::reconstruct;  // reconstruct(PolygonMesh&), reconstruct(points, polygons)
 

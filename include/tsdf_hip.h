@@ -635,6 +635,58 @@ int tsdf_hip_march_smooth(tsdf_handle h, float lambda, float mu, int iterations,
  * no host read falls inside, nor do the transfers of the host-array entry point). */
 int tsdf_hip_mesh_smooth_stats(uint64_t out[4]);
 
+/* meshNormals -- area-weighted per-vertex normals of a triangle mesh, from the mesh itself (after decimate or smooth have
+ * moved the vertices, the TSDF gradient no longer describes it); an extension with no counterpart in the reference.  The
+ * result is defined by the sequential host pass cpu_tsdf::mesh_post::normalArrays (csrc/prog/mesh_post.h) and equals it word
+ * for word:
+ *   1. the face vector of f = (a, b, c): e1 = (double)p_b - (double)p_a, e2 = (double)p_c - (double)p_a componentwise,
+ *      g_f = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), every difference, product and subtraction rounded
+ *      once, no FMA.  |g_f| is twice the face's area: the weighting is by area.  A face with a repeated index, or whose
+ *      corners are distinct vertices at one position, gives the exact zero vector.  A face with a coordinate that is not
+ *      finite at any corner is SKIPPED: it adds nothing and is counted.  No finite input overflows (|g| < 1e78).
+ *   2. per component s_i = +0.0; then, over the faces that name i in ascending face index, s_i += g_f once per corner that
+ *      names i (a face (i, i, b) adds its zero vector twice, a face given twice adds twice).  The order of the adds is part
+ *      of the definition.
+ *   3. l2 = (sx sx + sy sy) + sz sz, each operation rounded once, l = sqrt(l2), the IEEE square root.  l2 == 0: the normal
+ *      is three +0.0f.  Otherwise n_i = ((float)(sx / l), (float)(sy / l), (float)(sz / l)): divisions, not a product with a
+ *      reciprocal.
+ *   4. flags[i] is the OR of 1: no face names i; 2: rule 3 wrote zero (every vertex with bit 1 has it); 4: a face that names
+ *      i was skipped.
+ *   5. ORIENTATION: the normal points to the side from which the corners a -> b -> c appear counter-clockwise, along
+ *      (p_b - p_a) x (p_c - p_a).  On a mesh of tsdf_hip_march that is the direction of increasing d: out of the surface,
+ *      into observed free space.
+ *   verts, faces   HOST arrays (pinned memory is used directly, pageable memory is staged): n_verts x 3 floats, n_faces x 3
+ *                  vertex indices.  faces == NULL: a triangle SOUP -- n_verts is a multiple of 3, face f has the corners
+ *                  3f, 3f + 1, 3f + 2, and n_faces is n_verts / 3 (or 0: no face at all).
+ *   out_normals    n_verts x 3 floats.       flags   n_verts bytes, rule 4's bits; nullable.
+ * E_INVALID, checked before any device call: NULL verts or out_normals with n_verts > 0, device < 0, more than 2^31 vertices
+ * or more than 1431655765 faces (the 3 n_faces entries of the inverted index are indexed with 32 bits), a soup whose n_verts
+ * is not a multiple of 3 or whose n_faces is neither 0 nor n_verts / 3.  E_INVALID with nothing written: a face naming a
+ * vertex >= n_verts.  n_verts == 0 (with no face) is OK and touches no device.  E_NOMEM, with the bytes in
+ * tsdf_hip_last_error, when the mesh (25 bytes per vertex, 12 per face) or the working set (4 bytes per vertex, 80 per face
+ * and the sort's temporary storage; a soup needs none) does not fit.
+ * Cost: one radix sort of the 3 n_faces keys vertex << 32 | face builds the inverted index; then ONE lane walks each
+ * vertex's faces so that the adds keep the host's order: a lane's time is its vertex's valence, 4-8 on a marched mesh; a
+ * vertex named by thousands of faces makes one lane walk them all.  A soup needs no sort: one kernel, one lane per face. */
+int tsdf_hip_mesh_normals(int device, const float *verts, uint64_t n_verts, const uint32_t *faces /* NULL = soup */,
+                          uint64_t n_faces, float *out_normals, uint8_t *flags /* nullable */);
+/* The same for the handle's mesh: the INDEXED mesh of the last tsdf_hip_march_flatten / _march_decimate (moved by
+ * _march_smooth or not) while one is valid, otherwise the soup of the last tsdf_hip_march / _march_cleanup.  *n_verts
+ * (nullable) says which: the indexed mesh's vertex count, or 3 x the soup's triangle count; *n_zero (nullable): the vertices
+ * whose normal is zero.  The normals live in a buffer of their own on the handle; the mesh itself (positions, colours, faces,
+ * cells, the soup) is not touched.  Every later tsdf_hip_march, _march_cleanup, _march_flatten, _march_decimate or
+ * _march_smooth drops them (whether or not it succeeds), and so do tsdf_hip_reset and tsdf_hip_destroy.  E_INVALID when no
+ * march has run.  On a multi-GPU handle the host-held merged mesh goes through tsdf_hip_mesh_normals on the first slab's
+ * device; the result equals one handle holding the whole grid. */
+int tsdf_hip_march_normals(tsdf_handle h, uint64_t *n_verts /* nullable */, uint64_t *n_zero /* nullable */);
+/* The normals tsdf_hip_march_normals left on the handle: as many rows of 3 floats as its *n_verts said, in the order of the
+ * vertices tsdf_hip_march_fetch_indexed or tsdf_hip_march_fetch returns.  E_INVALID while there are none. */
+int tsdf_hip_march_fetch_normals(tsdf_handle h, float *normals);
+/* Report-only, of the last normals pass (either entry point) on the calling thread: out[0] = vertices, out[1] = skipped
+ * faces, out[2] = zero normals, out[3] = device microseconds from the first kernel to the last (HIP events on the stream; no
+ * host read falls inside, nor do the transfers of the host-array entry point). */
+int tsdf_hip_mesh_normals_stats(uint64_t out[4]);
+
 /* getOccupiedVoxelIndices -- src/lib/tsdf_volume_octree.cpp:590-609 (+ OctreeNode::getLeaves, src/lib/octree.cpp:99-109):
  * the voxels with w > 0 && fabsf(d) < 1, d and w being the floats tsdf_hip_download returns (PACKED layout:
  * w = min(k, max_weight); a NaN distance is not listed), in the reference's leaf order: ascending key
