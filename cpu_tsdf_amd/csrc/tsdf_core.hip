@@ -58,7 +58,7 @@ static TsdfTuning &tuning_storage() {
                          env_int("TSDF_HIP_CULL", 1), std::max(1, env_int("TSDF_HIP_VOL_CHUNK", 256)),
                          env_int("TSDF_HIP_PLAIN_KERNEL", 0), env_int("TSDF_HIP_ALLOC_TRIES", 3), env_int("TSDF_HIP_ALLIN", 1),
                          env_int("TSDF_HIP_REFCULL_PLAIN", 0), env_int("TSDF_HIP_LIVE_LOG2TX", 5), env_int("TSDF_HIP_ZFAST", 1), env_int("TSDF_HIP_FUSE2", 1), env_int("TSDF_HIP_IMPLIED_D", 1),
-                         env_int("TSDF_HIP_PIPE", 1), std::max(1, env_int("TSDF_HIP_LAB_CHUNK", 16 << 20)), env_int("TSDF_HIP_FRAME_PAIRS", 1)};
+                         env_int("TSDF_HIP_PIPE", 1), std::max(1, env_int("TSDF_HIP_LAB_CHUNK", 16 << 20))};
   return t;
 }
 
@@ -111,7 +111,7 @@ extern "C" int tsdf_hip_set_tuning(const char *name, int value) {
   else if (n == "lab_chunk")
     t.lab_chunk = std::max(1, value);
   else if (n == "frame_pairs")
-    t.frame_pairs = value;
+    (void)value;  // a removed knob (the colour kernels always gather pixel records): the name is accepted and ignored, so that a caller's loop that puts knobs back does not stop half way and leave the others set
   else
     return TSDF_HIP_E_INVALID;
   return TSDF_HIP_OK;

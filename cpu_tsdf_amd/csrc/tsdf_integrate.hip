@@ -63,10 +63,6 @@
                          // 2048^3 without colour: 7.61 ms at 8 against 7.81 at 7, 8.98 for k_integrate's own row loop:
                          // profiles/r06_ab_pipe_c0_call02.txt)
 #endif
-#ifndef TSDF_WPE_PIPEC
-#define TSDF_WPE_PIPEC 5  // k_integrate_pc: 91 VGPRs, no scratch (six waves: 80 VGPRs + ten spill operations in the row loop, whose
-                          // waits undo the pipeline)
-#endif
 #ifndef TSDF_WPE_K2
 #define TSDF_WPE_K2 5  // k_integrate2: issue + retire of a row back to back
 #endif
@@ -100,7 +96,6 @@ struct IntegrateArgs {
   int zl0;            // allocated-plane index of the first integrated plane
   int log2TX, TX, TY; // thread tile: TX quads along x, TY rows along y (TX*TY == 256)
   int rpb;            // row groups (of TY rows) per block
-  unsigned bgra_off;  // byte offset of the colour image from the depth image (same buffer descriptor)
   int expf_fused_r;      // the host libm's expf fuses r = InvLn2N * x - k (tsdf_expf_glibc; probed by tsdf_hip_set_weighting)
   int ref_cull;          // replicate the reference's frustum cull (getFrustumCulledVoxels): six plane tests per voxel centre
   float cull[24];        // its planes l, r, t, b, far, near (tsdf_hip_set_reference_cull), 4 floats each
@@ -536,7 +531,7 @@ static __device__ __forceinline__ unsigned tsdf_nonzero_bytes(uint32_t x) {
 
 // The counting instances' counters: per quantity a stripe of slots in the handle's counter array, a block adding to the slot of its
 // number; the host sums each stripe.
-enum {  // one frame: k_integrate, k_integrate_p, k_integrate_pc -> tsdf_integrate_collect
+enum {  // one frame: k_integrate, k_integrate_p -> tsdf_integrate_collect
   TSDF_CNT_STRIPE = 1024,
   TSDF_CNT_OBSERVED = 0,    // voxels brought to addObservation (all k_integrate_plain counts: TSDF_CNT_STRIPE slots)
   TSDF_CNT_CHANGED = 1024,  // bytes of voxel words whose VALUE changed: what any layout-preserving kernel has to write
@@ -589,10 +584,10 @@ static __device__ __forceinline__ void tsdf_count_out(const BlockCoords &bc, uns
 // (Never with ALLIN.  A slab wholly in view that the reference's cull cuts takes this instance for all its blocks: the
 // alternative -- an ALLIN pass over the blocks flagged 1 plus an interval pass over those flagged 2 -- was built and
 // measured slower, profiles/r04_refcull_dual_launch_measured_and_removed.txt.)
-// PAIRS (only with COLOR): `depth` is the frame as 8-byte records {depth bits, bgra} per pixel (k_frame_pairs below), and a
-// voxel's depth and colour come with ONE 8-byte gather instead of two 4-byte ones from the [depth | bgra] planes: the same bits
-// from half the vector-memory instructions, address computations and tag look-ups, and from one cache line.
-template <int ORDER, bool COLOR, bool FASTPROJ, bool COUNT, bool PACKED, bool ALLIN = false, bool LIVE = false, bool PAIRS = false>
+// COLOR: `depth` is the frame as 8-byte records {depth bits, bgra} per pixel (k_frame_pairs below), and a voxel's depth and
+// colour come with ONE 8-byte gather (two 4-byte ones from [depth | bgra] planes were measured slower and removed:
+// docs/DESIGN_HISTORY.md).  Without colour `depth` is the depth plane itself.
+template <int ORDER, bool COLOR, bool FASTPROJ, bool COUNT, bool PACKED, bool ALLIN = false, bool LIVE = false>
 static __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_WPE_OF(ORDER, COLOR, FASTPROJ, COUNT, PACKED, ALLIN) < TSDF_WPE_MAX ? TSDF_WPE_OF(ORDER, COLOR, FASTPROJ, COUNT, PACKED, ALLIN) : TSDF_WPE_MAX, TSDF_WPE_MAX)))
 k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt, uint32_t *__restrict__ RGB,
             uint8_t *__restrict__ K8, const float *__restrict__ depth, const double *__restrict__ cam,
@@ -601,7 +596,6 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
             const uint32_t *__restrict__ row_iv) {
   // brick-level frustum cull (k_cull below): a block none of whose voxels can be observed leaves at once
   static_assert(!(ALLIN && LIVE), "the ALLIN instance knows no row intervals");
-  static_assert(!PAIRS || COLOR, "pixel records carry the colour: the colourless frame is the depth plane itself");
   const BlockCoords bc = tsdf_block_coords(a.zfast);
   bool strad = false;  // LIVE: this block's rows need their intervals (block-uniform)
   if (LIVE) {
@@ -665,10 +659,10 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
   const rsrc_t rsC = make_rsrc(COLOR ? RGB + br.e0 : (uint32_t *)D, COLOR ? br.span * 4u : 0u);
   const rsrc_t rsK = make_rsrc(PACKED && !COLOR ? K8 + br.e0 : (uint8_t *)D, PACKED && !COLOR ? br.span : 0u);
   const unsigned npix = (unsigned)a.W * (unsigned)a.H;
-  const rsrc_t rsF = make_rsrc(depth, PAIRS ? npix * 8u : COLOR ? a.bgra_off + npix * 4u : npix * 4u);  // [depth ... bgra], or the records
+  const rsrc_t rsF = make_rsrc(depth, COLOR ? npix * 8u : npix * 4u);  // the records, or the depth plane
   // ALLIN: every pixel index is valid, so the gather can address the frame by INDEX (stride 4, or 8 for records; `idxen`):
   // no shift per pixel, and no range check is wanted (NUM_RECORDS at its maximum, whichever unit the hardware counts it in)
-  const i4_rsrc rsFi = make_rsrc_2d(depth, PAIRS ? 8u : 4u, 0xffffffffu);
+  const i4_rsrc rsFi = make_rsrc_2d(depth, COLOR ? 8u : 4u, 0xffffffffu);
   if (xq < a.qpr) {
     const int x4 = xq * 4;
     const float cz = ctrz[a.z_global0 + zl];
@@ -800,17 +794,14 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
       uint32_t cs[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        // a valid pixel offset is < npix*4; -1 becomes 0xfffffffc, beyond the descriptor with or without the
-        // colour image's scalar offset (records: < npix*8, and 0xfffffff8)
-        if (PAIRS) {
+        // a valid pixel offset is < npix*4; -1 becomes 0xfffffffc, beyond the descriptor (records: < npix*8, and 0xfffffff8)
+        if (COLOR) {
           const u2 zc = ALLIN ? tsdf_struct_buffer_load_u32x2(rsFi, pix[j], 0, 0, TSDF_GATHER_AUX) : bload64(rsF, (unsigned)pix[j] << 3, 0u);
           zs[j] = __uint_as_float(zc.x), cs[j] = zc.y;
         } else if (ALLIN) {
           zs[j] = __uint_as_float(tsdf_struct_buffer_load_u32(rsFi, pix[j], 0, 0, TSDF_GATHER_AUX));
-          if (COLOR) cs[j] = tsdf_struct_buffer_load_u32(rsFi, pix[j], 0, (int)a.bgra_off, TSDF_GATHER_AUX);
         } else {
           zs[j] = __uint_as_float(bload32(rsF, (unsigned)pix[j] << 2, 0u));
-          if (COLOR) cs[j] = bload32(rsF, (unsigned)pix[j] << 2, a.bgra_off);
         }
       }
       // [phase: hinge / normalise (hpp:159-198)]
@@ -1073,7 +1064,7 @@ k_integrate(const IntegrateArgs a, float *__restrict__ D, float *__restrict__ Wt
 // the distance words per WAVE and pass (the implied-distance decision of k_integrate, a scalar branch whose two paths
 // differ by one load: the wait is conservative by that one load at most).
 // (Tried on top, round 6: stage A requesting the PLANE words BEFORE it projects -- they come from HBM, the gathers from L2, and
-// depend on nothing the projection works out.  No effect, here or in k_integrate_pc: 7.47 against 7.47 ms, 13.16 against 13.20
+// depend on nothing the projection works out.  No effect: 7.47 against 7.47 ms
 // (profiles/r06_ab_planefirst_call10.txt): the stage the pipeline gives every load already covers them.  Not kept.)
 // Same arithmetic as k_integrate<ORDER, false, true, COUNT, true, true, false>, operation for operation; the host
 // launches it instead of that instance when, additionally, every row step of a block is whole (ny a multiple of TY),
@@ -1153,7 +1144,7 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
       const unsigned soff = (unsigned)r * row_step;
       const bool d_read = !(r < 64 && (quiet >> r & 1ull));
       // [phase: hinge / normalise (hpp:159-198)]
-      // (These opening tests -- raw / act / any, the ballot exit, any_div -- stand in this kernel, in k_integrate_pc and, any_div, in
+      // (These opening tests -- raw / act / any, the ballot exit, any_div -- stand in this kernel and, any_div, in
       // k_integrate: as shared functions, with or without their loops, by reference or by value, they change a timed instance's code.)
       float raw[4];
       bool act[4];
@@ -1273,257 +1264,6 @@ k_integrate_p(const IntegrateArgs a, float *__restrict__ D, uint8_t *__restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_integrate_pc (round 6): the HEADLINE instance -- ALLIN, PACKED, integrate_color -- on k_integrate_p's two-stage pipeline.
-// A row in flight holds more here (four colour gathers and the colour|count words besides the depths: 20 registers per row,
-// two rows), so this kernel runs FEWER waves per SIMD than k_integrate's 64-register instance; what it buys is that a wave
-// never sits in the frame gather's s_waitcnt with nothing else to issue (k_integrate: ~80 % VALU-active at eight waves).
-// The voxel words are requested in stage A by the quads PREDICTED to be observed -- the quad's own outcome in the last row
-// whose stage B has run, i.e. two rows back -- through an exec-free device: an unpredicted quad's byte offset is poisoned
-// (all ones: beyond every descriptor's range, the hardware returns zero and fetches nothing), so stage A always issues the
-// same TEN loads and the compiler can count them behind the row that waits.  An observed quad the predictor missed asks in
-// stage B and waits there (in order: also for the next row's gathers -- rare: where a surface begins along y).
-// Arithmetic: k_integrate<ORDER, true, true, COUNT, true, true, false>'s, operation for operation.
-// MEASURED (profiles/r06_ab_pipec_call04.txt, five alternations, 2048^3 + colour): 12.80 ms at five waves (91 VGPRs), 12.78-13.46 at
-// four, against 12.59-12.64 for k_integrate's own row loop at eight waves -- no gain, nor on a configs[4] slab (12.21 against
-// 12.14): with colour the row moves 58.6 GB per launch, 4.6 TB/s = 82 % of what this box's plain read-modify-write sweep
-// reaches, while the VALU is 80 % busy -- two limiters at once, neither of which the pipeline touches.  OFF by default (knob
-// pipe, bit 1); kept, oracle-gated like every instance (tests/test_integrate_gpu.py), for hardware where the balance differs.
-// (Waves per SIMD: TSDF_WPE_PIPEC, at the top of the file.)
-struct PipeRowC {
-  float gz[4];
-  uint32_t z[4];   // gathered depths (in flight)
-  uint32_t cs[4];  // gathered bgra (in flight)
-  u4 c4;           // the quad's colour|count words (in flight; zero where not asked)
-  u4 d4;           // its distance words (in flight)
-};
-
-template <int ORDER, bool COUNT, bool PAIRS>
-static __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_WPE_PIPEC < TSDF_WPE_MAX ? TSDF_WPE_PIPEC : TSDF_WPE_MAX, TSDF_WPE_MAX)))
-k_integrate_pc(const IntegrateArgs a, float *__restrict__ D, uint32_t *__restrict__ RGB, const float *__restrict__ depth,
-               const double *__restrict__ cam, const float *__restrict__ ctrx, const float *__restrict__ ctry,
-               const float *__restrict__ ctrz, unsigned long long *__restrict__ n_obs, uint8_t *__restrict__ band) {
-  const BlockCoords bc = tsdf_block_coords(a.zfast);
-  const unsigned tid = threadIdx.x;
-  __shared__ f2 s_rcp[256];  // (the three tables: see tsdf_rcp_entry)
-  __shared__ f4 s_yt[256];
-  __shared__ f4 s_cx[256];
-  __shared__ uint8_t s_bin[1024];
-  TSDF_BAND_DECL;
-  s_rcp[tid] = tsdf_rcp_entry(a, tid);
-  {
-    const int yy = (int)bc.by * a.rpb * a.TY + (int)tid;
-    const float cy_ = ctry[yy < a.ny ? yy : a.ny - 1], cz_ = ctrz[a.z_global0 + (int)bc.bz];
-    f4 t = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < 3; ++q) t[q] = tsdf_row_part<ORDER>(a.m, q, cy_, cz_);
-    s_yt[tid] = t;
-  }
-  tsdf_park_centres(a, bc, ctrx, s_cx, tid);
-  if (a.implied_d) tsdf_flags_before(a, bc, band, s_bin, tid);
-  __syncthreads();
-  const uint64_t quiet = a.implied_d ? tsdf_quiet_passes(a, s_bin, tid) : 0ull;
-  const int tx = (int)(tid & (unsigned)(a.TX - 1));
-  const int ty = (int)(tid >> a.log2TX);
-  const int xq = (int)bc.bx * a.TX + tx;
-  const int zl = (int)bc.bz;
-  const Rcp32 rneg = rcp32_prepare(a.neg);
-  unsigned cnt = 0, chg = 0, imp = 0, rdb = 0;
-  const BlockRows br = tsdf_block_rows(a, bc);  // (rows: a multiple of TY, the host checked)
-  const rsrc_t rsD = make_rsrc(D + br.e0, br.span * 4u);
-  const rsrc_t rsC = make_rsrc(RGB + br.e0, br.span * 4u);
-  const i4_rsrc rsFi = make_rsrc_2d(depth, PAIRS ? 8u : 4u, 0xffffffffu);  // PAIRS: pixel records (see k_integrate)
-  const uint32_t pbits = __float_as_uint(a.pos_over_neg);
-  if (xq < a.qpr) {
-    float zt[3];
-    tsdf_plane_part<ORDER>(a.m, ctrz[a.z_global0 + zl], zt);
-    const unsigned voff = (unsigned)(ty * (int)a.pitch + xq * 4) * 4u;
-    const unsigned row_step = (unsigned)a.TY * (unsigned)a.pitch * 4u;
-    bool obs_a = true, obs_b = true;  // this quad's outcome in the last even / odd row whose stage B has run (the predictor)
-
-    // ---- stage A ----------------------------------------------------------------------------------------------------
-    auto issue = [&](const int r, PipeRowC &R, const bool pred) {
-      const f4 ytv = s_yt[ty + r * a.TY];
-      asm volatile("" ::: "memory");
-      int pix[4];
-      project_quad_allin<ORDER>(a, a.m, cam, s_cx[tid], ytv, zt, pix, R.gz);
-      const unsigned soff = (unsigned)r * row_step;
-      const bool d_read = !(r < 64 && (quiet >> r & 1ull));  // wave-uniform (implied distances, see k_integrate)
-      // [phase: voxel loads]
-      const unsigned offp = pred ? voff : 0x7ffffff0u;  // an unpredicted quad asks for nothing: its offset lies beyond the descriptor
-      R.d4 = bload128(rsD, d_read ? offp : 0x7ffffff0u, soff);
-      R.c4 = bload128(rsC, offp, soff);
-      // [phase: frame gather]
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (PAIRS) {  // (stage A then issues SIX loads, statically as before)
-          const u2 zc = tsdf_struct_buffer_load_u32x2(rsFi, pix[j], 0, 0, TSDF_GATHER_AUX);
-          R.z[j] = zc.x, R.cs[j] = zc.y;
-        } else {
-          R.z[j] = tsdf_struct_buffer_load_u32(rsFi, pix[j], 0, 0, TSDF_GATHER_AUX);
-          R.cs[j] = tsdf_struct_buffer_load_u32(rsFi, pix[j], 0, (int)a.bgra_off, TSDF_GATHER_AUX);
-        }
-      }
-      if (COUNT) rdb += pred ? (d_read ? 32u : 16u) : 0u;
-    };
-
-    // ---- stage B ----------------------------------------------------------------------------------------------------
-    auto consume = [&](const int r, PipeRowC &R, const bool pred, bool &obs_out) {
-      const unsigned soff = (unsigned)r * row_step;
-      const bool d_read = !(r < 64 && (quiet >> r & 1ull));
-      // [phase: hinge / normalise (hpp:159-198)]
-      // (the opening tests as in k_integrate_p, spelled out in both: see there)
-      float raw[4];
-      bool act[4];
-      bool any = false;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        raw[j] = __uint_as_float(R.z[j]) - R.gz[j];  // hpp:159
-        act[j] = raw[j] >= -a.neg;                   // hpp:152 and :193-196 in one compare (see k_integrate)
-        any |= act[j];
-      }
-      obs_out = any;
-      if (__builtin_amdgcn_ballot_w64(any) == 0ull) return;  // nothing of this wave's row is observed
-      // [phase: leave the row if nothing is observed; late voxel loads]
-      if (any && !pred) {  // an observed quad the predictor missed: its words are requested now, and retired here
-        if (d_read) R.d4 = bload128(rsD, voff, soff);
-        R.c4 = bload128(rsC, voff, soff);
-        if (COUNT) rdb += d_read ? 32u : 16u;
-        asm volatile("" ::"v"(R.d4), "v"(R.c4));
-      }
-      bool any_div = false;
-      if (__builtin_fminf(__builtin_fminf(raw[0], raw[1]), __builtin_fminf(raw[2], raw[3])) <= a.pos) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) any_div |= act[j] && !(raw[j] > a.pos);
-      }
-      // [phase: decode count / weight (PACKED)]
-      const uint32_t c0[4] = {R.c4.x, R.c4.y, R.c4.z, R.c4.w};
-      uint32_t d0u[4] = {R.d4.x, R.d4.y, R.d4.z, R.d4.w};
-      // [phase: band / implied-distance flags, hinge rest test]
-      bool off_hinge = any_div;
-      if (d_read) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) off_hinge |= d0u[j] != pbits;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) off_hinge |= c0[j] < 0x01000000u;
-      }
-      const bool d_moves = __builtin_amdgcn_ballot_w64(any && off_hinge) != 0ull;  // wave-uniform
-      // [phase: colour update (octree.cpp:328-337)]
-      // (voxel by voxel, nothing kept: the rare distance block below works its operands out again -- registers are what
-      // this kernel is short of)
-      uint32_t cv[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {  // colour and count: every observed voxel
-        float w = (float)(c0[j] >> 24);  // tsdf_decode_w: max_weight is an integer equal to kmax here (ALLIN)
-        asm volatile("" : "+v"(w));      // (keeps LLVM from turning the colour sums into integer multiplies: see k_integrate's decode step)
-        const uint32_t k1 = min(c0[j], a.kcap | 0xffffffu) + a.kinc;  // min(k + 1, kmax) << 24 | old rgb (v_cvt_pk_u8 rewrites bytes 0-2)
-        const f2 yh = s_rcp[c0[j] >> 24];
-        Rcp32 rs;
-        rs.nb = -(w + 1.f);
-        rs.y = yh.x;
-        const float hy = yh.y;
-        float dd = 0.f;
-        cv[j] = c0[j];
-        add_observation_fast<true, false>(dd, w, cv[j], 0.f, R.cs[j], a.wmax, rs, k1, &hy);
-      }
-      // [phase: d update (octree.cpp:152-163)]
-      if (d_moves) {  // (a tenth of the observed wave-rows: surfaces, first observations)
-        float d0[4], dn[4], dv[4], w0[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (!d_read) d0u[j] = c0[j] < 0x01000000u ? 0xbf800000u : pbits;  // never observed: the reset value; else the hinge value
-          d0[j] = __uint_as_float(d0u[j]);
-          dn[j] = a.pos_over_neg;  // hpp:189-192
-          w0[j] = (float)(c0[j] >> 24);
-        }
-        if (any_div) {
-          TSDF_BAND(TSDF_BAND_CELL(r)) = 1;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) dn[j] = raw[j] > a.pos ? a.pos_over_neg : div32_fast(raw[j], rneg);  // hpp:198
-        }
-        bool safe = true;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          Rcp32 rs;
-          rs.nb = -(w0[j] + 1.f);
-          rs.y = s_rcp[c0[j] >> 24].x;
-          dv[j] = div32_fast(d0[j] * w0[j] + dn[j], rs);
-          safe &= !act[j] || __builtin_amdgcn_classf(dv[j], 0x108);  // the guard on the RESULT (k_integrate)
-        }
-        // [phase: IEEE fallback (rare)]
-        if (!safe) {
-          asm volatile("");
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            float wv = w0[j];
-            dv[j] = d0[j];
-            cv[j] = c0[j] & 0xffffffu;
-            add_observation_ieee<true>(dv[j], wv, cv[j], dn[j], R.cs[j], a.wmax);
-            cv[j] |= (min(c0[j], a.kcap | 0xffffffu) + a.kinc) & 0xff000000u;
-          }
-        }
-        uint32_t diff_d = 0u, dn_u[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          dn_u[j] = act[j] ? __float_as_uint(dv[j]) : d0u[j];
-          diff_d |= dn_u[j] ^ d0u[j];
-          if (COUNT) chg += dn_u[j] != d0u[j] ? 4u : 0u;
-        }
-        if (diff_d) bstore128(rsD, voff, soff, (u4){dn_u[0], dn_u[1], dn_u[2], dn_u[3]});
-      }
-      // [phase: select / change detection / store]
-      uint32_t diff_c = 0u;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        cv[j] = act[j] ? cv[j] : c0[j];
-        diff_c |= cv[j] ^ c0[j];
-        if (COUNT) {
-          cnt += act[j] ? 1u : 0u;
-          imp += act[j] && !d_read ? 1u : 0u;
-          chg += cv[j] != c0[j] ? 4u : 0u;
-        }
-      }
-      if (diff_c) bstore128(rsC, voff, soff, (u4){cv[0], cv[1], cv[2], cv[3]});
-    };
-
-    PipeRowC A, B;
-    const int nr = br.rows / a.TY;  // (the grid's last block may be shorter: the host checked that ny is a multiple of TY)
-    issue(0, A, true);
-    int r = 0;
-    for (; r + 2 < nr; r += 2) {  // steady state: every trip issues two rows and consumes two
-      const bool pb = obs_b;      // row r + 1 asks by the outcome of row r - 1
-      issue(r + 1, B, pb);
-      const bool pa = obs_a;      // what row r asked by: row r - 2's outcome (the first two rows ask)
-      consume(r, A, pa, obs_a);
-      const bool pa2 = obs_a;     // row r + 2 asks by the outcome of row r
-      issue(r + 2, A, pa2);
-      consume(r + 1, B, pb, obs_b);
-    }
-    if (r + 1 < nr) {
-      const bool pb = obs_b;
-      issue(r + 1, B, pb);
-      const bool pa = obs_a;
-      consume(r, A, pa, obs_a);
-      consume(r + 1, B, pb, obs_b);
-    } else {
-      const bool pa = obs_a;
-      consume(r, A, pa, obs_a);
-    }
-  }
-  if (band) {  // tsdf_flags_write_out's loop, spelled out: through the helper this kernel comes out with 91 VGPRs and ~40 more instructions
-    const BandCells c = tsdf_band_cells(a, bc, br);
-    for (int i = TSDF_BAND_FIRST; i < c.n_fl; i += TSDF_BAND_STEP) {
-      const int yg = c.yg0 + (i >> c.lf), xc = c.xc0 + (i & (c.fxb - 1));
-      if (TSDF_BAND(i) && yg < a.band_fy && xc < a.band_fx) band[((int64_t)(a.zl0 + zl) * a.band_fy + yg) * a.band_fx + xc] = 1;
-    }
-  }
-  if (COUNT) {
-    __shared__ unsigned s_count[4];
-    tsdf_count_out(bc, s_count, n_obs, tid, cnt, chg, imp, rdb);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // Two frames per sweep.  k_integrate waits for HBM with all the requests the register file lets it
 // keep in flight: half of its time is arithmetic, the other half latency it cannot cover.  When TWO frames
 // are at hand, this kernel reads a quad's voxel words once, applies frame A's observation and then frame B's to the
@@ -1535,12 +1275,11 @@ k_integrate_pc(const IntegrateArgs a, float *__restrict__ D, uint32_t *__restric
 // Anything else takes two ordinary launches (tsdf_integrate_launch2).
 struct Frame2 {
   float m[12];        // frame B's cam_from_vol
-  unsigned bgra_off;  // ... and the byte offset of its colour image from its depth image
 };
 // A row's loads are issued and retired back to back, at TSDF_WPE_K2 waves per SIMD (top of the file): keeping two rows in
 // flight costs 32 more registers of row state, and occupancy wins.
 
-template <int ORDER, bool COLOR, bool COUNT, bool PAIRS>
+template <int ORDER, bool COLOR, bool COUNT>
 static __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_WPE_K2, TSDF_WPE_MAX)))
 k_integrate2(const IntegrateArgs a, const Frame2 fb, float *__restrict__ D, uint32_t *__restrict__ RGB, uint8_t *__restrict__ K8,
              const float *__restrict__ depthA, const float *__restrict__ depthB, const double *__restrict__ cam,
@@ -1576,8 +1315,7 @@ k_integrate2(const IntegrateArgs a, const Frame2 fb, float *__restrict__ D, uint
   const rsrc_t rsD = make_rsrc(D + br.e0, br.span * 4u);
   const rsrc_t rsC = make_rsrc(COLOR ? RGB + br.e0 : (uint32_t *)D, COLOR ? br.span * 4u : 0u);
   const rsrc_t rsK = make_rsrc(!COLOR ? K8 + br.e0 : (uint8_t *)D, !COLOR ? br.span : 0u);
-  static_assert(!PAIRS || COLOR, "pixel records carry the colour");
-  const unsigned fstride = PAIRS ? 8u : 4u;  // PAIRS: both frames as pixel records (see k_integrate)
+  const unsigned fstride = COLOR ? 8u : 4u;  // COLOR: both frames as pixel records (see k_integrate)
   const i4_rsrc rsFA = make_rsrc_2d(depthA, fstride, 0xffffffffu), rsFB = make_rsrc_2d(depthB, fstride, 0xffffffffu);
   const uint32_t hinge_bits = __float_as_uint(a.pos_over_neg);
   if (xq < a.qpr) {
@@ -1606,22 +1344,22 @@ k_integrate2(const IntegrateArgs a, const Frame2 fb, float *__restrict__ D, uint
       project_quad_allin<ORDER>(a, fb.m, cam, s_cx[tid], s_ytB[ty + r * a.TY], ztB, pixB, L.gzB);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if (PAIRS) {
+        if (COLOR) {
           const u2 zc = tsdf_struct_buffer_load_u32x2(rsFA, pixA[j], 0, 0, TSDF_GATHER_AUX);
           L.zsA[j] = __uint_as_float(zc.x), L.csA[j] = zc.y;
         } else {
           L.zsA[j] = __uint_as_float(tsdf_struct_buffer_load_u32(rsFA, pixA[j], 0, 0, TSDF_GATHER_AUX));
-          L.csA[j] = COLOR ? tsdf_struct_buffer_load_u32(rsFA, pixA[j], 0, (int)a.bgra_off, TSDF_GATHER_AUX) : 0u;
+          L.csA[j] = 0u;
         }
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if (PAIRS) {
+        if (COLOR) {
           const u2 zc = tsdf_struct_buffer_load_u32x2(rsFB, pixB[j], 0, 0, TSDF_GATHER_AUX);
           L.zsB[j] = __uint_as_float(zc.x), L.csB[j] = zc.y;
         } else {
           L.zsB[j] = __uint_as_float(tsdf_struct_buffer_load_u32(rsFB, pixB[j], 0, 0, TSDF_GATHER_AUX));
-          L.csB[j] = COLOR ? tsdf_struct_buffer_load_u32(rsFB, pixB[j], 0, (int)fb.bgra_off, TSDF_GATHER_AUX) : 0u;
+          L.csB[j] = 0u;
         }
       }
       L.d4 = bload128(rsD, voff, soff);
@@ -2542,42 +2280,15 @@ static bool slab_all_inside(const tsdf_hip_volume *h, const float T[12]) {
   return all_inside;
 }
 
-// The PLANAR frame (colourless launches; colour launches with knob frame_pairs = 0): the fast kernels read it through ONE
-// buffer descriptor based at the depth image, with the colour image at a 32-bit byte offset from it.  True, and *off (0
-// without colour), when the caller's buffers already lie so: the colour image behind the depth image, within 2 GB.
-// (Colour launches otherwise gather pixel records: k_frame_pairs below.)
-static bool frame_bgra_offset(const tsdf_params &p, const float *d_depth, const uint32_t *d_bgra, unsigned *off) {
-  *off = 0;
-  if (!p.integrate_color) return true;
+// Do a colour launch's two images form [depth | bgra]: the colour image behind the depth image, within 2 GB?  No kernel
+// needs that layout; a colour image that lies otherwise ends a staged frame (include/tsdf_hip.h, tsdf_hip_organize).
+static bool frame_is_planar(const tsdf_params &p, const float *d_depth, const uint32_t *d_bgra) {
   const size_t npx = (size_t)p.image_width * p.image_height;
   const char *zd = (const char *)d_depth, *cb = (const char *)d_bgra;
-  if (!(cb >= zd + npx * 4 && (size_t)(cb - zd) + npx * 4 < (1ull << 31))) return false;
-  *off = (unsigned)(cb - zd);
-  return true;
+  return cb >= zd + npx * 4 && (size_t)(cb - zd) + npx * 4 < (1ull << 31);
 }
 
-// ... the question alone: do the caller's two images already form a planar frame?
-static bool frame_is_planar(const tsdf_params &p, const float *d_depth, const uint32_t *d_bgra) {
-  unsigned off;
-  return frame_bgra_offset(p, d_depth, d_bgra, &off);
-}
-
-// Frame staging: caller buffers laid out otherwise are copied into the handle's [depth | bgra] allocation first (two
-// device copies of 1.2 MB each at 640x480), and *d_depth then points there.
-static int stage_frame(tsdf_handle h, const float **d_depth, const uint32_t *d_bgra, unsigned *bgra_off) {
-  if (frame_bgra_offset(h->p, *d_depth, d_bgra, bgra_off)) return TSDF_HIP_OK;
-  const size_t npx = (size_t)h->p.image_width * h->p.image_height;
-  h->frame_staged = 0;  // the repack overwrites what tsdf_hip_organize left there
-  if (*d_depth != h->frame_depth)
-    TSDF_HIP_TRY(hipMemcpyAsync(h->frame_depth, *d_depth, npx * 4, hipMemcpyDeviceToDevice, h->stream));
-  if (d_bgra != h->frame_bgra)
-    TSDF_HIP_TRY(hipMemcpyAsync(h->frame_bgra, d_bgra, npx * 4, hipMemcpyDeviceToDevice, h->stream));
-  *d_depth = h->frame_depth;
-  *bgra_off = (unsigned)(npx * 4);
-  return TSDF_HIP_OK;
-}
-
-// The frame as 8-byte pixel records {depth bits, bgra} for the colour fast kernels (PAIRS): one pass over the frame per call
+// The frame as 8-byte pixel records {depth bits, bgra} for the colour fast kernels: one pass over the frame per call
 // (2.4 MB read, 2.4 MB written at 640x480) against a kernel that gathers each pixel thousands of times.  BITS are copied --
 // integer loads, so NaN payloads and the alpha byte arrive untouched -- two pixels per thread, one 16-byte store.
 static __global__ void __launch_bounds__(256)
@@ -2594,7 +2305,7 @@ k_frame_pairs(const uint32_t *__restrict__ depth, const uint32_t *__restrict__ b
 
 static int launch_frame_pairs(tsdf_handle h, const float *d_depth, const uint32_t *d_bgra, uint2 *out) {
   const unsigned npix = (unsigned)h->p.image_width * (unsigned)h->p.image_height;
-  if (!out || !d_depth || !d_bgra) {  // (an error, never a quiet return to the planar frame)
+  if (!out || !d_depth || !d_bgra) {
     tsdf_set_error("colour launch without its pixel-record buffer or frame");
     return TSDF_HIP_E_INVALID;
   }
@@ -2604,15 +2315,8 @@ static int launch_frame_pairs(tsdf_handle h, const float *d_depth, const uint32_
   return TSDF_HIP_OK;
 }
 
-// The colour fast kernels read pixel records unless the knob says otherwise: tsdf_hip_create allocates both record buffers
-// for every handle with integrate_color (or fails), so there is no third case in which a launch could fall back quietly
-static bool frame_pairs_apply(tsdf_handle h) { return tsdf_tuning().frame_pairs && h->p.integrate_color; }
-
-// planes fastest when the frame outgrows an XCD's L2 (knob zfast: -1 auto, 0 / 1 force)
-static int zfast_for(const tsdf_params &p, unsigned gx) {
-  const size_t frame_bytes = (size_t)p.image_width * p.image_height * (p.integrate_color ? 8 : 4);
-  return tsdf_tuning().zfast < 0 ? (frame_bytes > (3u << 20) && gx <= 65535u) : (tsdf_tuning().zfast != 0 && gx <= 65535u);
-}
+// planes fastest in the hardware grid (knob zfast: 1 on, 0 off), where the x chunks fit a grid's z extent
+static int zfast_for(unsigned gx) { return tsdf_tuning().zfast != 0 && gx <= 65535u; }
 
 // The kernels keep the "band seen" flags per block in LDS with block-local row groups: they are the volume's row groups
 // only if every block starts on a multiple of 4 rows (always, unless the rows_per_block knob was turned below 4);
@@ -2623,11 +2327,11 @@ static uint8_t *band_flags_for(tsdf_handle h, const IntegrateArgs &a) {
   return band;
 }
 
-// The software-pipelined row loop (k_integrate_p / k_integrate_pc): ALLIN, PACKED, every block's rows present, resting
-// hinge (knob pipe: bit 0 = without colour, k_integrate_p; bit 1 = with colour, k_integrate_pc).
-static bool pipelined_rows_apply(tsdf_handle h, const IntegrateArgs &a, bool color, bool fastproj, bool allin, bool live) {
-  return (tsdf_tuning().pipe & (color ? 2 : 1)) && fastproj && allin && !live && h->packed && a.hinge_fixed && a.neg_in_window &&
-         a.ny % a.TY == 0;
+// The software-pipelined row loop (k_integrate_p): no colour, ALLIN, PACKED, every block's rows present, resting hinge
+// (knob pipe, bit 0).
+static bool pipelined_rows_apply(tsdf_handle h, const IntegrateArgs &a, bool fastproj, bool allin, bool live) {
+  return (tsdf_tuning().pipe & 1) && !h->p.integrate_color && fastproj && allin && !live && h->packed && a.hinge_fixed &&
+         a.neg_in_window && a.ny % a.TY == 0;
 }
 
 // The plain family: k_integrate_plain (plain_mode 1-4) or, plain_mode 0, the kernels of the handle's own colour mode
@@ -2842,35 +2546,30 @@ static int plan_live(tsdf_handle h, const float T[12], bool all_inside, bool rc_
   return pl.nothing_observable ? TSDF_HIP_OK : launch_rows_and_cull(h, T, rc_rows, pl);
 }
 
-// Dispatch: the instance of k_integrate (or, `pipe`, of the pipelined kernels) for this launch.
+// Dispatch: the instance of k_integrate (or, `pipe`, of k_integrate_p) for this launch.  With colour d_depth holds pixel records.
 static void dispatch_fast(tsdf_handle h, const LaunchPlan &pl, const float *d_depth, bool count, bool fastproj, bool allin,
-                          bool pipe, bool pairs, uint8_t *band_arg) {
+                          bool pipe, uint8_t *band_arg) {
   const IntegrateArgs &a = pl.a;
   const dim3 grid(a.zfast ? pl.gz : pl.gx, pl.gy, a.zfast ? pl.gx : pl.gz), block(256);
   const bool sse = h->p.xform_order == TSDF_XFORM_PCL_SSE, color = h->p.integrate_color != 0;
-  pairs = pairs && color;  // (`pairs`: d_depth holds pixel records)
   if (pipe) {
     with_consts(
-        [&](auto SSE, auto COUNT, auto PAIRS) {
-          if (color)
-            hipLaunchKernelGGL((k_integrate_pc<xform_order_of(SSE), COUNT, PAIRS>), grid, block, 0, h->stream, a, pl.D, pl.RGB, d_depth,
-                               h->cam64, pl.ctrx, pl.ctry, h->ctr[2], h->counter, band_arg);
-          else if constexpr (!PAIRS)
-            hipLaunchKernelGGL((k_integrate_p<xform_order_of(SSE), COUNT>), grid, block, 0, h->stream, a, pl.D, pl.K8, d_depth,
-                               h->cam64, pl.ctrx, pl.ctry, h->ctr[2], h->counter, band_arg);
+        [&](auto SSE, auto COUNT) {
+          hipLaunchKernelGGL((k_integrate_p<xform_order_of(SSE), COUNT>), grid, block, 0, h->stream, a, pl.D, pl.K8, d_depth,
+                             h->cam64, pl.ctrx, pl.ctry, h->ctr[2], h->counter, band_arg);
         },
-        sse, count, pairs);
+        sse, count);
     return;
   }
   with_consts(
-      [&](auto SSE, auto COLOR, auto FASTPROJ, auto COUNT, auto PACKED, auto ALLIN, auto LIVE, auto PAIRS) {
-        // (never built: ALLIN without the fast projection, ALLIN with LIVE, pixel records without colour)
-        if constexpr (!(ALLIN && (!FASTPROJ || LIVE)) && !(PAIRS && !COLOR))
-          hipLaunchKernelGGL((k_integrate<xform_order_of(SSE), COLOR, FASTPROJ, COUNT, PACKED, ALLIN, LIVE, PAIRS>), grid, block, 0,
+      [&](auto SSE, auto COLOR, auto FASTPROJ, auto COUNT, auto PACKED, auto ALLIN, auto LIVE) {
+        // (never built: ALLIN without the fast projection, ALLIN with LIVE)
+        if constexpr (!(ALLIN && (!FASTPROJ || LIVE)))
+          hipLaunchKernelGGL((k_integrate<xform_order_of(SSE), COLOR, FASTPROJ, COUNT, PACKED, ALLIN, LIVE>), grid, block, 0,
                              h->stream, a, pl.D, pl.Wt, pl.RGB, pl.K8, d_depth, h->cam64, pl.ctrx, pl.ctry, h->ctr[2], h->counter,
                              pl.live, band_arg, h->row_iv);
       },
-      sse, color, fastproj, count, h->packed, allin, pl.live != nullptr, pairs);
+      sse, color, fastproj, count, h->packed, allin, pl.live != nullptr);
 }
 
 // Validation of a launch, in the order the errors have always been reported.
@@ -2915,38 +2614,33 @@ int tsdf_integrate_launch(tsdf_handle h, const float *d_depth, const uint32_t *d
     return launch_plain_family(h, a, pl.gz, plain_mode, d_depth, d_bgra, T, count);
   }
   // Colour: the fast kernels gather pixel records built from the caller's two images wherever they lie (k_frame_pairs, queued
-  // right in front of the kernel below) -- no repack into [depth | bgra]; a staged frame ends where the repack would have
-  // ended it.  Without colour, or with the knob off: the planar frame.
-  const bool pairs = frame_pairs_apply(h);
-  if (pairs) {
-    if (!frame_is_planar(h->p, d_depth, d_bgra)) h->frame_staged = 0;
-    a.bgra_off = 0;  // (the record instances do not read it)
-  } else if (const int e = stage_frame(h, &d_depth, d_bgra, &a.bgra_off)) {
-    return e;
-  }
+  // right in front of the kernel below); a colour image that does not lie behind its depth image ends a staged frame
+  // (include/tsdf_hip.h, tsdf_hip_organize).  Without colour: the depth plane itself.
+  const bool color = h->p.integrate_color != 0;
+  if (color && !frame_is_planar(h->p, d_depth, d_bgra)) h->frame_staged = 0;
   const LaunchKind kind = launch_kind(h, T, a, rc, rc_rows);
   if (kind.live)
     if (const int e = plan_live(h, T, kind.all_inside, rc_rows, pl)) return e;
   if (count) TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, TSDF_CNT_SLOTS * sizeof(unsigned long long), h->stream));
   const bool pose_ok = pose_is_finite(T);
-  const bool fastproj = fast_projection_ok(hh, h->p.integrate_color != 0);
+  const bool fastproj = fast_projection_ok(hh, color);
   h->last_launch[0] = h->last_launch[1] = h->last_launch[2] = h->last_launch[3] = 0;
   uint8_t *band_arg = band_flags_for(h, a);
   a.implied_d = implied_distances(h, a, band_arg != nullptr);
   h->last_implied_on = a.implied_d != 0;
   if (pose_ok && !pl.nothing_observable) {
     const bool live = pl.live != nullptr, allin = fastproj && kind.allin && !live;
-    const bool pipe = pipelined_rows_apply(h, a, h->p.integrate_color != 0, fastproj, kind.allin, live);
-    a.zfast = zfast_for(h->p, pl.gx);
+    const bool pipe = pipelined_rows_apply(h, a, fastproj, kind.allin, live);
+    a.zfast = zfast_for(pl.gx);
     h->last_launch[0] = (allin ? 1 : 0) | (pipe ? 0x100 : 0);  // bit 8: the pipelined row loop
     h->last_launch[1] = fastproj;
     h->last_launch[2] = live ? (rc_rows ? 2 : 1) : 0;
     h->last_launch[3] = (int)std::min<uint64_t>((uint64_t)pl.gx * pl.gy * pl.gz, 0x7fffffffu);
-    if (pairs) {
+    if (color) {
       if (const int e = launch_frame_pairs(h, d_depth, d_bgra, h->frame_pairs[0])) return e;
       d_depth = reinterpret_cast<const float *>(h->frame_pairs[0]);
     }
-    dispatch_fast(h, pl, d_depth, count, fastproj, allin, pipe, pairs, band_arg);
+    dispatch_fast(h, pl, d_depth, count, fastproj, allin, pipe, band_arg);
     TSDF_HIP_TRY(hipGetLastError());
   }
   h->count_slots = count ? TSDF_CNT_SLOTS : 0;
@@ -3024,14 +2718,12 @@ int tsdf_integrate_launch2(tsdf_handle h, const float *dA, const uint32_t *cA, c
   // both poses pass fusable_pose (fast projection; the slab all inside with its margins; a reference cull that keeps the
   // whole slab, so no row intervals) on a PACKED handle whose grid and weights admit ALLIN under cull = 1 -- which is
   // launch_kind's allin && !live.  (The predicate also asks for h->packed, which `ok` requires anyway.)
-  // Colour: both frames as pixel records (k_frame_pairs; the callers' images may lie anywhere), else as [depth | bgra] in place
-  const bool pairs = frame_pairs_apply(h);
-  a.bgra_off = fb.bgra_off = 0;  // (set below for a planar pair; the record instances do not read them)
-  const bool pipe_wins = !color && tsdf_tuning().fuse2 == 1 && pipelined_rows_apply(h, a, color, true, true, false);
+  // Colour: both frames as pixel records (k_frame_pairs; the callers' images may lie anywhere)
+  const bool pipe_wins = !color && tsdf_tuning().fuse2 == 1 && pipelined_rows_apply(h, a, true, true, false);
   const bool ok = tsdf_tuning().fuse2 && !pipe_wins && tsdf_tuning().cull == 1 && tsdf_tuning().allin && h->packed && !h->cn[0] && !h->weight_by_depth &&
                   !h->weight_by_variance && !tsdf_tuning().plain_kernel && (h->nx & 3) == 0 && a.wmax_is_int && (float)h->kmax == p.max_weight &&
                   pl.gy <= 65535u && pl.gz <= 65535u && pl.gz > 0 &&
-                  (pairs || (frame_bgra_offset(p, dA, cA, &a.bgra_off) && frame_bgra_offset(p, dB, cB, &fb.bgra_off))) && fusable_pose(h, hh, TA, planesA) && fusable_pose(h, hh, TB, planesB);
+                  fusable_pose(h, hh, TA, planesA) && fusable_pose(h, hh, TB, planesB);
   if (fused) *fused = ok;
   if (!ok) {  // two launches, each with its own planes; with `count` the first one's counters are read before the second runs
     int rc = tsdf_hip_set_reference_cull(h, planesA);
@@ -3058,22 +2750,21 @@ int tsdf_integrate_launch2(tsdf_handle h, const float *dA, const uint32_t *cA, c
   h->last_implied_on = false;
   h->last_launch[0] = 2, h->last_launch[1] = 1, h->last_launch[2] = 0;
   h->last_launch[3] = (int)std::min<uint64_t>((uint64_t)pl.gx * pl.gy * pl.gz, 0x7fffffffu);
-  a.zfast = zfast_for(p, pl.gx);
+  a.zfast = zfast_for(pl.gx);
   const dim3 grid(a.zfast ? pl.gz : pl.gx, pl.gy, a.zfast ? pl.gx : pl.gz), block(256);
-  if (pairs) {
-    // (a staged frame ends where the two launches' repack would have ended it: include/tsdf_hip.h, tsdf_hip_organize)
+  if (color) {
+    // (a staged frame ends where the two launches would have ended it: include/tsdf_hip.h, tsdf_hip_organize)
     if (!frame_is_planar(p, dA, cA) || !frame_is_planar(p, dB, cB)) h->frame_staged = 0;
     if (const int e = launch_frame_pairs(h, dA, cA, h->frame_pairs[0])) return e;
     if (const int e = launch_frame_pairs(h, dB, cB, h->frame_pairs[1])) return e;
     dA = reinterpret_cast<const float *>(h->frame_pairs[0]), dB = reinterpret_cast<const float *>(h->frame_pairs[1]);
   }
   with_consts(
-      [&](auto SSE, auto COLOR, auto COUNT, auto PAIRS) {
-        if constexpr (!(PAIRS && !COLOR))
-          hipLaunchKernelGGL((k_integrate2<xform_order_of(SSE), COLOR, COUNT, PAIRS>), grid, block, 0, h->stream, a, fb, h->d, h->rgb, h->k8,
-                             dA, dB, h->cam64, h->ctr[0], h->ctr[1], h->ctr[2], h->counter, band_arg);
+      [&](auto SSE, auto COLOR, auto COUNT) {
+        hipLaunchKernelGGL((k_integrate2<xform_order_of(SSE), COLOR, COUNT>), grid, block, 0, h->stream, a, fb, h->d, h->rgb, h->k8,
+                           dA, dB, h->cam64, h->ctr[0], h->ctr[1], h->ctr[2], h->counter, band_arg);
       },
-      p.xform_order == TSDF_XFORM_PCL_SSE, color, count, pairs);
+      p.xform_order == TSDF_XFORM_PCL_SSE, color, count);
   TSDF_HIP_TRY(hipGetLastError());
   h->count_slots = count ? TSDF_CNT2_SLOTS : 0;
   h->count_ran = true;

@@ -77,7 +77,7 @@ struct OccArgs {
 #define OCC_BYTE_SLOTS 64  // counters[2 ..]: requested bytes, striped (one address for every block costs milliseconds)
 
 // Which quads may the scan leave unread?  A voxel is listed iff w > 0 && |d| < 1.  While tsdf_hip_volume::band_exact holds,
-// every distance of an owned plane is what the flag-keeping integrate kernels (k_integrate, k_integrate_p / _pc, k_integrate2)
+// every distance of an owned plane is what the flag-keeping integrate kernels (k_integrate, k_integrate_p, k_integrate2)
 // made of the reset value -1, and a flag of 0 says that no launch since the reset observed a voxel of that 64 x 4 x 1 cell
 // with `act && !(raw > pos)` (any_div in tsdf_integrate.hip: each of those kernels sets the cell's flag in every branch that
 // updates a distance with any_div true -- the fast ladder and the IEEE fallback alike -- and a wave only rests its distances

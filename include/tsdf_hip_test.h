@@ -82,8 +82,9 @@ int tsdf_hip_selftest_read_sweep(tsdf_handle h, int stride_bytes, uint64_t *span
 int tsdf_hip_selftest_occupancy_mc(int out[2]);
 
 /* Test / A-B hook: set a launch-shape knob ("rows_per_block", "blocks_per_cu", "fast_projection",
- * "mc_flush_at", "mc_skip", "cull", "vol_chunk", "plain_kernel", "alloc_tries", "allin", "refcull_plain", "live_log2tx", "fuse2", "lab_chunk", "frame_pairs" -- the
- * TSDF_HIP_* environment variables, which the product library reads once) at run time.  No knob changes results. */
+ * "mc_flush_at", "mc_skip", "cull", "vol_chunk", "plain_kernel", "alloc_tries", "allin", "refcull_plain", "live_log2tx", "fuse2", "lab_chunk", "implied_d", "pipe", "zfast" -- the
+ * TSDF_HIP_* environment variables, which the product library reads once) at run time.  No knob changes results.
+ * The name of the removed knob "frame_pairs" is still accepted and does nothing; any other unknown name is TSDF_HIP_E_INVALID. */
 int tsdf_hip_set_tuning(const char *name, int value);
 
 /* Test hook: position-dependent 64-bit checksums of the handle's OWNED planes, computed on the device (sum over the words

@@ -22,7 +22,6 @@ CASES = {
     "k_integrate f32w": (False, capi.LAYOUT_F32W, 0, 1, False, (1, False, False)),
     "k_integrate live": (True, capi.LAYOUT_PACKED, 0, 1, True, (0, False, True)),
     "k_integrate_p": (False, capi.LAYOUT_PACKED, 1, 1, False, (1, True, False)),
-    "k_integrate_pc": (True, capi.LAYOUT_PACKED, 3, 1, False, (1, True, False)),
     "k_integrate2": (False, capi.LAYOUT_PACKED, 1, 2, False, (2, False, False)),
     "k_integrate2 colour": (True, capi.LAYOUT_PACKED, 1, 2, False, (2, False, False)),
 }

@@ -47,7 +47,7 @@ def main():
         if rng.rand() < 0.3:   # a box of cubic voxels: other counts along y and z (the bench's slabs are such grids)
             res3 = (res, int(rng.choice([res // 2, res, res + 8])), int(rng.choice([res // 2, res + 24])))
         size3 = tuple(size * r / res for r in res3)
-        # round 6: about a third of the cases sit where the software-pipelined row loop applies (k_integrate_p / _pc: the
+        # round 6: about a third of the cases sit where the software-pipelined row loop applies (k_integrate_p: the
         # PACKED layout with an integer weight limit, equal truncation limits, every voxel in range and in the image)
         friendly = bool(rng.rand() < 0.35)
         if friendly:
@@ -80,10 +80,10 @@ def main():
             v.setCameraIntrinsics(fx, fy, cx, cy)
         # round 6: the launch knobs that pick between the plain and the software-pipelined row loop and the block height, and
         # frame pairing through the pinned ring (two frames per sweep where both poses see the whole slab)
-        knobs = {"pipe": int(rng.choice([0, 1, 3])), "rows_per_block": int(rng.choice([8, 16, 32, 64])), "fuse2": int(rng.choice([1, 2]))}
+        knobs = {"pipe": int(rng.choice([0, 1, 1])), "rows_per_block": int(rng.choice([8, 16, 32, 64])), "fuse2": int(rng.choice([1, 2]))}
         pairing = bool(rng.rand() < 0.35)
-        if friendly and rng.rand() < 0.8:   # most of the friendly cases really take the pipelined loop, colour included (bit 1)
-            knobs["pipe"], pairing = 3, False
+        if friendly and rng.rand() < 0.8:   # most of the colourless friendly cases really take the pipelined loop
+            knobs["pipe"], pairing = 1, False
         for k, val in knobs.items():
             capi.set_tuning(k, val)
         v.reset()

@@ -60,4 +60,4 @@ def test_timed_kernel_instances_stay_within_their_register_budget():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_guard.py"), "--check"], cwd=ROOT, text=True,
                          capture_output=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert out.stdout.count("ok ") == 6 and "BAD" not in out.stdout, out.stdout  # (4 instances until round 5; + k_integrate_p, k_integrate_pc)
+    assert out.stdout.count("ok ") == 5 and "BAD" not in out.stdout, out.stdout  # (4 instances until round 5; + k_integrate_p)

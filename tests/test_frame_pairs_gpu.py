@@ -1,11 +1,11 @@
-"""GPU tier: the frame as 8-byte pixel records (k_frame_pairs + the PAIRS instances of k_integrate, k_integrate_pc and
-k_integrate2, cpu_tsdf_amd/csrc/tsdf_integrate.hip; knob frame_pairs).
+"""GPU tier: the frame as 8-byte pixel records (k_frame_pairs + the colour instances of k_integrate and k_integrate2,
+cpu_tsdf_amd/csrc/tsdf_integrate.hip).
 
 The colour fast kernels gather {depth, bgra} of a pixel with one 8-byte load from records the handle builds from the caller's
-two images right before the launch, instead of two 4-byte loads from the planar frame.  The bits loaded are the same, so the
-bar is bit equality everywhere: the record pass against numpy, and knob on == knob off == the CPU oracle (the reference's
-integrateCloud, include/cpu_tsdf/impl/tsdf_volume_octree.hpp:48-218) for every instance that reads records, on the smallest
-grid that still has several wave-rows per block (64 x 16 x 8 voxels, a 33 x 17 image: odd width, odd pixel count)."""
+two images right before the launch.  The bar is bit equality everywhere: the record pass against numpy, and the CPU oracle
+(the reference's integrateCloud, include/cpu_tsdf/impl/tsdf_volume_octree.hpp:48-218) for every instance that reads records,
+on the smallest grid that still has several wave-rows per block (64 x 16 x 8 voxels, a 33 x 17 image: odd width, odd pixel
+count)."""
 import ctypes as C
 
 import numpy as np
@@ -26,7 +26,7 @@ _U32P = C.POINTER(C.c_uint32)
 @pytest.fixture(autouse=True)
 def _knobs_back(gpu):
     yield
-    for name, value in (("frame_pairs", 1), ("pipe", 1), ("fuse2", 1), ("cull", 1), ("allin", 1), ("plain_kernel", 0)):
+    for name, value in (("pipe", 1), ("fuse2", 1), ("cull", 1), ("allin", 1), ("plain_kernel", 0)):
         capi.set_tuning(name, value)
 
 
@@ -105,13 +105,12 @@ def test_k_frame_pairs_interleaves_bits_and_leaves_the_images_alone(gpu, w, h):
     assert not out[0::2][~inside].any() and not out[1::2][~inside].any()
 
 
-# ---- knob on == knob off == oracle, per instance -----------------------------------------------------------------------
+# ---- records == oracle, per instance ---------------------------------------------------------------------------------
 
-def run_single(kind, knob):
+def run_single(kind):
     """Four frames through the single-frame entry point: three through the instance `kind` names, the fourth through its
-    counting twin (the observed-voxel count).  Returns the planes' bits and the counts."""
-    capi.set_tuning("frame_pairs", knob)
-    capi.set_tuning("pipe", 3 if kind == "pc" else 0)
+    counting twin (the observed-voxel count)."""
+    capi.set_tuning("pipe", 0)
     capi.set_tuning("cull", 0 if kind == "general" else 1)
     vol, sc = small_volume()
     if kind == "general":
@@ -126,29 +125,26 @@ def run_single(kind, knob):
         want = ov.integrate(dep, col, T) if kind == "general" else ov.integrate_culled(dep, col, tr, T)
         got = vol.integrateCloud(dep, col, tr, count=count)
         if count:
-            assert got == want, (kind, knob, i, got, want)
-            counts.append(got)
+            assert got == want, (kind, i, got, want)
         info = launch_info(vol)
-        expect = {"allin": (1, 0, False), "count": (1, 0, False), "pc": (1, 0, True), "general": (0, 0, False), "live": (0, 2, False)}[kind]
-        assert (info[0], info[2], info[4]) == expect and info[1] == 1, (kind, knob, i, info)
-    bits = planes_equal(vol, ov, f"{kind}, frame_pairs = {knob}")
+        expect = {"allin": (1, 0, False), "count": (1, 0, False), "general": (0, 0, False), "live": (0, 2, False)}[kind]
+        assert (info[0], info[2], info[4]) == expect and info[1] == 1, (kind, i, info)
+    planes_equal(vol, ov, kind)
     assert ov.w.max() == 4 and (ov.w > 0).mean() > 0.2 and (np.abs(ov.d) < 1).sum() > 100  # counts reach 4, a band exists
     vol.close()
-    return bits, counts
 
 
-@pytest.mark.parametrize("kind", ["allin", "count", "general", "live", "pc"])
+@pytest.mark.parametrize("kind", ["allin", "count", "general", "live"])
 def test_records_and_planar_frame_give_the_oracles_voxels(gpu, kind):
-    on, off = run_single(kind, 1), run_single(kind, 0)
-    assert on[1] == off[1] and all(np.array_equal(a, b) for a, b in zip(on[0], off[0]))
+    """(The planar gather the name recalls is gone: the oracle is the bar.)"""
+    run_single(kind)
 
 
-def run_pairs(knob, poses, expect_fused):
-    capi.set_tuning("frame_pairs", knob)
+def run_pairs(poses, expect_fused):
     capi.set_tuning("fuse2", 2)
     vol, sc = small_volume()
     ov = OracleVolume(vol._p)
-    keep, counts = [], []
+    keep = []
     for k in range(2):
         pair, want = [], []
         for i in (2 * k, 2 * k + 1):
@@ -159,16 +155,14 @@ def run_pairs(knob, poses, expect_fused):
             pair.append((t[0].data_ptr(), t[1].data_ptr(), tr))
             want.append(ov.integrate_culled(dep, col, tr, synth.cam_from_vol_f32(tr)))
         fused, got = vol.integrateCloudDevice2(pair[0], pair[1], count=(k == 1))
-        assert fused == expect_fused[k], (knob, k, fused, launch_info(vol))
+        assert fused == expect_fused[k], (k, fused, launch_info(vol))
         if fused:
             assert launch_info(vol)[0] == 2
         if got is not None:
-            assert got == want, (knob, k, got, want)
-            counts.append(got)
+            assert got == want, (k, got, want)
     vol.synchronize()
-    bits = planes_equal(vol, ov, f"pairs, frame_pairs = {knob}")
+    planes_equal(vol, ov, "pairs")
     vol.close()
-    return bits, counts
 
 
 @pytest.mark.parametrize("fallback", [False, True])
@@ -176,8 +170,7 @@ def test_two_frames_per_sweep_from_records(gpu, fallback):
     """k_integrate2 with both frames as records; and a pair one of whose poses does not see the whole grid: two launches."""
     poses = (lambda i: pose_close(i) if i == 1 else pose_outside(i)) if fallback else pose_outside
     expect = [False, True] if fallback else [True, True]
-    on, off = run_pairs(1, poses, expect), run_pairs(0, poses, expect)
-    assert on[1] == off[1] and all(np.array_equal(a, b) for a, b in zip(on[0], off[0]))
+    run_pairs(poses, expect)
 
 
 # ---- the first and the last pixel ------------------------------------------------------------------------------------
@@ -185,28 +178,24 @@ def test_two_frames_per_sweep_from_records(gpu, fallback):
 def test_first_and_last_pixel_with_nan_depth_there(gpu):
     """A pose from which voxels project to pixel 0 and to pixel W*H - 1 (checked below on the centres), a frame whose depth is
     NaN at exactly those two pixels, then frames with a depth there."""
-    planes = {}
-    for knob in (1, 0):
-        capi.set_tuning("frame_pairs", knob)
-        vol, sc = small_volume()
-        ov = OracleVolume(vol._p)
-        tr = pose_close(1)
-        T = synth.cam_from_vol_f32(tr).reshape(3, 4).astype(np.float64)
-        cx_, cy_, cz_ = (ov.centers(a).astype(np.float64) for a in range(3))
-        g = np.stack(np.meshgrid(cx_, cy_, cz_, indexing="ij"), -1).reshape(-1, 3) @ T[:, :3].T + T[:, 3]
-        u = np.trunc(g[:, 0] * sc.fx / g[:, 2] + sc.cx).astype(np.int64)
-        v = np.trunc(g[:, 1] * sc.fy / g[:, 2] + sc.cy).astype(np.int64)
-        ok = (g[:, 0] * sc.fx / g[:, 2] + sc.cx > 0.01) & (g[:, 1] * sc.fy / g[:, 2] + sc.cy > 0.01)  # (not the cell (-1, 0) that truncates to 0)
-        assert ((u == 0) & (v == 0) & ok).any() and ((u == W - 1) & (v == H - 1)).any()
-        assert ((u < 0) | (u >= W)).any()  # ... and some fall outside: pixel -1
-        for i in range(3):
-            dep, col = frame_for(tr, 300 + i)
-            dep[0, 0] = dep[H - 1, W - 1] = np.nan if i == 0 else dep[1, 1]
-            assert vol.integrateCloud(dep, col, tr, count=True) == ov.integrate_culled(dep, col, tr, synth.cam_from_vol_f32(tr))
-            assert launch_info(vol)[0] == 0
-        planes[knob] = planes_equal(vol, ov, f"pixel extremes, frame_pairs = {knob}")
-        vol.close()
-    assert all(np.array_equal(a, b) for a, b in zip(planes[1], planes[0]))
+    vol, sc = small_volume()
+    ov = OracleVolume(vol._p)
+    tr = pose_close(1)
+    T = synth.cam_from_vol_f32(tr).reshape(3, 4).astype(np.float64)
+    cx_, cy_, cz_ = (ov.centers(a).astype(np.float64) for a in range(3))
+    g = np.stack(np.meshgrid(cx_, cy_, cz_, indexing="ij"), -1).reshape(-1, 3) @ T[:, :3].T + T[:, 3]
+    u = np.trunc(g[:, 0] * sc.fx / g[:, 2] + sc.cx).astype(np.int64)
+    v = np.trunc(g[:, 1] * sc.fy / g[:, 2] + sc.cy).astype(np.int64)
+    ok = (g[:, 0] * sc.fx / g[:, 2] + sc.cx > 0.01) & (g[:, 1] * sc.fy / g[:, 2] + sc.cy > 0.01)  # (not the cell (-1, 0) that truncates to 0)
+    assert ((u == 0) & (v == 0) & ok).any() and ((u == W - 1) & (v == H - 1)).any()
+    assert ((u < 0) | (u >= W)).any()  # ... and some fall outside: pixel -1
+    for i in range(3):
+        dep, col = frame_for(tr, 300 + i)
+        dep[0, 0] = dep[H - 1, W - 1] = np.nan if i == 0 else dep[1, 1]
+        assert vol.integrateCloud(dep, col, tr, count=True) == ov.integrate_culled(dep, col, tr, synth.cam_from_vol_f32(tr))
+        assert launch_info(vol)[0] == 0
+    planes_equal(vol, ov, "pixel extremes")
+    vol.close()
 
 
 # ---- where the caller's two images lie --------------------------------------------------------------------------------

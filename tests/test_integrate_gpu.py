@@ -748,9 +748,9 @@ def test_every_reachable_k_integrate_instance_equals_the_oracle(gpu):
         # k_integrate_p (the software-pipelined row loop: ALLIN, PACKED, no colour): transform order x counting
         capi.set_tuning("fast_projection", 1)
         capi.set_tuning("allin", 1)
-        capi.set_tuning("pipe", 3)
+        capi.set_tuning("pipe", 1)
+        color = False
         for order in (0, 1):
-          for color in (False, True):  # k_integrate_p / k_integrate_pc
             vol, sc = make_volume(res, W, H, color=color, order=order, max_weight=100.0)
             vol.reset()
             ov = OracleVolume(vol._p)
@@ -802,17 +802,16 @@ def test_every_reachable_k_integrate_instance_equals_the_oracle(gpu):
         capi.set_tuning("pipe", 1)
         capi.set_tuning("fuse2", 1)
     # 8 x {certified: general, ALLIN, row intervals (camera inside), row intervals (cull); exact projection: the same without
-    # ALLIN} x counting or not: all 80 k_integrate instances (the row-interval one twice) + the 4 + 4 of k_integrate_p /
-    # k_integrate_pc + the 8 of k_integrate2
-    assert len(hit) == 2 * 2 * 2 * 2 * (4 + 3) + 8 + 8, len(hit)
+    # ALLIN} x counting or not: all 80 k_integrate instances (the row-interval one twice) + the 4 of k_integrate_p + the 8 of
+    # k_integrate2
+    assert len(hit) == 2 * 2 * 2 * 2 * (4 + 3) + 4 + 8, len(hit)
 
 
-@pytest.mark.parametrize("color", [False, True], ids=["k_integrate_p", "k_integrate_pc"])
+@pytest.mark.parametrize("color", [False], ids=["k_integrate_p"])
 @pytest.mark.parametrize("rows_per_block", [8, 16, 24, 32, 40, 48, 64, 96])
 def test_pipelined_row_loop_equals_the_oracle_and_the_plain_row_loop(gpu, rows_per_block, color):
-    """k_integrate_p / k_integrate_pc (round 6: two rows in flight per wave, stage A = projection + every load of a row, stage
-    B = update + stores; with colour the voxel words are asked by a predictor two rows back, an observed quad it missed asks
-    late) on a 96^3 grid, whose blocks walk 1, 2, 3, 4, 5, 6, 8 or 12 row steps (TY = 8 rows per step; with 5 and 8 the grid's last
+    """k_integrate_p (round 6: two rows in flight per wave, stage A = projection + every load of a row, stage
+    B = update + stores) on a 96^3 grid, whose blocks walk 1, 2, 3, 4, 5, 6, 8 or 12 row steps (TY = 8 rows per step; with 5 and 8 the grid's last
     block is SHORTER than the others: 16 of 40 rows, 32 of 64): the tail of
     one row, of a pair, the odd tail behind the steady-state loop and the loop itself -- noisy depth with NaN holes, frames
     past the weight limit (max_weight 4), counting on alternate frames -- against the oracle voxel for voxel, against
@@ -821,7 +820,7 @@ def test_pipelined_row_loop_equals_the_oracle_and_the_plain_row_loop(gpu, rows_p
     outs = []
     try:
         capi.set_tuning("rows_per_block", rows_per_block)
-        for pipe in (3, 0):
+        for pipe in (1, 0):
             capi.set_tuning("pipe", pipe)
             vol, sc = make_volume(96, color=color, max_weight=4.0)
             vol.reset()
@@ -844,7 +843,7 @@ def test_pipelined_row_loop_equals_the_oracle_and_the_plain_row_loop(gpu, rows_p
         assert np.array_equal(outs[0][0][1], outs[1][0][1]) and outs[0][1] == outs[1][1]
         assert (outs[0][0][2] is None and outs[1][0][2] is None) or np.array_equal(outs[0][0][2], outs[1][0][2])
         # 100 rows are no multiple of the 8 rows of a step: the launch takes k_integrate's instance by itself
-        capi.set_tuning("pipe", 3)
+        capi.set_tuning("pipe", 1)
         vol, sc = make_volume(96, color=color, res3=(96, 100, 96))
         vol.reset()
         ov = OracleVolume(vol._p)
@@ -860,10 +859,9 @@ def test_pipelined_row_loop_equals_the_oracle_and_the_plain_row_loop(gpu, rows_p
 
 
 def test_planes_fastest_block_order_changes_nothing(gpu):
-    """Knob zfast (tsdf_block_coords): the hardware grid handed out planes-first -- what a launch uses by itself when the
-    frame outgrows an XCD's L2 (1280x960 + colour) -- against the default order and the oracle: the whole grid in view
-    (ALLIN), a camera inside (row intervals, block flags indexed by logical coordinates), a Z-slab handle on a grid several
-    x chunks wide, counting or not; and a frame big enough to switch it on by itself."""
+    """Knob zfast (tsdf_block_coords): the hardware grid handed out planes-first (the default) against x-chunks-first and the
+    oracle: the whole grid in view (ALLIN), a camera inside (row intervals, block flags indexed by logical coordinates), a
+    Z-slab handle on a grid several x chunks wide, counting or not; and a large frame."""
     outs = {}
     try:
         for zfast in (0, 1):
@@ -897,10 +895,10 @@ def test_planes_fastest_block_order_changes_nothing(gpu):
                 vol.close()
             outs[zfast] = res
     finally:
-        capi.set_tuning("zfast", -1)
+        capi.set_tuning("zfast", 1)
     for (d0, w0), (d1, w1) in zip(outs[0], outs[1]):
         assert np.array_equal(d0.view(np.uint32), d1.view(np.uint32)) and np.array_equal(w0, w1)
-    # a 1024x768 colour frame (6.3 MB) switches the order on by itself
+    # a large frame: 1024x768 + colour (6.3 MB of records)
     vol, sc = make_volume(32, 1024, 768, color=True)
     vol.reset()
     ov = OracleVolume(vol._p)

@@ -111,21 +111,21 @@ def test_general_and_all_inside_instances_equal_the_oracle(gpu, order, color):
                    for count in (True, False)}, sorted(hit)
 
 
-@pytest.mark.parametrize("color", [False, True], ids=["k_integrate_p", "k_integrate_pc"])
+@pytest.mark.parametrize("color", [False, True], ids=["k_integrate_p", "k_integrate"])
 @pytest.mark.parametrize("order", [0, 1])
 @pytest.mark.parametrize("res", [32, 64])
 def test_pipelined_row_loop_instances_equal_the_oracle(gpu, res, order, color):
-    """k_integrate_p / k_integrate_pc, whose row part (s_yt) is filled per block: at 32^3, and at 64^3 where a block walks
-    several row steps and free-space / quiet waves occur."""
+    """Knob pipe on: k_integrate_p without colour, k_integrate's own ALLIN instance with it; their row part (s_yt) is filled
+    per block: at 32^3, and at 64^3 where a block walks several row steps and free-space / quiet waves occur."""
     ov, counts = family_oracle(res, color, order, wmax_of(order))
     hit = set()
     try:
         capi.set_tuning("fast_projection", 1)
         capi.set_tuning("allin", 1)
-        capi.set_tuning("pipe", 3)
+        capi.set_tuning("pipe", 1)
         vol, _ = family_volume(res, color, order, wmax_of(order))
         vol.reset()
-        run_family(vol, res, color, counts, lambda info: info[0] == 1 and info[1] == 1 and info[2] == 0 and info[4], hit, ("kp",))
+        run_family(vol, res, color, counts, lambda info: info[0] == 1 and info[1] == 1 and info[2] == 0 and info[4] == (not color), hit, ("kp",))
         compare(vol, ov)
         vol.close()
     finally:
@@ -179,14 +179,14 @@ def test_forced_and_unforced_instances_agree_plane_for_plane(gpu, color):
     ov, counts = family_oracle(res, color, 0, wmax)
     outs = {}
     try:
-        for name, allin, pipe, rpb in (("allin", 1, 0, 64), ("general", 0, 0, 64), ("pipe", 1, 3, 64), ("pipe rows 8", 1, 3, 8),
+        for name, allin, pipe, rpb in (("allin", 1, 0, 64), ("general", 0, 0, 64), ("pipe", 1, 1, 64), ("pipe rows 8", 1, 1, 8),
                                        ("allin rows 8", 1, 0, 8)):
             capi.set_tuning("allin", allin)
             capi.set_tuning("pipe", pipe)
             capi.set_tuning("rows_per_block", rpb)
             vol, _ = family_volume(res, color, 0, wmax)
             vol.reset()
-            got = run_family(vol, res, color, counts, lambda info: info[0] == allin and info[4] == bool(pipe), tag=(name,))
+            got = run_family(vol, res, color, counts, lambda info: info[0] == allin and info[4] == bool(pipe and not color), tag=(name,))
             compare(vol, ov)
             outs[name] = (vol.download(), got)
             vol.close()

@@ -20,14 +20,12 @@ sys.path.insert(0, ROOT)
 
 # mangled-name prefix -> (what, max VGPRs, max scratch bytes, least occupancy)
 BUDGET = {
-    # (the last template argument of the colour kernels is PAIRS: the instances that gather pixel records, which is what runs
-    # by default; their planar twins -- knob frame_pairs = 0 -- differ in the gather instructions alone)
-    "_ZL11k_integrateILi0ELb1ELb1ELb0ELb1ELb1ELb0ELb1EE": ("k_integrate ALLIN PACKED colour (headline)", 64, 16, 8),
-    "_ZL11k_integrateILi0ELb0ELb1ELb0ELb1ELb1ELb0ELb0EE": ("k_integrate ALLIN PACKED no colour", 64, 16, 8),
+    # (the colour instances gather the frame as 8-byte pixel records, the colourless ones from the depth plane)
+    "_ZL11k_integrateILi0ELb1ELb1ELb0ELb1ELb1ELb0EE": ("k_integrate ALLIN PACKED colour (headline)", 64, 16, 8),
+    "_ZL11k_integrateILi0ELb0ELb1ELb0ELb1ELb1ELb0EE": ("k_integrate ALLIN PACKED no colour", 64, 16, 8),
     "_ZL13k_integrate_pILi0ELb0EE": ("k_integrate_p (software-pipelined rows, no colour)", 64, 16, 8),
-    "_ZL14k_integrate_pcILi0ELb0ELb1EE": ("k_integrate_pc (software-pipelined rows, colour: opt-in)", 96, 0, 5),
-    "_ZL12k_integrate2ILi0ELb1ELb0ELb1EE": ("k_integrate2 colour", 96, 0, 5),
-    "_ZL12k_integrate2ILi0ELb0ELb0ELb0EE": ("k_integrate2 no colour", 96, 0, 5),
+    "_ZL12k_integrate2ILi0ELb1ELb0EE": ("k_integrate2 colour", 96, 0, 5),
+    "_ZL12k_integrate2ILi0ELb0ELb0EE": ("k_integrate2 no colour", 96, 0, 5),
 }
 
 
