@@ -128,8 +128,7 @@ static int align_launch(tsdf_handle h, const float *d_xyz, size_t n, const doubl
   }
   a.min_weight = min_weight;
   a.r_max = r_max;
-  for (int i = 0; i < 2; ++i)
-    if (!h->align_ev[i]) TSDF_HIP_TRY(hipEventCreate(&h->align_ev[i]));
+  if (const int rc = h->align_ev.ensure(2)) return rc;
   const unsigned grid = align_grid(n);
   TSDF_HIP_TRY(hipEventRecord(h->align_ev[0], h->stream));
   hipLaunchKernelGGL(k_align_system, dim3(grid), dim3(ALIGN_BLOCK), 0, h->stream, make_view(h), h->z_begin, h->z_end, a, d_xyz, n,
@@ -160,8 +159,8 @@ extern "C" int tsdf_hip_align_system(tsdf_handle h, const float *xyz, size_t n, 
   const size_t wb = align_work_bytes();
   int rc = tsdf_ensure_scratch(h, wb + 6 * n * sizeof(float) + n + 16);
   if (rc) return rc;
-  double *d_work = (double *)h->scratch;
-  float *d_xyz = (float *)((char *)h->scratch + wb), *d_q = d_xyz + 3 * n;
+  double *d_work = (double *)h->scratch.p;
+  float *d_xyz = (float *)((char *)h->scratch.p + wb), *d_q = d_xyz + 3 * n;
   unsigned char *d_used = (unsigned char *)(d_q + 3 * n);
   if ((rc = tsdf_to_device(h, d_xyz, xyz, 3 * n * sizeof(float)))) return rc;
   if ((rc = align_launch(h, d_xyz, n, vol_from_src, min_weight, r_max, d_work, used ? d_used : nullptr, xyz_vol ? d_q : nullptr))) return rc;
@@ -183,7 +182,7 @@ extern "C" int tsdf_hip_align_system_device(tsdf_handle h, const float *d_xyz, s
   TSDF_ENTER(h);
   int rc = tsdf_ensure_scratch(h, align_work_bytes());
   if (rc) return rc;
-  double *d_work = (double *)h->scratch;
+  double *d_work = (double *)h->scratch.p;
   if ((rc = align_launch(h, d_xyz, n, vol_from_src, min_weight, r_max, d_work, nullptr, nullptr))) return rc;
   uint64_t usec = 0;
   if ((rc = align_collect(h, d_work, out, &usec))) return rc;
@@ -209,8 +208,8 @@ extern "C" int tsdf_hip_align(tsdf_handle h, const float *xyz, size_t n, const d
     const size_t wb = align_work_bytes();
     int rc = tsdf_ensure_scratch(h, wb + 3 * n * sizeof(float));
     if (rc) return rc;
-    d_work = (double *)h->scratch;
-    d_xyz = (float *)((char *)h->scratch + wb);
+    d_work = (double *)h->scratch.p;
+    d_xyz = (float *)((char *)h->scratch.p + wb);
     if ((rc = tsdf_to_device(h, d_xyz, xyz, 3 * n * sizeof(float)))) return rc;
   }
   uint64_t usec = 0, n_used = 0;

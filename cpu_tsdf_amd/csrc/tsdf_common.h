@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "tsdf_hip.h"
+#include "tsdf_own.h"  // DevBuf, EventSet, PinnedStage; tsdf_set_error, tsdf_hip_fail, TSDF_HIP_TRY
 
 struct tsdf_hip_pipeline;  // tsdf_pipeline.hip: pinned staging ring of tsdf_hip_integrate_async
 struct tsdf_hip_multi;     // tsdf_multi.hip: the Z-slab handles of a multi-GPU volume
@@ -63,12 +64,8 @@ struct tsdf_hip_volume {
   // integrate_color: the frame of the launch in flight as 8-byte pixel records {depth bits, bgra}, written by k_frame_pairs on
   // the handle's stream right before the colour fast kernel that gathers from it ([1]: frame B of k_integrate2)
   uint2 *frame_pairs[2] = {nullptr, nullptr};
-  // pinned two-slot bounce buffer every host<->device transfer of caller memory goes through (tsdf_to_host /
-  // tsdf_to_device in tsdf_core.hip)
-  char *bounce = nullptr;
-  hipEvent_t bounce_ev[2] = {nullptr, nullptr};
-  bool bounce_busy[2] = {false, false};
-  unsigned bounce_turn = 0;  // slot of the next chunk: consecutive small transfers alternate instead of queueing on one slot
+  // every host<->device transfer of caller memory goes through it, in chunks of 2 MiB (tsdf_to_host / tsdf_to_device)
+  PinnedStage bounce{2u << 20};
   double *cam64 = nullptr;         // fx, fy, cx, cy on the device
   tsdf_hip_pipeline *pipe = nullptr;
   int frame_staged = 0;            // tsdf_hip_organize left a frame in [frame_depth | frame_bgra]
@@ -87,10 +84,8 @@ struct tsdf_hip_volume {
   uint32_t rest_bits = 0;
   unsigned long long last_implied = 0, last_read_bytes = 0;  // tsdf_hip_last_read_detail
   bool last_implied_on = false;
-  uint8_t *live = nullptr;         // brick-cull flags, one per k_integrate block
-  size_t live_cap = 0;
-  uint32_t *row_iv = nullptr;      // row intervals of a LIVE launch (k_rows, tsdf_integrate.hip), one word per voxel row
-  size_t row_iv_cap = 0;
+  DevBuf live;                     // brick-cull flags, one byte per k_integrate block
+  DevBuf row_iv;                   // row intervals of a LIVE launch (k_rows, tsdf_integrate.hip), one uint32_t per voxel row
   bool ctr_increasing[3] = {false, false, false};  // the axis' centre table strictly increases (checked at create)
   unsigned long long *counter = nullptr;  // device scratch (n_observed etc.): 2048 slots
   unsigned long long last_observed = 0, last_changed_bytes = 0;  // tsdf_hip_last_count_detail
@@ -104,18 +99,13 @@ struct tsdf_hip_volume {
   bool count_ran = false;  // that launch really ran (finite pose, something observable)
   hipStream_t stream = nullptr;
   // marching-cubes result buffers (owned, reused between calls)
-  float *mc_verts = nullptr;
-  uint8_t *mc_rgb = nullptr;
-  uint64_t *mc_cell = nullptr;
+  DevBuf mc_verts, mc_rgb, mc_cell;  // float[9], uint8_t[9], uint64_t per triangle
   uint64_t mc_ntri = 0;
   bool mc_valid = false;   // the last tsdf_hip_march on this handle succeeded (tsdf_hip_march_cleanup / _flatten work on its result)
-  size_t mc_cap = 0;       // triangles the output buffers hold
   bool mc_has_rgb = false;
-  uint64_t *mc_keys = nullptr, *mc_vals = nullptr;  // active-cell list (Morton key, packed cell)
-  size_t mc_cells_cap = 0;
-  uint8_t *mc_need = nullptr;  // k_mc_need's per-wave-plane and per-block verdicts (tsdf_march.hip)
-  size_t mc_need_cap = 0;
-  hipEvent_t mc_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // tsdf_hip_march_timing
+  DevBuf mc_keys;           // active-cell list: one uint64_t (Morton key, packed cell) per cell
+  DevBuf mc_need;           // k_mc_need's per-wave-plane and per-block verdicts (tsdf_march.hip)
+  EventSet<4> mc_ev;        // tsdf_hip_march_timing
   float mc_ms[3] = {0.f, 0.f, 0.f};                            // classify, sort + scan, emit of the last call
   uint64_t mc_ncells = 0;
   uint64_t mc_d_bytes = 0;   // distance bytes the last classify pass requested (tsdf_hip_march_stats)
@@ -123,20 +113,19 @@ struct tsdf_hip_volume {
   bool mc_counts_pass = false;  // ... and the corner weights not gathered: their test could not fail (tsdf_march.hip counts_pass)
   bool mc_halo_vouched = false;  // a slab of a set, during tsdf_multi_march: halo plane z_end is a fresh copy of a plane of the
                                  // neighbour, and every slab's planes hold only what integrate launches wrote (band_exact)
-  hipEvent_t align_ev[2] = {nullptr, nullptr};  // tsdf_hip_align_stats: around the system kernels of the last call
+  EventSet<2> align_ev;                         // tsdf_hip_align_stats: around the system kernels of the last call
   uint64_t align_stats[4] = {0, 0, 0, 0};       // points, used, iterations, device microseconds
-  hipEvent_t shift_ev[2] = {nullptr, nullptr};  // tsdf_hip_shift_stats: around the work of the last tsdf_hip_shift (tsdf_shift.hip)
+  EventSet<2> shift_ev;                         // tsdf_hip_shift_stats: around the work of the last tsdf_hip_shift (tsdf_shift.hip)
   bool shift_timed = false;                     // ... both have been recorded
   uint64_t shift_stats[3] = {0, 0, 0};          // voxels that kept a value, voxels reset, 1 if the band flags were carried over
-  hipEvent_t merge_ev[3] = {nullptr, nullptr, nullptr};  // tsdf_hip_merge (tsdf_merge.hip) with this handle as dst: around the kernel; [2] hands
+  EventSet<3> merge_ev;                                  // tsdf_hip_merge (tsdf_merge.hip) with this handle as dst: around the kernel; [2] hands
                                                          // the order of the two streams over (recorded on src's, then on dst's)
   bool merge_timed = false;                     // ... [0] and [1] have been recorded (a merge with an empty launch box records nothing)
-  unsigned long long *merge_count = nullptr;    // device: voxels the last merge's kernel merged (a counter of its own: an asynchronous
+  DevBuf merge_count;                           // device, one unsigned long long: voxels the last merge's kernel merged (a counter of its own: an asynchronous
                                                 // merge leaves it for tsdf_hip_merge_stats, whatever runs in between)
   uint64_t merge_stats[3] = {0, 0, 0};          // voxels in the launch box, voxels merged (once read back), 1 if live band flags were dropped
   bool merge_count_pending = false;             // merge_stats[1] is still on the device
-  void *scratch = nullptr;
-  size_t scratch_bytes = 0;
+  DevBuf scratch;  // grown by tsdf_ensure_scratch
   tsdf_occ_state *occ = nullptr;
   tsdf_meshpost_state *mp = nullptr;
   tsdf_flatten_state *fl = nullptr;
@@ -217,16 +206,6 @@ int tsdf_ray_list_advance(tsdf_handle s, const float rot[9], const float origin[
 int tsdf_ray_list_route(tsdf_handle s, const int32_t *d_list, unsigned count, int n_slab, const int *z_end,
                         unsigned *d_counters, int32_t *d_outbox, int32_t *d_finbox);
 int tsdf_ray_deliver(tsdf_handle s, const int32_t *d_fin, unsigned count, float *d_out, int64_t n_pix, const double *inv);
-
-// Error plumbing -------------------------------------------------------------------------------
-void tsdf_set_error(const std::string &msg);
-int tsdf_hip_fail(hipError_t e, const char *what, const char *file, int line);
-
-#define TSDF_HIP_TRY(expr)                                              \
-  do {                                                                  \
-    hipError_t _e = (expr);                                             \
-    if (_e != hipSuccess) return tsdf_hip_fail(_e, #expr, __FILE__, __LINE__); \
-  } while (0)
 
 // Every entry point works on its handle's device and leaves the caller's current device as it found it
 // (a process may hold handles on several GPUs, or share the thread with another HIP user such as torch).
@@ -327,14 +306,9 @@ static inline float tsdf_node_size(const tsdf_params &p, int axis) {
 // division), and the unit of tsdf_hip_esdf's distances.
 static inline float tsdf_voxel_edge(const tsdf_params &p) { return p.size[0] / p.res[0]; }
 int tsdf_ensure_scratch(tsdf_hip_volume *v, size_t bytes);
-// Copies between DEVICE memory and the CALLER's host memory, through the handle's pinned bounce buffer in chunks
-// (two slots, the host memcpy of one chunk overlapping the DMA of the next).  tsdf_to_host returns with the
-// data in `dst` (everything queued on the stream before it has completed); tsdf_to_device returns as soon as
-// `src` has been consumed, the device copy being ordered on the handle's stream like any other work.
+// Copies between DEVICE memory and the CALLER's host memory: the handle's PinnedStage (tsdf_own.h) on the handle's stream.
 int tsdf_to_host(tsdf_hip_volume *v, void *dst, const void *dev_src, size_t bytes);
 int tsdf_to_device(tsdf_hip_volume *v, void *dev_dst, const void *src, size_t bytes);
-// Is `p` host memory the runtime knows as pinned?  (What these two, and the mesh passes' mp_to_host / mp_to_device, copy directly.)
-bool tsdf_is_pinned_host(const void *p);
 void tsdf_pipeline_destroy(tsdf_hip_volume *v);
 // Free v->occ / v->mp / v->fl and null them (free_volume; a handle that never ran the feature has none).  The mesh passes
 // of a set keep their device memory on the first slab's device, so these run before tsdf_multi_free.

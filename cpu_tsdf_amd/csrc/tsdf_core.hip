@@ -230,18 +230,7 @@ static int fill_u32(tsdf_hip_volume *v, void *p, uint32_t value, int64_t n) {
   return TSDF_HIP_OK;
 }
 
-int tsdf_ensure_scratch(tsdf_hip_volume *v, size_t bytes) {
-  if (bytes <= v->scratch_bytes) return TSDF_HIP_OK;
-  if (v->scratch) {
-    TSDF_HIP_TRY(hipStreamSynchronize(v->stream));
-    TSDF_HIP_TRY(hipFree(v->scratch));
-    v->scratch = nullptr;
-    v->scratch_bytes = 0;
-  }
-  TSDF_HIP_TRY(hipMalloc(&v->scratch, bytes));
-  v->scratch_bytes = bytes;
-  return TSDF_HIP_OK;
-}
+int tsdf_ensure_scratch(tsdf_hip_volume *v, size_t bytes) { return v->scratch.reserve(bytes, v->stream); }
 
 // ---- exact LAB colours (host finish) ------------------------------------------------------------------------------------
 void tsdf_lab2rgb_host_many(const float *L, const float *A, const float *B, size_t n, uint32_t *out) {
@@ -279,14 +268,13 @@ int tsdf_lab_exact_colors(tsdf_hip_volume *v, const int64_t *d_idx, size_t n, ui
   if (!n) return TSDF_HIP_OK;
   if (!v->lab_img || !v->cn[0] || !v->cn[1] || !v->cn[2]) return TSDF_HIP_E_INVALID;
   const size_t chunk = (size_t)tsdf_tuning().lab_chunk;  // voxels per round trip (16 M by default: 192 MB of floats)
-  float *d_lab = nullptr;
-  uint32_t *d_words = nullptr;
+  DevBuf lab_buf, words_buf;
   const size_t m = std::min(n, chunk);
-  TSDF_HIP_TRY(hipMalloc(&d_lab, m * 3 * sizeof(float)));
-  if (write_plane && hipMalloc(&d_words, m * sizeof(uint32_t)) != hipSuccess) {
-    (void)hipFree(d_lab);
-    return tsdf_hip_fail(hipErrorOutOfMemory, "hipMalloc", __FILE__, __LINE__);
-  }
+  if (const int rc = lab_buf.alloc(m * 3 * sizeof(float))) return rc;
+  if (write_plane)
+    if (const int rc = words_buf.alloc(m * sizeof(uint32_t))) return rc;
+  float *d_lab = lab_buf.as<float>();
+  uint32_t *d_words = words_buf.as<uint32_t>();
   std::vector<float> lab(m * 3);
   std::vector<uint32_t> words(m);
   int rc = TSDF_HIP_OK;
@@ -303,8 +291,6 @@ int tsdf_lab_exact_colors(tsdf_hip_volume *v, const int64_t *d_idx, size_t n, ui
       if (hipStreamSynchronize(v->stream) != hipSuccess) rc = TSDF_HIP_E_HIP;
     }
   }
-  (void)hipFree(d_lab);
-  if (d_words) (void)hipFree(d_words);
   return rc;
 }
 
@@ -314,20 +300,15 @@ int tsdf_lab_exact_colors(tsdf_hip_volume *v, const int64_t *d_idx, size_t n, ui
 // (measured: every other integrateCloud taking 22 ms instead of 2.2 ms after a renderView into a fresh array).
 // Going through pinned memory costs one host memcpy (~10 GB/s, overlapped with the DMA chunk by chunk) and is
 // the same every time.
-static const size_t kBounceChunk = 2u << 20;
-
-static int bounce_ready(tsdf_hip_volume *v) {
-  if (!v->bounce) {
-    TSDF_HIP_TRY(hipHostMalloc((void **)&v->bounce, 2 * kBounceChunk, hipHostMallocDefault));
-    for (int i = 0; i < 2; ++i) TSDF_HIP_TRY(hipEventCreateWithFlags(&v->bounce_ev[i], hipEventDisableTiming));
-  }
-  return TSDF_HIP_OK;
+int PinnedStage::ready() {
+  if (!slots) TSDF_HIP_TRY(hipHostMalloc((void **)&slots, 2 * chunk, hipHostMallocDefault));
+  return ev.ensure(2, hipEventDisableTiming);
 }
 
-static int bounce_wait(tsdf_hip_volume *v, int slot) {
-  if (v->bounce_busy[slot]) {
-    TSDF_HIP_TRY(hipEventSynchronize(v->bounce_ev[slot]));
-    v->bounce_busy[slot] = false;
+int PinnedStage::wait(int slot) {
+  if (busy[slot]) {
+    TSDF_HIP_TRY(hipEventSynchronize(ev[slot]));
+    busy[slot] = false;
   }
   return TSDF_HIP_OK;
 }
@@ -343,63 +324,68 @@ bool tsdf_is_pinned_host(const void *p) {
   return attr.type == hipMemoryTypeHost;
 }
 
-int tsdf_to_host(tsdf_hip_volume *v, void *dst, const void *dev_src, size_t bytes) {
+int PinnedStage::to_host(void *dst, const void *dev_src, size_t bytes, hipStream_t s) {
   if (!bytes) return TSDF_HIP_OK;
   if (bytes >= (64u << 10) && tsdf_is_pinned_host(dst)) {
-    TSDF_HIP_TRY(hipMemcpyAsync(dst, dev_src, bytes, hipMemcpyDeviceToHost, v->stream));
-    TSDF_HIP_TRY(hipStreamSynchronize(v->stream));
+    TSDF_HIP_TRY(hipMemcpyAsync(dst, dev_src, bytes, hipMemcpyDeviceToHost, s));
+    TSDF_HIP_TRY(hipStreamSynchronize(s));
     return TSDF_HIP_OK;
   }
-  int rc = bounce_ready(v);
+  int rc = ready();
   if (rc) return rc;
-  const size_t chunks = (bytes + kBounceChunk - 1) / kBounceChunk;
-  const unsigned turn = v->bounce_turn;
-  v->bounce_turn += (unsigned)chunks;
+  const size_t chunks = (bytes + chunk - 1) / chunk;
+  const unsigned first = turn;
+  turn += (unsigned)chunks;
   for (size_t k = 0; k <= chunks; ++k) {
     if (k < chunks) {  // queue chunk k into its slot (free: chunk k-2 left it in the previous iteration)
-      const int slot = (int)((turn + k) & 1);
-      if ((rc = bounce_wait(v, slot))) return rc;
-      const size_t off = k * kBounceChunk, len = std::min(kBounceChunk, bytes - off);
-      TSDF_HIP_TRY(hipMemcpyAsync(v->bounce + slot * kBounceChunk, (const char *)dev_src + off, len, hipMemcpyDeviceToHost,
-                                  v->stream));
-      TSDF_HIP_TRY(hipEventRecord(v->bounce_ev[slot], v->stream));
-      v->bounce_busy[slot] = true;
+      const int slot = (int)((first + k) & 1);
+      if ((rc = wait(slot))) return rc;
+      const size_t off = k * chunk, len = std::min(chunk, bytes - off);
+      TSDF_HIP_TRY(hipMemcpyAsync(slots + slot * chunk, (const char *)dev_src + off, len, hipMemcpyDeviceToHost, s));
+      TSDF_HIP_TRY(hipEventRecord(ev[slot], s));
+      busy[slot] = true;
     }
     if (k > 0) {  // hand chunk k-1 to the caller while chunk k is in flight
-      const int slot = (int)((turn + k - 1) & 1);
-      if ((rc = bounce_wait(v, slot))) return rc;
-      const size_t off = (k - 1) * kBounceChunk, len = std::min(kBounceChunk, bytes - off);
-      memcpy((char *)dst + off, v->bounce + slot * kBounceChunk, len);
+      const int slot = (int)((first + k - 1) & 1);
+      if ((rc = wait(slot))) return rc;
+      const size_t off = (k - 1) * chunk, len = std::min(chunk, bytes - off);
+      memcpy((char *)dst + off, slots + slot * chunk, len);
     }
   }
   return TSDF_HIP_OK;
 }
 
-int tsdf_to_device(tsdf_hip_volume *v, void *dev_dst, const void *src, size_t bytes) {
+int PinnedStage::to_device(void *dev_dst, const void *src, size_t bytes, hipStream_t s) {
   if (!bytes) return TSDF_HIP_OK;
   if (bytes >= (64u << 10) && tsdf_is_pinned_host(src)) {
-    // (the caller may reuse `src` when the call returns, as with the bounce path: wait for the copy)
-    TSDF_HIP_TRY(hipMemcpyAsync(dev_dst, src, bytes, hipMemcpyHostToDevice, v->stream));
-    TSDF_HIP_TRY(hipStreamSynchronize(v->stream));
+    // (the caller may reuse `src` when the call returns, as with the staged path: wait for the copy)
+    TSDF_HIP_TRY(hipMemcpyAsync(dev_dst, src, bytes, hipMemcpyHostToDevice, s));
+    TSDF_HIP_TRY(hipStreamSynchronize(s));
     return TSDF_HIP_OK;
   }
-  int rc = bounce_ready(v);
+  int rc = ready();
   if (rc) return rc;
-  const size_t chunks = (bytes + kBounceChunk - 1) / kBounceChunk;
-  const unsigned turn = v->bounce_turn;
-  v->bounce_turn += (unsigned)chunks;
+  const size_t chunks = (bytes + chunk - 1) / chunk;
+  const unsigned first = turn;
+  turn += (unsigned)chunks;
   for (size_t k = 0; k < chunks; ++k) {
-    const int slot = (int)((turn + k) & 1);
-    if ((rc = bounce_wait(v, slot))) return rc;  // the copy that last read this slot has finished
-    const size_t off = k * kBounceChunk, len = std::min(kBounceChunk, bytes - off);
-    memcpy(v->bounce + slot * kBounceChunk, (const char *)src + off, len);
-    TSDF_HIP_TRY(hipMemcpyAsync((char *)dev_dst + off, v->bounce + slot * kBounceChunk, len, hipMemcpyHostToDevice, v->stream));
-    TSDF_HIP_TRY(hipEventRecord(v->bounce_ev[slot], v->stream));
-    v->bounce_busy[slot] = true;
+    const int slot = (int)((first + k) & 1);
+    if ((rc = wait(slot))) return rc;  // the copy that last read this slot has finished
+    const size_t off = k * chunk, len = std::min(chunk, bytes - off);
+    memcpy(slots + slot * chunk, (const char *)src + off, len);
+    TSDF_HIP_TRY(hipMemcpyAsync((char *)dev_dst + off, slots + slot * chunk, len, hipMemcpyHostToDevice, s));
+    TSDF_HIP_TRY(hipEventRecord(ev[slot], s));
+    busy[slot] = true;
   }
   return TSDF_HIP_OK;
 }
 
+int tsdf_to_host(tsdf_hip_volume *v, void *dst, const void *dev_src, size_t bytes) { return v->bounce.to_host(dst, dev_src, bytes, v->stream); }
+int tsdf_to_device(tsdf_hip_volume *v, void *dev_dst, const void *src, size_t bytes) { return v->bounce.to_device(dev_dst, src, bytes, v->stream); }
+
+// What a member's destructor does not free is what is allocated once at create (or by tsdf_hip_set_weighting) and only here.
+// The mesh passes of a set keep their memory on the first slab's device, so the feature states go before tsdf_multi_free;
+// `delete v` runs the members' destructors on the handle's device.
 static void free_volume(tsdf_hip_volume *v) {
   if (!v) return;
   tsdf_occupied_release(v);
@@ -409,45 +395,11 @@ static void free_volume(tsdf_hip_volume *v) {
   if (v->multi) tsdf_multi_free(v);
   TsdfDeviceScope scope(v->device);
   tsdf_pipeline_destroy(v);
-  if (v->d) (void)hipFree(v->d);
-  if (v->w) (void)hipFree(v->w);
-  if (v->rgb) (void)hipFree(v->rgb);
-  if (v->k8) (void)hipFree(v->k8);
-  for (int c = 0; c < 4; ++c)
-    if (v->cn[c]) (void)hipFree(v->cn[c]);
-  if (v->vm) (void)hipFree(v->vm);
-  if (v->vn) (void)hipFree(v->vn);
-  if (v->lab_lut) (void)hipFree(v->lab_lut);
-  if (v->lab_img) (void)hipFree(v->lab_img);
-  for (int a = 0; a < 3; ++a)
-    if (v->ctr[a]) (void)hipFree(v->ctr[a]);
-  if (v->frame_depth) (void)hipFree(v->frame_depth);
-  for (int i = 0; i < 2; ++i)
-    if (v->frame_pairs[i]) (void)hipFree(v->frame_pairs[i]);
-  if (v->bounce) (void)hipHostFree(v->bounce);
-  for (int i = 0; i < 2; ++i)
-    if (v->bounce_ev[i]) (void)hipEventDestroy(v->bounce_ev[i]);
-  if (v->cam64) (void)hipFree(v->cam64);
-  if (v->live) (void)hipFree(v->live);
-  if (v->row_iv) (void)hipFree(v->row_iv);
-  if (v->band) (void)hipFree(v->band);
-  if (v->counter) (void)hipFree(v->counter);
-  if (v->mc_verts) (void)hipFree(v->mc_verts);
-  if (v->mc_rgb) (void)hipFree(v->mc_rgb);
-  if (v->mc_cell) (void)hipFree(v->mc_cell);
-  if (v->mc_keys) (void)hipFree(v->mc_keys);
-  if (v->mc_vals) (void)hipFree(v->mc_vals);
-  if (v->mc_need) (void)hipFree(v->mc_need);
-  for (int i = 0; i < 4; ++i)
-    if (v->mc_ev[i]) (void)hipEventDestroy(v->mc_ev[i]);
-  for (int i = 0; i < 2; ++i)
-    if (v->align_ev[i]) (void)hipEventDestroy(v->align_ev[i]);
-  for (int i = 0; i < 2; ++i)
-    if (v->shift_ev[i]) (void)hipEventDestroy(v->shift_ev[i]);
-  for (int i = 0; i < 3; ++i)
-    if (v->merge_ev[i]) (void)hipEventDestroy(v->merge_ev[i]);
-  if (v->merge_count) (void)hipFree(v->merge_count);
-  if (v->scratch) (void)hipFree(v->scratch);
+  void *const once[] = {v->d,       v->w,       v->rgb,         v->k8,        v->cn[0],          v->cn[1],          v->cn[2], v->cn[3], v->vm,
+                        v->vn,      v->lab_lut, v->lab_img,     v->ctr[0],    v->ctr[1],         v->ctr[2],         v->frame_depth,
+                        v->frame_pairs[0], v->frame_pairs[1], v->cam64, v->band, v->counter};
+  for (void *q : once)
+    if (q) (void)hipFree(q);
   delete v;
 }
 
@@ -961,7 +913,7 @@ static int block_transfer(tsdf_handle h, int x0, int y0, int z0, int nx, int ny,
     for (int k = 0; k < 2; ++k) {
       if (!hosts[k]) continue;
       float *hp = hosts[k] + (int64_t)zc * plane;
-      float *dev = (float *)h->scratch;
+      float *dev = (float *)h->scratch.p;
       if (DOWN) {
         if (k == 0)
           hipLaunchKernelGGL(k_block_f32<true>, dim3(blocks), dim3(256), 0, h->stream, a, h->d, dev);
@@ -995,9 +947,9 @@ static int block_transfer(tsdf_handle h, int x0, int y0, int z0, int nx, int ny,
       uint8_t *hp = rgb + (int64_t)zc * plane * 3;
       std::vector<float> lab((size_t)n * 3);
       for (int c = 0; c < 3; ++c) {
-        hipLaunchKernelGGL(k_block_f32<true>, dim3(blocks), dim3(256), 0, h->stream, a, h->cn[c], (float *)h->scratch);
+        hipLaunchKernelGGL(k_block_f32<true>, dim3(blocks), dim3(256), 0, h->stream, a, h->cn[c], (float *)h->scratch.p);
         TSDF_HIP_TRY(hipGetLastError());
-        if ((rc = tsdf_to_host(h, lab.data() + (size_t)c * n, h->scratch, n * sizeof(float)))) return rc;
+        if ((rc = tsdf_to_host(h, lab.data() + (size_t)c * n, h->scratch.p, n * sizeof(float)))) return rc;
       }
       std::vector<uint32_t> words((size_t)n);
       tsdf_lab2rgb_host_many(lab.data(), lab.data() + n, lab.data() + 2 * n, (size_t)n, words.data());
@@ -1010,13 +962,13 @@ static int block_transfer(tsdf_handle h, int x0, int y0, int z0, int nx, int ny,
       uint8_t *hp = rgb + (int64_t)zc * plane * 3;
       if (DOWN) {
         hipLaunchKernelGGL(k_block_rgb<true>, dim3(blocks), dim3(256), 0, h->stream, a, h->rgb,
-                           (uint8_t *)h->scratch);
+                           (uint8_t *)h->scratch.p);
         TSDF_HIP_TRY(hipGetLastError());
-        if ((rc = tsdf_to_host(h, hp, h->scratch, n * 3))) return rc;
+        if ((rc = tsdf_to_host(h, hp, h->scratch.p, n * 3))) return rc;
       } else {
-        if ((rc = tsdf_to_device(h, h->scratch, hp, n * 3))) return rc;
+        if ((rc = tsdf_to_device(h, h->scratch.p, hp, n * 3))) return rc;
         hipLaunchKernelGGL(k_block_rgb<false>, dim3(blocks), dim3(256), 0, h->stream, a, h->rgb,
-                           (uint8_t *)h->scratch);
+                           (uint8_t *)h->scratch.p);
         TSDF_HIP_TRY(hipGetLastError());
         TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
       }
@@ -1057,7 +1009,7 @@ static int variance_block(tsdf_handle h, int x0, int y0, int z0, int nx, int ny,
     const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
     for (int k = 0; k < 2; ++k) {
       if (!hosts[k]) continue;
-      float *hp = hosts[k] + (int64_t)zc * plane, *dev = (float *)h->scratch;
+      float *hp = hosts[k] + (int64_t)zc * plane, *dev = (float *)h->scratch.p;
       if (DOWN) {
         hipLaunchKernelGGL(k_block_f32<true>, dim3(blocks), dim3(256), 0, h->stream, a, planes[k], dev);
         TSDF_HIP_TRY(hipGetLastError());
@@ -1103,9 +1055,9 @@ extern "C" int tsdf_hip_download_color_state(tsdf_handle h, int plane_index, int
     const int64_t n = plane * bz;
     BlockArgs a{0, 0, z0 + zc - h->z_first, h->nx, h->ny, bz, h->ny, h->pitch};
     const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_block_f32<true>, dim3(blocks), dim3(256), 0, h->stream, a, h->cn[plane_index], (float *)h->scratch);
+    hipLaunchKernelGGL(k_block_f32<true>, dim3(blocks), dim3(256), 0, h->stream, a, h->cn[plane_index], (float *)h->scratch.p);
     TSDF_HIP_TRY(hipGetLastError());
-    if ((rc = tsdf_to_host(h, out + (int64_t)zc * plane, h->scratch, n * sizeof(float)))) return rc;
+    if ((rc = tsdf_to_host(h, out + (int64_t)zc * plane, h->scratch.p, n * sizeof(float)))) return rc;
   }
   return TSDF_HIP_OK;
 }

@@ -200,8 +200,8 @@ static int dc_core(MpWork &w, hipStream_t s, const float *d_verts, const uint8_t
                    float cell_size, DcLayout &L, uint64_t *n_out, uint64_t *n_kept, const char *who) {
   const uint32_t n = (uint32_t)n_verts, nf = (uint32_t)n_faces;
   int rc = dc_layout(n, nf, s, L);
-  if (rc || (rc = mp_reserve(&w.buf, &w.cap, L.total, s, "mesh decimate")) || (rc = mp_work_begin(w, MP_IDX_COUNTERS, 2, s))) return rc;
-  char *b = (char *)w.buf;
+  if (rc || (rc = w.buf.reserve(L.total, s, "mesh decimate")) || (rc = mp_work_begin(w, MP_IDX_COUNTERS, 2, s))) return rc;
+  char *b = (char *)w.buf.p;
   uint64_t *key_a = (uint64_t *)(b + L.key_a), *keys = (uint64_t *)(b + L.key_b);
   uint32_t *idx_a = (uint32_t *)(b + L.idx_a), *order = (uint32_t *)(b + L.idx_b), *outidx = (uint32_t *)(b + L.outidx);
   uint32_t *remap = (uint32_t *)(b + L.remap), *mapped = (uint32_t *)(b + L.mapped), *faces_out = (uint32_t *)(b + L.faces);
@@ -210,17 +210,17 @@ static int dc_core(MpWork &w, hipStream_t s, const float *d_verts, const uint8_t
   const dim3 blk(256), grid_n((n + 255u) / 256u), grid_f((nf + 255u) / 256u);
 
   TSDF_HIP_TRY(hipEventRecord(w.ev[0], s));
-  hipLaunchKernelGGL(k_dc_key, grid_n, blk, 0, s, d_verts, n, (double)cell_size, key_a, idx_a, w.counters);
+  hipLaunchKernelGGL(k_dc_key, grid_n, blk, 0, s, d_verts, n, (double)cell_size, key_a, idx_a, w.count());
   TSDF_HIP_TRY(hipGetLastError());
   size_t tmp_bytes = L.tmp_bytes;
   TSDF_HIP_TRY(rocprim::radix_sort_pairs(b + L.tmp, tmp_bytes, key_a, keys, idx_a, order, (size_t)n, 0u, 64u, s));
-  hipLaunchKernelGGL(k_dc_heads, grid_n, blk, 0, s, keys, order, n, first, w.counters);
+  hipLaunchKernelGGL(k_dc_heads, grid_n, blk, 0, s, keys, order, n, first, w.count());
   TSDF_HIP_TRY(hipGetLastError());
   tmp_bytes = L.tmp_bytes;
   TSDF_HIP_TRY(rocprim::exclusive_scan(b + L.tmp, tmp_bytes, MpKeepIt(first, MpKeepCount()), outidx, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
   // the range flag and the cluster count in one read
   unsigned long long counts[MP_IDX_COUNTERS] = {0};
-  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, sizeof counts, hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.count(), sizeof counts, hipMemcpyDeviceToHost, s));
   TSDF_HIP_TRY(hipStreamSynchronize(s));
   if (counts[DC_C_RANGE]) {
     tsdf_set_error(dc_extent_text(who, cell_size));
@@ -232,8 +232,8 @@ static int dc_core(MpWork &w, hipStream_t s, const float *d_verts, const uint8_t
     return TSDF_HIP_E_HIP;
   }
   L.c_rgb = mp_up((size_t)m * 12), L.c_counts = L.c_rgb + mp_up((size_t)m * 3), L.c_total = L.c_counts + mp_up((size_t)m * 4);
-  if ((rc = mp_reserve(&w.cells, &w.cells_cap, L.c_total, s, "mesh decimate"))) return rc;
-  char *c = (char *)w.cells;
+  if ((rc = w.cells.reserve(L.c_total, s, "mesh decimate"))) return rc;
+  char *c = (char *)w.cells.p;
   hipLaunchKernelGGL(k_dc_reduce, grid_n, blk, 0, s, d_verts, d_rgb, keys, order, n, outidx, remap, (float *)c, (uint8_t *)(c + L.c_rgb),
                      (uint32_t *)(c + L.c_counts));
   TSDF_HIP_TRY(hipGetLastError());
@@ -242,7 +242,7 @@ static int dc_core(MpWork &w, hipStream_t s, const float *d_verts, const uint8_t
     while (bits < 32u && ((uint64_t)1 << bits) < m) ++bits;
     uint64_t *key_lm = (uint64_t *)(b + L.key_lm), *lm_a = (uint64_t *)(b + L.lm_a), *lm_b = (uint64_t *)(b + L.lm_b);
     uint32_t *hi_a = (uint32_t *)(b + L.hi_a), *hi_b = (uint32_t *)(b + L.hi_b), *ord_a = (uint32_t *)(b + L.ord_a), *ord_b = (uint32_t *)(b + L.ord_b);
-    hipLaunchKernelGGL(k_dc_faces, grid_f, blk, 0, s, d_faces, nf, n_verts, remap, bits, mapped, key_lm, hi_a, ord_a, w.counters);
+    hipLaunchKernelGGL(k_dc_faces, grid_f, blk, 0, s, d_faces, nf, n_verts, remap, bits, mapped, key_lm, hi_a, ord_a, w.count());
     TSDF_HIP_TRY(hipGetLastError());
     // The sorts read only the bits that can be set.  The temporary storage was sized for all bits; should fewer bits ever ask
     // for more of it, all bits are sorted (the upper ones are zero: the same order).
@@ -258,12 +258,12 @@ static int dc_core(MpWork &w, hipStream_t s, const float *d_verts, const uint8_t
     TSDF_HIP_TRY(hipGetLastError());
     tmp_bytes = L.tmp_bytes;
     TSDF_HIP_TRY(rocprim::radix_sort_pairs(b + L.tmp, tmp_bytes, lm_a, lm_b, ord_b, ord_a, (size_t)nf, 0u, bits_lm, s));
-    hipLaunchKernelGGL(k_dc_keep, grid_f, blk, 0, s, lm_b, ord_a, mapped, nf, bits, keep, w.counters);
+    hipLaunchKernelGGL(k_dc_keep, grid_f, blk, 0, s, lm_b, ord_a, mapped, nf, bits, keep, w.count());
     TSDF_HIP_TRY(hipGetLastError());
     if ((rc = mp_compact_faces(s, b + L.tmp, L.tmp_bytes, mapped, keep, offset, nf, faces_out))) return rc;
   }
   TSDF_HIP_TRY(hipEventRecord(w.ev[1], s));
-  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, sizeof counts, hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.count(), sizeof counts, hipMemcpyDeviceToHost, s));
   TSDF_HIP_TRY(hipStreamSynchronize(s));
   if (counts[DC_C_BAD]) {
     tsdf_set_error(std::string(who) + ": a face names a vertex index >= n_verts");
@@ -315,16 +315,16 @@ static int dc_mesh(int device, const float *verts, const uint8_t *rgb, uint64_t 
   const size_t b_verts = mp_up((size_t)n_verts * 12), b_rgb = rgb ? mp_up((size_t)n_verts * 3) : 0, b_faces = faces ? (size_t)n_faces * 12 : 0;
   int rc = c.open(device, b_verts + b_rgb + b_faces, who);
   if (rc) return rc;
-  float *d_verts = (float *)c.in;
-  uint8_t *d_rgb = rgb ? (uint8_t *)c.in + b_verts : nullptr;
-  uint32_t *d_faces = faces && n_faces ? (uint32_t *)((char *)c.in + b_verts + b_rgb) : nullptr;
+  float *d_verts = (float *)c.in.p;
+  uint8_t *d_rgb = rgb ? (uint8_t *)c.in.p + b_verts : nullptr;
+  uint32_t *d_faces = faces && n_faces ? (uint32_t *)((char *)c.in.p + b_verts + b_rgb) : nullptr;
   if ((rc = c.upload(d_verts, verts, (size_t)n_verts * 12)) || (d_rgb && (rc = c.upload(d_rgb, rgb, (size_t)n_verts * 3))) ||
       (d_faces && (rc = c.upload(d_faces, faces, b_faces))))
     return rc;
   DcLayout L;
   uint64_t m = 0, kept = 0;
   if ((rc = dc_core(c.work, c.s, d_verts, d_rgb, n_verts, d_faces, n_faces, cell_size, L, &m, &kept, who))) return rc;
-  const char *b = (const char *)c.work.buf, *o = (const char *)c.work.cells;
+  const char *b = (const char *)c.work.buf.p, *o = (const char *)c.work.cells.p;
   if (remap && (rc = c.download(remap, b + L.remap, (size_t)n_verts * 4))) return rc;
   if (out_verts && (rc = c.download(out_verts, o, (size_t)m * 12))) return rc;
   if (out_rgb && (rc = c.download(out_rgb, o + L.c_rgb, (size_t)m * 3))) return rc;
@@ -380,11 +380,11 @@ extern "C" int tsdf_hip_march_decimate(tsdf_handle h, float cell_size, uint64_t 
     TSDF_ENTER(h);
     DcLayout L;
     uint64_t m = 0, kept = 0;
-    const uint8_t *d_rgb = h->mc_has_rgb ? h->mc_rgb : nullptr;
-    if ((rc = dc_core(st->work, h->stream, h->mc_verts, d_rgb, 3 * n, nullptr, n, cell_size, L, &m, &kept, who))) return rc;
+    const uint8_t *d_rgb = h->mc_has_rgb ? h->mc_rgb.as<uint8_t>() : nullptr;
+    if ((rc = dc_core(st->work, h->stream, h->mc_verts.as<float>(), d_rgb, 3 * n, nullptr, n, cell_size, L, &m, &kept, who))) return rc;
     if ((rc = mp_idx_layout(h, st, m, kept, "mesh decimate"))) return rc;
-    const char *b = (const char *)st->work.buf, *c = (const char *)st->work.cells;
-    char *o = (char *)st->out;
+    const char *b = (const char *)st->work.buf.p, *c = (const char *)st->work.cells.p;
+    char *o = (char *)st->out.p;
     TSDF_HIP_TRY(hipMemcpyAsync(o, c, (size_t)m * 12, hipMemcpyDeviceToDevice, h->stream));
     if (d_rgb) TSDF_HIP_TRY(hipMemcpyAsync(o + st->o_rgb, c + L.c_rgb, (size_t)m * 3, hipMemcpyDeviceToDevice, h->stream));
     if ((rc = mp_idx_fill(h, st, m, kept, (const uint32_t *)(b + L.faces), (const uint8_t *)(b + L.keep), (const uint32_t *)(b + L.offset)))) return rc;

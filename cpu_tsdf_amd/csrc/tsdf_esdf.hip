@@ -50,34 +50,18 @@ struct tsdf_esdf_state {
   bool valid = false;        // a tsdf_hip_esdf has completed on this handle and no tsdf_hip_shift has moved the indices since
   int box[6] = {0, 0, 0, 0, 0, 0};  // x0, y0, z0, nx, ny, nz
   int words = 0;             // 64-bit sign words per row
-  uint32_t *d2 = nullptr;    // [nz][ny][nx]
-  size_t d2_cap = 0;         // voxels
-  uint64_t *sign = nullptr;  // [nz][ny][words]: bit x & 63 of word x >> 6 = neg(v) at compute time
-  size_t sign_cap = 0;       // words
-  uint2 *stack = nullptr;    // the envelopes of one batch of lines
-  size_t stack_cap = 0;      // entries
-  unsigned long long *count = nullptr;  // device: sites
+  DevBuf d2;                 // uint32_t [nz][ny][nx]
+  DevBuf sign;               // uint64_t [nz][ny][words]: bit x & 63 of word x >> 6 = neg(v) at compute time
+  DevBuf stack;              // uint2: the envelopes of one batch of lines
+  DevBuf count;              // one unsigned long long: sites
   uint64_t sites = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  EventSet<2> ev;
   float ms = 0.f;
 };
-
-static void esdf_free_buffers(tsdf_esdf_state *st) {
-  if (st->d2) (void)hipFree(st->d2);
-  if (st->sign) (void)hipFree(st->sign);
-  if (st->stack) (void)hipFree(st->stack);
-  st->d2 = nullptr, st->sign = nullptr, st->stack = nullptr;
-  st->d2_cap = st->sign_cap = st->stack_cap = 0;
-  st->valid = false;
-}
 
 void tsdf_esdf_release(tsdf_hip_volume *v) {
   if (!v->esdf) return;
   TsdfDeviceScope scope(v->device);
-  esdf_free_buffers(v->esdf);
-  if (v->esdf->count) (void)hipFree(v->esdf->count);
-  for (hipEvent_t e : v->esdf->ev)
-    if (e) (void)hipEventDestroy(e);
   delete v->esdf;
   v->esdf = nullptr;
 }
@@ -88,7 +72,9 @@ void tsdf_esdf_invalidate(tsdf_hip_volume *v) {
 
 // tsdf_hip_reset: the field is dropped, memory included (the stream has been synchronised)
 void tsdf_esdf_drop(tsdf_hip_volume *v) {
-  if (v->esdf) esdf_free_buffers(v->esdf);
+  if (!v->esdf) return;
+  v->esdf->d2.release(), v->esdf->sign.release(), v->esdf->stack.release();
+  v->esdf->valid = false;
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
@@ -316,19 +302,6 @@ static int esdf_nomem(size_t bytes) {
   return TSDF_HIP_E_NOMEM;
 }
 
-template <typename T>
-static bool esdf_grow(T *&p, size_t &cap, size_t n) {
-  if (n <= cap) return true;
-  if (p) (void)hipFree(p);
-  p = nullptr, cap = 0;
-  if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) {
-    p = nullptr;
-    return false;
-  }
-  cap = n;
-  return true;
-}
-
 extern "C" int tsdf_hip_esdf(tsdf_handle h, const int32_t box[6], int32_t r_max, float min_weight, uint64_t *n_sites) {
   if (!h) return TSDF_HIP_E_INVALID;
   if (r_max < 0) {
@@ -369,14 +342,18 @@ extern "C" int tsdf_hip_esdf(tsdf_handle h, const int32_t box[6], int32_t r_max,
   const size_t outer_max = (size_t)std::max(by, bz);
   const size_t batch = std::max<size_t>(1, std::min(outer_max, ESDF_STACK_CAP / per_outer));
   const size_t stack_entries = batch * bx * depth;
-  TSDF_HIP_TRY(hipStreamSynchronize(h->stream));  // (a fetch_device may still be reading the buffers that are about to grow)
-  const size_t need = nvox * 4 + rows * words * 8 + stack_entries * sizeof(uint2);
-  if (!esdf_grow(st->d2, st->d2_cap, nvox) || !esdf_grow(st->sign, st->sign_cap, rows * (size_t)words) ||
-      !esdf_grow(st->stack, st->stack_cap, stack_entries))
-    return esdf_nomem(need);
-  if (!st->count) TSDF_HIP_TRY(hipMalloc(&st->count, sizeof(unsigned long long)));
-  for (hipEvent_t &e : st->ev)
-    if (!e) TSDF_HIP_TRY(hipEventCreate(&e));
+  // (a fetch_device may still be reading the buffers that are about to grow: reserve waits for the stream first)
+  const size_t b_d2 = nvox * 4, b_sign = rows * words * 8, b_stack = stack_entries * sizeof(uint2);
+  auto room = [&](DevBuf &buf, size_t bytes) {
+    const int rc = buf.reserve(bytes, h->stream, "tsdf_hip_esdf");
+    return rc == TSDF_HIP_E_NOMEM ? esdf_nomem(b_d2 + b_sign + b_stack) : rc;
+  };
+  if (const int rc = room(st->d2, b_d2)) return rc;
+  if (const int rc = room(st->sign, b_sign)) return rc;
+  if (const int rc = room(st->stack, b_stack)) return rc;
+  if (const int rc = st->count.reserve(sizeof(unsigned long long), h->stream)) return rc;
+  if (const int rc = st->ev.ensure(2)) return rc;
+  uint32_t *const d2 = st->d2.as<uint32_t>();
   EsdfArgs a;
   a.x0 = b[0], a.y0 = b[1], a.z0 = b[2], a.bx = bx, a.by = by, a.bz = bz;
   a.nx = h->nx, a.ny = h->ny, a.nz = h->nz;
@@ -388,9 +365,10 @@ extern "C" int tsdf_hip_esdf(tsdf_handle h, const int32_t box[6], int32_t r_max,
   a.r = r_max > 32767 ? 0 : r_max;
   a.r2 = (uint32_t)a.r * (uint32_t)a.r;
   a.words = words;
-  TSDF_HIP_TRY(hipMemsetAsync(st->count, 0, sizeof(unsigned long long), h->stream));
+  TSDF_HIP_TRY(hipMemsetAsync(st->count.p, 0, sizeof(unsigned long long), h->stream));
   TSDF_HIP_TRY(hipEventRecord(st->ev[0], h->stream));
-  hipLaunchKernelGGL(k_esdf_scan_x, dim3((unsigned)by, (unsigned)bz), dim3(256), 0, h->stream, a, st->d2, st->sign, st->count);
+  hipLaunchKernelGGL(k_esdf_scan_x, dim3((unsigned)by, (unsigned)bz), dim3(256), 0, h->stream, a, d2, st->sign.as<uint64_t>(),
+                     st->count.as<unsigned long long>());
   TSDF_HIP_TRY(hipGetLastError());
   for (int axis = 1; axis <= 2; ++axis) {
     const int outer = axis == 1 ? bz : by, n = axis == 1 ? by : bz;
@@ -399,15 +377,15 @@ extern "C" int tsdf_hip_esdf(tsdf_handle h, const int32_t box[6], int32_t r_max,
       const int no = std::min((int)batch, outer - o0);
       const unsigned blocks = (unsigned)(((int64_t)no * bx + 255) / 256);
       if (axis == 1)
-        hipLaunchKernelGGL(k_esdf_axis<1>, dim3(blocks), dim3(256), 0, h->stream, st->d2, st->stack, bx, by, bz, o0, no, a.r2);
+        hipLaunchKernelGGL(k_esdf_axis<1>, dim3(blocks), dim3(256), 0, h->stream, d2, st->stack.as<uint2>(), bx, by, bz, o0, no, a.r2);
       else
-        hipLaunchKernelGGL(k_esdf_axis<2>, dim3(blocks), dim3(256), 0, h->stream, st->d2, st->stack, bx, by, bz, o0, no, a.r2);
+        hipLaunchKernelGGL(k_esdf_axis<2>, dim3(blocks), dim3(256), 0, h->stream, d2, st->stack.as<uint2>(), bx, by, bz, o0, no, a.r2);
       TSDF_HIP_TRY(hipGetLastError());
     }
   }
   TSDF_HIP_TRY(hipEventRecord(st->ev[1], h->stream));
   unsigned long long n = 0;
-  TSDF_HIP_TRY(hipMemcpyAsync(&n, st->count, sizeof n, hipMemcpyDeviceToHost, h->stream));
+  TSDF_HIP_TRY(hipMemcpyAsync(&n, st->count.p, sizeof n, hipMemcpyDeviceToHost, h->stream));
   TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
   st->ms = 0.f;
   (void)hipEventElapsedTime(&st->ms, st->ev[0], st->ev[1]);
@@ -434,17 +412,17 @@ extern "C" int tsdf_hip_esdf_fetch(tsdf_handle h, uint32_t *d2, float *dist) {
   if (!st) return TSDF_HIP_E_INVALID;
   const int64_t nvox = (int64_t)st->box[3] * st->box[4] * st->box[5];
   int rc = TSDF_HIP_OK;
-  if (d2 && (rc = tsdf_to_host(h, d2, st->d2, (size_t)nvox * 4))) return rc;
+  if (d2 && (rc = tsdf_to_host(h, d2, st->d2.p, (size_t)nvox * 4))) return rc;
   if (!dist) return TSDF_HIP_OK;
   const int64_t chunk = std::min<int64_t>(nvox, 16 << 20);  // staged through the handle's scratch
   if ((rc = tsdf_ensure_scratch(h, (size_t)chunk * 4))) return rc;
   const float voxel = tsdf_voxel_edge(h->p);
   for (int64_t off = 0; off < nvox; off += chunk) {
     const int64_t c = std::min(chunk, nvox - off);
-    hipLaunchKernelGGL(k_esdf_dist, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, h->stream, st->d2, st->sign, st->box[3], st->words, off, c,
-                       voxel, (float *)h->scratch);
+    hipLaunchKernelGGL(k_esdf_dist, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, h->stream, st->d2.as<uint32_t>(), st->sign.as<uint64_t>(), st->box[3], st->words, off, c,
+                       voxel, (float *)h->scratch.p);
     TSDF_HIP_TRY(hipGetLastError());
-    if ((rc = tsdf_to_host(h, dist + off, h->scratch, (size_t)c * 4))) return rc;
+    if ((rc = tsdf_to_host(h, dist + off, h->scratch.p, (size_t)c * 4))) return rc;
   }
   return TSDF_HIP_OK;
 }
@@ -456,12 +434,12 @@ extern "C" int tsdf_hip_esdf_fetch_device(tsdf_handle h, uint32_t *d_d2, float *
   tsdf_esdf_state *st = esdf_ready(h, "tsdf_hip_esdf_fetch_device");
   if (!st) return TSDF_HIP_E_INVALID;
   const int64_t nvox = (int64_t)st->box[3] * st->box[4] * st->box[5];
-  if (d_d2) TSDF_HIP_TRY(hipMemcpyAsync(d_d2, st->d2, (size_t)nvox * 4, hipMemcpyDeviceToDevice, h->stream));
+  if (d_d2) TSDF_HIP_TRY(hipMemcpyAsync(d_d2, st->d2.p, (size_t)nvox * 4, hipMemcpyDeviceToDevice, h->stream));
   if (d_dist) {
     const int64_t chunk = (int64_t)1 << 30;
     for (int64_t off = 0; off < nvox; off += chunk) {
       const int64_t c = std::min(chunk, nvox - off);
-      hipLaunchKernelGGL(k_esdf_dist, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, h->stream, st->d2, st->sign, st->box[3], st->words, off, c,
+      hipLaunchKernelGGL(k_esdf_dist, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, h->stream, st->d2.as<uint32_t>(), st->sign.as<uint64_t>(), st->box[3], st->words, off, c,
                          tsdf_voxel_edge(h->p), d_dist + off);
       TSDF_HIP_TRY(hipGetLastError());
     }
@@ -477,10 +455,10 @@ extern "C" int tsdf_hip_esdf_sample(tsdf_handle h, const float *xyz, size_t n, f
   if (!st) return TSDF_HIP_E_INVALID;
   int rc = tsdf_ensure_scratch(h, n * 17 + 16);
   if (rc) return rc;
-  float *d_xyz = (float *)h->scratch, *d_dist = d_xyz + 3 * n;
+  float *d_xyz = (float *)h->scratch.p, *d_dist = d_xyz + 3 * n;
   unsigned char *d_found = (unsigned char *)(d_dist + n);
   if ((rc = tsdf_to_device(h, d_xyz, xyz, n * 12))) return rc;
-  hipLaunchKernelGGL(k_esdf_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, make_view(h), st->d2, st->sign, st->box[0],
+  hipLaunchKernelGGL(k_esdf_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, make_view(h), st->d2.as<uint32_t>(), st->sign.as<uint64_t>(), st->box[0],
                      st->box[1], st->box[2], st->box[3], st->box[4], st->box[5], st->words, tsdf_voxel_edge(h->p), d_xyz, n, d_dist, d_found);
   TSDF_HIP_TRY(hipGetLastError());
   if ((rc = tsdf_to_host(h, dist, d_dist, n * 4))) return rc;
@@ -492,7 +470,7 @@ extern "C" int tsdf_hip_esdf_stats(tsdf_handle h, uint64_t out[4]) {
   out[0] = out[1] = out[2] = out[3] = 0;
   const tsdf_esdf_state *st = h->esdf;
   if (!st) return TSDF_HIP_OK;
-  out[2] = st->d2_cap * 4 + st->sign_cap * 8 + st->stack_cap * sizeof(uint2);
+  out[2] = st->d2.cap + st->sign.cap + st->stack.cap;
   if (!st->valid) return TSDF_HIP_OK;
   out[0] = (uint64_t)st->box[3] * st->box[4] * st->box[5];
   out[1] = st->sites;

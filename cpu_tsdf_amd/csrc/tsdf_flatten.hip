@@ -57,9 +57,6 @@ void tsdf_flatten_invalidate(tsdf_hip_volume *v) {
 void tsdf_flatten_release(tsdf_hip_volume *v) {
   if (!v->fl) return;
   TsdfDeviceScope scope(v->device);  // (a set keeps its indexed mesh on the host: work and out are empty)
-  mp_work_free(v->fl->work);
-  if (v->fl->out) (void)hipFree(v->fl->out);
-  if (v->fl->nm_out) (void)hipFree(v->fl->nm_out);
   delete v->fl;
   v->fl = nullptr;
 }
@@ -234,8 +231,8 @@ static int fl_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
                    FlLayout &L, uint64_t *n_out, uint64_t *n_kept, const char *who) {
   const uint32_t n = (uint32_t)n_verts, nf = (uint32_t)n_faces;
   int rc = fl_layout(n, nf, s, L);
-  if (rc || (rc = mp_reserve(&w.buf, &w.cap, L.total, s, "mesh flatten")) || (rc = mp_work_begin(w, FL_COUNTERS, 2, s))) return rc;
-  char *b = (char *)w.buf;
+  if (rc || (rc = w.buf.reserve(L.total, s, "mesh flatten")) || (rc = mp_work_begin(w, FL_COUNTERS, 2, s))) return rc;
+  char *b = (char *)w.buf.p;
   uint64_t *key_a = (uint64_t *)(b + L.key_a), *key_b = (uint64_t *)(b + L.key_b);
   uint32_t *idx_a = (uint32_t *)(b + L.idx_a), *order = (uint32_t *)(b + L.idx_b), *cellno = (uint32_t *)(b + L.cellno);
   float4 *pos = (float4 *)(b + L.pos);
@@ -249,7 +246,7 @@ static int fl_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
   const dim3 blk(256), grid_n((n + 255u) / 256u);
 
   TSDF_HIP_TRY(hipEventRecord(w.ev[0], s));
-  hipLaunchKernelGGL(k_fl_key, grid_n, blk, 0, s, d_verts, n, (double)min_dist, key_a, idx_a, w.counters);
+  hipLaunchKernelGGL(k_fl_key, grid_n, blk, 0, s, d_verts, n, (double)min_dist, key_a, idx_a, w.count());
   TSDF_HIP_TRY(hipGetLastError());
   size_t tmp_bytes = L.tmp_bytes;
   TSDF_HIP_TRY(rocprim::radix_sort_pairs(b + L.tmp, tmp_bytes, key_a, key_b, idx_a, order, (size_t)n, 0u, 64u, s));
@@ -259,7 +256,7 @@ static int fl_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
   TSDF_HIP_TRY(rocprim::inclusive_scan(b + L.tmp, tmp_bytes, head, cellno, (size_t)n, rocprim::plus<uint32_t>(), s));
   unsigned long long counts[FL_COUNTERS] = {0};
   uint32_t n_cells = 0;
-  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, sizeof counts, hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.count(), sizeof counts, hipMemcpyDeviceToHost, s));
   TSDF_HIP_TRY(hipMemcpyAsync(&n_cells, cellno + (n - 1u), sizeof n_cells, hipMemcpyDeviceToHost, s));
   TSDF_HIP_TRY(hipStreamSynchronize(s));
   const uint32_t n_fin = (uint32_t)counts[FL_C_FINITE];
@@ -284,29 +281,29 @@ static int fl_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
       for (uint32_t k = 0; k < batch; ++k) {
         ++round;
         hipLaunchKernelGGL(k_fl_round, grid_u, blk, 0, s, g, order, state, round == 1u ? nullptr : list[round & 1u], list[(round + 1u) & 1u],
-                           w.counters, (int)(round % 3u), (int)((round + 1u) % 3u), (int)((round + 2u) % 3u), round);
+                           w.count(), (int)(round % 3u), (int)((round + 1u) % 3u), (int)((round + 2u) % 3u), round);
         TSDF_HIP_TRY(hipGetLastError());
       }
       unsigned long long left = 0;
-      TSDF_HIP_TRY(hipMemcpyAsync(&left, w.counters + FL_C_LIST + (round + 1u) % 3u, sizeof left, hipMemcpyDeviceToHost, s));
+      TSDF_HIP_TRY(hipMemcpyAsync(&left, w.count() + FL_C_LIST + (round + 1u) % 3u, sizeof left, hipMemcpyDeviceToHost, s));
       TSDF_HIP_TRY(hipStreamSynchronize(s));
       undecided = (uint32_t)left;
       batch = std::min(64u, batch * 2u);
     }
   }
-  hipLaunchKernelGGL(k_fl_remap, grid_n, blk, 0, s, g, n, order, state, flag, seed_of, w.counters);
+  hipLaunchKernelGGL(k_fl_remap, grid_n, blk, 0, s, g, n, order, state, flag, seed_of, w.count());
   TSDF_HIP_TRY(hipGetLastError());
   tmp_bytes = L.tmp_bytes;
   TSDF_HIP_TRY(rocprim::exclusive_scan(b + L.tmp, tmp_bytes, MpKeepIt(flag, MpKeepCount()), outidx, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
   hipLaunchKernelGGL(k_fl_out, grid_n, blk, 0, s, n, flag, seed_of, outidx, remap, seeds);
   TSDF_HIP_TRY(hipGetLastError());
   if (nf) {
-    hipLaunchKernelGGL(k_fl_faces, dim3((nf + 255u) / 256u), blk, 0, s, d_faces, nf, n_verts, remap, mapped, keep, w.counters);
+    hipLaunchKernelGGL(k_fl_faces, dim3((nf + 255u) / 256u), blk, 0, s, d_faces, nf, n_verts, remap, mapped, keep, w.count());
     TSDF_HIP_TRY(hipGetLastError());
     if ((rc = mp_compact_faces(s, b + L.tmp, L.tmp_bytes, mapped, keep, offset, nf, faces_out))) return rc;
   }
   TSDF_HIP_TRY(hipEventRecord(w.ev[1], s));
-  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, sizeof counts, hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.count(), sizeof counts, hipMemcpyDeviceToHost, s));
   TSDF_HIP_TRY(hipStreamSynchronize(s));
   if (counts[FL_C_BAD]) {
     tsdf_set_error(std::string(who) + ": a face names a vertex index >= n_verts");
@@ -354,13 +351,13 @@ extern "C" int tsdf_hip_mesh_flatten(int device, const float *verts, uint64_t n_
   const size_t b_verts = mp_up((size_t)n_verts * 12), b_faces = faces ? (size_t)n_faces * 12 : 0;
   int rc = c.open(device, b_verts + b_faces, "tsdf_hip_mesh_flatten");
   if (rc) return rc;
-  float *d_verts = (float *)c.in;
-  uint32_t *d_faces = faces && n_faces ? (uint32_t *)((char *)c.in + b_verts) : nullptr;
+  float *d_verts = (float *)c.in.p;
+  uint32_t *d_faces = faces && n_faces ? (uint32_t *)((char *)c.in.p + b_verts) : nullptr;
   if ((rc = c.upload(d_verts, verts, (size_t)n_verts * 12)) || (d_faces && (rc = c.upload(d_faces, faces, b_faces)))) return rc;
   FlLayout L;
   uint64_t m = 0, kept = 0;
   if ((rc = fl_core(c.work, c.s, d_verts, n_verts, d_faces, n_faces, min_dist, L, &m, &kept, "tsdf_hip_mesh_flatten"))) return rc;
-  const char *b = (const char *)c.work.buf;
+  const char *b = (const char *)c.work.buf.p;
   if (remap && (rc = c.download(remap, b + L.remap, (size_t)n_verts * 4))) return rc;
   if (seeds && (rc = c.download(seeds, b + L.seeds, (size_t)m * 4))) return rc;
   if (out_faces && (rc = c.download(out_faces, b + L.faces, (size_t)kept * 12))) return rc;
@@ -413,11 +410,11 @@ extern "C" int tsdf_hip_march_flatten(tsdf_handle h, float min_dist, uint64_t *n
     TSDF_ENTER(h);
     FlLayout L;
     uint64_t m = 0, kept = 0;
-    if ((rc = fl_core(st->work, h->stream, h->mc_verts, 3 * n, nullptr, n, min_dist, L, &m, &kept, who))) return rc;
+    if ((rc = fl_core(st->work, h->stream, h->mc_verts.as<float>(), 3 * n, nullptr, n, min_dist, L, &m, &kept, who))) return rc;
     if ((rc = mp_idx_layout(h, st, m, kept, "mesh flatten"))) return rc;
-    const char *b = (const char *)st->work.buf;
-    char *o = (char *)st->out;
-    hipLaunchKernelGGL(k_fl_gather_out, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, h->mc_verts, h->mc_has_rgb ? h->mc_rgb : nullptr,
+    const char *b = (const char *)st->work.buf.p;
+    char *o = (char *)st->out.p;
+    hipLaunchKernelGGL(k_fl_gather_out, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, h->mc_verts.as<float>(), h->mc_has_rgb ? h->mc_rgb.as<uint8_t>() : nullptr,
                        (const uint32_t *)(b + L.seeds), (uint32_t)m, (float *)o, (uint8_t *)(o + st->o_rgb));
     TSDF_HIP_TRY(hipGetLastError());
     if ((rc = mp_idx_fill(h, st, m, kept, (const uint32_t *)(b + L.faces), (const uint8_t *)(b + L.keep), (const uint32_t *)(b + L.offset)))) return rc;
@@ -447,7 +444,7 @@ extern "C" int tsdf_hip_march_fetch_indexed(tsdf_handle h, float *verts, uint8_t
   }
   if (!m) return TSDF_HIP_OK;
   TSDF_ENTER(h);
-  const char *o = (const char *)st->out;
+  const char *o = (const char *)st->out.p;
   int rc = TSDF_HIP_OK;
   if (verts && (rc = tsdf_to_host(h, verts, o, m * 12))) return rc;
   if (rgb && (rc = tsdf_to_host(h, rgb, o + st->o_rgb, m * 3))) return rc;

@@ -105,7 +105,7 @@ extern "C" int tsdf_hip_organize(tsdf_handle h, const float *xyz, size_t xyz_str
   const size_t b_z = npx * 8, b_xyz = ((n * xyz_stride * 4 + 15) / 16) * 16, b_c = bgra ? n * bgra_stride : 0;
   int rc = tsdf_ensure_scratch(h, b_z + b_xyz + b_c + 16);
   if (rc) return rc;
-  char *sp = (char *)h->scratch;
+  char *sp = (char *)h->scratch.p;
   unsigned long long *zbuf = (unsigned long long *)sp;
   IngestArgs a;
   a.xyz = (const float *)(sp + b_z);

@@ -2486,25 +2486,6 @@ static void shrink_to_index_box(tsdf_handle h, const float T[12], LaunchPlan &pl
   pl.gz = (unsigned)(hi[2] - lo[2] + 1);
 }
 
-// the handle's scratch for a LIVE launch: nb block flags, nrows interval words
-static int grow_live_scratch(tsdf_handle h, size_t nb, size_t nrows) {
-  if (nb <= h->live_cap && nrows <= h->row_iv_cap) return TSDF_HIP_OK;
-  TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
-  if (nb > h->live_cap) {
-    if (h->live) TSDF_HIP_TRY(hipFree(h->live));
-    h->live = nullptr, h->live_cap = 0;
-    TSDF_HIP_TRY(hipMalloc(&h->live, nb));
-    h->live_cap = nb;
-  }
-  if (nrows > h->row_iv_cap) {
-    if (h->row_iv) TSDF_HIP_TRY(hipFree(h->row_iv));
-    h->row_iv = nullptr, h->row_iv_cap = 0;
-    TSDF_HIP_TRY(hipMalloc(&h->row_iv, nrows * sizeof(uint32_t)));
-    h->row_iv_cap = nrows;
-  }
-  return TSDF_HIP_OK;
-}
-
 // LIVE, step 3: k_rows writes every row's interval, k_cull flags, inside the box, the blocks none of whose voxels can be
 // observed.
 static int launch_rows_and_cull(tsdf_handle h, const float T[12], bool rc_rows, LaunchPlan &pl) {
@@ -2522,15 +2503,18 @@ static int launch_rows_and_cull(tsdf_handle h, const float T[12], bool rc_rows, 
   ra.rc = rc_rows ? 1 : 0;
   for (int i = 0; i < 24; ++i) ra.cull[i] = rc_rows ? h->cull_planes[i] : 0.f;
   const size_t nb = (size_t)pl.gx * pl.gy * pl.gz, nrows = (size_t)rows * pl.gz;
-  if (const int e = grow_live_scratch(h, nb, nrows)) return e;
+  // the handle's scratch for a LIVE launch: nb block flags, nrows interval words
+  if (const int e = h->live.reserve(nb, h->stream)) return e;
+  if (const int e = h->row_iv.reserve(nrows * sizeof(uint32_t), h->stream)) return e;
   const dim3 row_grid((unsigned)((nrows + 255) / 256)), block(256);
   if (ra.nx <= TSDF_ROWS_LDS_NX)
-    hipLaunchKernelGGL(k_rows<true>, row_grid, block, 0, h->stream, ra, pl.ctrx, pl.ctry, h->ctr[2], h->row_iv);
+    hipLaunchKernelGGL(k_rows<true>, row_grid, block, 0, h->stream, ra, pl.ctrx, pl.ctry, h->ctr[2], h->row_iv.as<uint32_t>());
   else
-    hipLaunchKernelGGL(k_rows<false>, row_grid, block, 0, h->stream, ra, pl.ctrx, pl.ctry, h->ctr[2], h->row_iv);
-  hipLaunchKernelGGL(k_cull, dim3((unsigned)((nb + 255) / 256)), block, 0, h->stream, c, pl.ctrx, pl.ctry, h->ctr[2], h->row_iv, h->live);
+    hipLaunchKernelGGL(k_rows<false>, row_grid, block, 0, h->stream, ra, pl.ctrx, pl.ctry, h->ctr[2], h->row_iv.as<uint32_t>());
+  hipLaunchKernelGGL(k_cull, dim3((unsigned)((nb + 255) / 256)), block, 0, h->stream, c, pl.ctrx, pl.ctry, h->ctr[2], h->row_iv.as<uint32_t>(),
+                     h->live.as<uint8_t>());
   TSDF_HIP_TRY(hipGetLastError());
-  pl.live = h->live;
+  pl.live = h->live.as<uint8_t>();
   return TSDF_HIP_OK;
 }
 
@@ -2567,7 +2551,7 @@ static void dispatch_fast(tsdf_handle h, const LaunchPlan &pl, const float *d_de
         if constexpr (!(ALLIN && (!FASTPROJ || LIVE)))
           hipLaunchKernelGGL((k_integrate<xform_order_of(SSE), COLOR, FASTPROJ, COUNT, PACKED, ALLIN, LIVE>), grid, block, 0,
                              h->stream, a, pl.D, pl.Wt, pl.RGB, pl.K8, d_depth, h->cam64, pl.ctrx, pl.ctry, h->ctr[2], h->counter,
-                             pl.live, band_arg, h->row_iv);
+                             pl.live, band_arg, h->row_iv.as<uint32_t>());
       },
       sse, color, fastproj, count, h->packed, allin, pl.live != nullptr);
 }
@@ -2874,15 +2858,13 @@ static __global__ void k_expf(const float *__restrict__ in, float *__restrict__ 
   if (i < n) out[i] = tsdf_expf_glibc(in[i], fused_r != 0);
 }
 static int device_expf(const float *in, size_t n, float *out, int fused_r) {
-  float *di = nullptr, *dout = nullptr;
-  TSDF_HIP_TRY(hipMalloc(&di, n * 4));
-  TSDF_HIP_TRY(hipMalloc(&dout, n * 4));
-  TSDF_HIP_TRY(hipMemcpy(di, in, n * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_expf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, di, dout, n, fused_r);
+  DevBuf di, dout;
+  if (const int rc = di.alloc(n * 4)) return rc;
+  if (const int rc = dout.alloc(n * 4)) return rc;
+  TSDF_HIP_TRY(hipMemcpy(di.p, in, n * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_expf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, di.as<float>(), dout.as<float>(), n, fused_r);
   TSDF_HIP_TRY(hipGetLastError());
-  TSDF_HIP_TRY(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost));
-  (void)hipFree(di);
-  (void)hipFree(dout);
+  TSDF_HIP_TRY(hipMemcpy(out, dout.p, n * 4, hipMemcpyDeviceToHost));
   return TSDF_HIP_OK;
 }
 
@@ -3004,18 +2986,15 @@ static __global__ void k_selftest_div64(const double *a, const double *b, double
 template <typename T, typename K>
 static int selftest_div(K kernel, const T *a, const T *b, T *out, size_t n) {
   if (!a || !b || !out || !n) return TSDF_HIP_E_INVALID;
-  T *da = nullptr, *db = nullptr, *dout = nullptr;
-  TSDF_HIP_TRY(hipMalloc(&da, n * sizeof(T)));
-  TSDF_HIP_TRY(hipMalloc(&db, n * sizeof(T)));
-  TSDF_HIP_TRY(hipMalloc(&dout, n * sizeof(T)));
-  TSDF_HIP_TRY(hipMemcpy(da, a, n * sizeof(T), hipMemcpyHostToDevice));
-  TSDF_HIP_TRY(hipMemcpy(db, b, n * sizeof(T), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, da, db, dout, n);
+  DevBuf da, db, dout;
+  if (const int rc = da.alloc(n * sizeof(T))) return rc;
+  if (const int rc = db.alloc(n * sizeof(T))) return rc;
+  if (const int rc = dout.alloc(n * sizeof(T))) return rc;
+  TSDF_HIP_TRY(hipMemcpy(da.p, a, n * sizeof(T), hipMemcpyHostToDevice));
+  TSDF_HIP_TRY(hipMemcpy(db.p, b, n * sizeof(T), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, da.as<T>(), db.as<T>(), dout.as<T>(), n);
   TSDF_HIP_TRY(hipGetLastError());
-  TSDF_HIP_TRY(hipMemcpy(out, dout, n * sizeof(T), hipMemcpyDeviceToHost));
-  (void)hipFree(da);
-  (void)hipFree(db);
-  (void)hipFree(dout);
+  TSDF_HIP_TRY(hipMemcpy(out, dout.p, n * sizeof(T), hipMemcpyDeviceToHost));
   return TSDF_HIP_OK;
 }
 
@@ -3200,23 +3179,18 @@ static __global__ void k_selftest_div_count(const float *a, const uint32_t *k, f
 
 extern "C" int tsdf_hip_selftest_div_count(const float *a, const uint32_t *k, float *out, uint8_t *fast, size_t n) {
   if (!a || !k || !out || !fast || !n) return TSDF_HIP_E_INVALID;
-  float *da = nullptr, *dout = nullptr;
-  uint32_t *dk = nullptr;
-  unsigned char *df = nullptr;
-  TSDF_HIP_TRY(hipMalloc(&da, n * 4));
-  TSDF_HIP_TRY(hipMalloc(&dk, n * 4));
-  TSDF_HIP_TRY(hipMalloc(&dout, n * 4));
-  TSDF_HIP_TRY(hipMalloc(&df, n));
-  TSDF_HIP_TRY(hipMemcpy(da, a, n * 4, hipMemcpyHostToDevice));
-  TSDF_HIP_TRY(hipMemcpy(dk, k, n * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_selftest_div_count, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, da, dk, dout, df, n);
+  DevBuf da, dk, dout, df;
+  if (const int rc = da.alloc(n * 4)) return rc;
+  if (const int rc = dk.alloc(n * 4)) return rc;
+  if (const int rc = dout.alloc(n * 4)) return rc;
+  if (const int rc = df.alloc(n)) return rc;
+  TSDF_HIP_TRY(hipMemcpy(da.p, a, n * 4, hipMemcpyHostToDevice));
+  TSDF_HIP_TRY(hipMemcpy(dk.p, k, n * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_selftest_div_count, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, da.as<float>(), dk.as<uint32_t>(), dout.as<float>(),
+                     df.as<unsigned char>(), n);
   TSDF_HIP_TRY(hipGetLastError());
-  TSDF_HIP_TRY(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost));
-  TSDF_HIP_TRY(hipMemcpy(fast, df, n, hipMemcpyDeviceToHost));
-  (void)hipFree(da);
-  (void)hipFree(dk);
-  (void)hipFree(dout);
-  (void)hipFree(df);
+  TSDF_HIP_TRY(hipMemcpy(out, dout.p, n * 4, hipMemcpyDeviceToHost));
+  TSDF_HIP_TRY(hipMemcpy(fast, df.p, n, hipMemcpyDeviceToHost));
   return TSDF_HIP_OK;
 }
 
@@ -3229,16 +3203,13 @@ static __global__ void k_selftest_cvt_pk_u8(const float *in, uint32_t *out, size
 
 extern "C" int tsdf_hip_selftest_cvt_pk_u8(const float *in, size_t n, uint32_t *out) {
   if (!in || !out || !n) return TSDF_HIP_E_INVALID;
-  float *d_in = nullptr;
-  uint32_t *d_out = nullptr;
-  TSDF_HIP_TRY(hipMalloc(&d_in, n * 4));
-  TSDF_HIP_TRY(hipMalloc(&d_out, n * 4));
-  TSDF_HIP_TRY(hipMemcpy(d_in, in, n * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_selftest_cvt_pk_u8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_in, d_out, n);
+  DevBuf d_in, d_out;
+  if (const int rc = d_in.alloc(n * 4)) return rc;
+  if (const int rc = d_out.alloc(n * 4)) return rc;
+  TSDF_HIP_TRY(hipMemcpy(d_in.p, in, n * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_selftest_cvt_pk_u8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_in.as<float>(), d_out.as<uint32_t>(), n);
   TSDF_HIP_TRY(hipGetLastError());
-  TSDF_HIP_TRY(hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost));
-  (void)hipFree(d_in);
-  (void)hipFree(d_out);
+  TSDF_HIP_TRY(hipMemcpy(out, d_out.p, n * 4, hipMemcpyDeviceToHost));
   return TSDF_HIP_OK;
 }
 
@@ -3253,35 +3224,28 @@ extern "C" int tsdf_hip_selftest_rgb2lab(const uint8_t *bgra, size_t n, float *l
   if (!bgra || !lab4 || !n || n > (size_t)1 << 30) return TSDF_HIP_E_INVALID;
   float lut[256];
   tsdf_lab_curve(lut);
-  uint32_t *d_px = nullptr;
-  float *d_lut = nullptr;
-  float4 *d_lab = nullptr;
-  TSDF_HIP_TRY(hipMalloc(&d_px, n * 4));
-  TSDF_HIP_TRY(hipMalloc(&d_lut, sizeof lut));
-  TSDF_HIP_TRY(hipMalloc(&d_lab, n * sizeof(float4)));
-  TSDF_HIP_TRY(hipMemcpy(d_px, bgra, n * 4, hipMemcpyHostToDevice));
-  TSDF_HIP_TRY(hipMemcpy(d_lut, lut, sizeof lut, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_lab_image, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_px, d_lut, d_lab, (int)n);
+  DevBuf d_px, d_lut, d_lab;
+  if (const int rc = d_px.alloc(n * 4)) return rc;
+  if (const int rc = d_lut.alloc(sizeof lut)) return rc;
+  if (const int rc = d_lab.alloc(n * sizeof(float4))) return rc;
+  TSDF_HIP_TRY(hipMemcpy(d_px.p, bgra, n * 4, hipMemcpyHostToDevice));
+  TSDF_HIP_TRY(hipMemcpy(d_lut.p, lut, sizeof lut, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_lab_image, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_px.as<uint32_t>(), d_lut.as<float>(), d_lab.as<float4>(),
+                     (int)n);
   TSDF_HIP_TRY(hipGetLastError());
-  TSDF_HIP_TRY(hipMemcpy(lab4, d_lab, n * sizeof(float4), hipMemcpyDeviceToHost));
-  (void)hipFree(d_px);
-  (void)hipFree(d_lut);
-  (void)hipFree(d_lab);
+  TSDF_HIP_TRY(hipMemcpy(lab4, d_lab.p, n * sizeof(float4), hipMemcpyDeviceToHost));
   return TSDF_HIP_OK;
 }
 
 extern "C" int tsdf_hip_selftest_lab2rgb(const float *lab3, size_t n, uint32_t *rgb) {
   if (!lab3 || !rgb || !n) return TSDF_HIP_E_INVALID;
-  float *d_lab = nullptr;
-  uint32_t *d_rgb = nullptr;
-  TSDF_HIP_TRY(hipMalloc(&d_lab, n * 12));
-  TSDF_HIP_TRY(hipMalloc(&d_rgb, n * 4));
-  TSDF_HIP_TRY(hipMemcpy(d_lab, lab3, n * 12, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_selftest_lab2rgb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_lab, d_rgb, n);
+  DevBuf d_lab, d_rgb;
+  if (const int rc = d_lab.alloc(n * 12)) return rc;
+  if (const int rc = d_rgb.alloc(n * 4)) return rc;
+  TSDF_HIP_TRY(hipMemcpy(d_lab.p, lab3, n * 12, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_selftest_lab2rgb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_lab.as<float>(), d_rgb.as<uint32_t>(), n);
   TSDF_HIP_TRY(hipGetLastError());
-  TSDF_HIP_TRY(hipMemcpy(rgb, d_rgb, n * 4, hipMemcpyDeviceToHost));
-  (void)hipFree(d_lab);
-  (void)hipFree(d_rgb);
+  TSDF_HIP_TRY(hipMemcpy(rgb, d_rgb.p, n * 4, hipMemcpyDeviceToHost));
   return TSDF_HIP_OK;
 }
 
@@ -3309,21 +3273,15 @@ static __global__ void k_selftest_record_gather(const uint2 *rec, int W, int H, 
 static int selftest_record_gather(const float *img, int W, int H, const int32_t *uv, uint32_t *out, int n) {
   const size_t npx = (size_t)W * H;
   if (npx > (size_t)1 << 24) return TSDF_HIP_E_INVALID;
-  struct DeviceBuffers {  // freed on every way out, the early returns of TSDF_HIP_TRY included
-    void *p[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~DeviceBuffers() {
-      for (void *q : p)
-        if (q) (void)hipFree(q);
-    }
-  } buf;
-  TSDF_HIP_TRY(hipMalloc(&buf.p[0], npx * 8));
-  TSDF_HIP_TRY(hipMalloc(&buf.p[1], (npx + 2) * 8));  // two guard records behind the last one
-  TSDF_HIP_TRY(hipMalloc(&buf.p[2], (size_t)n * 8));
-  TSDF_HIP_TRY(hipMalloc(&buf.p[3], (size_t)n * 8));
-  uint32_t *d_img = static_cast<uint32_t *>(buf.p[0]);
-  uint2 *d_rec = static_cast<uint2 *>(buf.p[1]);
-  int *d_uv = static_cast<int *>(buf.p[2]);
-  unsigned *d_out = static_cast<unsigned *>(buf.p[3]);
+  DevBuf buf[4];
+  if (const int rc = buf[0].alloc(npx * 8)) return rc;
+  if (const int rc = buf[1].alloc((npx + 2) * 8)) return rc;  // two guard records behind the last one
+  if (const int rc = buf[2].alloc((size_t)n * 8)) return rc;
+  if (const int rc = buf[3].alloc((size_t)n * 8)) return rc;
+  uint32_t *d_img = buf[0].as<uint32_t>();
+  uint2 *d_rec = buf[1].as<uint2>();
+  int *d_uv = buf[2].as<int>();
+  unsigned *d_out = buf[3].as<unsigned>();
   TSDF_HIP_TRY(hipMemcpy(d_img, img, npx * 8, hipMemcpyHostToDevice));
   TSDF_HIP_TRY(hipMemcpy(d_uv, uv, (size_t)n * 8, hipMemcpyHostToDevice));
   TSDF_HIP_TRY(hipMemset(d_rec, 0xa5, (npx + 2) * 8));
@@ -3351,22 +3309,17 @@ extern "C" int tsdf_hip_selftest_struct_oob(const float *img, int W, int H, int 
   const bool records = planes == 2 && plane == -1;  // the record form (include/tsdf_hip_test.h)
   if (!img || !uv || !out || n <= 0 || W <= 0 || H <= 0 || planes < 1 || (!records && (plane < 0 || plane >= planes))) return TSDF_HIP_E_INVALID;
   if (records) return selftest_record_gather(img, W, H, uv, out, n);
-  float *d_img = nullptr;
-  int *d_uv = nullptr;
-  unsigned *d_out = nullptr;
+  DevBuf d_img, d_uv, d_out;
   const size_t npx = (size_t)W * H;
-  TSDF_HIP_TRY(hipMalloc(&d_img, npx * 4 * planes));
-  TSDF_HIP_TRY(hipMalloc(&d_uv, (size_t)n * 8));
-  TSDF_HIP_TRY(hipMalloc(&d_out, (size_t)n * 4));
-  TSDF_HIP_TRY(hipMemcpy(d_img, img, npx * 4 * planes, hipMemcpyHostToDevice));
-  TSDF_HIP_TRY(hipMemcpy(d_uv, uv, (size_t)n * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_selftest_struct_oob, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_img, W, H,
-                     (unsigned)(npx * 4 * plane), d_uv, d_out, n);
+  if (const int rc = d_img.alloc(npx * 4 * planes)) return rc;
+  if (const int rc = d_uv.alloc((size_t)n * 8)) return rc;
+  if (const int rc = d_out.alloc((size_t)n * 4)) return rc;
+  TSDF_HIP_TRY(hipMemcpy(d_img.p, img, npx * 4 * planes, hipMemcpyHostToDevice));
+  TSDF_HIP_TRY(hipMemcpy(d_uv.p, uv, (size_t)n * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_selftest_struct_oob, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_img.as<float>(), W, H,
+                     (unsigned)(npx * 4 * plane), d_uv.as<int>(), d_out.as<unsigned>(), n);
   TSDF_HIP_TRY(hipGetLastError());
-  TSDF_HIP_TRY(hipMemcpy(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost));
-  (void)hipFree(d_img);
-  (void)hipFree(d_uv);
-  (void)hipFree(d_out);
+  TSDF_HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   return TSDF_HIP_OK;
 }
 
@@ -3397,23 +3350,18 @@ extern "C" int tsdf_hip_selftest_project(tsdf_handle h, const float *g, size_t n
     tsdf_set_error("fast projection disabled for this camera");
     return TSDF_HIP_E_UNSUPPORTED;
   }
-  float *dg = nullptr;
-  int *dpf = nullptr, *dpe = nullptr;
-  unsigned char *da = nullptr;
-  TSDF_HIP_TRY(hipMalloc(&dg, n * 12));
-  TSDF_HIP_TRY(hipMalloc(&dpf, n * 4));
-  TSDF_HIP_TRY(hipMalloc(&dpe, n * 4));
-  TSDF_HIP_TRY(hipMalloc(&da, n));
-  TSDF_HIP_TRY(hipMemcpy(dg, g, n * 12, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_selftest_project, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, a.a, h->cam64, dg, n, dpf, dpe, da);
+  DevBuf dg, dpf, dpe, da;
+  if (const int rc = dg.alloc(n * 12)) return rc;
+  if (const int rc = dpf.alloc(n * 4)) return rc;
+  if (const int rc = dpe.alloc(n * 4)) return rc;
+  if (const int rc = da.alloc(n)) return rc;
+  TSDF_HIP_TRY(hipMemcpy(dg.p, g, n * 12, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_selftest_project, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, a.a, h->cam64, dg.as<float>(), n, dpf.as<int>(),
+                     dpe.as<int>(), da.as<unsigned char>());
   TSDF_HIP_TRY(hipGetLastError());
-  TSDF_HIP_TRY(hipMemcpy(pix_fast, dpf, n * 4, hipMemcpyDeviceToHost));
-  TSDF_HIP_TRY(hipMemcpy(pix_exact, dpe, n * 4, hipMemcpyDeviceToHost));
-  TSDF_HIP_TRY(hipMemcpy(ambiguous, da, n, hipMemcpyDeviceToHost));
-  (void)hipFree(dg);
-  (void)hipFree(dpf);
-  (void)hipFree(dpe);
-  (void)hipFree(da);
+  TSDF_HIP_TRY(hipMemcpy(pix_fast, dpf.p, n * 4, hipMemcpyDeviceToHost));
+  TSDF_HIP_TRY(hipMemcpy(pix_exact, dpe.p, n * 4, hipMemcpyDeviceToHost));
+  TSDF_HIP_TRY(hipMemcpy(ambiguous, da.p, n, hipMemcpyDeviceToHost));
   return TSDF_HIP_OK;
 }
 #endif  // TSDF_HIP_TEST_HOOKS

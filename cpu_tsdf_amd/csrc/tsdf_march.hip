@@ -650,20 +650,6 @@ static float host_voxel_center(const tsdf_params &p, int a, int i) {  // tsdf_vo
   return (float)(((size_t)i + 0.5) * p.size[a] / (double)p.res[a] - off);
 }
 
-template <typename T>
-static int ensure_buf(T **buf, size_t *cap_elems, size_t need, hipStream_t s) {
-  if (need <= *cap_elems && *buf) return TSDF_HIP_OK;
-  if (*buf) {
-    TSDF_HIP_TRY(hipStreamSynchronize(s));
-    TSDF_HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *cap_elems = 0;
-  }
-  TSDF_HIP_TRY(hipMalloc(buf, need * sizeof(T)));
-  *cap_elems = need;
-  return TSDF_HIP_OK;
-}
-
 static int march_single(tsdf_handle h, float w_min, int color_mode, uint64_t *n_tri);
 
 extern "C" int tsdf_hip_march(tsdf_handle h, float w_min, int color_mode, uint64_t *n_tri) {
@@ -752,27 +738,20 @@ static int march_single(tsdf_handle h, float w_min, int color_mode, uint64_t *n_
     n.gx = a.need_gx, n.rows = a.need_rows, n.by = a.need_by;
     n.zb = a.zb;
     const size_t n_need = (size_t)n.gx * n.rows * n.n_planes, n_blk = (size_t)grid.x * grid.y * grid.z;
-    if (n_need + n_blk > h->mc_need_cap) {
-      TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
-      if (h->mc_need) (void)hipFree(h->mc_need);
-      h->mc_need = nullptr, h->mc_need_cap = 0;
-      TSDF_HIP_TRY(hipMalloc(&h->mc_need, n_need + n_blk));
-      h->mc_need_cap = n_need + n_blk;
-    }
-    a.need = h->mc_need;
-    a.need_blk = h->mc_need + n_need;
+    if (const int rc = h->mc_need.reserve(n_need + n_blk, h->stream)) return rc;
+    a.need = h->mc_need.as<uint8_t>();
+    a.need_blk = a.need + n_need;
     need_args = n;
     need_elems = n_need;
     need_blocks = n_blk;
   }
   unsigned long long counts[2 + MC_NEED_SLOTS] = {0};
-  for (int i = 0; i < 4; ++i)
-    if (!h->mc_ev[i]) TSDF_HIP_TRY(hipEventCreate(&h->mc_ev[i]));
+  if (const int rc = h->mc_ev.ensure(4)) return rc;
   h->mc_ms[0] = h->mc_ms[1] = h->mc_ms[2] = 0.f;
   h->mc_ncells = 0;
   // pass 1 with the capacity we already have; if the surface turned out larger, grow and repeat
   for (int attempt = 0; attempt < 2; ++attempt) {
-    const size_t cap = h->mc_cells_cap;
+    const size_t cap = h->mc_keys.cap / sizeof(uint64_t);
     TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, (attempt == 0 ? 2 + MC_NEED_SLOTS : 2) * sizeof(unsigned long long), h->stream));
     TSDF_HIP_TRY(hipEventRecord(h->mc_ev[0], h->stream));
     if (a.need && attempt == 0) {  // (inside the classify phase's timing)
@@ -787,21 +766,18 @@ static int march_single(tsdf_handle h, float w_min, int color_mode, uint64_t *n_
       TSDF_HIP_TRY(hipGetLastError());
     }
     if (!h->packed)
-      hipLaunchKernelGGL(k_mc_classify<0>, grid, block, 0, h->stream, a, h->mc_keys, (uint64_t)cap, h->counter);
+      hipLaunchKernelGGL(k_mc_classify<0>, grid, block, 0, h->stream, a, h->mc_keys.as<uint64_t>(), (uint64_t)cap, h->counter);
     else if (h->rgb)
-      hipLaunchKernelGGL(k_mc_classify<1>, grid, block, 0, h->stream, a, h->mc_keys, (uint64_t)cap, h->counter);
+      hipLaunchKernelGGL(k_mc_classify<1>, grid, block, 0, h->stream, a, h->mc_keys.as<uint64_t>(), (uint64_t)cap, h->counter);
     else
-      hipLaunchKernelGGL(k_mc_classify<2>, grid, block, 0, h->stream, a, h->mc_keys, (uint64_t)cap, h->counter);
+      hipLaunchKernelGGL(k_mc_classify<2>, grid, block, 0, h->stream, a, h->mc_keys.as<uint64_t>(), (uint64_t)cap, h->counter);
     TSDF_HIP_TRY(hipGetLastError());
     TSDF_HIP_TRY(hipEventRecord(h->mc_ev[1], h->stream));
     TSDF_HIP_TRY(hipMemcpyAsync(counts, h->counter, sizeof counts, hipMemcpyDeviceToHost, h->stream));
     TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
     if (counts[0] <= cap) break;
     const size_t need = (size_t)counts[0] + (size_t)counts[0] / 8 + 1024;
-    size_t c1 = h->mc_cells_cap;
-    const int rc = ensure_buf(&h->mc_keys, &c1, need, h->stream);
-    if (rc) return rc;
-    h->mc_cells_cap = need;
+    if (const int rc = h->mc_keys.reserve(need * sizeof(uint64_t), h->stream)) return rc;
   }
   const uint64_t n_cells = counts[0], ntri = counts[1];
   (void)hipEventElapsedTime(&h->mc_ms[0], h->mc_ev[0], h->mc_ev[1]);  // the last (successful) classify pass
@@ -840,7 +816,7 @@ static int march_single(tsdf_handle h, float w_min, int color_mode, uint64_t *n_
   uint64_t *vals_out = nullptr;
   uint32_t *off = nullptr;
   size_t tmp_bytes_sort = 0, tmp_bytes_scan = 0;
-  TSDF_HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes_sort, h->mc_keys, vals_out, (size_t)n_cells, MC_KEY_SHIFT,
+  TSDF_HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes_sort, h->mc_keys.as<uint64_t>(), vals_out, (size_t)n_cells, MC_KEY_SHIFT,
                                         MC_KEY_SHIFT + key_bits, h->stream));
   TSDF_HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes_scan, McCountIt(vals_out, McCountOf()), off, 0u, (size_t)n_cells,
                                        rocprim::plus<uint32_t>(), h->stream));
@@ -850,45 +826,35 @@ static int march_single(tsdf_handle h, float w_min, int color_mode, uint64_t *n_
   const size_t total = b_keys + b_cnt + up(std::max(tmp_bytes_sort, tmp_bytes_scan));
   int rc = tsdf_ensure_scratch(h, total);
   if (rc) return rc;
-  char *sp = (char *)h->scratch;
+  char *sp = (char *)h->scratch.p;
   vals_out = (uint64_t *)sp;  // the sorted cell words
   off = (uint32_t *)(sp + b_keys);
   void *tmp = sp + b_keys + b_cnt;
-  TSDF_HIP_TRY(rocprim::radix_sort_keys(tmp, tmp_bytes_sort, h->mc_keys, vals_out, (size_t)n_cells, MC_KEY_SHIFT,
+  TSDF_HIP_TRY(rocprim::radix_sort_keys(tmp, tmp_bytes_sort, h->mc_keys.as<uint64_t>(), vals_out, (size_t)n_cells, MC_KEY_SHIFT,
                                         MC_KEY_SHIFT + key_bits, h->stream));
   const unsigned cell_blocks = (unsigned)((n_cells + 255) / 256);
   TSDF_HIP_TRY(rocprim::exclusive_scan(tmp, tmp_bytes_scan, McCountIt(vals_out, McCountOf()), off, 0u, (size_t)n_cells,
                                        rocprim::plus<uint32_t>(), h->stream));
 
   // output buffers
-  if (ntri > h->mc_cap) {
-    TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->mc_verts) (void)hipFree(h->mc_verts);
-    if (h->mc_rgb) (void)hipFree(h->mc_rgb);
-    if (h->mc_cell) (void)hipFree(h->mc_cell);
-    h->mc_verts = nullptr;
-    h->mc_rgb = nullptr;
-    h->mc_cell = nullptr;
-    h->mc_cap = 0;
+  if (ntri > std::min(h->mc_verts.cap / 36, std::min(h->mc_rgb.cap / 9, h->mc_cell.cap / 8))) {  // triangles all three hold
     const size_t cap = (size_t)ntri + (size_t)ntri / 8 + 1024;
-    TSDF_HIP_TRY(hipMalloc(&h->mc_verts, cap * 9 * sizeof(float)));
-    TSDF_HIP_TRY(hipMalloc(&h->mc_rgb, cap * 9));
-    TSDF_HIP_TRY(hipMalloc(&h->mc_cell, cap * sizeof(uint64_t)));
-    h->mc_cap = cap;
+    if ((rc = h->mc_verts.reserve(cap * 9 * sizeof(float), h->stream))) return rc;
+    if ((rc = h->mc_rgb.reserve(cap * 9, h->stream))) return rc;
+    if ((rc = h->mc_cell.reserve(cap * sizeof(uint64_t), h->stream))) return rc;
   }
   if (color_mode == 1 && h->lab_img) {
     // setColorByRGB on LABNode voxels (:226-231 -> LABNode::getRGB): the emit kernel reads the rgb plane; put the EXACT
     // bytes there for the cells it is about to read (host pow, tsdf_lab_exact_colors)
-    int64_t *d_idx = nullptr;
-    TSDF_HIP_TRY(hipMalloc(&d_idx, (size_t)n_cells * sizeof(int64_t)));
+    DevBuf idx;
+    if ((rc = idx.alloc((size_t)n_cells * sizeof(int64_t)))) return rc;
+    int64_t *d_idx = idx.as<int64_t>();
     hipLaunchKernelGGL(k_mc_cell_index, dim3(cell_blocks), dim3(256), 0, h->stream, a, vals_out, n_cells, d_idx);
-    const int rcx = tsdf_lab_exact_colors(h, d_idx, (size_t)n_cells, nullptr, true);
-    (void)hipFree(d_idx);
-    if (rcx) return rcx;
+    if ((rc = tsdf_lab_exact_colors(h, d_idx, (size_t)n_cells, nullptr, true))) return rc;
   }
   TSDF_HIP_TRY(hipEventRecord(h->mc_ev[2], h->stream));
-  hipLaunchKernelGGL(k_mc_emit, dim3(cell_blocks), dim3(256), 0, h->stream, a, vals_out, off, n_cells, h->mc_verts,
-                     color_mode ? h->mc_rgb : nullptr, h->mc_cell);
+  hipLaunchKernelGGL(k_mc_emit, dim3(cell_blocks), dim3(256), 0, h->stream, a, vals_out, off, n_cells, h->mc_verts.as<float>(),
+                     color_mode ? h->mc_rgb.as<uint8_t>() : nullptr, h->mc_cell.as<uint64_t>());
   TSDF_HIP_TRY(hipGetLastError());
   TSDF_HIP_TRY(hipEventRecord(h->mc_ev[3], h->stream));
   TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
@@ -941,9 +907,9 @@ extern "C" int tsdf_hip_march_fetch(tsdf_handle h, float *verts, uint8_t *rgb, u
     return TSDF_HIP_E_INVALID;
   }
   int rc = TSDF_HIP_OK;
-  if (verts && (rc = tsdf_to_host(h, verts, h->mc_verts, n * 9 * sizeof(float)))) return rc;
-  if (rgb && (rc = tsdf_to_host(h, rgb, h->mc_rgb, n * 9))) return rc;
-  if (cell && (rc = tsdf_to_host(h, cell, h->mc_cell, n * sizeof(uint64_t)))) return rc;
+  if (verts && (rc = tsdf_to_host(h, verts, h->mc_verts.p, n * 9 * sizeof(float)))) return rc;
+  if (rgb && (rc = tsdf_to_host(h, rgb, h->mc_rgb.p, n * 9))) return rc;
+  if (cell && (rc = tsdf_to_host(h, cell, h->mc_cell.p, n * sizeof(uint64_t)))) return rc;
   TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
   return TSDF_HIP_OK;
 }
@@ -957,14 +923,14 @@ extern "C" int tsdf_hip_march_fetch_device(tsdf_handle h, float *d_verts, uint8_
   const size_t n = (size_t)h->mc_ntri;
   if (!n) return TSDF_HIP_OK;
   if (d_verts)
-    TSDF_HIP_TRY(hipMemcpyAsync(d_verts, h->mc_verts, n * 9 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    TSDF_HIP_TRY(hipMemcpyAsync(d_verts, h->mc_verts.p, n * 9 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   if (d_rgb) {
     if (!h->mc_has_rgb) {
       tsdf_set_error("the last tsdf_hip_march ran without a colour mode");
       return TSDF_HIP_E_INVALID;
     }
-    TSDF_HIP_TRY(hipMemcpyAsync(d_rgb, h->mc_rgb, n * 9, hipMemcpyDeviceToDevice, h->stream));
+    TSDF_HIP_TRY(hipMemcpyAsync(d_rgb, h->mc_rgb.p, n * 9, hipMemcpyDeviceToDevice, h->stream));
   }
-  if (d_cell) TSDF_HIP_TRY(hipMemcpyAsync(d_cell, h->mc_cell, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, h->stream));
+  if (d_cell) TSDF_HIP_TRY(hipMemcpyAsync(d_cell, h->mc_cell.p, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, h->stream));
   return TSDF_HIP_OK;
 }

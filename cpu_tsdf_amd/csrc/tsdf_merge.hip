@@ -208,9 +208,8 @@ extern "C" int tsdf_hip_merge(tsdf_handle dst, tsdf_handle src, const double src
     dst->merge_timed = dst->merge_count_pending = false;
     return TSDF_HIP_OK;
   }
-  for (hipEvent_t &e : dst->merge_ev)
-    if (!e) TSDF_HIP_TRY(hipEventCreate(&e));
-  if (!dst->merge_count) TSDF_HIP_TRY(hipMalloc(&dst->merge_count, sizeof(unsigned long long)));
+  if (const int rc = dst->merge_ev.ensure(3)) return rc;
+  if (const int rc = dst->merge_count.reserve(sizeof(unsigned long long), dst->stream)) return rc;
   MergeArgs a;
   for (int i = 0; i < 12; ++i) a.M[i] = (float)src_from_dst[i];
   a.min_weight = min_weight;
@@ -225,19 +224,19 @@ extern "C" int tsdf_hip_merge(tsdf_handle dst, tsdf_handle src, const double src
   // everything queued on src's stream so far is read; nothing queued on it later overtakes the read
   TSDF_HIP_TRY(hipEventRecord(dst->merge_ev[2], src->stream));
   TSDF_HIP_TRY(hipStreamWaitEvent(dst->stream, dst->merge_ev[2], 0));
-  TSDF_HIP_TRY(hipMemsetAsync(dst->merge_count, 0, sizeof(unsigned long long), dst->stream));
+  TSDF_HIP_TRY(hipMemsetAsync(dst->merge_count.p, 0, sizeof(unsigned long long), dst->stream));
   TSDF_HIP_TRY(hipEventRecord(dst->merge_ev[0], dst->stream));
   const bool color = dst->rgb && src->rgb && dst->p.integrate_color && src->p.integrate_color;
   if (dst->packed) {
     if (color)
-      hipLaunchKernelGGL((k_merge<true, true>), grid, block, 0, dst->stream, g, a, dst->merge_count);
+      hipLaunchKernelGGL((k_merge<true, true>), grid, block, 0, dst->stream, g, a, dst->merge_count.as<unsigned long long>());
     else
-      hipLaunchKernelGGL((k_merge<true, false>), grid, block, 0, dst->stream, g, a, dst->merge_count);
+      hipLaunchKernelGGL((k_merge<true, false>), grid, block, 0, dst->stream, g, a, dst->merge_count.as<unsigned long long>());
   } else {
     if (color)
-      hipLaunchKernelGGL((k_merge<false, true>), grid, block, 0, dst->stream, g, a, dst->merge_count);
+      hipLaunchKernelGGL((k_merge<false, true>), grid, block, 0, dst->stream, g, a, dst->merge_count.as<unsigned long long>());
     else
-      hipLaunchKernelGGL((k_merge<false, false>), grid, block, 0, dst->stream, g, a, dst->merge_count);
+      hipLaunchKernelGGL((k_merge<false, false>), grid, block, 0, dst->stream, g, a, dst->merge_count.as<unsigned long long>());
   }
   TSDF_HIP_TRY(hipGetLastError());
   // Only here, behind everything that can still fail before the kernel is queued: a call that fails earlier leaves dst's record
@@ -255,7 +254,7 @@ extern "C" int tsdf_hip_merge(tsdf_handle dst, tsdf_handle src, const double src
   TSDF_HIP_TRY(hipStreamWaitEvent(src->stream, dst->merge_ev[2], 0));
   if (n_merged) {
     unsigned long long n = 0;
-    TSDF_HIP_TRY(hipMemcpyAsync(&n, dst->merge_count, sizeof n, hipMemcpyDeviceToHost, dst->stream));
+    TSDF_HIP_TRY(hipMemcpyAsync(&n, dst->merge_count.p, sizeof n, hipMemcpyDeviceToHost, dst->stream));
     TSDF_HIP_TRY(hipStreamSynchronize(dst->stream));
     dst->merge_stats[1] = *n_merged = n;
     dst->merge_count_pending = false;
@@ -271,7 +270,7 @@ extern "C" int tsdf_hip_merge_stats(tsdf_handle h, uint64_t out[4]) {
   TSDF_HIP_TRY(hipEventSynchronize(h->merge_ev[1]));
   if (h->merge_count_pending) {  // (nothing has been queued on the counter since: the next merge resets this state first)
     unsigned long long n = 0;
-    TSDF_HIP_TRY(hipMemcpy(&n, h->merge_count, sizeof n, hipMemcpyDeviceToHost));
+    TSDF_HIP_TRY(hipMemcpy(&n, h->merge_count.p, sizeof n, hipMemcpyDeviceToHost));
     h->merge_stats[1] = n;
     h->merge_count_pending = false;
   }

@@ -1,8 +1,8 @@
 // Internal: what the three mesh passes on the GPU -- tsdf_meshpost.hip (cleanupMesh), tsdf_flatten.hip (flattenVertices) and
 // tsdf_decimate.hip (decimateMesh) -- share.  Declared here and defined in tsdf_meshgrid.hip: the cell table (the uniform grid
 // of cpu_tsdf::mesh_post::PointGrid, csrc/prog/mesh_post.h, over points sorted by the host's cell key), the working set of a
-// pass, a handle-less call with its copies of caller memory (pinned: direct; pageable: staged), and the indexed mesh of a
-// handle.  tsdf_smooth.hip (smoothMesh), which moves the vertices of that indexed mesh, and tsdf_normals.hip (meshNormals),
+// pass, a handle-less call with its copies of caller memory (PinnedStage, tsdf_own.h: pinned memory directly, pageable
+// memory through two pinned slots of MP_STAGE bytes), and the indexed mesh of a handle.  tsdf_smooth.hip (smoothMesh), which moves the vertices of that indexed mesh, and tsdf_normals.hip (meshNormals),
 // which reads it or the soup, use the working set, the call and the staging too, and mp_lower_bound.  Defined here, because the passes' own kernels inline or instantiate them: mp_cell_key, mp_for_links (the host's
 // forNeighbours), mp_face_remap and k_mp_compact.
 #pragma once
@@ -122,16 +122,13 @@ struct MpKeepCount {
 using MpKeepIt = rocprim::transform_iterator<const uint8_t *, MpKeepCount, uint32_t>;
 
 struct MpWork {  // the working set of one pass: a handle's, or a handle-less call's
-  void *buf = nullptr;  // per-point and per-face arrays + rocprim's temporary storage
-  size_t cap = 0;
-  void *cells = nullptr;  // per-cell arrays (sized once the number of occupied cells is known)
-  size_t cells_cap = 0;
-  unsigned long long *counters = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // timed intervals on the stream (cleanup: two; flatten, decimate: one, ev[0 .. 1])
+  DevBuf buf;       // per-point and per-face arrays + rocprim's temporary storage
+  DevBuf cells;     // per-cell arrays (sized once the number of occupied cells is known)
+  DevBuf counters;  // unsigned long long each
+  EventSet<4> ev;   // timed intervals on the stream (cleanup: two; flatten, decimate: one, ev[0 .. 1])
+  unsigned long long *count() const { return counters.as<unsigned long long>(); }
 };
 
-void mp_work_free(MpWork &w);
-int mp_reserve(void **p, size_t *cap, size_t need, hipStream_t s, const char *who);
 // on first use the n_counters counters and the first n_events events; queues the zeroing of the counters
 int mp_work_begin(MpWork &w, int n_counters, int n_events, hipStream_t s);
 
@@ -174,27 +171,22 @@ struct MpStats {  // the four words of a pass's *_stats entry point; each pass k
   }
 };
 
-struct MpStage {  // two pinned slots for pageable caller memory
-  char *pinned = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~MpStage();
-  int ready();
-};
-
-int mp_to_device(MpStage &st, void *dst, const void *src, size_t bytes, hipStream_t s);
-int mp_to_host(MpStage &st, void *dst, const void *src, size_t bytes, hipStream_t s);
-
-struct MpCall {  // a host-array entry point: everything it allocates goes when it returns (there is no handle to keep it for)
+// A host-array entry point: everything it allocates goes when it returns (there is no handle to keep it for).  Its copies of
+// caller memory are the handle's (PinnedStage, tsdf_own.h) with slots of MP_STAGE bytes, which they were not always: pageable
+// results now come back overlapped, not chunk after chunk; an upload from pinned memory waits for its copy before it returns,
+// as tsdf_to_device does; and a pageable upload no longer ends with a stream synchronise, the slots' busy flags guarding them
+// for the way back.  The bytes and their order are the same.
+struct MpCall {
   std::optional<TsdfDeviceScope> scope;  // (first, so restored last)
   hipStream_t s = nullptr;
-  void *in = nullptr;  // the caller's arrays on the device
+  DevBuf in;  // the caller's arrays on the device
   MpWork work;
-  MpStage stage;
+  PinnedStage stage{MP_STAGE};
   ~MpCall();
   // after the caller's own argument checks: is there such a device; on it, a stream and in_bytes for the inputs
   int open(int device, size_t in_bytes, const char *who);
-  int upload(void *dst, const void *src, size_t bytes) { return mp_to_device(stage, dst, src, bytes, s); }
-  int download(void *dst, const void *src, size_t bytes) { return mp_to_host(stage, dst, src, bytes, s); }
+  int upload(void *dst, const void *src, size_t bytes) { return stage.to_device(dst, src, bytes, s); }
+  int download(void *dst, const void *src, size_t bytes) { return stage.to_host(dst, src, bytes, s); }
 };
 
 #define MP_IDX_COUNTERS 8  // MpWork::counters of the passes that share a handle's tsdf_flatten_state (flatten, decimate)
@@ -203,8 +195,8 @@ struct tsdf_flatten_state {  // per handle (tsdf_hip_volume::fl): the indexed me
   MpWork work;
   bool valid = false, has_rgb = false;
   uint64_t n_verts = 0, n_faces = 0;
-  void *out = nullptr;  // one handle: vertices, faces, cell keys, colours (device)
-  size_t out_cap = 0, o_faces = 0, o_cell = 0, o_rgb = 0;
+  DevBuf out;  // one handle: vertices, faces, cell keys, colours (device)
+  size_t o_faces = 0, o_cell = 0, o_rgb = 0;
   std::vector<float> h_verts;  // a multi-GPU set: the same on the host, like its soup
   std::vector<uint8_t> h_rgb;
   std::vector<uint32_t> h_faces;
@@ -213,8 +205,7 @@ struct tsdf_flatten_state {  // per handle (tsdf_hip_volume::fl): the indexed me
   // of their own; every later march, cleanup, flatten, decimate, smooth or reset drops them (nm_valid)
   bool nm_valid = false;
   uint64_t nm_n = 0;       // vertices they describe
-  void *nm_out = nullptr;  // one handle: normals, flags (device)
-  size_t nm_cap = 0;
+  DevBuf nm_out;           // one handle: normals, flags (device)
   std::vector<float> h_normals;  // a multi-GPU set: on the host
 };
 

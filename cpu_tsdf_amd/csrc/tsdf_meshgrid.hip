@@ -54,14 +54,14 @@ struct MpCellLayout {  // MpWork::cells: cell_key (at 0), cell_start, nbr
 };
 
 int mp_cells_reserve(MpWork &w, uint32_t n_cells, hipStream_t s, const char *who) {
-  return mp_reserve(&w.cells, &w.cells_cap, MpCellLayout(n_cells).total, s, who);
+  return w.cells.reserve(MpCellLayout(n_cells).total, s, who);
 }
 
 int mp_cells_build(MpWork &w, hipStream_t s, const uint64_t *keys, const uint32_t *head, uint32_t n, uint32_t n_cells, MpGrid &g) {
   const MpCellLayout C(n_cells);
-  uint64_t *cell_key = (uint64_t *)w.cells;
-  uint32_t *cell_start = (uint32_t *)((char *)w.cells + C.start);
-  int32_t *nbr = (int32_t *)((char *)w.cells + C.nbr);
+  uint64_t *cell_key = (uint64_t *)w.cells.p;
+  uint32_t *cell_start = (uint32_t *)((char *)w.cells.p + C.start);
+  int32_t *nbr = (int32_t *)((char *)w.cells.p + C.nbr);
   const dim3 blk(256);
   hipLaunchKernelGGL(k_mp_cells, dim3((n + 255u) / 256u), blk, 0, s, keys, head, g.cellno, n, cell_key, cell_start);
   TSDF_HIP_TRY(hipGetLastError());
@@ -73,37 +73,10 @@ int mp_cells_build(MpWork &w, hipStream_t s, const uint64_t *keys, const uint32_
 }
 
 // ---- the working set ---------------------------------------------------------------------------------------------------------
-void mp_work_free(MpWork &w) {
-  if (w.buf) (void)hipFree(w.buf);
-  if (w.cells) (void)hipFree(w.cells);
-  if (w.counters) (void)hipFree(w.counters);
-  for (hipEvent_t e : w.ev)
-    if (e) (void)hipEventDestroy(e);
-  w = MpWork();
-}
-
-int mp_reserve(void **p, size_t *cap, size_t need, hipStream_t s, const char *who) {
-  if (need <= *cap && *p) return TSDF_HIP_OK;
-  if (*p) {
-    TSDF_HIP_TRY(hipStreamSynchronize(s));
-    TSDF_HIP_TRY(hipFree(*p));
-    *p = nullptr, *cap = 0;
-  }
-  if (hipMalloc(p, need) != hipSuccess) {
-    *p = nullptr;
-    (void)hipGetLastError();
-    tsdf_set_error(std::string(who) + ": " + std::to_string(need) + " bytes of device memory for the working set are not available");
-    return TSDF_HIP_E_NOMEM;
-  }
-  *cap = need;
-  return TSDF_HIP_OK;
-}
-
 int mp_work_begin(MpWork &w, int n_counters, int n_events, hipStream_t s) {
-  if (!w.counters) TSDF_HIP_TRY(hipMalloc(&w.counters, (size_t)n_counters * sizeof(unsigned long long)));
-  for (int i = 0; i < n_events; ++i)
-    if (!w.ev[i]) TSDF_HIP_TRY(hipEventCreate(&w.ev[i]));
-  TSDF_HIP_TRY(hipMemsetAsync(w.counters, 0, (size_t)n_counters * sizeof(unsigned long long), s));
+  if (const int rc = w.counters.reserve((size_t)n_counters * sizeof(unsigned long long), s)) return rc;
+  if (const int rc = w.ev.ensure(n_events)) return rc;
+  TSDF_HIP_TRY(hipMemsetAsync(w.count(), 0, (size_t)n_counters * sizeof(unsigned long long), s));
   return TSDF_HIP_OK;
 }
 
@@ -141,59 +114,8 @@ int mp_check_counts(const char *who, uint64_t n_faces, const uint64_t *n_verts) 
 }
 
 // ---- a handle-less call ------------------------------------------------------------------------------------------------------
-MpStage::~MpStage() {
-  if (pinned) (void)hipHostFree(pinned);
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-}
-
-int MpStage::ready() {
-  if (pinned) return TSDF_HIP_OK;
-  TSDF_HIP_TRY(hipHostMalloc((void **)&pinned, 2 * (size_t)MP_STAGE, hipHostMallocDefault));
-  for (int i = 0; i < 2; ++i) TSDF_HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-  return TSDF_HIP_OK;
-}
-
-int mp_to_device(MpStage &st, void *dst, const void *src, size_t bytes, hipStream_t s) {
-  if (!bytes) return TSDF_HIP_OK;
-  if (bytes >= (64u << 10) && tsdf_is_pinned_host(src)) {
-    TSDF_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-    return TSDF_HIP_OK;
-  }
-  if (const int rc = st.ready()) return rc;
-  for (size_t off = 0, k = 0; off < bytes; off += MP_STAGE, ++k) {
-    const int slot = (int)(k & 1);
-    if (k >= 2) TSDF_HIP_TRY(hipEventSynchronize(st.ev[slot]));  // the copy that last read this slot has finished
-    const size_t len = std::min((size_t)MP_STAGE, bytes - off);
-    memcpy(st.pinned + (size_t)slot * MP_STAGE, (const char *)src + off, len);
-    TSDF_HIP_TRY(hipMemcpyAsync((char *)dst + off, st.pinned + (size_t)slot * MP_STAGE, len, hipMemcpyHostToDevice, s));
-    TSDF_HIP_TRY(hipEventRecord(st.ev[slot], s));
-  }
-  TSDF_HIP_TRY(hipStreamSynchronize(s));  // (the slots are free again for the way back)
-  return TSDF_HIP_OK;
-}
-
-int mp_to_host(MpStage &st, void *dst, const void *src, size_t bytes, hipStream_t s) {
-  if (!bytes) return TSDF_HIP_OK;
-  if (bytes >= (64u << 10) && tsdf_is_pinned_host(dst)) {
-    TSDF_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
-    TSDF_HIP_TRY(hipStreamSynchronize(s));
-    return TSDF_HIP_OK;
-  }
-  if (const int rc = st.ready()) return rc;
-  for (size_t off = 0; off < bytes; off += MP_STAGE) {
-    const size_t len = std::min((size_t)MP_STAGE, bytes - off);
-    TSDF_HIP_TRY(hipMemcpyAsync(st.pinned, (const char *)src + off, len, hipMemcpyDeviceToHost, s));
-    TSDF_HIP_TRY(hipStreamSynchronize(s));
-    memcpy((char *)dst + off, st.pinned, len);
-  }
-  return TSDF_HIP_OK;
-}
-
-MpCall::~MpCall() {
+MpCall::~MpCall() {  // (the members free their memory after this, the stream being idle)
   if (s) (void)hipStreamSynchronize(s);
-  mp_work_free(work);
-  if (in) (void)hipFree(in);
   if (s) (void)hipStreamDestroy(s);
 }
 
@@ -207,9 +129,7 @@ int MpCall::open(int device, size_t in_bytes, const char *who) {
   scope.emplace(device);
   TSDF_HIP_TRY(scope->err);
   TSDF_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  if (hipMalloc(&in, in_bytes) != hipSuccess) {
-    in = nullptr;
-    (void)hipGetLastError();
+  if (in.alloc(in_bytes)) {
     tsdf_set_error(std::string(who) + ": " + std::to_string(in_bytes) + " bytes of device memory for the mesh are not available");
     return TSDF_HIP_E_NOMEM;
   }
@@ -235,16 +155,16 @@ int mp_idx_layout(tsdf_handle h, tsdf_flatten_state *st, uint64_t m, uint64_t ke
   MpTake take;
   take((size_t)m * 12);  // the vertices, at 0
   st->o_faces = take((size_t)kept * 12), st->o_cell = take((size_t)kept * 8), st->o_rgb = take((size_t)m * 3);
-  return mp_reserve(&st->out, &st->out_cap, take.o, h->stream, who);
+  return st->out.reserve(take.o, h->stream, who);
 }
 
 int mp_idx_fill(tsdf_handle h, tsdf_flatten_state *st, uint64_t m, uint64_t kept, const uint32_t *d_faces, const uint8_t *d_keep,
                 const uint32_t *d_offset) {
-  char *o = (char *)st->out;
+  char *o = (char *)st->out.p;
   const uint64_t n = h->mc_ntri;
   if (kept) {
     TSDF_HIP_TRY(hipMemcpyAsync(o + st->o_faces, d_faces, (size_t)kept * 12, hipMemcpyDeviceToDevice, h->stream));
-    hipLaunchKernelGGL((k_mp_compact<uint64_t, 1>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->mc_cell, d_keep, d_offset, n,
+    hipLaunchKernelGGL((k_mp_compact<uint64_t, 1>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->mc_cell.as<uint64_t>(), d_keep, d_offset, n,
                        (uint64_t *)(o + st->o_cell));
     TSDF_HIP_TRY(hipGetLastError());
   }

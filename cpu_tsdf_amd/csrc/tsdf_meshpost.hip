@@ -46,7 +46,6 @@ static thread_local MpStats g_mp_stats;  // tsdf_hip_mesh_cleanup_stats
 void tsdf_meshpost_release(tsdf_hip_volume *v) {
   if (!v->mp) return;
   TsdfDeviceScope scope(v->device);
-  mp_work_free(v->mp->work);
   delete v->mp;
   v->mp = nullptr;
 }
@@ -214,8 +213,8 @@ static int mp_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
                    int min_neighbors, MpLayout &L, uint64_t *n_kept) {
   const uint32_t n = (uint32_t)n_faces, min_nb = (uint32_t)min_neighbors;
   int rc = mp_layout(n, s, L);
-  if (rc || (rc = mp_reserve(&w.buf, &w.cap, L.total, s, "mesh cleanup")) || (rc = mp_work_begin(w, MP_COUNTERS, 4, s))) return rc;
-  char *b = (char *)w.buf;
+  if (rc || (rc = w.buf.reserve(L.total, s, "mesh cleanup")) || (rc = mp_work_begin(w, MP_COUNTERS, 4, s))) return rc;
+  char *b = (char *)w.buf.p;
   uint64_t *key_a = (uint64_t *)(b + L.key_a), *key_b = (uint64_t *)(b + L.key_b);
   uint32_t *idx_a = (uint32_t *)(b + L.idx_a), *idx_b = (uint32_t *)(b + L.idx_b), *cellno = (uint32_t *)(b + L.cellno);
   float4 *cen = (float4 *)(b + L.cen);
@@ -225,7 +224,7 @@ static int mp_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
   const dim3 blk(256), grid_n((n + 255u) / 256u);
 
   TSDF_HIP_TRY(hipEventRecord(w.ev[0], s));
-  hipLaunchKernelGGL(k_mp_centroid, grid_n, blk, 0, s, d_verts, n_verts, d_faces, n, (double)face_dist, key_a, idx_a, w.counters);
+  hipLaunchKernelGGL(k_mp_centroid, grid_n, blk, 0, s, d_verts, n_verts, d_faces, n, (double)face_dist, key_a, idx_a, w.count());
   TSDF_HIP_TRY(hipGetLastError());
   size_t tmp_bytes = L.tmp_bytes;
   TSDF_HIP_TRY(rocprim::radix_sort_pairs(b + L.tmp, tmp_bytes, key_a, key_b, idx_a, idx_b, (size_t)n, 0u, 64u, s));
@@ -236,7 +235,7 @@ static int mp_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
   TSDF_HIP_TRY(hipEventRecord(w.ev[1], s));
   unsigned long long counts[MP_COUNTERS] = {0};
   uint32_t n_cells = 0;
-  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, MP_C_TESTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.count(), MP_C_TESTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   TSDF_HIP_TRY(hipMemcpyAsync(&n_cells, cellno + (n - 1u), sizeof n_cells, hipMemcpyDeviceToHost, s));
   TSDF_HIP_TRY(hipStreamSynchronize(s));
   if (counts[MP_C_BAD]) {
@@ -254,17 +253,17 @@ static int mp_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
     TSDF_HIP_TRY(hipMemsetAsync(any_heavy, 0, n, s));
     TSDF_HIP_TRY(hipMemsetAsync(members, 0, (size_t)n * 4, s));
     const dim3 grid_f((n_fin + 255u) / 256u);
-    hipLaunchKernelGGL(k_mp_degree, grid_f, blk, 0, s, g, min_nb, heavy, parent, w.counters);
+    hipLaunchKernelGGL(k_mp_degree, grid_f, blk, 0, s, g, min_nb, heavy, parent, w.count());
     TSDF_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_mp_link, grid_f, blk, 0, s, g, heavy, parent, w.counters);
+    hipLaunchKernelGGL(k_mp_link, grid_f, blk, 0, s, g, heavy, parent, w.count());
     TSDF_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_mp_count, grid_f, blk, 0, s, n_fin, heavy, parent, any_heavy, members);
     TSDF_HIP_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_mp_keep, grid_n, blk, 0, s, n, n_fin, min_nb, idx_b, heavy, parent, any_heavy, members, keep, w.counters);
+  hipLaunchKernelGGL(k_mp_keep, grid_n, blk, 0, s, n, n_fin, min_nb, idx_b, heavy, parent, any_heavy, members, keep, w.count());
   TSDF_HIP_TRY(hipGetLastError());
   TSDF_HIP_TRY(hipEventRecord(w.ev[3], s));
-  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, sizeof counts, hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.count(), sizeof counts, hipMemcpyDeviceToHost, s));
   TSDF_HIP_TRY(hipStreamSynchronize(s));
   // device time = the two intervals on the stream; the host's read of the counts between them (a copy of 8 words, a
   // synchronise, the sizing of the cell table) is not in it
@@ -304,13 +303,13 @@ extern "C" int tsdf_hip_mesh_cleanup(int device, const float *verts, uint64_t n_
   const size_t b_verts = mp_up((size_t)n_verts * 12), b_faces = faces ? (size_t)n_faces * 12 : 0;
   int rc = c.open(device, b_verts + b_faces, "tsdf_hip_mesh_cleanup");
   if (rc) return rc;
-  float *d_verts = (float *)c.in;
-  uint32_t *d_faces = faces ? (uint32_t *)((char *)c.in + b_verts) : nullptr;
+  float *d_verts = (float *)c.in.p;
+  uint32_t *d_faces = faces ? (uint32_t *)((char *)c.in.p + b_verts) : nullptr;
   if ((rc = c.upload(d_verts, verts, (size_t)n_verts * 12)) || (faces && (rc = c.upload(d_faces, faces, b_faces)))) return rc;
   MpLayout L;
   uint64_t kept = 0;
   if ((rc = mp_core(c.work, c.s, d_verts, n_verts, d_faces, n_faces, face_dist, min_neighbors, L, &kept))) return rc;
-  if ((rc = c.download(keep, (char *)c.work.buf + L.keep, (size_t)n_faces))) return rc;
+  if ((rc = c.download(keep, (char *)c.work.buf.p + L.keep, (size_t)n_faces))) return rc;
   if (n_kept) *n_kept = kept;
   return TSDF_HIP_OK;
 }
@@ -336,12 +335,12 @@ extern "C" int tsdf_hip_march_cleanup(tsdf_handle h, float face_dist, int min_ne
   tsdf_meshpost_state *st = h->mp;
   MpLayout L;
   uint64_t kept = 0;
-  int rc = mp_core(st->work, h->stream, h->mc_verts, 3 * n, nullptr, n, face_dist, min_neighbors, L, &kept);
+  int rc = mp_core(st->work, h->stream, h->mc_verts.as<float>(), 3 * n, nullptr, n, face_dist, min_neighbors, L, &kept);
   if (rc) return rc;
   if (kept < n && kept) {
     // stable compaction of vertices, colours and cell keys: each array into the handle's scratch and back (the working set's
     // cell numbers are done with: their 4 n bytes take the offsets)
-    char *b = (char *)st->work.buf;
+    char *b = (char *)st->work.buf.p;
     const uint8_t *keep = (const uint8_t *)(b + L.keep);
     uint32_t *offset = (uint32_t *)(b + L.cellno);
     size_t tmp_bytes = L.tmp_bytes;
@@ -349,20 +348,20 @@ extern "C" int tsdf_hip_march_cleanup(tsdf_handle h, float face_dist, int min_ne
                                          h->stream));
     if ((rc = tsdf_ensure_scratch(h, (size_t)kept * 36))) return rc;
     const dim3 blk(256);
-    hipLaunchKernelGGL((k_mp_compact<float, 9>), dim3((unsigned)((9 * n + 255) / 256)), blk, 0, h->stream, h->mc_verts, keep, offset, 9 * n,
-                       (float *)h->scratch);
+    hipLaunchKernelGGL((k_mp_compact<float, 9>), dim3((unsigned)((9 * n + 255) / 256)), blk, 0, h->stream, h->mc_verts.as<float>(), keep, offset, 9 * n,
+                       (float *)h->scratch.p);
     TSDF_HIP_TRY(hipGetLastError());
-    TSDF_HIP_TRY(hipMemcpyAsync(h->mc_verts, h->scratch, (size_t)kept * 36, hipMemcpyDeviceToDevice, h->stream));
+    TSDF_HIP_TRY(hipMemcpyAsync(h->mc_verts.p, h->scratch.p, (size_t)kept * 36, hipMemcpyDeviceToDevice, h->stream));
     if (h->mc_has_rgb) {
-      hipLaunchKernelGGL((k_mp_compact<uint8_t, 9>), dim3((unsigned)((9 * n + 255) / 256)), blk, 0, h->stream, h->mc_rgb, keep, offset, 9 * n,
-                         (uint8_t *)h->scratch);
+      hipLaunchKernelGGL((k_mp_compact<uint8_t, 9>), dim3((unsigned)((9 * n + 255) / 256)), blk, 0, h->stream, h->mc_rgb.as<uint8_t>(), keep, offset, 9 * n,
+                         (uint8_t *)h->scratch.p);
       TSDF_HIP_TRY(hipGetLastError());
-      TSDF_HIP_TRY(hipMemcpyAsync(h->mc_rgb, h->scratch, (size_t)kept * 9, hipMemcpyDeviceToDevice, h->stream));
+      TSDF_HIP_TRY(hipMemcpyAsync(h->mc_rgb.p, h->scratch.p, (size_t)kept * 9, hipMemcpyDeviceToDevice, h->stream));
     }
-    hipLaunchKernelGGL((k_mp_compact<uint64_t, 1>), dim3((unsigned)((n + 255) / 256)), blk, 0, h->stream, h->mc_cell, keep, offset, n,
-                       (uint64_t *)h->scratch);
+    hipLaunchKernelGGL((k_mp_compact<uint64_t, 1>), dim3((unsigned)((n + 255) / 256)), blk, 0, h->stream, h->mc_cell.as<uint64_t>(), keep, offset, n,
+                       (uint64_t *)h->scratch.p);
     TSDF_HIP_TRY(hipGetLastError());
-    TSDF_HIP_TRY(hipMemcpyAsync(h->mc_cell, h->scratch, (size_t)kept * 8, hipMemcpyDeviceToDevice, h->stream));
+    TSDF_HIP_TRY(hipMemcpyAsync(h->mc_cell.p, h->scratch.p, (size_t)kept * 8, hipMemcpyDeviceToDevice, h->stream));
     TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
   }
   h->mc_ntri = kept;

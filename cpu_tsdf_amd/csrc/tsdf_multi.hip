@@ -893,8 +893,8 @@ static int shift_slab_z(tsdf_hip_multi *m, int k, int sz, int nz_grid, bool with
       if (with_band) {  // through a copy: the two plane ranges overlap
         const size_t n = cells * (size_t)(own1 - own0);
         if (const int rc = tsdf_ensure_scratch(s, n)) return rc;
-        TSDF_HIP_TRY(hipMemcpyAsync(s->scratch, s->band + (size_t)(own0 + sz - s->z_first) * cells, n, hipMemcpyDeviceToDevice, s->stream));
-        TSDF_HIP_TRY(hipMemcpyAsync(s->band + (size_t)(own0 - s->z_first) * cells, s->scratch, n, hipMemcpyDeviceToDevice, s->stream));
+        TSDF_HIP_TRY(hipMemcpyAsync(s->scratch.p, s->band + (size_t)(own0 + sz - s->z_first) * cells, n, hipMemcpyDeviceToDevice, s->stream));
+        TSDF_HIP_TRY(hipMemcpyAsync(s->band + (size_t)(own0 - s->z_first) * cells, s->scratch.p, n, hipMemcpyDeviceToDevice, s->stream));
       }
     }
   }

@@ -185,37 +185,37 @@ static int nm_core(MpWork &w, hipStream_t s, const float *d_verts, uint64_t n_ve
   NmLayout L;
   if (!soup) {
     const unsigned end_bit = 32u + nm_bits(n_verts);
-    if ((rc = nm_layout(n, e, end_bit, s, L)) || (rc = mp_reserve(&w.buf, &w.cap, L.total, s, "mesh normals"))) return rc;
+    if ((rc = nm_layout(n, e, end_bit, s, L)) || (rc = w.buf.reserve(L.total, s, "mesh normals"))) return rc;
   }
   if ((rc = mp_work_begin(w, MP_IDX_COUNTERS, 2, s))) return rc;
   TSDF_HIP_TRY(hipEventRecord(w.ev[0], s));
   if (soup) {
     if (nf) {
-      hipLaunchKernelGGL(k_nm_soup, grid_f, blk, 0, s, d_verts, nf, d_normals, d_flags, w.counters);
+      hipLaunchKernelGGL(k_nm_soup, grid_f, blk, 0, s, d_verts, nf, d_normals, d_flags, w.count());
       TSDF_HIP_TRY(hipGetLastError());
     } else {  // vertices and no face: rule 4's bits 1 | 2 everywhere
       TSDF_HIP_TRY(hipMemsetAsync(d_normals, 0, (size_t)n * 12, s));
       TSDF_HIP_TRY(hipMemsetAsync(d_flags, 3, (size_t)n, s));
     }
   } else {
-    char *b = (char *)w.buf;
+    char *b = (char *)w.buf.p;
     double4 *rec = (double4 *)(b + L.rec);
     uint64_t *key_a = (uint64_t *)(b + L.key_a), *keys = (uint64_t *)(b + L.key_b);
     uint32_t *row = (uint32_t *)(b + L.row);
     if (nf) {
-      hipLaunchKernelGGL(k_nm_face, grid_f, blk, 0, s, d_verts, d_faces, nf, n_verts, rec, key_a, w.counters);
+      hipLaunchKernelGGL(k_nm_face, grid_f, blk, 0, s, d_verts, d_faces, nf, n_verts, rec, key_a, w.count());
       TSDF_HIP_TRY(hipGetLastError());
       size_t tmp_bytes = L.tmp_bytes;
       TSDF_HIP_TRY(rocprim::radix_sort_keys(b + L.tmp, tmp_bytes, key_a, keys, (size_t)e, 0u, 32u + nm_bits(n_verts), s));
     }
     hipLaunchKernelGGL(k_nm_rows, dim3(n / 256u + 1u), blk, 0, s, keys, e, n, row);
     TSDF_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_nm_vertex, grid_n, blk, 0, s, keys, row, rec, n, d_normals, d_flags, w.counters);
+    hipLaunchKernelGGL(k_nm_vertex, grid_n, blk, 0, s, keys, row, rec, n, d_normals, d_flags, w.count());
     TSDF_HIP_TRY(hipGetLastError());
   }
   TSDF_HIP_TRY(hipEventRecord(w.ev[1], s));
   unsigned long long counts[MP_IDX_COUNTERS] = {0};
-  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, sizeof counts, hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.count(), sizeof counts, hipMemcpyDeviceToHost, s));
   TSDF_HIP_TRY(hipStreamSynchronize(s));
   if (counts[NM_C_BAD]) {
     tsdf_set_error(std::string(who) + ": a face names a vertex index >= n_verts");
@@ -260,7 +260,7 @@ extern "C" int tsdf_hip_mesh_normals(int device, const float *verts, uint64_t n_
                o_flags = take((size_t)n_verts);
   int rc = c.open(device, take.o, who);
   if (rc) return rc;
-  char *in = (char *)c.in;
+  char *in = (char *)c.in.p;
   if ((rc = c.upload(in + o_verts, verts, (size_t)n_verts * 12)) || (!soup && (rc = c.upload(in + o_faces, faces, (size_t)n_faces * 12)))) return rc;
   uint64_t zero = 0;
   if ((rc = nm_core(c.work, c.s, (const float *)(in + o_verts), n_verts, (const uint32_t *)(in + o_faces), soup, n_faces, (float *)(in + o_normals),
@@ -301,10 +301,10 @@ extern "C" int tsdf_hip_march_normals(tsdf_handle h, uint64_t *n_verts, uint64_t
   } else {
     TSDF_ENTER(h);
     const size_t o_flags = mp_up((size_t)n * 12);
-    if (const int rc = mp_reserve(&st->nm_out, &st->nm_cap, o_flags + (size_t)n, h->stream, "mesh normals")) return rc;
-    const char *o = (const char *)st->out;
-    if (const int rc = nm_core(st->work, h->stream, soup ? h->mc_verts : (const float *)o, n, soup ? nullptr : (const uint32_t *)(o + st->o_faces), soup,
-                               k, (float *)st->nm_out, (uint8_t *)st->nm_out + o_flags, &zero, who))
+    if (const int rc = st->nm_out.reserve(o_flags + (size_t)n, h->stream, "mesh normals")) return rc;
+    const char *o = (const char *)st->out.p;
+    if (const int rc = nm_core(st->work, h->stream, soup ? h->mc_verts.as<float>() : (const float *)o, n, soup ? nullptr : (const uint32_t *)(o + st->o_faces), soup,
+                               k, (float *)st->nm_out.p, (uint8_t *)st->nm_out.p + o_flags, &zero, who))
       return rc;
   }
   st->nm_valid = true;
@@ -329,7 +329,7 @@ extern "C" int tsdf_hip_march_fetch_normals(tsdf_handle h, float *normals) {
     return TSDF_HIP_OK;
   }
   TSDF_ENTER(h);
-  if (const int rc = tsdf_to_host(h, normals, st->nm_out, n * 12)) return rc;
+  if (const int rc = tsdf_to_host(h, normals, st->nm_out.p, n * 12)) return rc;
   TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
   return TSDF_HIP_OK;
 }

@@ -28,11 +28,10 @@
 struct tsdf_occ_state {
   bool valid = false;      // a tsdf_hip_occupied has completed on this handle
   uint64_t n = 0;
-  uint64_t *keys = nullptr;  // sorted Morton keys (device)
-  size_t keys_cap = 0;
+  DevBuf keys;             // sorted Morton keys, one uint64_t each
   uint64_t d_bytes = 0;    // distance bytes the scan requested
   bool used_flags = false;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // scan begin / end, sort end, emit begin / end
+  EventSet<5> ev;                                                    // scan begin / end, sort end, emit begin / end
   float ms[3] = {0.f, 0.f, 0.f};                                     // scan, count read-back + sort, emit (of the fetches since)
   bool emit_pending = false;  // ev[3], ev[4] bracket an emit whose time has not been read yet
   // a multi-GPU set: the merged list (host) and where each entry came from (slab << 48 | index in the slab's list)
@@ -50,9 +49,6 @@ static tsdf_occ_state *occ_state(tsdf_hip_volume *v) {  // created by the first 
 void tsdf_occupied_release(tsdf_hip_volume *v) {
   if (!v->occ) return;
   TsdfDeviceScope scope(v->device);
-  if (v->occ->keys) (void)hipFree(v->occ->keys);
-  for (hipEvent_t e : v->occ->ev)
-    if (e) (void)hipEventDestroy(e);
   delete v->occ;
   v->occ = nullptr;
 }
@@ -272,6 +268,12 @@ static int occ_nomem(uint64_t n, size_t bytes) {
   return TSDF_HIP_E_NOMEM;
 }
 
+// room for `bytes` in b; out of memory is this entry point's own message, about the n voxels and the `told` bytes
+static int occ_reserve(tsdf_handle h, DevBuf &b, size_t bytes, uint64_t n, size_t told) {
+  const int rc = b.reserve(bytes, h->stream, "tsdf_hip_occupied");
+  return rc == TSDF_HIP_E_NOMEM ? occ_nomem(n, told) : rc;
+}
+
 static int occ_multi(tsdf_handle h, const int32_t box[6], uint64_t *n);
 static int occ_multi_fetch(tsdf_handle h, int32_t *idx, float *d, float *w, uint8_t *rgb);
 
@@ -308,22 +310,21 @@ extern "C" int tsdf_hip_occupied(tsdf_handle h, const int32_t box[6], uint64_t *
   a.fx = h->band_fx, a.fy = h->band_fy;
   const dim3 grid((unsigned)((a.x1 - a.xb + 255) / 256), (unsigned)((a.y1 - a.yb + 15) / 16), (unsigned)((a.z1 - a.z0 + OCC_ZB - 1) / OCC_ZB));
   if (grid.y > 65535u || grid.z > 65535u) return TSDF_HIP_E_UNSUPPORTED;
-  for (int i = 0; i < 5; ++i)
-    if (!st->ev[i]) TSDF_HIP_TRY(hipEventCreate(&st->ev[i]));
+  if (const int rc = st->ev.ensure(5)) return rc;
   st->ms[0] = st->ms[1] = st->ms[2] = 0.f;
   st->emit_pending = false;
   unsigned long long counts[2 + OCC_BYTE_SLOTS] = {0};
   // pass 1 with the capacity at hand (tsdf_hip_march's cell buffer, shared); if the band turned out larger, grow and repeat
   for (int attempt = 0; attempt < 2; ++attempt) {
-    const size_t cap = h->mc_keys ? h->mc_cells_cap : 0;
+    const size_t cap = h->mc_keys.cap / sizeof(uint64_t);
     TSDF_HIP_TRY(hipMemsetAsync(h->counter, 0, sizeof counts, h->stream));
     TSDF_HIP_TRY(hipEventRecord(st->ev[0], h->stream));
     if (!h->packed)
-      hipLaunchKernelGGL(k_occ_scan<0>, grid, dim3(256), 0, h->stream, a, h->mc_keys, (uint64_t)cap, h->counter);
+      hipLaunchKernelGGL(k_occ_scan<0>, grid, dim3(256), 0, h->stream, a, h->mc_keys.as<uint64_t>(), (uint64_t)cap, h->counter);
     else if (h->rgb)
-      hipLaunchKernelGGL(k_occ_scan<1>, grid, dim3(256), 0, h->stream, a, h->mc_keys, (uint64_t)cap, h->counter);
+      hipLaunchKernelGGL(k_occ_scan<1>, grid, dim3(256), 0, h->stream, a, h->mc_keys.as<uint64_t>(), (uint64_t)cap, h->counter);
     else
-      hipLaunchKernelGGL(k_occ_scan<2>, grid, dim3(256), 0, h->stream, a, h->mc_keys, (uint64_t)cap, h->counter);
+      hipLaunchKernelGGL(k_occ_scan<2>, grid, dim3(256), 0, h->stream, a, h->mc_keys.as<uint64_t>(), (uint64_t)cap, h->counter);
     TSDF_HIP_TRY(hipGetLastError());
     TSDF_HIP_TRY(hipEventRecord(st->ev[1], h->stream));
     TSDF_HIP_TRY(hipMemcpyAsync(counts, h->counter, sizeof counts, hipMemcpyDeviceToHost, h->stream));
@@ -334,13 +335,8 @@ extern "C" int tsdf_hip_occupied(tsdf_handle h, const int32_t box[6], uint64_t *
       return TSDF_HIP_E_INVALID;
     }
     const size_t need = (size_t)counts[0] + (size_t)counts[0] / 8 + 1024;
-    if (h->mc_keys) (void)hipFree(h->mc_keys);
-    h->mc_keys = nullptr, h->mc_cells_cap = 0;
-    if (hipMalloc(&h->mc_keys, need * sizeof(uint64_t)) != hipSuccess) {
-      h->mc_keys = nullptr;
-      return occ_nomem(counts[0], need * sizeof(uint64_t) + (size_t)counts[0] * sizeof(uint64_t));
-    }
-    h->mc_cells_cap = need;
+    if (const int rc = occ_reserve(h, h->mc_keys, need * sizeof(uint64_t), counts[0], need * sizeof(uint64_t) + (size_t)counts[0] * sizeof(uint64_t)))
+      return rc;
   }
   const uint64_t count = counts[0];
   (void)hipEventElapsedTime(&st->ms[0], st->ev[0], st->ev[1]);  // the last (successful) scan
@@ -352,28 +348,15 @@ extern "C" int tsdf_hip_occupied(tsdf_handle h, const int32_t box[6], uint64_t *
     int coord_bits = 1;
     while ((1 << coord_bits) < std::max(h->nx, std::max(h->ny, h->nz))) ++coord_bits;
     const unsigned key_bits = 3u * (unsigned)coord_bits;
-    if (count > st->keys_cap) {
-      if (st->keys) (void)hipFree(st->keys);
-      st->keys = nullptr, st->keys_cap = 0;
+    if (count * sizeof(uint64_t) > st->keys.cap) {
       const size_t cap = (size_t)count + (size_t)count / 8 + 1024;
-      if (hipMalloc(&st->keys, cap * sizeof(uint64_t)) != hipSuccess) {
-        st->keys = nullptr;
-        return occ_nomem(count, cap * sizeof(uint64_t));
-      }
-      st->keys_cap = cap;
+      if (const int rc = occ_reserve(h, st->keys, cap * sizeof(uint64_t), count, cap * sizeof(uint64_t))) return rc;
     }
+    uint64_t *const found = h->mc_keys.as<uint64_t>(), *const sorted = st->keys.as<uint64_t>();
     size_t tmp_bytes = 0;
-    TSDF_HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, h->mc_keys, st->keys, (size_t)count, 0u, key_bits, h->stream));
-    if (tmp_bytes > h->scratch_bytes) {
-      if (h->scratch) (void)hipFree(h->scratch);
-      h->scratch = nullptr, h->scratch_bytes = 0;
-      if (hipMalloc(&h->scratch, tmp_bytes) != hipSuccess) {
-        h->scratch = nullptr;
-        return occ_nomem(count, tmp_bytes);
-      }
-      h->scratch_bytes = tmp_bytes;
-    }
-    TSDF_HIP_TRY(rocprim::radix_sort_keys(h->scratch, tmp_bytes, h->mc_keys, st->keys, (size_t)count, 0u, key_bits, h->stream));
+    TSDF_HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, found, sorted, (size_t)count, 0u, key_bits, h->stream));
+    if (const int rc = occ_reserve(h, h->scratch, tmp_bytes, count, tmp_bytes)) return rc;
+    TSDF_HIP_TRY(rocprim::radix_sort_keys(h->scratch.p, tmp_bytes, found, sorted, (size_t)count, 0u, key_bits, h->stream));
     TSDF_HIP_TRY(hipEventRecord(st->ev[2], h->stream));
     TSDF_HIP_TRY(hipStreamSynchronize(h->stream));
     (void)hipEventElapsedTime(&st->ms[1], st->ev[1], st->ev[2]);  // count read-back, buffer growth, sort
@@ -416,7 +399,7 @@ extern "C" int tsdf_hip_occupied_fetch(tsdf_handle h, int32_t *idx, float *d, fl
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
   const size_t b_idx = idx ? up(chunk * 12) : 0, b_d = d ? up(chunk * 4) : 0, b_w = w ? up(chunk * 4) : 0, b_rgb = rgb ? up(chunk * 3) : 0;
   if ((rc = tsdf_ensure_scratch(h, b_idx + b_d + b_w + b_rgb))) return rc;
-  char *sp = (char *)h->scratch;
+  char *sp = (char *)h->scratch.p;
   int32_t *s_idx = idx ? (int32_t *)sp : nullptr;
   float *s_d = d ? (float *)(sp + b_idx) : nullptr;
   float *s_w = w ? (float *)(sp + b_idx + b_d) : nullptr;
@@ -426,7 +409,7 @@ extern "C" int tsdf_hip_occupied_fetch(tsdf_handle h, int32_t *idx, float *d, fl
     const uint64_t c = std::min<uint64_t>(chunk, st->n - off);
     occ_collect_emit_time(st);
     TSDF_HIP_TRY(hipEventRecord(st->ev[3], h->stream));
-    hipLaunchKernelGGL(k_occ_emit, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, h->stream, e, st->keys + off, c, s_idx, s_d, s_w,
+    hipLaunchKernelGGL(k_occ_emit, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, h->stream, e, st->keys.as<uint64_t>() + off, c, s_idx, s_d, s_w,
                        (uint32_t *)nullptr, s_rgb);
     TSDF_HIP_TRY(hipGetLastError());
     TSDF_HIP_TRY(hipEventRecord(st->ev[4], h->stream));
@@ -457,7 +440,7 @@ extern "C" int tsdf_hip_occupied_fetch_device(tsdf_handle h, int32_t *d_idx, flo
   if (st->n > 0xffffffffull * 256ull) return TSDF_HIP_E_UNSUPPORTED;
   occ_collect_emit_time(st);
   TSDF_HIP_TRY(hipEventRecord(st->ev[3], h->stream));
-  hipLaunchKernelGGL(k_occ_emit, dim3((unsigned)((st->n + 255) / 256)), dim3(256), 0, h->stream, occ_emit_args(h), st->keys, st->n, d_idx,
+  hipLaunchKernelGGL(k_occ_emit, dim3((unsigned)((st->n + 255) / 256)), dim3(256), 0, h->stream, occ_emit_args(h), st->keys.as<uint64_t>(), st->n, d_idx,
                      d_d, d_w, d_rgb, (uint8_t *)nullptr);
   TSDF_HIP_TRY(hipGetLastError());
   TSDF_HIP_TRY(hipEventRecord(st->ev[4], h->stream));

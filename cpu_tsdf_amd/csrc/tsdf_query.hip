@@ -374,8 +374,8 @@ static int raycast_impl(tsdf_handle h, const float rot[9], const float origin[3]
   const int64_t n = (int64_t)a.nw * a.nh;
   int rc = tsdf_ensure_scratch(h, (size_t)n * 8 * sizeof(float) + 16);
   if (rc) return rc;
-  float *d_out = (float *)h->scratch;
-  unsigned *d_inc = (unsigned *)((char *)h->scratch + (size_t)n * 8 * sizeof(float));
+  float *d_out = (float *)h->scratch.p;
+  unsigned *d_inc = (unsigned *)((char *)h->scratch.p + (size_t)n * 8 * sizeof(float));
   TSDF_HIP_TRY(hipMemsetAsync(d_inc, 0, sizeof(unsigned), h->stream));
   const GridView g = make_view(h);
   hipLaunchKernelGGL(k_raycast<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, g, a, d_out, d_inc,
@@ -430,7 +430,7 @@ extern "C" int tsdf_hip_raycast_advance(tsdf_handle h, const float rot[9], const
   const int64_t n = (int64_t)a.nw * a.nh;
   int rc = tsdf_ensure_scratch(h, 16);
   if (rc) return rc;
-  unsigned *d_inc = (unsigned *)h->scratch;
+  unsigned *d_inc = (unsigned *)h->scratch.p;
   TSDF_HIP_TRY(hipMemsetAsync(d_inc, 0, sizeof(unsigned), h->stream));
   TSDF_HIP_TRY(hipMemsetAsync(d_delta, 0, (size_t)n * RAY_REC * sizeof(int32_t), h->stream));
   const GridView g = make_view(h);
@@ -464,7 +464,7 @@ extern "C" int tsdf_hip_raycast_advance_list(tsdf_handle h, const float rot[9], 
   if (make_ray_args(h, rot, origin, downsample, a)) return TSDF_HIP_E_INVALID;
   int rc = tsdf_ensure_scratch(h, 16);
   if (rc) return rc;
-  unsigned *d_inc = (unsigned *)h->scratch;
+  unsigned *d_inc = (unsigned *)h->scratch.p;
   TSDF_HIP_TRY(hipMemsetAsync(d_inc, 0, sizeof(unsigned), h->stream));
   hipLaunchKernelGGL(k_raycast<true>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, make_view(h), a,
                      (float *)nullptr, d_inc, (const int *)d_records, (int *)d_records,
@@ -722,17 +722,17 @@ extern "C" int tsdf_hip_lookup_rgb(tsdf_handle h, const float *xyz, size_t n, ui
   if (h->lab_img) {  // LABNode::getRGB: exact bytes through the host's pow
     int rc = tsdf_ensure_scratch(h, n * 12);
     if (rc) return rc;
-    float *d_xyz = (float *)h->scratch;
+    float *d_xyz = (float *)h->scratch.p;
     if ((rc = tsdf_to_device(h, d_xyz, xyz, n * 12))) return rc;
-    int64_t *d_idx = nullptr;
-    TSDF_HIP_TRY(hipMalloc(&d_idx, n * sizeof(int64_t)));
+    DevBuf idx_buf;
+    if ((rc = idx_buf.alloc(n * sizeof(int64_t)))) return rc;
+    int64_t *d_idx = idx_buf.as<int64_t>();
     hipLaunchKernelGGL(k_lookup_index, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, make_view(h), h->z_begin, h->z_end,
                        d_xyz, n, d_idx);
     std::vector<int64_t> idx(n);
     std::vector<uint32_t> words(n);
     rc = tsdf_to_host(h, idx.data(), d_idx, n * sizeof(int64_t));
     if (!rc) rc = tsdf_lab_exact_colors(h, d_idx, n, words.data(), false);
-    (void)hipFree(d_idx);
     if (rc) return rc;
     for (size_t i = 0; i < n; ++i) {
       const bool hit = idx[i] >= 0;
@@ -745,7 +745,7 @@ extern "C" int tsdf_hip_lookup_rgb(tsdf_handle h, const float *xyz, size_t n, ui
   }
   int rc = tsdf_ensure_scratch(h, n * 16);
   if (rc) return rc;
-  float *d_xyz = (float *)h->scratch;
+  float *d_xyz = (float *)h->scratch.p;
   unsigned char *d_rgb = (unsigned char *)(d_xyz + 3 * n), *d_found = d_rgb + 3 * n;
   if ((rc = tsdf_to_device(h, d_xyz, xyz, n * 12))) return rc;
   hipLaunchKernelGGL(k_lookup_rgb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, make_view(h), h->z_begin, h->z_end,
@@ -783,7 +783,7 @@ extern "C" int tsdf_hip_selftest_containing(tsdf_handle h, const float *xyz, siz
   TSDF_ENTER(h);
   int rc = tsdf_ensure_scratch(h, n * 24);
   if (rc) return rc;
-  float *d_xyz = (float *)h->scratch;
+  float *d_xyz = (float *)h->scratch.p;
   int *d_idx = (int *)(d_xyz + 3 * n);
   if ((rc = tsdf_to_device(h, d_xyz, xyz, n * 12))) return rc;
   hipLaunchKernelGGL(k_selftest_containing, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, make_view(h), d_xyz,
@@ -829,7 +829,7 @@ extern "C" int tsdf_hip_sample(tsdf_handle h, const float *xyz, size_t n, float 
   const size_t fl = 16 * n;
   int rc = tsdf_ensure_scratch(h, fl * sizeof(float) + n + 16);
   if (rc) return rc;
-  float *d_xyz = (float *)h->scratch, *d_val = d_xyz + 3 * n, *d_grad = d_val + n, *d_hess = d_grad + 3 * n;
+  float *d_xyz = (float *)h->scratch.p, *d_val = d_xyz + 3 * n, *d_grad = d_val + n, *d_hess = d_grad + 3 * n;
   unsigned char *d_ok = (unsigned char *)(d_hess + 9 * n);
   if ((rc = tsdf_to_device(h, d_xyz, xyz, 3 * n * sizeof(float)))) return rc;
   const GridView g = make_view(h);

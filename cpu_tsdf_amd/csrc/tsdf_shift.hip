@@ -186,17 +186,16 @@ int tsdf_shift_band(tsdf_hip_volume *v, int sx, int sy, int sz) {
   if (!v->band_exact || !v->band) return TSDF_HIP_OK;
   const size_t n = (size_t)v->band_fx * v->band_fy * v->nz_alloc;
   if (const int rc = tsdf_ensure_scratch(v, n)) return rc;
-  TSDF_HIP_TRY(hipMemcpyAsync(v->scratch, v->band, n, hipMemcpyDeviceToDevice, v->stream));
+  TSDF_HIP_TRY(hipMemcpyAsync(v->scratch.p, v->band, n, hipMemcpyDeviceToDevice, v->stream));
   const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 256 * 8));
-  hipLaunchKernelGGL(k_shift_band, dim3(grid), dim3(256), 0, v->stream, (const uint8_t *)v->scratch, v->band, v->band_fx, v->band_fy,
+  hipLaunchKernelGGL(k_shift_band, dim3(grid), dim3(256), 0, v->stream, (const uint8_t *)v->scratch.p, v->band, v->band_fx, v->band_fy,
                      v->nz_alloc, v->nx, v->ny, sx, sy, sz);
   TSDF_HIP_TRY(hipGetLastError());
   return TSDF_HIP_OK;
 }
 
 int tsdf_shift_mark(tsdf_hip_volume *v, int which) {
-  for (hipEvent_t &e : v->shift_ev)
-    if (!e) TSDF_HIP_TRY(hipEventCreate(&e));
+  if (const int rc = v->shift_ev.ensure(2)) return rc;
   TSDF_HIP_TRY(hipEventRecord(v->shift_ev[which], v->stream));
   v->shift_timed = true;
   return TSDF_HIP_OK;

@@ -183,8 +183,8 @@ static int sm_core(MpWork &w, hipStream_t s, const float *d_in, uint64_t n_verts
                    int iterations, int keep_boundary, float *d_out, SmLayout &L, uint64_t *n_fixed, const char *who) {
   const uint32_t n = (uint32_t)n_verts, nf = (uint32_t)n_faces, e = 6u * nf;
   int rc = sm_layout(n, e, s, L);
-  if (rc || (rc = mp_reserve(&w.buf, &w.cap, L.total, s, "mesh smooth")) || (rc = mp_work_begin(w, MP_IDX_COUNTERS, 2, s))) return rc;
-  char *b = (char *)w.buf;
+  if (rc || (rc = w.buf.reserve(L.total, s, "mesh smooth")) || (rc = mp_work_begin(w, MP_IDX_COUNTERS, 2, s))) return rc;
+  char *b = (char *)w.buf.p;
   uint4 *pos[2] = {(uint4 *)(b + L.pos_a), (uint4 *)(b + L.pos_b)};
   uint32_t *row = (uint32_t *)(b + L.row), *degree = (uint32_t *)(b + L.degree);
   uint8_t *fixed = (uint8_t *)(b + L.fixed), *boundary = (uint8_t *)(b + L.boundary), *head = (uint8_t *)(b + L.head);
@@ -195,22 +195,22 @@ static int sm_core(MpWork &w, hipStream_t s, const float *d_in, uint64_t n_verts
   TSDF_HIP_TRY(hipEventRecord(w.ev[0], s));
   TSDF_HIP_TRY(hipMemsetAsync(boundary, 0, (size_t)n, s));
   if (nf) {
-    hipLaunchKernelGGL(k_sm_edges, dim3((nf + 255u) / 256u), blk, 0, s, d_faces, nf, n_verts, key_a, w.counters);
+    hipLaunchKernelGGL(k_sm_edges, dim3((nf + 255u) / 256u), blk, 0, s, d_faces, nf, n_verts, key_a, w.count());
     TSDF_HIP_TRY(hipGetLastError());
     size_t tmp_bytes = L.tmp_bytes;
     TSDF_HIP_TRY(rocprim::radix_sort_keys(b + L.tmp, tmp_bytes, key_a, keys, (size_t)e, 0u, 64u, s));
-    hipLaunchKernelGGL(k_sm_heads, grid_e, blk, 0, s, keys, e, head, boundary, w.counters);
+    hipLaunchKernelGGL(k_sm_heads, grid_e, blk, 0, s, keys, e, head, boundary, w.count());
     TSDF_HIP_TRY(hipGetLastError());
     tmp_bytes = L.tmp_bytes;
     TSDF_HIP_TRY(rocprim::exclusive_scan(b + L.tmp, tmp_bytes, MpKeepIt(head, MpKeepCount()), offset, 0u, (size_t)e, rocprim::plus<uint32_t>(), s));
     hipLaunchKernelGGL(k_sm_cols, grid_e, blk, 0, s, keys, head, offset, e, cols);
     TSDF_HIP_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_sm_rows, dim3(n / 256u + 1u), blk, 0, s, keys, offset, e, n, w.counters, row);
+  hipLaunchKernelGGL(k_sm_rows, dim3(n / 256u + 1u), blk, 0, s, keys, offset, e, n, w.count(), row);
   TSDF_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_sm_pack, grid_n, blk, 0, s, (const uint32_t *)d_in, n, pos[0]);
   TSDF_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_sm_fixed, grid_n, blk, 0, s, pos[0], row, cols, boundary, n, keep_boundary, fixed, degree, w.counters);
+  hipLaunchKernelGGL(k_sm_fixed, grid_n, blk, 0, s, pos[0], row, cols, boundary, n, keep_boundary, fixed, degree, w.count());
   TSDF_HIP_TRY(hipGetLastError());
   int at = 0;  // the buffer that holds the last step's result
   for (int it = 0; it < iterations; ++it)
@@ -219,11 +219,11 @@ static int sm_core(MpWork &w, hipStream_t s, const float *d_in, uint64_t n_verts
       TSDF_HIP_TRY(hipGetLastError());
       at ^= 1;
     }
-  hipLaunchKernelGGL(k_sm_unpack, grid_n, blk, 0, s, pos[at], n, w.counters, (uint32_t *)d_out);
+  hipLaunchKernelGGL(k_sm_unpack, grid_n, blk, 0, s, pos[at], n, w.count(), (uint32_t *)d_out);
   TSDF_HIP_TRY(hipGetLastError());
   TSDF_HIP_TRY(hipEventRecord(w.ev[1], s));
   unsigned long long counts[MP_IDX_COUNTERS] = {0};
-  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.counters, sizeof counts, hipMemcpyDeviceToHost, s));
+  TSDF_HIP_TRY(hipMemcpyAsync(counts, w.count(), sizeof counts, hipMemcpyDeviceToHost, s));
   TSDF_HIP_TRY(hipStreamSynchronize(s));
   if (counts[SM_C_BAD]) {
     tsdf_set_error(std::string(who) + ": a face names a vertex index >= n_verts");
@@ -266,13 +266,13 @@ extern "C" int tsdf_hip_mesh_smooth(int device, const float *verts, uint64_t n_v
   const size_t b_verts = mp_up((size_t)n_verts * 12), b_faces = (size_t)n_faces * 12;
   int rc = c.open(device, b_verts + b_faces, who);
   if (rc) return rc;
-  float *d_verts = (float *)c.in;
-  uint32_t *d_faces = n_faces ? (uint32_t *)((char *)c.in + b_verts) : nullptr;
+  float *d_verts = (float *)c.in.p;
+  uint32_t *d_faces = n_faces ? (uint32_t *)((char *)c.in.p + b_verts) : nullptr;
   if ((rc = c.upload(d_verts, verts, (size_t)n_verts * 12)) || (d_faces && (rc = c.upload(d_faces, faces, b_faces)))) return rc;
   SmLayout L;
   uint64_t n_fixed = 0;
   if ((rc = sm_core(c.work, c.s, d_verts, n_verts, d_faces, n_faces, lambda, mu, iterations, keep_boundary, d_verts, L, &n_fixed, who))) return rc;
-  const char *b = (const char *)c.work.buf;
+  const char *b = (const char *)c.work.buf.p;
   if ((rc = c.download(out_verts, d_verts, (size_t)n_verts * 12))) return rc;
   if (fixed && (rc = c.download(fixed, b + L.fixed, (size_t)n_verts))) return rc;
   if (degree && (rc = c.download(degree, b + L.degree, (size_t)n_verts * 4))) return rc;
@@ -302,7 +302,7 @@ extern "C" int tsdf_hip_march_smooth(tsdf_handle h, float lambda, float mu, int 
   } else {
     TSDF_ENTER(h);
     SmLayout L;
-    char *o = (char *)st->out;
+    char *o = (char *)st->out.p;
     if (const int rc = sm_core(st->work, h->stream, (const float *)o, m, (const uint32_t *)(o + st->o_faces), k, lambda, mu, iterations, keep_boundary,
                                (float *)o, L, &fixed, who))
       return rc;

@@ -1,7 +1,7 @@
 """GPU tier: the host-array entry points of the three mesh passes on a mesh LARGER than their pinned staging buffer.
 
-Pageable caller memory goes through two pinned slots of 4 MiB (MP_STAGE, csrc/tsdf_meshgrid.hip: mp_to_device / mp_to_host);
-every other mesh of the suite fits one slot.  Here the vertices are 12.6 MB -- four chunks on the way in, so both slots are
+Pageable caller memory goes through two pinned slots of 4 MiB (MP_STAGE; MpCall::upload / download in csrc/tsdf_meshgrid.h,
+on the library's one PinnedStage); every other mesh of the suite fits one slot.  Here the vertices are 12.6 MB -- four chunks on the way in, so both slots are
 used twice and the wait for a slot's earlier copy runs -- and remap is 4.2 MB: two chunks on the way back.  The soup is a
 lattice on which every result is known by construction (no model runs at this size):
   vertex v = (v % 1024, (v / 1024) % 1024, v / 1048576), face f = vertices 3f, 3f+1, 3f+2
