@@ -258,6 +258,28 @@ bool TSDFVolumeOctree::integratePlanar(const float *depth, const unsigned char *
   return true;
 }
 
+// ---- deintegrateCloud (not in the reference): tsdf_hip_deintegrate ------------------------------------------------------------
+bool TSDFVolumeOctree::deintegratePlanar(const float *depth, const unsigned char *bgra, int width, int height,
+                                         const Eigen::Affine3d &trans, uint64_t *removed) {
+  if (!ready("deintegrateCloud")) return false;
+  if (width != p_.image_width || height != p_.image_height) {
+    PCL_ERROR("[cpu_tsdf::TSDFVolumeOctree::deintegrateCloud] cloud is %dx%d but setImageSize said %dx%d\n", width,
+              height, p_.image_width, p_.image_height);
+    return false;
+  }
+  if (!applyReferenceCull(trans)) return false;  // the planes integrateCloud had for this pose
+  const Eigen::Affine3f trans_inv = trans.inverse().cast<float>();  // hpp:54
+  float T[12];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 4; ++c) T[4 * r + c] = trans_inv.matrix()(r, c);
+  const int rc = tsdf_hip_deintegrate(h_, depth, p_.integrate_color ? bgra : nullptr, T, removed);
+  if (rc) {
+    report("deintegrateCloud", rc);
+    return false;
+  }
+  return true;
+}
+
 bool TSDFVolumeOctree::beginFrame(int width, int height, float **depth, unsigned char **bgra) {
   if (!ready("integrateCloud")) return false;
   if (width != p_.image_width || height != p_.image_height) {

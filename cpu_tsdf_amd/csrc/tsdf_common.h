@@ -125,6 +125,9 @@ struct tsdf_hip_volume {
                                                 // merge leaves it for tsdf_hip_merge_stats, whatever runs in between)
   uint64_t merge_stats[3] = {0, 0, 0};          // voxels in the launch box, voxels merged (once read back), 1 if live band flags were dropped
   bool merge_count_pending = false;             // merge_stats[1] is still on the device
+  EventSet<2> deint_ev;                         // tsdf_hip_deintegrate_stats: around the kernel of the last tsdf_hip_deintegrate (tsdf_deintegrate.hip)
+  bool deint_timed = false;                     // ... both have been recorded (a call with a non-finite pose launches nothing)
+  uint64_t deint_stats[3] = {0, 0, 0};          // of the last call that counted: voxels selected, weights lowered, voxels back at the reset state
   DevBuf scratch;  // grown by tsdf_ensure_scratch
   tsdf_occ_state *occ = nullptr;
   tsdf_meshpost_state *mp = nullptr;

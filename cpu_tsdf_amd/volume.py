@@ -642,6 +642,54 @@ class TSDFVolumeOctree:
         capi.check(capi.load().tsdf_hip_merge_stats(self._need(), out), "merge_stats")
         return tuple(int(v) for v in out)
 
+    def deintegrateCloud(self, depth, bgra=None, trans=None, count=False):
+        """Not in the reference: take a frame back out of the volume on the GPU (tsdf_hip_deintegrate; the rule and every
+        refusal are in include/tsdf_hip.h) -- ``integrateCloud``'s arguments, with the pose the frame was integrated under.
+        The frame, the pose and the reference cull select exactly the voxels integrateCloud observed, with the same
+        distance and colour; each loses one count and that observation from its running means, and a voxel whose weight
+        reaches 0 returns to the reset state.  A voxel at the weight limit has forgotten how many frames it saw and loses
+        one count like any other.  The band flags survive: reconstruct / getOccupiedVoxelIndices / integrateCloud keep
+        their skips.  Returns True, or the number of voxels whose weight went down when ``count`` is set.  "RGB" colour,
+        no depth / variance weighting, not on setDevices volumes."""
+        h = self._need()
+        trans = np.eye(4) if trans is None else np.asarray(trans, dtype=np.float64)
+        depth = capi.f32c(depth)
+        if depth.shape != (self._p.image_height, self._p.image_width):
+            raise ValueError("depth image must be (image_height, image_width)")
+        col = None
+        if self._p.integrate_color:
+            if bgra is None:
+                raise ValueError("integrate_color is set: a (H, W, 4) uint8 bgra image is required")
+            col = np.ascontiguousarray(bgra, dtype=np.uint8)
+            if col.shape != (self._p.image_height, self._p.image_width, 4):
+                raise ValueError("bgra image must be (image_height, image_width, 4)")
+        self._apply_reference_cull(trans)
+        T = cam_from_vol_f32(trans)
+        n = C.c_uint64(0)
+        capi.check(
+            capi.load().tsdf_hip_deintegrate(h, capi.as_f32p(depth), capi.as_u8p(col) if col is not None else None,
+                                             capi.as_f32p(T), C.byref(n) if count else None), "deintegrate")
+        return int(n.value) if count else True
+
+    def deintegrateCloudDevice(self, depth_ptr, bgra_ptr, trans, count=False):
+        """Same, with device pointers (the frame already resident in HBM); asynchronous unless count."""
+        h = self._need()
+        self._apply_reference_cull(np.asarray(trans, dtype=np.float64))
+        T = cam_from_vol_f32(np.asarray(trans, dtype=np.float64))
+        n = C.c_uint64(0)
+        capi.check(
+            capi.load().tsdf_hip_deintegrate_device(h, C.c_void_p(depth_ptr), C.c_void_p(bgra_ptr) if bgra_ptr else None,
+                                                    capi.as_f32p(T), C.byref(n) if count else None), "deintegrate_device")
+        return int(n.value) if count else True
+
+    def deintegrateStats(self):
+        """Report-only: (voxels the frame selected, voxels whose weight went down, of those the voxels that returned to
+        unobserved -- all three of the last deintegrateCloud with ``count`` --, device microseconds of the last one's
+        kernel).  Waits for it to finish."""
+        out = (C.c_uint64 * 4)()
+        capi.check(capi.load().tsdf_hip_deintegrate_stats(self._need(), out), "deintegrate_stats")
+        return tuple(int(v) for v in out)
+
     def computeDistanceField(self, r_max=0, min_weight=0.0, box=None):
         """Not in the reference: the exact Euclidean distance transform of the volume's zero crossing, on the GPU
         (tsdf_hip_esdf; the rule and every refusal are in include/tsdf_hip.h).  A voxel of ``box`` = (x0, y0, z0, nx, ny, nz)

@@ -178,6 +178,20 @@ class TSDFVolumeOctree : public TSDFInterface {
   // weight limit.  false (and a PCL_ERROR) before reset() of either volume and on any refusal, which changes nothing.
   bool mergeVolume(const TSDFVolumeOctree &src, const Eigen::Affine3d *dst_from_src = nullptr, float min_weight = 0.f,
                    uint64_t *merged = nullptr);
+  // Not in the reference: take a cloud back out of the volume on the GPU (tsdf_hip_deintegrate: the rule and every refusal
+  // are in include/tsdf_hip.h) -- integrateCloud's signature, with the pose the cloud was integrated under; followed by
+  // integrateCloud under a corrected pose this is what a loop closure asks of the map.  The cloud, the pose and the
+  // reference cull select exactly the voxels integrateCloud observed, with the same distance and colour; each loses one
+  // count and that observation from its running means, and a voxel whose weight reaches 0 returns to the reset state.  A
+  // voxel at the weight limit has forgotten how many clouds it saw and loses one count like any other.  *removed
+  // (optional) receives the number of voxels whose weight went down.  The call waits for the kernel.  "RGB" colour, no
+  // depth / variance weighting, not on a setDevices set.  false (and a PCL_ERROR) before reset() and on any refusal, which
+  // changes nothing.  deintegratePlanar: the same on planar images, as integratePlanar.
+  template <typename PointT, typename NormalT>
+  bool deintegrateCloud(const pcl::PointCloud<PointT> &cloud, const pcl::PointCloud<NormalT> &normals,
+                        const Eigen::Affine3d &trans = Eigen::Affine3d::Identity(), uint64_t *removed = nullptr);
+  bool deintegratePlanar(const float *depth, const unsigned char *bgra, int width, int height, const Eigen::Affine3d &trans,
+                         uint64_t *removed = nullptr);
   // Not in the reference: the exact Euclidean distance transform of the volume's zero crossing, on the GPU (tsdf_hip_esdf:
   // the rule and every refusal are in include/tsdf_hip.h) -- what a planner or a collision checker asks of the map.  A voxel
   // is a site iff it is observed (weight > min_weight, d not NaN) and a 6-neighbour is observed with the other sign of d;

@@ -857,6 +857,52 @@ int tsdf_hip_esdf_fetch_device(tsdf_handle h, uint32_t *d_d2, float *d_dist);
 int tsdf_hip_esdf_sample(tsdf_handle h, const float *xyz, size_t n, float *dist, uint8_t *found);
 int tsdf_hip_esdf_stats(tsdf_handle h, uint64_t out[4]);
 
+/* deintegrateCloud -- NOT IN THE REFERENCE (its running averages only grow).  Takes a frame back out of the volume: the
+ * first half of correcting a frame's pose after a loop closure (remove it under the old pose, integrate it under the new
+ * one; BundleFusion, Dai et al. 2017, section 6) without a reset and a second pass over the whole sequence.
+ *   depth, bgra, cam_from_vol   as for tsdf_hip_integrate (host frame, through the handle's staging; the call waits) and
+ *                               tsdf_hip_integrate_device (device frame); bgra is needed iff integrate_color.
+ *   n_removed                   nullable; the number of voxels whose weight went down (out[1] below).  Without it the
+ *                               device call is asynchronous on the handle's stream and nothing is counted.
+ * RULE.  The frame, the pose and the reference-cull planes in force on the handle (tsdf_hip_set_reference_cull) SELECT
+ * exactly the voxels tsdf_hip_integrate would bring to addObservation, with the same d_new -- the same transform order,
+ * fp64 projection, sensor range, image bounds, NaN test, d_new < -max_dist_neg rejection, max_dist_pos clamp and division
+ * by max_dist_neg: one copy of the device code serves both -- and, with colour, the same pixel colour c_obs.
+ * Per selected voxel with stored d, w (PACKED: w = min(k, max_weight)) and colour bytes c, every operation in fp32 and
+ * rounded on its own (no contraction), IEEE division:
+ *   w == 0            nothing is written.
+ *   W = ceilf(w), w' = W - 1.  Weights below saturation are integers (W == w); at saturation W = ceil(max_weight) = kmax,
+ *                     so the PACKED count (k' = k - 1) and the F32W weight (w' = W - 1) agree for every max_weight.
+ *   w' <= 0           the voxel returns to the state tsdf_hip_reset leaves: d = -1, w = 0 / k = 0, colour bytes 0.
+ *   otherwise         d' = d where d and d_new have the same bits (a mean of equal values does not move: free space stays
+ *                     exactly at the hinge value), else d' = (d * W - d_new) / w';
+ *                     per colour channel x = (W * c - c_obs) / w', c' = (uint8)(min(max(x, 0), 255) + 0.5f) -- nearest,
+ *                     because the forward update truncated and a second truncation would bias dark;
+ *                     w / k <- w'.
+ * Below saturation the weights are exactly those of the other frames alone, and d and the colour are their mean up to
+ * rounding (DESIGN.md 3.21 has the figures of the host model).  SATURATION: a voxel at max_weight has forgotten how many frames it saw; it loses one count like any
+ * other, which weights the removed frame at 1 / kmax of the stored mean.  That is an approximation, and the only one.
+ * Nothing checks that the frame was ever integrated: removing a stranger subtracts it all the same.
+ * The "band seen" flags and the implied-distance record SURVIVE (unlike tsdf_hip_merge): the kernel sets a cell's flag where
+ * it lowers a weight with an observation inside the band (d_new off the hinge value), the rule the integrate kernels set it
+ * by, so tsdf_hip_march, tsdf_hip_occupied and the PACKED integrate launches go on skipping what they skipped.  Where the
+ * handle's record does not cover this call's hinge value (F32W layout, non-integer max_weight, truncation limits changed
+ * since the reset) every lowered weight sets its cell's flag; where the flags are already inexact none are kept.
+ * Like every writer of the planes the call first launches a frame held back by frame pairing and invalidates the distance
+ * field of tsdf_hip_esdf; it covers exactly the planes the handle's integrate launches write (Z-slab handles work; their
+ * halo planes are the caller's to refresh, as after an integrate).  A pose with a non-finite entry selects nothing: OK, 0.
+ * TSDF_HIP_E_INVALID: a NULL handle, frame or pose; integrate_color without bgra.
+ * TSDF_HIP_E_UNSUPPORTED, with the reason in tsdf_hip_last_error and the planes untouched: weight_by_depth or
+ * weight_by_variance on, or the variance state allocated; TSDF_COLOR_RGB_NORMALIZED / TSDF_COLOR_LAB; a multi-GPU set
+ * (tsdf_hip_create_multi: a follow-up).
+ * tsdf_hip_deintegrate_stats: report-only.  out[0] = voxels the frame selected, out[1] = voxels whose weight went down,
+ * out[2] = of those, voxels that returned to unobserved -- all three of the last call that passed n_removed; out[3] =
+ * device microseconds of the last call's kernel (HIP events on the stream; waits for the second one; 0 if none ran). */
+int tsdf_hip_deintegrate(tsdf_handle h, const float *depth, const uint8_t *bgra, const float cam_from_vol[12], uint64_t *n_removed);
+int tsdf_hip_deintegrate_device(tsdf_handle h, const float *d_depth, const uint32_t *d_bgra, const float cam_from_vol[12],
+                                uint64_t *n_removed);
+int tsdf_hip_deintegrate_stats(tsdf_handle h, uint64_t out[4]);
+
 /* Block transfer of raw voxels (parity tests, save/load, halo exchange).  Coordinates are global
  * grid indices; the block must lie inside the handle's slab + halo.  Any pointer may be NULL.
  * rgb is 3 bytes per voxel (r,g,b).  *_device variants take device pointers (rgb then 4 bytes). */
