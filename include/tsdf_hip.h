@@ -111,7 +111,12 @@ typedef struct tsdf_params {
 /* Fill *p with the reference constructor defaults (tsdf_volume_octree.cpp:54-85). */
 void tsdf_hip_default_params(tsdf_params *p);
 
-/* reset() -- tsdf_volume_octree.cpp:201-219: allocate the grid, every voxel (d=-1, w=0). */
+/* reset() -- tsdf_volume_octree.cpp:201-219: allocate the grid, every voxel (d=-1, w=0).
+ * tsdf_hip_reset on a handle in use erases the voxels, the "band seen" flags and the implied-distance record, and drops the
+ * distance field of tsdf_hip_esdf and the normals of tsdf_hip_march_normals.  The soup of the last tsdf_hip_march, the
+ * indexed mesh made from it and the list of tsdf_hip_occupied are plain data and STAY on the handle: the fetches keep
+ * returning the meshes of the volume as it was, and tsdf_hip_occupied_fetch names the same voxels and gathers the reset
+ * values (d = -1, w = 0).  tsdf_hip_destroy ends everything. */
 int tsdf_hip_create(const tsdf_params *p, tsdf_handle *out);
 int tsdf_hip_reset(tsdf_handle h);
 int tsdf_hip_destroy(tsdf_handle h);
@@ -830,12 +835,14 @@ int tsdf_hip_merge_stats(tsdf_handle dst, uint64_t out[4]);
  *   rounded one and the product one fp32 multiplication, so the field is bit for bit
  *   np.sqrt(d2.astype(np.float32)) * np.float32(voxel), negated where neg(v).
  * LIFETIME, as tsdf_hip_occupied's list: the field describes the volume AT THE TIME OF THE CALL -- the sign as well, which
- * is recorded then -- and stays valid, and STALE BY DESIGN, across later integrates, marches, uploads and downloads.  It is
- * dropped by tsdf_hip_reset, tsdf_hip_destroy and the next tsdf_hip_esdf on the handle that is not refused.
- * After tsdf_hip_shift the fetches and the sample return E_INVALID until the field has been computed again: the indices
- * moved.  The same before the first tsdf_hip_esdf.  Like every entry point that reads the planes, the call first launches
- * a frame held back by frame pairing.  The volume's planes and "band seen" flags are neither written nor invalidated, and
- * the results tsdf_hip_march and tsdf_hip_occupied keep on the handle survive the call.  The call waits for its kernels.
+ * is recorded then -- and stays valid, and STALE BY DESIGN, across later integrates, marches, uploads and downloads, and
+ * across a tsdf_hip_merge with the handle as dst or as src.  It is dropped by tsdf_hip_reset, tsdf_hip_destroy and the next
+ * tsdf_hip_esdf on the handle that is not refused.  After tsdf_hip_shift the fetches and the sample return E_INVALID until
+ * the field has been computed again: the indices moved.  The same after tsdf_hip_deintegrate / _deintegrate_device (a frame
+ * is taken back to correct it: a field that still shows it is ended, not left stale), and before the first tsdf_hip_esdf.
+ * Like every entry point that reads the planes, the call first launches a frame held back by frame pairing.  The volume's
+ * planes and "band seen" flags are neither written nor invalidated, and the results tsdf_hip_march and tsdf_hip_occupied
+ * keep on the handle survive the call.  The call waits for its kernels.
  *   tsdf_hip_esdf_fetch         d2 and dist of the box to the host, [z][y][x] of the box; either may be NULL.
  *   tsdf_hip_esdf_fetch_device  the same into DEVICE buffers of the caller, asynchronous on the handle's stream.
  *   tsdf_hip_esdf_sample        per point (n x 3 floats, volume coordinates) the value of the voxel that CONTAINS it -- the
@@ -888,9 +895,12 @@ int tsdf_hip_esdf_stats(tsdf_handle h, uint64_t out[4]);
  * by, so tsdf_hip_march, tsdf_hip_occupied and the PACKED integrate launches go on skipping what they skipped.  Where the
  * handle's record does not cover this call's hinge value (F32W layout, non-integer max_weight, truncation limits changed
  * since the reset) every lowered weight sets its cell's flag; where the flags are already inexact none are kept.
- * Like every writer of the planes the call first launches a frame held back by frame pairing and invalidates the distance
- * field of tsdf_hip_esdf; it covers exactly the planes the handle's integrate launches write (Z-slab handles work; their
- * halo planes are the caller's to refresh, as after an integrate).  A pose with a non-finite entry selects nothing: OK, 0.
+ * Like every writer of the planes the call first launches a frame held back by frame pairing.  Unlike the other writers
+ * (integrate, upload, merge, which leave a distance field of tsdf_hip_esdf valid and stale) it ENDS that field: the fetches
+ * and the sample return E_INVALID until the next tsdf_hip_esdf.  A list of tsdf_hip_occupied and the meshes of
+ * tsdf_hip_march stay, as after an integrate.  It covers exactly the planes the handle's integrate launches write (Z-slab
+ * handles work; their halo planes are the caller's to refresh, as after an integrate).  A pose with a non-finite entry
+ * selects nothing: OK, 0.
  * TSDF_HIP_E_INVALID: a NULL handle, frame or pose; integrate_color without bgra.
  * TSDF_HIP_E_UNSUPPORTED, with the reason in tsdf_hip_last_error and the planes untouched: weight_by_depth or
  * weight_by_variance on, or the variance state allocated; TSDF_COLOR_RGB_NORMALIZED / TSDF_COLOR_LAB; a multi-GPU set

@@ -71,9 +71,15 @@ def legal_ops(c):
         ops.append("upload_variance")
     if c.mode not in COLOUR_MODES and c.grid == "64":
         ops.append("save_load")   # (.vol needs a cubic power-of-two grid; RGB_NORMALIZED / LAB have no .vol form)
-    if c.mode in COLOUR_MODES or SHAPES[c.shape] is not None:
-        ops.append("refused")     # (a weighted single handle has no call of the list that it refuses)
+    ops.append("refused")         # (every mode refuses deintegrateCloud and mergeVolume; the colour modes and the sets refuse more)
     return ops
+
+
+def refused_is_drawn(c):
+    """The cases whose plans DRAW `refused` steps from their deck; the others (a weighted single handle, which had no call to
+    refuse before deintegrateCloud and mergeVolume came) get one refused step at a fixed place, so that their draws stay as
+    they were."""
+    return c.mode in COLOUR_MODES or SHAPES[c.shape] is not None
 
 
 class Setup:
@@ -155,7 +161,7 @@ class Setup:
         return x0, y0, z0, int(rng.randint(rx // 2, rx - x0 + 1)), int(rng.randint(ry // 2, ry - y0 + 1)), nz
 
     def _plan(self, rng):
-        legal = legal_ops(self.case)
+        legal = [o for o in legal_ops(self.case) if o != "refused" or refused_is_drawn(self.case)]
         deck = list(legal) + [o for o in ("shift", "shift", "upload", "save_load") if o in legal]
         extras = [o for o in legal if o != "reset"]
         deck += [extras[rng.randint(len(extras))] for _ in range(EXTRA_STEPS)]
@@ -182,6 +188,8 @@ class Setup:
             elif op == "upload_variance":
                 e["box"], e["which"], e["seed"] = self.seam_box(rng), ["M", "ns", "both"][rng.randint(3)], int(rng.randint(1 << 30))
             plan.append(e)
+        if not refused_is_drawn(self.case):
+            plan.insert(1, dict(op="refused"))   # right after the first frame
         return plan + [dict(op="host"), dict(op="host")]   # the ending: a damaged state plane shows in rgb or w
 
 

@@ -207,13 +207,8 @@ class Model:
         mode = 1 if self.color else 0
         verts, rgb, cells = self.ov.march(w_min, mode)
         rgb = rgb if mode else None
-        if cleanup is not None and len(cells):
-            from tests.test_meshpost_gpu import centroids, oracle_groups
-            label, sizes = oracle_groups(centroids(verts), cleanup[0])
-            keep = sizes[label] > cleanup[1]
-            k3 = np.repeat(keep, 3)
-            verts, cells = verts[k3], cells[keep]
-            rgb = rgb[k3] if rgb is not None else None
+        if cleanup is not None:
+            verts, rgb, cells = cleaned_soup(verts, rgb, cells, *cleanup)
         if flatten is None:
             n = len(cells)
             return {"vertices": self.to_world(verts), "polygons": np.arange(3 * n, dtype=np.int32).reshape(n, 3), "rgb": rgb, "cells": cells}
@@ -240,6 +235,18 @@ class Model:
         """tests/align_cases.restate on the model's voxels (vol: the product object, for its parameters and mirror only)."""
         from tests import align_cases
         return align_cases.restate(vol, self.ov, self.ov.w, pts, T, min_weight, r_max)
+
+
+def cleaned_soup(verts, rgb, cells, face_dist, min_neighbors):
+    """tsdf_hip_march_cleanup on a soup (3 vertices per cell key; rgb may be None): the cleanup oracle of
+    tests/test_meshpost_gpu.py decides which faces stay."""
+    if not len(cells):
+        return verts, rgb, cells
+    from tests.test_meshpost_gpu import centroids, oracle_groups
+    label, sizes = oracle_groups(centroids(verts), face_dist)
+    keep = sizes[label] > min_neighbors
+    k3 = np.repeat(keep, 3)
+    return verts[k3], (rgb[k3] if rgb is not None else None), cells[keep]
 
 
 def assert_same_mesh(got, want, what):

@@ -1,5 +1,6 @@
 """Test helper: write a synthetic `integrate` input directory -- PCD clouds (ascii / binary /
-binary_compressed) + pose files (.txt or .transform) -- and read back the PLY / run the programs."""
+binary_compressed) + pose files (.txt or .transform) -- and read back the PLY / run the programs.  Also the three readers
+of a volume's bookkeeping that several GPU test modules share (read_detail, march_stats, march)."""
 import os
 import struct
 import subprocess
@@ -171,6 +172,37 @@ def read_ply(path):
     vals = np.array([r.split() for r in rows[:nv]], dtype=np.float64) if nv else np.zeros((0, 3))
     faces = np.array([r.split()[1:] for r in rows[nv:nv + nf]], dtype=np.int32) if nf else np.zeros((0, 3), np.int32)
     return vals[:, :3].astype(np.float32), (vals[:, 3:6].astype(np.uint8) if has_rgb else None), faces
+
+
+def read_detail(vol):
+    """tsdf_hip_last_read_detail: (observed voxels whose distance was rebuilt from the count, 1 if implied distances were on)."""
+    import ctypes as C
+
+    from cpu_tsdf_amd import capi
+    out = (C.c_uint64 * 3)()
+    capi.check(capi.load().tsdf_hip_last_read_detail(vol._need(), out), "last_read_detail")
+    assert int(out[2]) >= 4 * (int(out[0]) > 0)  # the launch requested plane bytes
+    return int(out[0]), int(out[1])
+
+
+def march_stats(vol):
+    import ctypes as C
+
+    from cpu_tsdf_amd import capi
+    st = (C.c_uint64 * 4)()
+    capi.check(capi.load().tsdf_hip_march_stats(vol._need(), st), "march_stats")
+    return [int(v) for v in st]
+
+
+def march(vol, color=True, w_min=1.0):
+    """reconstruct(want_cells=True) and tsdf_hip_march_stats of it."""
+    from cpu_tsdf_amd.volume import MarchingCubesTSDFOctree
+    mc = MarchingCubesTSDFOctree()
+    mc.setInputTSDF(vol)
+    mc.setMinWeight(w_min)
+    mc.setColorByRGB(color)
+    mesh = mc.reconstruct(want_cells=True)
+    return mesh, march_stats(vol)
 
 
 def run(exe, args, timeout=600):

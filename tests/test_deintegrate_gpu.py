@@ -10,12 +10,12 @@ import pytest
 import torch  # at collection time, before libtsdf_hip.so brings in the system's HIP runtime (see tests/conftest.py)
 
 from cpu_tsdf_amd import capi, synth
-from cpu_tsdf_amd.volume import MarchingCubesTSDFOctree
 from oracle.oracle import OracleVolume
 from tests import deintegrate_cases as dc
 from tests import pose_cases
 from tests.common import assert_same_f32
 from tests.sequence_model import assert_same_mesh, compare
+from tests.sequence_util import march, read_detail
 from tests.test_occupied_gpu import check as check_occupied
 
 pytestmark = pytest.mark.gpu
@@ -48,23 +48,6 @@ def same_planes(got, want, what):
     assert_same_f32(got[1], want[1], what + ": w")
     if want[2] is not None:
         assert np.array_equal(got[2], want[2]), what + ": rgb"
-
-
-def read_detail(vol):
-    out = (C.c_uint64 * 3)()
-    capi.check(capi.load().tsdf_hip_last_read_detail(vol._need(), out), "last_read_detail")
-    return int(out[0]), int(out[1])
-
-
-def march(vol, color, w_min=1.0):
-    mc = MarchingCubesTSDFOctree()
-    mc.setInputTSDF(vol)
-    mc.setMinWeight(w_min)
-    mc.setColorByRGB(color)
-    mesh = mc.reconstruct(want_cells=True)
-    st = (C.c_uint64 * 4)()
-    capi.check(capi.load().tsdf_hip_march_stats(vol._need(), st), "march_stats")
-    return mesh, [int(v) for v in st]
 
 
 def raw_call(vol, dep, col, T, n=None, device=False):

@@ -15,16 +15,10 @@ import pytest
 from cpu_tsdf_amd import capi, synth
 from oracle.oracle import OracleVolume
 from tests.common import assert_same_f32, frames, make_volume
+from tests.sequence_util import read_detail  # noqa: F401  (tests/test_api_sequences_gpu.py takes it from here)
 from tests.test_fused2_gpu import device_frame
 
 pytestmark = pytest.mark.gpu
-
-
-def read_detail(vol):
-    out = (C.c_uint64 * 3)()
-    capi.check(capi.load().tsdf_hip_last_read_detail(vol._need(), out), "last_read_detail")
-    assert int(out[2]) >= 4 * (int(out[0]) > 0)  # the launch requested plane bytes
-    return int(out[0]), int(out[1])
 
 
 def launch_info(vol):

@@ -10,9 +10,9 @@ import pytest
 import torch  # at collection time, before libtsdf_hip.so brings in the system's HIP runtime (see tests/conftest.py)
 
 from cpu_tsdf_amd import capi, synth
-from cpu_tsdf_amd.volume import MarchingCubesTSDFOctree
 from tests import merge_cases as mc
 from tests.common import assert_same_f32, frames, make_volume
+from tests.sequence_util import march, read_detail
 
 pytestmark = pytest.mark.gpu
 PACKED, F32W = capi.LAYOUT_PACKED, capi.LAYOUT_F32W
@@ -223,23 +223,6 @@ def test_merging_two_fused_halves_against_fusing_all_frames(fused_scene, which):
 
 
 # ---- 4. the readers after a merge ---------------------------------------------------------------------------------------------
-def march(vol):
-    mcu = MarchingCubesTSDFOctree()
-    mcu.setInputTSDF(vol)
-    mcu.setMinWeight(1.0)
-    mcu.setColorByRGB(True)
-    mesh = mcu.reconstruct(want_cells=True)
-    st = (C.c_uint64 * 4)()
-    capi.check(capi.load().tsdf_hip_march_stats(vol._need(), st), "march_stats")
-    return mesh, [int(v) for v in st]
-
-
-def read_detail(vol):
-    out = (C.c_uint64 * 3)()
-    capi.check(capi.load().tsdf_hip_last_read_detail(vol._need(), out), "last_read_detail")
-    return [int(v) for v in out]
-
-
 def test_readers_after_a_merge_equal_a_twin_that_was_uploaded(gpu):
     """dst holds two frames from one side and nothing but integrateCloud has written it: its band flags are live and say
     where NOT to look.  src holds two frames from the other side, so the merged surface lies where dst never observed

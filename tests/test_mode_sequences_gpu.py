@@ -98,6 +98,20 @@ class ModeDriver(Driver):
     def compare(self, what):
         compare_all(self.vol, self.model, what, self.single)
 
+    def plain_volume(self):
+        """An empty 32^3 volume of the first family (TSDF_COLOR_RGB, no weighting), F32W with the case's truncation limits and
+        max_weight: only the mode stands between it and a merge with the case's volume."""
+        if getattr(self, "other", None) is None:
+            self.other, _ = make_volume(32, mode_cases.W, mode_cases.H, color=self.color, trunc=self.setup.trunc, max_weight=self.setup.wmax)
+            self.other.setLayout(capi.LAYOUT_F32W)
+            self.other.reset()
+        return self.other
+
+    def close(self):
+        super().close()
+        if getattr(self, "other", None) is not None:
+            self.other.close()
+
     def next_frame(self):
         tr, dep, col = self.setup.frame(self.frame_no)
         self.frame_no += 1
@@ -154,8 +168,20 @@ class ModeDriver(Driver):
         self.flags_gone = False
 
     def op_refused(self, what):
-        """Calls the mode refuses, with the documented code; step() then finds nothing changed."""
+        """Calls the mode refuses, with the documented code; step() then finds nothing changed (compare: d, w, rgb and the
+        state planes)."""
         lib, h, UNSUPPORTED = self.lib, self.vol._need(), capi.E_UNSUPPORTED
+        # every mode, weighted or RGB_NORMALIZED / LAB, on either shape: no frame is taken back out, nothing is merged in or out
+        tr, dep, col = self.setup.frame(self.frame_no)   # (looked at, not consumed: the plan's frames stay the replay's)
+        T, col = self.model.pose(tr), (col if self.color else None)
+        other = self.plain_volume()
+        for name, call in (("deintegrateCloud", lambda: self.vol.deintegrateCloud(dep, col, T, count=True)),
+                           ("mergeVolume as dst", lambda: self.vol.mergeVolume(other, np.eye(4), 0.0, count=True)),
+                           ("mergeVolume as src", lambda: other.mergeVolume(self.vol, np.eye(4), 0.0, count=True))):
+            with pytest.raises(capi.TsdfHipError) as err:
+                call()
+            assert err.value.code == UNSUPPORTED, (what, name, err.value.code)
+        assert not any(a.any() for a in other.download()[1:] if a is not None), f"{what}: the other volume of the refused merges"
         if self.case.mode in COLOUR_MODES:
             rgb = np.full((2, 3, 4, 3), 200, np.uint8)
             assert lib.tsdf_hip_upload(h, 1, 1, self.starts[1] - 1, 4, 3, 2, None, None, capi.as_u8p(rgb)) == UNSUPPORTED, what
@@ -224,6 +250,8 @@ def test_mode_sequences_equal_the_model_after_every_step(gpu, tmp_path, case):
             warnings.simplefilter("ignore", NonCubicQueryWarning)   # (the flat grid: the queries answer for its own geometry)
             dr.run_plan(tag)
         assert not dr.held
+        planned = sum(mode_cases.FRAME_OPS.get(e["op"], e.get("n", 0)) for e in dr.setup.plan)
+        assert dr.frame_no == planned, (dr.frame_no, planned)   # the frames mode_cases.replay integrates, no more and no fewer
         COUNTS[tag] = dr.model.assert_conditions(tag)   # tests/mode_cases.CONDITIONS, from the model the product just equalled
     finally:
         dr.close()

@@ -2,7 +2,8 @@
 OracleVolume that integrates the same frame on arrays rolled beforehand by other means (np.roll and index masks, not
 tests/shift_cases) -- also per colour mode and weighting, state planes included --, the pose rule against the geometry it
 stands for, the in-place uploads, the record's shift rule, and a replay of every case of tests/test_mode_sequences_gpu.py
-through the model alone: the conditions its inputs must meet (tests/mode_cases.CONDITIONS) and its tally of operations."""
+through the model alone: the conditions its inputs must meet (tests/mode_cases.CONDITIONS) and its tally of operations.  Last,
+every case of tests/test_feature_sequences_gpu.py through its driver without a product, and the floors on its inputs."""
 import collections
 
 import numpy as np
@@ -233,3 +234,41 @@ def test_the_plans_run_every_legal_operation_three_times_per_mode_and_shape():
         x = {e["s"][0] for c in mode_cases.CASES if c.grid == grid for e in mode_cases.Setup(c).plan
              if e["op"] == "shift" and not (e["s"][1] or e["s"][2])}
         assert x >= set(mode_cases.PURE_X), (grid, x)
+
+
+# ---- the feature sequences (tests/test_feature_sequences_gpu.py) through the models alone --------------------------------------
+FEATURE_STATS = {}
+
+
+def feature_sequences():
+    from tests import test_feature_sequences_gpu as fs
+    return fs
+
+
+def _feature_ids():
+    fs = feature_sequences()
+    return fs.CASES, fs.IDS
+
+
+@pytest.mark.parametrize("case", _feature_ids()[0], ids=_feature_ids()[1])
+def test_the_replay_of_every_feature_case_runs_through_the_models(case, tmp_path):
+    """Every case of tests/test_feature_sequences_gpu.py with the same seeds and draws and no product: the prelude's own
+    conditions hold of the models, and the figures the floors are asserted on are collected."""
+    fs = feature_sequences()
+    FEATURE_STATS[case] = stats = fs.run_case(*case, tmp_path, live=False)
+    print(fs.IDS[fs.CASES.index(case)], stats.summary())
+
+
+def test_the_feature_sequences_meet_their_floors():
+    """tests/feature_cases.assert_floors over all seeds of a shape (this test needs the replays above to have run in this
+    process): every operation and every chain call at least 5 times, removals that found no frame at most a quarter, merges,
+    removals, fields and fetches that are not empty, at least 5 E_INVALID states."""
+    fs = feature_sequences()
+    from tests.feature_cases import Stats
+    assert set(FEATURE_STATS) == set(fs.CASES), f"{len(set(fs.CASES) - set(FEATURE_STATS))} replays did not finish in this run"
+    total = {shape: Stats() for shape in fs.SHAPES}
+    for case, stats in FEATURE_STATS.items():
+        total[case[0]].add(stats)
+    for shape in fs.SHAPES:
+        print(shape, total[shape].summary())
+    fs.assert_all_floors(total)
