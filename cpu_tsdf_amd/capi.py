@@ -161,6 +161,9 @@ SIGNATURES = {
     "tsdf_hip_deintegrate": (C.c_int, [C.c_void_p, _f32p, _u8p, _f32p, _u64p]),
     "tsdf_hip_deintegrate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _f32p, _u64p]),
     "tsdf_hip_deintegrate_stats": (C.c_int, [C.c_void_p, _u64p]),
+    "tsdf_hip_reintegrate": (C.c_int, [C.c_void_p, _f32p, _u8p, _f32p, _f32p, _f32p, _f32p, _u64p]),
+    "tsdf_hip_reintegrate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _f32p, _f32p, _f32p, _f32p, _u64p]),
+    "tsdf_hip_reintegrate_stats": (C.c_int, [C.c_void_p, _u64p]),
     "tsdf_hip_esdf": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_float, _u64p]),
     "tsdf_hip_esdf_fetch": (C.c_int, [C.c_void_p, _u32p, _f32p]),
     "tsdf_hip_esdf_fetch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -195,6 +195,16 @@ bool TSDFVolumeOctree::applyReferenceCull(const Eigen::Affine3d &trans) const {
     }
     return true;
   }
+  float planes[24];
+  referenceCullPlanes(trans, planes);
+  cull_planes_set_ = true;
+  const int rc = tsdf_hip_set_reference_cull(h_, planes);
+  if (rc) report("integrateCloud (reference cull)", rc);
+  return rc == 0;
+}
+
+// The six planes pcl::FrustumCulling::applyFilter builds for the pose `trans` (tsdf_volume_octree.cpp:633-646)
+void TSDFVolumeOctree::referenceCullPlanes(const Eigen::Affine3d &trans, float planes[24]) const {
   using Eigen::Vector3f;
   using Eigen::Vector4f;
   Eigen::Matrix4f cam2robot;
@@ -226,13 +236,8 @@ bool TSDFVolumeOctree::applyReferenceCull(const Eigen::Affine3d &trans) const {
   const Vector3f a(fp_bl - T), b(fp_br - T), c(fp_tr - T), d(fp_tl - T);
   const Vector4f pl[6] = {plane(d.cross(a), T), plane(b.cross(c), T), plane(c.cross(d), T), plane(a.cross(b), T),
                           plane((fp_bl - fp_br).cross(fp_tr - fp_br), fp_c), plane((np_tr - np_br).cross(np_bl - np_br), np_c)};
-  float planes[24];
   for (int k = 0; k < 6; ++k)
     for (int i = 0; i < 4; ++i) planes[4 * k + i] = pl[k][i];
-  cull_planes_set_ = true;
-  const int rc = tsdf_hip_set_reference_cull(h_, planes);
-  if (rc) report("integrateCloud (reference cull)", rc);
-  return rc == 0;
 }
 
 // reference: include/cpu_tsdf/impl/tsdf_volume_octree.hpp:48-103
@@ -277,6 +282,39 @@ bool TSDFVolumeOctree::deintegratePlanar(const float *depth, const unsigned char
     report("deintegrateCloud", rc);
     return false;
   }
+  return true;
+}
+
+// ---- reintegrateCloud (not in the reference): tsdf_hip_reintegrate ------------------------------------------------------------
+bool TSDFVolumeOctree::reintegratePlanar(const float *depth, const unsigned char *bgra, int width, int height,
+                                         const Eigen::Affine3d &old_trans, const Eigen::Affine3d &new_trans, uint64_t *lowered,
+                                         uint64_t *observed) {
+  if (!ready("reintegrateCloud")) return false;
+  if (width != p_.image_width || height != p_.image_height) {
+    PCL_ERROR("[cpu_tsdf::TSDFVolumeOctree::reintegrateCloud] cloud is %dx%d but setImageSize said %dx%d\n", width,
+              height, p_.image_width, p_.image_height);
+    return false;
+  }
+  float planes[2][24], T[2][12];
+  const Eigen::Affine3d *trans[2] = {&old_trans, &new_trans};
+  for (int k = 0; k < 2; ++k) {
+    if (reference_cull_) referenceCullPlanes(*trans[k], planes[k]);  // the planes integrateCloud has for this pose
+    const Eigen::Affine3f trans_inv = trans[k]->inverse().cast<float>();  // hpp:54
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 4; ++c) T[k][4 * r + c] = trans_inv.matrix()(r, c);
+  }
+  uint64_t n[2] = {0, 0};
+  const bool count = lowered || observed;
+  const int rc = tsdf_hip_reintegrate(h_, depth, p_.integrate_color ? bgra : nullptr, T[0], reference_cull_ ? planes[0] : nullptr, T[1],
+                                      reference_cull_ ? planes[1] : nullptr, count ? n : nullptr);
+  if (rc) {
+    report("reintegrateCloud", rc);
+    return false;
+  }
+  cull_planes_set_ = reference_cull_;  // (the new pose's planes stay in force on the handle)
+  if (lowered) *lowered = n[0];
+  if (observed) *observed = n[1];
+  is_empty_ = false;
   return true;
 }
 

@@ -87,7 +87,7 @@ struct tsdf_hip_volume {
   DevBuf live;                     // brick-cull flags, one byte per k_integrate block
   DevBuf row_iv;                   // row intervals of a LIVE launch (k_rows, tsdf_integrate.hip), one uint32_t per voxel row
   bool ctr_increasing[3] = {false, false, false};  // the axis' centre table strictly increases (checked at create)
-  unsigned long long *counter = nullptr;  // device scratch (n_observed etc.): 2048 slots
+  unsigned long long *counter = nullptr;  // device scratch (n_observed etc.): 5120 slots (tsdf_core.hip)
   unsigned long long last_observed = 0, last_changed_bytes = 0;  // tsdf_hip_last_count_detail
   bool ref_cull = false;   // tsdf_hip_set_reference_cull: replicate getFrustumCulledVoxels with these planes
   float cull_planes[24] = {0};
@@ -128,6 +128,9 @@ struct tsdf_hip_volume {
   EventSet<2> deint_ev;                         // tsdf_hip_deintegrate_stats: around the kernel of the last tsdf_hip_deintegrate (tsdf_deintegrate.hip)
   bool deint_timed = false;                     // ... both have been recorded (a call with a non-finite pose launches nothing)
   uint64_t deint_stats[3] = {0, 0, 0};          // of the last call that counted: voxels selected, weights lowered, voxels back at the reset state
+  EventSet<2> reint_ev;                         // tsdf_hip_reintegrate_stats: around the kernel of the last tsdf_hip_reintegrate (tsdf_reintegrate.hip)
+  bool reint_timed = false;                     // ... both have been recorded
+  uint64_t reint_stats[5] = {0, 0, 0, 0, 0};    // of the last call that counted: selected by old, lowered, cleared, observed by new, selected by both
   DevBuf scratch;  // grown by tsdf_ensure_scratch
   tsdf_occ_state *occ = nullptr;
   tsdf_meshpost_state *mp = nullptr;

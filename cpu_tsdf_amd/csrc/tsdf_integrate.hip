@@ -2472,6 +2472,9 @@ bool tsdf_plain_launch_args(tsdf_handle h, const float T[12], IntegrateArgs *a, 
   return pose_is_finite(T);
 }
 
+// tsdf_plain_observe.h: the record as the launches below keep it, for a plain-family launch of another translation unit
+int tsdf_plain_implied_distances(tsdf_handle h, const IntegrateArgs &a, bool flags_kept) { return implied_distances(h, a, flags_kept); }
+
 // Asynchronous half: queues the launch on the handle's stream.  `count` selects the counting instance, whose striped
 // counters stay in h->counter until tsdf_integrate_collect reads them (a multi-GPU set launches every slab first and
 // collects afterwards, so the slabs count concurrently).

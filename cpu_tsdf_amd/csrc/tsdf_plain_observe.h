@@ -1,7 +1,7 @@
 // The per-voxel half of updateVoxel that the plain kernels share (tsdf_integrate.hip: k_integrate_plain, k_integrate_rgbn,
-// k_integrate_lab; tsdf_deintegrate.hip: k_deintegrate): the kernel arguments of an integrate launch, the exact projection, the
-// reference's frustum cull, "does this thread's voxel reach addObservation, and with what" (plain_observe) and the observation
-// count (plain_count).  One copy, so that a frame taken out of the volume selects exactly the voxels it was put into.
+// k_integrate_lab; tsdf_deintegrate.hip: k_deintegrate; tsdf_reintegrate.hip: k_reintegrate): the kernel arguments of an
+// integrate launch, the exact projection, the reference's frustum cull, "does this voxel reach addObservation, and with
+// what" (plain_observe_at; plain_observe for the thread's own voxel) and the observation count (plain_count).  One copy, so that a frame taken out of the volume selects exactly the voxels it was put into.
 // Internal; translation units that include it are compiled with -ffp-contract=off like the rest.
 #pragma once
 
@@ -87,13 +87,12 @@ struct PlainObs {
   int64_t vi;  // the voxel's index in the planes
 };
 
-// Does this thread's voxel reach addObservation?  If so, *o says with what.
+// Does the voxel (x, y) of the launch's plane zl reach addObservation?  If so, *o says with what.
 template <int ORDER>
-static __device__ __forceinline__ bool plain_observe(const IntegrateArgs &a, const double *__restrict__ cam,
-                                                     const float *__restrict__ ctrx, const float *__restrict__ ctry,
-                                                     const float *__restrict__ ctrz, const float *__restrict__ depth, PlainObs *o) {
-  const int x = (int)(blockIdx.x * 256u + threadIdx.x);
-  const int y = (int)blockIdx.y, zl = (int)blockIdx.z;
+static __device__ __forceinline__ bool plain_observe_at(const IntegrateArgs &a, const double *__restrict__ cam,
+                                                        const float *__restrict__ ctrx, const float *__restrict__ ctry,
+                                                        const float *__restrict__ ctrz, const float *__restrict__ depth,
+                                                        const int x, const int y, const int zl, PlainObs *o) {
   if (!(x < (int)a.pitch)) return false;  // the x centre table is NaN beyond nx: those lanes fail the range test
   const float cx = ctrx[x], cy = ctry[y], cz = ctrz[a.z_global0 + zl];
   float g[3];
@@ -113,6 +112,16 @@ static __device__ __forceinline__ bool plain_observe(const IntegrateArgs &a, con
   return true;
 }
 
+// ... this thread's voxel, in the grid of the plain family: (x blocks of 256, rows, planes)
+template <int ORDER>
+static __device__ __forceinline__ bool plain_observe(const IntegrateArgs &a, const double *__restrict__ cam,
+                                                     const float *__restrict__ ctrx, const float *__restrict__ ctry,
+                                                     const float *__restrict__ ctrz, const float *__restrict__ depth, PlainObs *o) {
+  const int x = (int)(blockIdx.x * 256u + threadIdx.x);
+  const int y = (int)blockIdx.y, zl = (int)blockIdx.z;
+  return plain_observe_at<ORDER>(a, cam, ctrx, ctry, ctrz, depth, x, y, zl, o);
+}
+
 // n_obs (NULL: no count): 1024 striped counters of the voxels that reached addObservation, one atomic per wave
 static __device__ __forceinline__ void plain_count(bool observed, unsigned long long *__restrict__ n_obs) {
   if (!n_obs) return;
@@ -126,3 +135,6 @@ static __device__ __forceinline__ void plain_count(bool observed, unsigned long 
 // tsdf_integrate_launch hands launch_plain_family, with the reference cull switched on only where its planes can bite --
 // and the number of planes (the grid's z extent).  False: the pose is not finite, nothing is to be launched.
 bool tsdf_plain_launch_args(tsdf_handle h, const float T[12], IntegrateArgs *a, unsigned *planes);
+// Host (tsdf_integrate.hip): the implied-distance record (rest_state, rest_bits) as a flag-keeping integrate launch with
+// these arguments updates it; `flags_kept`: the launch maintains the "band seen" flags.
+int tsdf_plain_implied_distances(tsdf_handle h, const IntegrateArgs &a, bool flags_kept);

@@ -690,6 +690,68 @@ class TSDFVolumeOctree:
         capi.check(capi.load().tsdf_hip_deintegrate_stats(self._need(), out), "deintegrate_stats")
         return tuple(int(v) for v in out)
 
+    def _repose_args(self, old_trans, new_trans):
+        """(T_old, planes_old, T_new, planes_new) of a re-pose: float32 arrays, planes None with setReferenceCull off."""
+        out = []
+        for trans in (old_trans, new_trans):
+            trans = np.eye(4) if trans is None else np.asarray(trans, dtype=np.float64)
+            planes = reference_cull_planes(self._p, trans) if getattr(self, "_reference_cull", True) else None
+            out += [np.ascontiguousarray(cam_from_vol_f32(trans).reshape(12)), planes]
+        return out
+
+    def reintegrateCloud(self, depth, bgra=None, old_trans=None, new_trans=None, count=False):
+        """Not in the reference: re-pose a fused frame in one sweep of the volume on the GPU (tsdf_hip_reintegrate; the
+        definition and every refusal are in include/tsdf_hip.h) -- what a corrected pose from a pose graph asks of the map.
+        The voxels come out, bit for bit, as ``deintegrateCloud(depth, bgra, old_trans)`` followed by
+        ``integrateCloud(depth, bgra, new_trans)`` leaves them, each half with the reference-cull planes of its own pose
+        (setReferenceCull, on by default), but every word is read and written once, and the band flags survive where the
+        two calls lose them: reconstruct / getOccupiedVoxelIndices / integrateCloud keep their skips.  The saturation caveat
+        of deintegrateCloud is inherited.  Returns True, or (voxels whose weight went down, voxels observed under the new
+        pose) when ``count`` is set.  "RGB" colour, no depth / variance weighting, not on setDevices volumes."""
+        h = self._need()
+        depth = capi.f32c(depth)
+        if depth.shape != (self._p.image_height, self._p.image_width):
+            raise ValueError("depth image must be (image_height, image_width)")
+        col = None
+        if self._p.integrate_color:
+            if bgra is None:
+                raise ValueError("integrate_color is set: a (H, W, 4) uint8 bgra image is required")
+            col = np.ascontiguousarray(bgra, dtype=np.uint8)
+            if col.shape != (self._p.image_height, self._p.image_width, 4):
+                raise ValueError("bgra image must be (image_height, image_width, 4)")
+        To, po, Tn, pn = self._repose_args(old_trans, new_trans)
+        n = (C.c_uint64 * 2)()
+        capi.check(
+            capi.load().tsdf_hip_reintegrate(h, capi.as_f32p(depth), capi.as_u8p(col) if col is not None else None,
+                                             capi.as_f32p(To), capi.as_f32p(po) if po is not None else None,
+                                             capi.as_f32p(Tn), capi.as_f32p(pn) if pn is not None else None,
+                                             n if count else None), "reintegrate")
+        self._cull_set = pn is not None
+        self._is_empty = False
+        return (int(n[0]), int(n[1])) if count else True
+
+    def reintegrateCloudDevice(self, depth_ptr, bgra_ptr, old_trans, new_trans, count=False):
+        """Same, with device pointers (the frame already resident in HBM); asynchronous unless count."""
+        h = self._need()
+        To, po, Tn, pn = self._repose_args(old_trans, new_trans)
+        n = (C.c_uint64 * 2)()
+        capi.check(
+            capi.load().tsdf_hip_reintegrate_device(h, C.c_void_p(depth_ptr), C.c_void_p(bgra_ptr) if bgra_ptr else None,
+                                                    capi.as_f32p(To), capi.as_f32p(po) if po is not None else None,
+                                                    capi.as_f32p(Tn), capi.as_f32p(pn) if pn is not None else None,
+                                                    n if count else None), "reintegrate_device")
+        self._cull_set = pn is not None
+        self._is_empty = False
+        return (int(n[0]), int(n[1])) if count else True
+
+    def reintegrateStats(self):
+        """Report-only: (voxels the old pose selected, voxels whose weight went down, of those the voxels the removal took
+        back to unobserved, voxels the new pose observed, voxels both poses selected -- all five of the last
+        reintegrateCloud with ``count`` --, device microseconds of the last one's kernel).  Waits for it to finish."""
+        out = (C.c_uint64 * 6)()
+        capi.check(capi.load().tsdf_hip_reintegrate_stats(self._need(), out), "reintegrate_stats")
+        return tuple(int(v) for v in out)
+
     def computeDistanceField(self, r_max=0, min_weight=0.0, box=None):
         """Not in the reference: the exact Euclidean distance transform of the volume's zero crossing, on the GPU
         (tsdf_hip_esdf; the rule and every refusal are in include/tsdf_hip.h).  A voxel of ``box`` = (x0, y0, z0, nx, ny, nz)

@@ -66,6 +66,28 @@ bool TSDFVolumeOctree::deintegrateCloud(const pcl::PointCloud<PointT> &cloud, co
                            (int)cloud.height, trans, removed);
 }
 
+// reintegrateCloud: deintegrateCloud's strip, then the out-of-line forwarder to tsdf_hip_reintegrate.
+template <typename PointT, typename NormalT>
+bool TSDFVolumeOctree::reintegrateCloud(const pcl::PointCloud<PointT> &cloud, const pcl::PointCloud<NormalT> &,
+                                        const Eigen::Affine3d &old_trans, const Eigen::Affine3d &new_trans, uint64_t *lowered,
+                                        uint64_t *observed) {
+  if (cloud.points.size() != (size_t)cloud.width * (size_t)cloud.height) {
+    PCL_ERROR("[cpu_tsdf::TSDFVolumeOctree::reintegrateCloud] cloud has %zu points but says %u x %u\n", cloud.points.size(),
+              (unsigned)cloud.width, (unsigned)cloud.height);
+    return false;
+  }
+  const size_t n = cloud.points.size();
+  std::vector<float> depth(n);
+  std::vector<uint32_t> bgra(n);
+  for (size_t i = 0; i < n; ++i) {
+    const PointT &pt = cloud.points[i];
+    depth[i] = pt.z;
+    bgra[i] = (uint32_t)pt.b | ((uint32_t)pt.g << 8) | ((uint32_t)pt.r << 16) | 0xff000000u;  // PCL order b, g, r, a
+  }
+  return reintegratePlanar(n ? &depth[0] : nullptr, n ? reinterpret_cast<const unsigned char *>(&bgra[0]) : nullptr, (int)cloud.width,
+                           (int)cloud.height, old_trans, new_trans, lowered, observed);
+}
+
 // alignCloud: x, y, z of the points with a finite z into one contiguous buffer (as integrateCloud strips its cloud), then
 // the out-of-line forwarder to tsdf_hip_align.
 template <typename PointT>

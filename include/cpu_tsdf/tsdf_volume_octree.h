@@ -192,6 +192,20 @@ class TSDFVolumeOctree : public TSDFInterface {
                         const Eigen::Affine3d &trans = Eigen::Affine3d::Identity(), uint64_t *removed = nullptr);
   bool deintegratePlanar(const float *depth, const unsigned char *bgra, int width, int height, const Eigen::Affine3d &trans,
                          uint64_t *removed = nullptr);
+  // Not in the reference: re-pose a fused cloud in ONE sweep of the volume on the GPU (tsdf_hip_reintegrate: the definition
+  // and every refusal are in include/tsdf_hip.h) -- what a corrected pose from a pose graph asks of the map.  The voxels
+  // come out, bit for bit, as deintegrateCloud(cloud, normals, old_trans) followed by integrateCloud(cloud, normals,
+  // new_trans) leaves them, each half with the default reference-cull planes of its own pose, but every word is read and
+  // written once and the band flags survive where the two calls lose them.  The saturation caveat of deintegrateCloud is
+  // inherited.  *lowered / *observed (optional) receive the voxels whose weight the removal lowered and the voxels the
+  // new pose observed.  The call waits for the kernel.  "RGB" colour, no depth / variance weighting, not on a setDevices
+  // set.  false (and a PCL_ERROR) before reset() and on any refusal, which changes nothing.  reintegratePlanar: the same
+  // on planar images.
+  template <typename PointT, typename NormalT>
+  bool reintegrateCloud(const pcl::PointCloud<PointT> &cloud, const pcl::PointCloud<NormalT> &normals, const Eigen::Affine3d &old_trans,
+                        const Eigen::Affine3d &new_trans, uint64_t *lowered = nullptr, uint64_t *observed = nullptr);
+  bool reintegratePlanar(const float *depth, const unsigned char *bgra, int width, int height, const Eigen::Affine3d &old_trans,
+                         const Eigen::Affine3d &new_trans, uint64_t *lowered = nullptr, uint64_t *observed = nullptr);
   // Not in the reference: the exact Euclidean distance transform of the volume's zero crossing, on the GPU (tsdf_hip_esdf:
   // the rule and every refusal are in include/tsdf_hip.h) -- what a planner or a collision checker asks of the map.  A voxel
   // is a site iff it is observed (weight > min_weight, d not NaN) and a 6-neighbour is observed with the other sign of d;
@@ -228,6 +242,7 @@ class TSDFVolumeOctree : public TSDFInterface {
   bool synchronous_ = false;
   mutable bool cull_planes_set_ = false;
   bool applyReferenceCull(const Eigen::Affine3d &trans) const;
+  void referenceCullPlanes(const Eigen::Affine3d &trans, float planes[24]) const;
   // pinned staging for renderView's readback (tsdf_hip_host_alloc): the GPU writes it by DMA, the conversion into the
   // returned PointCloud reads it -- no intermediate copy
   mutable float *view_buf_;

@@ -913,6 +913,51 @@ int tsdf_hip_deintegrate_device(tsdf_handle h, const float *d_depth, const uint3
                                 uint64_t *n_removed);
 int tsdf_hip_deintegrate_stats(tsdf_handle h, uint64_t out[4]);
 
+/* reintegrateCloud -- NOT IN THE REFERENCE.  Re-poses a fused frame in ONE sweep of the volume: both halves of correcting a
+ * frame's pose after a loop closure, for a caller who gets a corrected pose from a pose graph.
+ *   depth, bgra                 the frame, as for tsdf_hip_deintegrate (host frame: uploaded once through the handle's staging,
+ *                               the call waits; device frame: tsdf_hip_reintegrate_device); bgra is needed iff integrate_color.
+ *   cam_from_vol_old, planes_old   the pose the frame was integrated under and the reference-cull planes it had then
+ *   cam_from_vol_new, planes_new   the corrected pose and its planes; either planes pointer may be NULL: no cull for that pose
+ *   n                           nullable, 2 values: n[0] = voxels whose weight the removal lowered, n[1] = voxels the new
+ *                               pose brought to addObservation.  Without it the device call is asynchronous on the
+ *                               handle's stream and nothing is counted.
+ * DEFINITION.  The call leaves d, w / k and rgb of every voxel, bit for bit, as tsdf_hip_deintegrate(h, frame, old) with
+ * planes_old in force followed by tsdf_hip_integrate(h, frame, new) with planes_new in force leaves them.  Removal: the RULE
+ * above tsdf_hip_deintegrate (W = ceilf(w), the equal-bits clause, colour rounded to nearest, the reset state at w' <= 0).
+ * Addition: OctreeNode / RGBNode::addObservation with w_new = 1, as tsdf_hip_integrate applies it.  Each half selects its
+ * voxels as its own call does, with its own pose and its own six planes; voxels are independent of each other, so one
+ * kernel applies the removal and then the addition to a voxel in registers and writes each word once.
+ * COST (one MI355X): 0.97 x the time of the two calls where a pose's cull planes bite and tsdf_hip_integrate runs its
+ * plain kernel; 1.1-1.26 x where neither pose's planes bite and tsdf_hip_integrate runs its fast kernel -- there the two calls
+ * are the quicker way and keep the flags as well.
+ * SATURATION: the caveat of tsdf_hip_deintegrate is inherited -- a voxel at max_weight has forgotten how many frames it saw
+ * and loses one count like any other before the new observation is added.  Nothing checks that the frame was ever
+ * integrated under the old pose.
+ * STATE.  The "band seen" flags and the implied-distance record SURVIVE in every regime (the two calls lose the flags where
+ * the cull bites and the integrate goes through the plain kernel): the removal half sets a cell's flag as
+ * tsdf_hip_deintegrate does, deciding from the record as it stands before the call; the addition half sets it where the new
+ * pose observes a d_new off the hinge value; a voxel observed at exactly the hinge value in a flag-0 cell ends there.  The
+ * record is updated for the addition as by an integrate launch that keeps the flags.  After the call the planes in force on
+ * the handle are planes_new (NULL: none), as tsdf_hip_integrate_device2 keeps frame B's.  Like every writer of the planes the
+ * call first launches a frame held back by frame pairing and invalidates the distance field of tsdf_hip_esdf; it covers the
+ * planes the handle's integrate launches write (Z-slab handles work).
+ * A pose with a non-finite entry selects nothing: old not finite, the call is a tsdf_hip_integrate; new not finite, a
+ * tsdf_hip_deintegrate; both, nothing is written: OK, counts 0.
+ * TSDF_HIP_E_INVALID, before any device is touched: a NULL handle, frame, old or new pose; integrate_color without bgra.
+ * TSDF_HIP_E_UNSUPPORTED, with the reason in tsdf_hip_last_error, the voxel planes and the cull planes untouched: the handles
+ * tsdf_hip_deintegrate refuses -- weight_by_depth or weight_by_variance on, or the variance state allocated;
+ * TSDF_COLOR_RGB_NORMALIZED / TSDF_COLOR_LAB; a multi-GPU set (tsdf_hip_create_multi: still open).
+ * tsdf_hip_reintegrate_stats: report-only.  out[0] = voxels the old pose selected, out[1] = voxels whose weight went down,
+ * out[2] = of those, voxels the removal took back to unobserved, out[3] = voxels the new pose observed, out[4] = voxels both
+ * poses selected -- all five of the last call that passed n; out[5] = device microseconds of the last call's kernel (HIP
+ * events on the stream; waits for the second one; 0 if none ran). */
+int tsdf_hip_reintegrate(tsdf_handle h, const float *depth, const uint8_t *bgra, const float cam_from_vol_old[12], const float *planes_old,
+                         const float cam_from_vol_new[12], const float *planes_new, uint64_t *n);
+int tsdf_hip_reintegrate_device(tsdf_handle h, const float *d_depth, const uint32_t *d_bgra, const float cam_from_vol_old[12],
+                                const float *planes_old, const float cam_from_vol_new[12], const float *planes_new, uint64_t *n);
+int tsdf_hip_reintegrate_stats(tsdf_handle h, uint64_t out[6]);
+
 /* Block transfer of raw voxels (parity tests, save/load, halo exchange).  Coordinates are global
  * grid indices; the block must lie inside the handle's slab + halo.  Any pointer may be NULL.
  * rgb is 3 bytes per voxel (r,g,b).  *_device variants take device pointers (rgb then 4 bytes). */
