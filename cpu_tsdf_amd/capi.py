@@ -23,6 +23,7 @@ ALIGN_NO_POINTS, ALIGN_RANK_DEFICIENT = 7, 8  # statuses of tsdf_hip_align only
 XFORM_PCL_SSE, XFORM_LEFT_TO_RIGHT = 0, 1
 LAYOUT_AUTO, LAYOUT_F32W, LAYOUT_PACKED = 0, 1, 2
 COLOR_RGB, COLOR_RGB_NORMALIZED, COLOR_LAB = 0, 1, 2
+RAYS_AS_GIVEN = 1  # TSDF_HIP_RAYS_AS_GIVEN, flag of tsdf_hip_cast_rays
 
 
 class TsdfParams(C.Structure):
@@ -164,6 +165,10 @@ SIGNATURES = {
     "tsdf_hip_reintegrate": (C.c_int, [C.c_void_p, _f32p, _u8p, _f32p, _f32p, _f32p, _f32p, _u64p]),
     "tsdf_hip_reintegrate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _f32p, _f32p, _f32p, _f32p, _u64p]),
     "tsdf_hip_reintegrate_stats": (C.c_int, [C.c_void_p, _u64p]),
+    "tsdf_hip_cast_rays": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_size_t, C.c_int, _f32p, _u8p, _u8p]),
+    "tsdf_hip_cast_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "tsdf_hip_cast_rays_stats": (C.c_int, [C.c_void_p, _u64p]),
     "tsdf_hip_esdf": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_float, _u64p]),
     "tsdf_hip_esdf_fetch": (C.c_int, [C.c_void_p, _u32p, _f32p]),
     "tsdf_hip_esdf_fetch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -492,6 +492,45 @@ pcl::PointCloud<pcl::PointXYZRGBNormal>::Ptr TSDFVolumeOctree::renderColoredView
   return colored;
 }
 
+// ---- castRays (not in the reference): tsdf_hip_cast_rays ----------------------------------------------------------------------
+bool TSDFVolumeOctree::castRays(const float *origins, const float *directions, size_t n, pcl::PointCloud<pcl::PointXYZRGBNormal> &hits,
+                                std::vector<uint8_t> *status, const float *t_range) const {
+  if (!ready("castRays") || !cubicForQueries("castRays")) return false;
+  if (!origins || !directions || !n || n >= (1ull << 31)) {
+    PCL_ERROR("[cpu_tsdf::TSDFVolumeOctree::castRays] needs origins, directions and 0 < n < 2^31 rays\n");
+    return false;
+  }
+  std::vector<float> out(8 * n);
+  std::vector<uint8_t> rgb(p_.integrate_color ? 3 * n : 0), st(n);
+  const int rc = tsdf_hip_cast_rays(h_, origins, directions, t_range, n, 0, out.data(), p_.integrate_color ? rgb.data() : nullptr, st.data());
+  if (rc) {
+    report("castRays", rc);
+    return false;
+  }
+  hits = pcl::PointCloud<pcl::PointXYZRGBNormal>((uint32_t)n, 1);
+  hits.is_dense = false;
+  for (size_t i = 0; i < n; ++i) {
+    pcl::PointXYZRGBNormal &pt = hits.points[i];
+    const float *o = &out[8 * i];
+    pt.x = o[0];
+    pt.y = o[1];
+    pt.z = o[2];
+    pt.normal_x = o[3];
+    pt.normal_y = o[4];
+    pt.normal_z = o[5];
+    if (st[i] != 1) continue;  // a miss keeps the default colour, as in renderColoredView
+    if (p_.integrate_color) {
+      pt.r = rgb[3 * i];
+      pt.g = rgb[3 * i + 1];
+      pt.b = rgb[3 * i + 2];
+    } else if (std::fabs(o[0]) <= p_.size[0] / 2 && std::fabs(o[1]) <= p_.size[1] / 2 && std::fabs(o[2]) <= p_.size[2] / 2) {
+      pt.r = pt.g = pt.b = 127;  // the "NOCOLOR" octree's answer wherever it has a voxel (octree.cpp:172-177, 628-643)
+    }
+  }
+  if (status) status->swap(st);
+  return true;
+}
+
 pcl::PointCloud<pcl::Intensity>::Ptr TSDFVolumeOctree::getIntensityCloud(const Eigen::Affine3d &) const {
   return pcl::PointCloud<pcl::Intensity>::Ptr();  // the reference returns a null pointer too (:543-548)
 }

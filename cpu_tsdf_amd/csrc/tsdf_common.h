@@ -131,6 +131,11 @@ struct tsdf_hip_volume {
   EventSet<2> reint_ev;                         // tsdf_hip_reintegrate_stats: around the kernel of the last tsdf_hip_reintegrate (tsdf_reintegrate.hip)
   bool reint_timed = false;                     // ... both have been recorded
   uint64_t reint_stats[5] = {0, 0, 0, 0, 0};    // of the last call that counted: selected by old, lowered, cleared, observed by new, selected by both
+  EventSet<2> cast_ev;                          // tsdf_hip_cast_rays_stats: around the kernels of the last tsdf_hip_cast_rays (tsdf_castrays.hip)
+  bool cast_timed = false;                      // ... both have been recorded
+  DevBuf cast_count;                            // device, one unsigned long long of that call: hits in the low word, rays ended with status 2 or 3 in the
+                                                // high word (a counter of its own: an asynchronous call leaves it for the stats, whatever runs in between)
+  uint64_t cast_rays = 0;                       // rays of the last call
   DevBuf scratch;  // grown by tsdf_ensure_scratch
   tsdf_occ_state *occ = nullptr;
   tsdf_meshpost_state *mp = nullptr;

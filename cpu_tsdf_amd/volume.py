@@ -413,6 +413,63 @@ class TSDFVolumeOctree:
             rgb[hit] = c
         return cloud, rgb
 
+    def castRays(self, origins, directions, t_range=None, want_rgb=False, as_given=False):
+        """Not in the reference: cast n arbitrary rays into the fused volume on the GPU (tsdf_hip_cast_rays; the definition,
+        the admission rule and every refusal are in include/tsdf_hip.h).  ``origins`` / ``directions``: (n, 3) in the volume
+        frame, directions used as given (the step rule is the reference's only for unit directions); ``t_range``: (n, 2)
+        tmin, tmax per ray, None = the sensor distance bounds.  Returns (out (n, 8) float32: xyz, normal, t*, iterations --
+        what ``renderView(camera_frame=False)`` returns for a pixel with that direction, origin and range --, status (n,)
+        uint8: 0 miss, 1 hit, 2 not admitted, 3 stopped by the trip cap[, rgb (n, 3) uint8 with ``want_rgb``: the colour of
+        the voxel that contains the hit, 0 otherwise; 127,127,127 on a volume without integrateColor, as
+        ``renderColoredView``]).  ``as_given``: the rays are already coherent, march them in this order; the results never
+        depend on it (and today neither does the order: DESIGN.md 3.23).  One device, a whole-grid volume; no rgb on a "LAB"
+        volume."""
+        self._cubic_for_queries("castRays")
+        h = self._need()
+        org = capi.f32c(origins).reshape(-1, 3)
+        u = capi.f32c(directions).reshape(-1, 3)
+        n = len(org)
+        if len(u) != n:
+            raise ValueError("origins and directions must have the same length")
+        rng = None
+        if t_range is not None:
+            rng = capi.f32c(t_range).reshape(-1, 2)
+            if len(rng) != n:
+                raise ValueError("t_range must be (n, 2)")
+        out = np.empty((n, 8), np.float32)
+        status = np.empty(n, np.uint8)
+        rgb = np.empty((n, 3), np.uint8) if want_rgb else None
+        capi.check(
+            capi.load().tsdf_hip_cast_rays(h, capi.as_f32p(org), capi.as_f32p(u), capi.as_f32p(rng) if rng is not None else None, n,
+                                           capi.RAYS_AS_GIVEN if as_given else 0, capi.as_f32p(out), capi.as_u8p(rgb) if want_rgb else None,
+                                           capi.as_u8p(status)), "cast_rays")
+        if not want_rgb:
+            return out, status
+        if not self._p.integrate_color:  # the reference's NOCOLOR octree answers 127,127,127 wherever it finds a voxel
+            half = [np.float32(s) / np.float32(2) for s in self._p.size]
+            found = (status == 1) & (np.abs(out[:, 0]) <= half[0]) & (np.abs(out[:, 1]) <= half[1]) & (np.abs(out[:, 2]) <= half[2])
+            rgb[found] = 127
+        return out, status, rgb
+
+    def castRaysDevice(self, org_ptr, dir_ptr, t_range_ptr, n, out_ptr, rgb_ptr=0, status_ptr=0, as_given=False):
+        """Same, with device pointers on the volume's device (t_range_ptr, rgb_ptr, status_ptr may be 0); asynchronous on the
+        volume's stream.  The colour bytes are the library's (0 on a volume without colour)."""
+        self._cubic_for_queries("castRays")
+        capi.check(
+            capi.load().tsdf_hip_cast_rays_device(self._need(), C.c_void_p(org_ptr), C.c_void_p(dir_ptr),
+                                                  C.c_void_p(t_range_ptr) if t_range_ptr else None, int(n),
+                                                  capi.RAYS_AS_GIVEN if as_given else 0, C.c_void_p(out_ptr),
+                                                  C.c_void_p(rgb_ptr) if rgb_ptr else None, C.c_void_p(status_ptr) if status_ptr else None),
+            "cast_rays_device")
+        return True
+
+    def castRaysStats(self):
+        """Report-only, of the last castRays / castRaysDevice: (rays, hits, rays ended with status 2 or 3, device microseconds
+        of the call's kernels).  Waits for it to finish."""
+        out = (C.c_uint64 * 4)()
+        capi.check(capi.load().tsdf_hip_cast_rays_stats(self._need(), out), "cast_rays_stats")
+        return tuple(int(v) for v in out)
+
     def getFxn(self, pts):
         """Batched ``getFxn`` (tsdf_volume_octree.cpp:655-672): returns (ok, val)."""
         ok, val, _, _ = self.sample(pts, want_grad=False, want_hess=False)

@@ -206,6 +206,18 @@ class TSDFVolumeOctree : public TSDFInterface {
                         const Eigen::Affine3d &new_trans, uint64_t *lowered = nullptr, uint64_t *observed = nullptr);
   bool reintegratePlanar(const float *depth, const unsigned char *bgra, int width, int height, const Eigen::Affine3d &old_trans,
                          const Eigen::Affine3d &new_trans, uint64_t *lowered = nullptr, uint64_t *observed = nullptr);
+  // Not in the reference: cast n arbitrary rays into the fused volume on the GPU (tsdf_hip_cast_rays: the definition, the
+  // admission rule and every refusal are in include/tsdf_hip.h) -- line of sight, a simulated lidar, picking, view scoring.
+  // origins / directions: n x 3 floats, volume frame; a direction is used as given (the step rule is the reference's only for
+  // unit directions); t_range: n x 2 floats tmin, tmax per ray, nullptr = the sensor distance bounds.  Ray i gives point i
+  // of `hits` (n x 1, is_dense = false): exactly what renderView's loop (tsdf_volume_octree.cpp:290-421) computes for a
+  // pixel with that direction, origin and range, in the volume frame -- NaN x, y, z for a miss -- coloured as
+  // renderColoredView colours a hit (the voxel that contains it; 127,127,127 without setIntegrateColor).  *status
+  // (optional): per ray 0 miss, 1 hit, 2 not admitted (an input that is not finite, or a range of more than 2^24 trips),
+  // 3 stopped by the trip cap; no ray can hang the device.  One device, a whole-grid volume, not "LAB" with
+  // setIntegrateColor.  false (and a PCL_ERROR) before reset(), on a non-cubic grid and on any refusal, which changes nothing.
+  bool castRays(const float *origins, const float *directions, size_t n, pcl::PointCloud<pcl::PointXYZRGBNormal> &hits,
+                std::vector<uint8_t> *status = nullptr, const float *t_range = nullptr) const;
   // Not in the reference: the exact Euclidean distance transform of the volume's zero crossing, on the GPU (tsdf_hip_esdf:
   // the rule and every refusal are in include/tsdf_hip.h) -- what a planner or a collision checker asks of the map.  A voxel
   // is a site iff it is observed (weight > min_weight, d not NaN) and a 6-neighbour is observed with the other sign of d;

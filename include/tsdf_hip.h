@@ -958,6 +958,48 @@ int tsdf_hip_reintegrate_device(tsdf_handle h, const float *d_depth, const uint3
                                 const float *planes_old, const float cam_from_vol_new[12], const float *planes_new, uint64_t *n);
 int tsdf_hip_reintegrate_stats(tsdf_handle h, uint64_t out[6]);
 
+#define TSDF_HIP_RAYS_AS_GIVEN 1
+/* castRays -- NOT IN THE REFERENCE (its only ray query is renderView, the rays of one pinhole image).  Casts n arbitrary rays
+ * into the fused volume on the GPU: line of sight between points, a simulated lidar or second camera, picking, view scoring.
+ *   org, dir       n x 3 floats each, volume frame: ray i is o_i + t * u_i.  u_i is used AS GIVEN: not normalised, not checked
+ *                  for length.  The step rule below is the reference's only for unit directions.
+ *   t_range        n x 2 floats tmin_i, tmax_i (in units of |u_i|), or NULL: min_sensor_dist / max_sensor_dist for every ray
+ *   flags          bit 0, TSDF_HIP_RAYS_AS_GIVEN: "my rays are already coherent, march them in my order".  Without it the
+ *                  library may march them in any order; the results are per ray and never depend on it.  Today the bit
+ *                  changes nothing: the library always marches in the given order, because sorting the rays first did not
+ *                  pay even for randomly permuted rays (DESIGN.md 3.23's measurement).  Any other bit: E_INVALID.
+ *   out            n x 8 floats: x, y, z, nx, ny, nz, t*, iterations of ray i, volume frame
+ *   rgb            nullable, n x 3 bytes;  status: nullable, n bytes
+ * DEFINITION.  out[8 i ..] is exactly what k_raycast<false> -- tsdf_hip_raycast, renderView, tsdf_volume_octree.cpp:290-421 --
+ * writes for a pixel whose rotated direction du equals u_i, with the origin o_i and the sensor range [tmin_i, tmax_i]; every
+ * other constant of the loop (the first step, the refinement step, the leaf size, max_dist_neg) comes from the handle as for
+ * tsdf_hip_raycast.  Both kernels run one copy of the loop.  A miss has NaN x, y, z and a zero normal, t and iterations as
+ * the loop left them; a hit whose neighbourhood is not valid has NaN normals.
+ * Colour: the bytes tsdf_hip_lookup_rgb returns at the hit point (the voxel that contains it), read in the same kernel; 0, 0, 0
+ * for a miss, where that lookup finds no voxel, and on a volume without colour.
+ * status: 0 miss, 1 hit (x, y, z finite), 2 not admitted, 3 stopped by the trip cap.
+ * ADMISSION AND TERMINATION.  renderView's loop ends only through float progress of t; here termination does not depend on
+ * float arithmetic.  A ray is refused (status 2: NaN x, y, z, a zero normal, t = tmin_i, iterations 0, no voxel touched) when
+ * one of its 8 inputs is not finite, or when cap = 16 + 2 * ceil((tmax - tmin) / (leaf / 4)), computed in double, exceeds
+ * 2^24.  tmax <= tmin is admitted: the loop does not run, as in the reference.  An integer trip counter covers main-loop and
+ * refinement-walk iterations together and stands in the condition of both loops; a ray that reaches cap ends as a miss with
+ * status 3, t and iterations as at that moment.  `iterations` stays the reference's count (main loop only).  A ray that makes
+ * the reference's forward progress (at least leaf / 4 per main-loop iteration) never reaches its cap.
+ * Host form: staged through the handle's scratch and pinned stage, waits.  tsdf_hip_cast_rays_device: the same with device
+ * pointers on the handle's device, asynchronous on the handle's stream.
+ * Like every reader the call first launches a frame held back by frame pairing.
+ * TSDF_HIP_E_INVALID, before any device is touched: a NULL handle, org, dir or out; n == 0; n >= 2^31; unknown flag bits.
+ * TSDF_HIP_E_UNSUPPORTED, with the reason in tsdf_hip_last_error: a multi-GPU set (tsdf_hip_create_multi) -- cast into one
+ * whole-grid handle; a Z-slab handle that does not hold the whole grid; rgb != NULL on a TSDF_COLOR_LAB volume, whose exact
+ * bytes need the host's pow (pass NULL and use tsdf_hip_lookup_rgb).  A refusal writes nothing.
+ * tsdf_hip_cast_rays_stats: report-only, of the last call on the handle; synchronises.  out[0] = rays, out[1] = hits (status
+ * 1), out[2] = rays ended with status 2 or 3, out[3] = device microseconds of the call's kernels (HIP events on the stream). */
+int tsdf_hip_cast_rays(tsdf_handle h, const float *org, const float *dir, const float *t_range, size_t n, int flags, float *out,
+                       uint8_t *rgb, uint8_t *status);
+int tsdf_hip_cast_rays_device(tsdf_handle h, const float *d_org, const float *d_dir, const float *d_t_range, size_t n, int flags,
+                              float *d_out, uint8_t *d_rgb, uint8_t *d_status);
+int tsdf_hip_cast_rays_stats(tsdf_handle h, uint64_t out[4]);
+
 /* Block transfer of raw voxels (parity tests, save/load, halo exchange).  Coordinates are global
  * grid indices; the block must lie inside the handle's slab + halo.  Any pointer may be NULL.
  * rgb is 3 bytes per voxel (r,g,b).  *_device variants take device pointers (rgb then 4 bytes). */
